@@ -12,11 +12,17 @@ with the serial per-block loop replaced by batch calls).
   cpu_baseline  the oracle (oracle/rans4x16_oracle.c: the scalar C restatement of the reference's algorithm, pinned by
              the reference's fixtures) timed on this host's cores on a bounded sample - kind "port"
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  N > 1: one rank per GPU, either started by
-torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK in the environment) or - when those are absent - by
-this script itself, which then spawns N child ranks BEFORE it touches the GPU and relays rank 0's JSON line.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  N > 1: one rank per GPU,
+either started by torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK in the environment) or - when those are
+absent - by this script itself, which then spawns N child ranks BEFORE it touches the GPU and relays rank 0's JSON line.
 Blocks are independent: the global batch of N x blocks is cut by the library's own partition
 (rans4x16_hip_partition) and the ranks share nothing but the final barrier / max.
+
+A plain run sets up, warms up, times the K steps and prints the headline (value, enc_MBps / dec_MBps, ms_per_step).
+--full adds everything else, as before: the untimed gate step bit-compared with the CPU oracle, the roofline and chain
+figures (the library's timing hook, the one-workgroup probe), the configs[4] and heterogeneous legs, host_path and
+cpu_baseline (the --no-* options switch single ones off).  --dump-outputs DIR writes what the last timed step handed its
+caller (see dump_outputs) as .npy files, for comparing two builds output for output.
 """
 import argparse
 import ctypes as C
@@ -114,6 +120,38 @@ def cpu_baseline(order, blk_size, name, seconds_target=12.0):
         "value_1thread": round(one_thread, 1), "enc_1thread": round(blk_size * reps / te1 / 1e6, 1),
         "dec_1thread": round(blk_size * reps / td1 / 1e6, 1),
     }
+
+
+DUMP_LIMIT = 64 << 20          # bytes of array data --dump-outputs may write in all
+DUMP_MAX_BLOCKS = 1 << 18      # per-block arrays: all blocks up to this many, else a seeded sample of them
+
+
+def dump_outputs(out_dir, nblk, bs, slot, d_comp, comp_size, st_enc, d_back, back_size, st_dec, seed=1234):
+    """What the last timed step handed its caller, as DIR/<name>.npy: per block (float64) the compressed size, the
+    encode status, the decoded size and the decode status; for a seeded sample of eight blocks (the first and the last
+    among them, listed in sample_blocks) the compressed streams and the decoded bytes, concatenated in sample order
+    (float32).  Everything is a function of the arguments alone, so two builds can be compared file for file; if the
+    sampled bytes would pass DUMP_LIMIT, a seeded sample of their positions is written instead."""
+    rs = np.random.RandomState(seed)
+    idx = np.arange(nblk) if nblk <= DUMP_MAX_BLOCKS else np.sort(rs.choice(nblk, DUMP_MAX_BLOCKS, replace=False))
+    csz, bsz = comp_size.cpu().numpy(), back_size.cpu().numpy()
+    out = {"block_index": idx, "comp_size": csz[idx], "enc_status": st_enc.cpu().numpy()[idx],
+           "dec_size": bsz[idx], "dec_status": st_dec.cpu().numpy()[idx]}
+    out = {k: v.astype(np.float64) for k, v in out.items()}
+    sample = sorted(set([0, nblk - 1] + [int(x) for x in rs.randint(0, nblk, size=6)]))
+    out["sample_blocks"] = np.asarray(sample, dtype=np.float64)
+    comp = np.concatenate([d_comp[b * slot:b * slot + min(max(int(csz[b]), 0), slot)].cpu().numpy() for b in sample])
+    back = np.concatenate([d_back[b * bs:b * bs + min(max(int(bsz[b]), 0), bs)].cpu().numpy() for b in sample])
+    room = (DUMP_LIMIT - sum(v.nbytes for v in out.values())) // 4          # float32 elements left
+    if comp.size + back.size > room:
+        share = room / (comp.size + back.size)
+        comp, back = [a[np.unique(rs.randint(0, a.size, size=int(a.size * share)))] for a in (comp, back)]
+    out["comp_bytes"] = comp.astype(np.float32)
+    out["dec_bytes"] = back.astype(np.float32)
+    assert sum(v.nbytes for v in out.values()) <= DUMP_LIMIT
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def library_hash():
@@ -497,12 +535,18 @@ def main():
     ap.add_argument("--block-size", type=int, default=1 << 20)
     ap.add_argument("--data", default="q40+dir")
     ap.add_argument("--order", type=int, default=1)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-host", action="store_true", help="skip the PCIe-inclusive host-buffer figure")
-    ap.add_argument("--no-configs4", action="store_true", help="skip the mixed 64 KiB leg (BASELINE configs[4]'s shape)")
-    ap.add_argument("--no-hetero", action="store_true", help="skip the heterogeneous leg (blocks of any size, alphabet and order)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the gate against the CPU oracle, roofline / chain figures, the configs[4] "
+                         "and heterogeneous legs, host_path and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-host", action="store_true", help="with --full: skip the PCIe-inclusive host-buffer figure")
+    ap.add_argument("--no-configs4", action="store_true", help="with --full: skip the mixed 64 KiB leg (BASELINE configs[4]'s shape)")
+    ap.add_argument("--no-hetero", action="store_true", help="with --full: skip the heterogeneous leg (blocks of any size, alphabet and order)")
     ap.add_argument("--hetero-gib", type=float, default=16.0, help="bytes per GPU of the heterogeneous leg")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)                       # does not return
@@ -566,8 +610,9 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    dc.timing(True)
-    dc.timing_read(0); dc.timing_read(1)
+    if args.full:                                    # the library's chain-kernel events: for the roofline figures only
+        dc.timing(True)
+        dc.timing_read(0); dc.timing_read(1)
     mids = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
     begs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
     ends = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
@@ -578,76 +623,82 @@ def main():
         ends[k].record()
     barrier()
     elapsed = time.perf_counter() - t0
-    dc.timing(False)
-    enc_chain_ms, enc_launches = dc.timing_read(0)
-    dec_chain_ms, dec_launches = dc.timing_read(1)
+    if args.full:
+        dc.timing(False)
+        enc_chain_ms, enc_launches = dc.timing_read(0)
+        dec_chain_ms, dec_launches = dc.timing_read(1)
     t_enc = sum(b.elapsed_time(m) for b, m in zip(begs, mids)) / 1e3 / args.steps
     t_dec = sum(m.elapsed_time(e) for m, e in zip(mids, ends)) / 1e3 / args.steps
-
-    # ---- correctness gate: one more, untimed, step into CLEARED outputs (a step that silently wrote nothing must not
-    # pass on what the warm-up left behind): every block decodes to its input, every status is 0, and 64+ blocks -
-    # the first and last of every round of resident streams among them - are bit-compared with the CPU reference
-    d_back.zero_(); d_comp.zero_(); comp_size.zero_(); back_size.zero_()
-    st_enc.fill_(-1); st_dec.fill_(-1)
-    step()
-    torch.cuda.synchronize()
-    assert int((st_enc != 0).sum()) == 0 and int((st_dec != 0).sum()) == 0, "device reported failures"
-    assert torch.equal(back_size, in_size), "decoded sizes differ"
-    assert torch.equal(d_back, d_in), "round trip mismatch"
+    # what the last timed step returned: no block may have failed (a figure of failing calls is no figure)
+    assert int((st_enc != 0).sum()) == 0 and int((st_dec != 0).sum()) == 0, "device reported failures in the timed steps"
     csz = comp_size.cpu().numpy()
-    gate_blocks = 0
-    if rank == 0:
-        import cpu_libs
-        import datagen
-        chk = cpu_libs.oracle()
-        res = max(1, dec_spc * cus)
-        edges = [b for r in range(0, nblk, res) for b in (r, min(nblk, r + res) - 1)]
-        rs = np.random.RandomState(7)
-        sample = sorted(set(edges + [int(x) for x in rs.randint(0, nblk, size=64)]))
-        for b in sample:
-            want = chk.compress(block_bytes(args.data, bs, b, first).tobytes(), order)
-            got = d_comp[b * slot:b * slot + int(csz[b])].cpu().numpy().tobytes()
-            assert got == want, f"block {b}: device stream differs from the CPU reference"
-        gate_blocks = len(sample)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, nblk, bs, slot, d_comp, comp_size, st_enc, d_back, back_size, st_dec)
 
-    # ---- one workgroup alone: the per-step latency of a full set of streams without neighbours on the chip.  The SAME
-    # kernel as the full grid's, so the short-step routes that such a small batch would take by itself are switched
-    # off for these two calls (options of the context)
-    probe = None
-    if rank == 0:
-        probe = {}
-        saved = {k: dc.get_option(k) for k in ("dec_direct", "enc_direct")}
-        for k_ in saved:
-            dc.set_option(k_, 0)
-        try:
-            for which, spc, lanes in ((1, dec_spc, dec_lanes), (0, enc_spc, enc_lanes)):
-                k = lanes // 4 if which == 1 else spc          # decode: one wave per workgroup; encode: one workgroup per CU
-                k = min(k, nblk)
-                for timed in (False, True):                    # (a first call of this size sets up side streams etc.)
-                    dc.timing(timed); dc.timing_read(which)
-                    if which == 1:
-                        dc.uncompress(d_comp, comp_off[:k], comp_size[:k], d_back, in_off[:k], in_size[:k], back_size[:k], st_dec[:k], cap, xf_cap)
-                    else:
-                        dc.compress(d_in, in_off[:k], in_size[:k], d_comp, comp_off[:k], comp_cap[:k], comp_size[:k], st_enc[:k], order, bs)
-                    torch.cuda.synchronize()
-                ms, _ = dc.timing_read(which)
-                dc.timing(False)
-                probe[which] = (k, ms)
-        finally:
-            for k_, v_ in saved.items():
-                dc.set_option(k_, v_)
+    gate_blocks, probe = 0, None
+    if args.full:
+        # ---- correctness gate: one more, untimed, step into CLEARED outputs (a step that silently wrote nothing must not
+        # pass on what the warm-up left behind): every block decodes to its input, every status is 0, and 64+ blocks -
+        # the first and last of every round of resident streams among them - are bit-compared with the CPU reference
+        d_back.zero_(); d_comp.zero_(); comp_size.zero_(); back_size.zero_()
+        st_enc.fill_(-1); st_dec.fill_(-1)
+        step()
+        torch.cuda.synchronize()
+        assert int((st_enc != 0).sum()) == 0 and int((st_dec != 0).sum()) == 0, "device reported failures"
+        assert torch.equal(back_size, in_size), "decoded sizes differ"
+        assert torch.equal(d_back, d_in), "round trip mismatch"
+        csz = comp_size.cpu().numpy()
+        if rank == 0:
+            import cpu_libs
+            import datagen
+            chk = cpu_libs.oracle()
+            res = max(1, dec_spc * cus)
+            edges = [b for r in range(0, nblk, res) for b in (r, min(nblk, r + res) - 1)]
+            rs = np.random.RandomState(7)
+            sample = sorted(set(edges + [int(x) for x in rs.randint(0, nblk, size=64)]))
+            for b in sample:
+                want = chk.compress(block_bytes(args.data, bs, b, first).tobytes(), order)
+                got = d_comp[b * slot:b * slot + int(csz[b])].cpu().numpy().tobytes()
+                assert got == want, f"block {b}: device stream differs from the CPU reference"
+            gate_blocks = len(sample)
+
+        # ---- one workgroup alone: the per-step latency of a full set of streams without neighbours on the chip.  The SAME
+        # kernel as the full grid's, so the short-step routes that such a small batch would take by itself are switched
+        # off for these two calls (options of the context)
+        if rank == 0:
+            probe = {}
+            saved = {k: dc.get_option(k) for k in ("dec_direct", "enc_direct")}
+            for k_ in saved:
+                dc.set_option(k_, 0)
+            try:
+                for which, spc, lanes in ((1, dec_spc, dec_lanes), (0, enc_spc, enc_lanes)):
+                    k = lanes // 4 if which == 1 else spc          # decode: one wave per workgroup; encode: one workgroup per CU
+                    k = min(k, nblk)
+                    for timed in (False, True):                    # (a first call of this size sets up side streams etc.)
+                        dc.timing(timed); dc.timing_read(which)
+                        if which == 1:
+                            dc.uncompress(d_comp, comp_off[:k], comp_size[:k], d_back, in_off[:k], in_size[:k], back_size[:k], st_dec[:k], cap, xf_cap)
+                        else:
+                            dc.compress(d_in, in_off[:k], in_size[:k], d_comp, comp_off[:k], comp_cap[:k], comp_size[:k], st_enc[:k], order, bs)
+                        torch.cuda.synchronize()
+                    ms, _ = dc.timing_read(which)
+                    dc.timing(False)
+                    probe[which] = (k, ms)
+            finally:
+                for k_, v_ in saved.items():
+                    dc.set_option(k_, v_)
 
     ws_headline = dc.workspace_bytes()
     per_rank_ms = [round(x / args.steps * 1e3, 3) for x in shard.gather_over_ranks(dist, elapsed, red_dev)]
     elapsed = shard.max_over_ranks(dist, elapsed, red_dev)
     c4 = None
-    if not args.no_configs4:
+    if args.full and not args.no_configs4:
         del d_back, d_comp
         d_back = d_comp = None
         torch.cuda.empty_cache()
         c4 = configs4_leg(torch, H, dc, dev, dist, red_dev, shard, rank, world)
     het = None
-    if not args.no_hetero:
+    if args.full and not args.no_hetero:
         # (the headline's arenas are gone by now: the leg needs ~70 GB of its own beside the workspace)
         d_back = d_comp = None
         d_in = in_off = in_size = comp_off = comp_cap = None
@@ -671,60 +722,6 @@ def main():
         comp_bytes = int(csz.sum())
         ms_per_step = elapsed / args.steps * 1e3
         value = total_unc / (elapsed / args.steps) / 1e6
-        # dominant kernel = the slower chain kernel; algorithmic bytes = uncompressed + compressed
-        enc_avg = enc_chain_ms / max(enc_launches, 1)
-        dec_avg = dec_chain_ms / max(dec_launches, 1)
-        launches_per_step = max(enc_launches, 1) / args.steps
-        if enc_avg >= dec_avg:
-            kname, kavg = "k_enc_chain", enc_avg
-        else:
-            kname, kavg = "k_dec_chain", dec_avg
-        alg_bytes = (nblk * bs + comp_bytes) / launches_per_step
-        achieved = alg_bytes / (kavg / 1e3) / 1e9
-        # HBM bytes per launch from the PMC passes committed under profiles/ (rocprofv3 --pmc FETCH_SIZE /
-        # WRITE_SIZE, separate runs, gfx950 FETCH correction applied) - only if they were taken on this very
-        # workload AND with this very build of the library (its hash is stored with them): a kernel change without
-        # a counter refresh reports null, never a stale figure
-        traffic, traffic_source, sq, sq_all = None, None, None, {}
-        build = library_hash()
-        isa = {}
-        import glob
-        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_isa_counts.json")), reverse=True):
-            try:
-                with open(path) as f:
-                    j = json.load(f)
-                if j.get("library_sha256_16") == build:
-                    isa = j["kernels"]
-                    break
-            except (OSError, KeyError, ValueError):
-                pass
-        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
-            try:
-                with open(path) as f:
-                    pmc = json.load(f)
-                w = pmc["workload"]
-                if (w["blocks"], w["block_size"], w["data"], w["order"]) != (nblk, bs, args.data, order) \
-                        or pmc.get("library_sha256_16") != build:
-                    continue
-                for key, v in pmc["kernels"].items():       # the instantiation that did the work (k_dec_chain<true, 1>, not the
-                    if key.startswith(kname) and v["traffic_bytes"] > (traffic or 0):   # nested tables' k_dec_chain<true, 3>)
-                        traffic = v["traffic_bytes"]
-                        traffic_source = os.path.relpath(path, ROOT)
-                sq_all = pmc.get("sq", {})
-                sq = sq_all.get(kname)
-                break
-            except (OSError, KeyError, ValueError):
-                pass
-        chain = chain_figure(torch, dc, kname, dec_avg if kname == "k_dec_chain" else enc_avg, launches_per_step,
-                             nblk, bs, dec_spc if kname == "k_dec_chain" else enc_spc,
-                             dec_lanes if kname == "k_dec_chain" else enc_lanes, cus, probe, sq)
-        clk_khz = dc.L.rans4x16_hip_device_clock_khz(dc.ctx.h)
-        issue = {
-            "k_dec_chain": issue_figure("k_dec_chain", dec_avg, launches_per_step, nblk, bs, dec_spc, dec_lanes, cus, clk_khz,
-                                        sq_all.get("k_dec_chain"), isa.get("k_dec_chain<true,1>")),
-            "k_enc_chain": issue_figure("k_enc_chain", enc_avg, launches_per_step, nblk, bs, enc_spc, enc_lanes, cus, clk_khz,
-                                        sq_all.get("k_enc_chain"), isa.get("k_enc_chain<true,true>")),
-        }
         out = {
             "metric": "MB/s uncompressed throughput (encode+decode), rANS4x16 order-1, q40 blocks",
             "value": round(value, 1), "unit": "MB/s", "n_gpus": world, "steps": args.steps,
@@ -735,26 +732,81 @@ def main():
                        "order": order, "blocks_per_gpu": nblk, "block_size": bs,
                        "ratio": round(comp_bytes / (nblk * bs), 4)},
             "enc_MBps": round(nblk * bs / t_enc / 1e6, 1), "dec_MBps": round(nblk * bs / t_dec / 1e6, 1),
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic, "traffic_source": traffic_source, "library_sha256_16": build,
-                         "limiter": "instruction issue of lone waves x resident streams, not bandwidth (see issue, chain)",
-                         "issue": issue, "chain": chain, "avg_kernel_ms": round(kavg, 3),
-                         "enc_chain_ms": round(enc_avg, 3), "dec_chain_ms": round(dec_avg, 3),
-                         "algorithmic_bytes_per_launch": int(alg_bytes),
-                         "note": "avg_kernel_ms = HIP-event time of the chain kernel per step; the kernel is launched "
-                                 "once per LDS size class and all but one class exit in microseconds, so compare with "
-                                 "rocprof's TotalDurationNs / steps (profiles/r04_final_working_launches.csv)"},
             "workspace_GB": round(ws_headline / 2**30, 2),
-            "gate": {"roundtrip_blocks": nblk, "bytes_equal_cpu_blocks": gate_blocks,
-                     "how": "untimed extra step into cleared outputs after the timed ones"},
         }
+        if args.full:
+            # dominant kernel = the slower chain kernel; algorithmic bytes = uncompressed + compressed
+            enc_avg = enc_chain_ms / max(enc_launches, 1)
+            dec_avg = dec_chain_ms / max(dec_launches, 1)
+            launches_per_step = max(enc_launches, 1) / args.steps
+            if enc_avg >= dec_avg:
+                kname, kavg = "k_enc_chain", enc_avg
+            else:
+                kname, kavg = "k_dec_chain", dec_avg
+            alg_bytes = (nblk * bs + comp_bytes) / launches_per_step
+            achieved = alg_bytes / (kavg / 1e3) / 1e9
+            # HBM bytes per launch from the PMC passes committed under profiles/ (rocprofv3 --pmc FETCH_SIZE /
+            # WRITE_SIZE, separate runs, gfx950 FETCH correction applied) - only if they were taken on this very
+            # workload AND with this very build of the library (its hash is stored with them): a kernel change without
+            # a counter refresh reports null, never a stale figure
+            traffic, traffic_source, sq, sq_all = None, None, None, {}
+            build = library_hash()
+            isa = {}
+            import glob
+            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_isa_counts.json")), reverse=True):
+                try:
+                    with open(path) as f:
+                        j = json.load(f)
+                    if j.get("library_sha256_16") == build:
+                        isa = j["kernels"]
+                        break
+                except (OSError, KeyError, ValueError):
+                    pass
+            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
+                try:
+                    with open(path) as f:
+                        pmc = json.load(f)
+                    w = pmc["workload"]
+                    if (w["blocks"], w["block_size"], w["data"], w["order"]) != (nblk, bs, args.data, order) \
+                            or pmc.get("library_sha256_16") != build:
+                        continue
+                    for key, v in pmc["kernels"].items():       # the instantiation that did the work (k_dec_chain<true, 1>, not the
+                        if key.startswith(kname) and v["traffic_bytes"] > (traffic or 0):   # nested tables' k_dec_chain<true, 3>)
+                            traffic = v["traffic_bytes"]
+                            traffic_source = os.path.relpath(path, ROOT)
+                    sq_all = pmc.get("sq", {})
+                    sq = sq_all.get(kname)
+                    break
+                except (OSError, KeyError, ValueError):
+                    pass
+            chain = chain_figure(torch, dc, kname, dec_avg if kname == "k_dec_chain" else enc_avg, launches_per_step,
+                                 nblk, bs, dec_spc if kname == "k_dec_chain" else enc_spc,
+                                 dec_lanes if kname == "k_dec_chain" else enc_lanes, cus, probe, sq)
+            clk_khz = dc.L.rans4x16_hip_device_clock_khz(dc.ctx.h)
+            issue = {
+                "k_dec_chain": issue_figure("k_dec_chain", dec_avg, launches_per_step, nblk, bs, dec_spc, dec_lanes, cus, clk_khz,
+                                            sq_all.get("k_dec_chain"), isa.get("k_dec_chain<true,1>")),
+                "k_enc_chain": issue_figure("k_enc_chain", enc_avg, launches_per_step, nblk, bs, enc_spc, enc_lanes, cus, clk_khz,
+                                            sq_all.get("k_enc_chain"), isa.get("k_enc_chain<true,true>")),
+            }
+            out["roofline"] = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 2),
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                               "traffic": traffic, "traffic_source": traffic_source, "library_sha256_16": build,
+                               "limiter": "instruction issue of lone waves x resident streams, not bandwidth (see issue, chain)",
+                               "issue": issue, "chain": chain, "avg_kernel_ms": round(kavg, 3),
+                               "enc_chain_ms": round(enc_avg, 3), "dec_chain_ms": round(dec_avg, 3),
+                               "algorithmic_bytes_per_launch": int(alg_bytes),
+                               "note": "avg_kernel_ms = HIP-event time of the chain kernel per step; the kernel is launched "
+                                       "once per LDS size class and all but one class exit in microseconds, so compare with "
+                                       "rocprof's TotalDurationNs / steps (profiles/r04_final_working_launches.csv)"}
+            out["gate"] = {"roundtrip_blocks": nblk, "bytes_equal_cpu_blocks": gate_blocks,
+                           "how": "untimed extra step into cleared outputs after the timed ones"}
         out["per_rank_ms_per_step"] = {"each": per_rank_ms, "min": min(per_rank_ms), "max": max(per_rank_ms)}
         if c4:
             out["configs4"] = c4
         if het:
             out["hetero"] = het
-        if world == 1 and not args.no_host:
+        if args.full and world == 1 and not args.no_host:
             # The host-buffer calls are measured as a C program would see them: through their own context, with the
             # benchmark's device-resident context (its 35 GB workspace, its arenas) released first - an idle context
             # holding that much device memory was measured to cost these calls a quarter of their rate
@@ -769,7 +821,7 @@ def main():
                 print("before host_path: device memory free %.1f of %.1f GB; referrers of the codec: %s" % (
                     free / 1e9, total / 1e9, [type(o).__name__ for o in gc.get_objects() if type(o).__name__ in ("DeviceCodec", "_Ctx")]), file=sys.stderr)
             out["host_path"] = host_path(H, args.data, bs, order)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(order, bs, args.data)
         print(json.dumps(out), flush=True)
     if dist is not None:

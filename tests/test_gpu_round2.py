@@ -237,7 +237,7 @@ def test_bench_launches_its_own_ranks():
     env = dict(os.environ, R4X16_OVERSUBSCRIBE="1")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--blocks", "600",
-                        "--steps", "2", "--warmup", "1", "--no-cpu", "--no-host", "--hetero-gib", "0.25"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-host", "--hetero-gib", "0.25"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

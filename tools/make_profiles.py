@@ -73,7 +73,7 @@ for k, v in sq.items():
             v["lds_conflict_cycles_per_inst"] = round(v["SQ_LDS_BANK_CONFLICT"] / v["SQ_INSTS_LDS"], 3)
 traffic["sq"] = sq
 traffic["sq_how"] = ("rocprofv3 --kernel-trace --pmc <SQ counters> (own runs, no other tracing) -- python bench.py --steps 1 "
-                     "--warmup 1 --no-cpu --no-host; the working launch of each chain kernel")
+                     "--warmup 1 --full --no-cpu --no-host; the working launch of each chain kernel")
 with open(os.path.join(DST, f"{tag}_pmc_traffic.json"), "w") as f:
     json.dump(traffic, f, indent=1)
 os.makedirs(os.path.join(DST, "pmc"), exist_ok=True)

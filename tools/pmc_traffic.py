@@ -19,7 +19,7 @@ def per_launch(path, counter):
 fetch = per_launch(sys.argv[1], "FETCH_SIZE")
 write = per_launch(sys.argv[2], "WRITE_SIZE")
 out = {"how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, in a separate run, --pmc WRITE_SIZE) --output-format csv "
-              "-- python bench.py --steps 1 --warmup 1 --no-cpu; counters are KB; FETCH_SIZE is doubled per "
+              "-- python bench.py --steps 1 --warmup 1 --full --no-cpu; counters are KB; FETCH_SIZE is doubled per "
               "MI355X_MICROARCH.md (gfx950 reports half of a streaming read); average per working launch "
               "(launches within a factor ten of the kernel's largest)",
        "workload": {"blocks": int(sys.argv[3]), "block_size": int(sys.argv[4]), "data": sys.argv[5], "order": int(sys.argv[6])},

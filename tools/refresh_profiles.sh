@@ -10,9 +10,9 @@ PART=${1:-all}            # a: the bench line and the profiler passes; b: sweeps
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" != b ]; then
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- python3 $R/bench.py --no-cpu --no-host --no-configs4 --no-hetero > $O/bench_prof.json 2> $O/bench_prof.err
-P="--steps 1 --warmup 1 --no-cpu --no-host --no-configs4 --no-hetero"
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- python3 $R/bench.py --full --no-cpu --no-host --no-configs4 --no-hetero > $O/bench_prof.json 2> $O/bench_prof.err
+P="--steps 1 --warmup 1 --full --no-cpu --no-host --no-configs4 --no-hetero"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch --output-format csv -- python3 $R/bench.py $P > $O/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write --output-format csv -- python3 $R/bench.py $P > $O/write.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY SQ_WAIT_ANY \
