@@ -132,6 +132,26 @@ class _Ctx:
             raise KeyError(f"unknown option {name!r}")
         return v.value
 
+    def route_read(self, which, reset=True):
+        """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch") since the
+        last reset; needs option route_count = 1 while the calls run."""
+        w = ROUTE_WHICH[which]
+        kinds = ROUTE_KINDS[which]
+        arr = (C.c_long * len(kinds))()
+        rc = self.L.rans4x16_hip_route_read(self.h, w, arr, len(kinds), 1 if reset else 0)
+        if rc != len(kinds):
+            raise RuntimeError("route_read failed: " + self.error())
+        return dict(zip(kinds, arr))
+
+
+# include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
+ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3}
+ROUTE_KINDS = {
+    "encode": ("u16", "packed", "records"),
+    "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
+    "expand": ("wave", "workgroup"),
+    "launch": ("in_order", "side_by_side"),
+}
 
 _tls = threading.local()
 
@@ -152,6 +172,11 @@ def set_option(name, value):
 
 def get_option(name):
     return _thread_ctx().get_option(name)
+
+
+def route_read(which, reset=True):
+    """The route read-out of the calling thread's context (the one the host-batch helpers use): see _Ctx.route_read."""
+    return _thread_ctx().route_read(which, reset)
 
 
 def get_default_option(name):
@@ -302,6 +327,9 @@ class DeviceCodec:
     def get_option(self, name):
         return self.ctx.get_option(name)
 
+    def route_read(self, which, reset=True):
+        return self.ctx.route_read(which, reset)
+
     def timing_read(self, which, reset=True):
         ms = C.c_double(0)
         k = C.c_int(0)
@@ -313,10 +341,11 @@ class DeviceCodec:
     def workspace_bytes(self):
         return self.L.rans4x16_hip_workspace_bytes(self.ctx.h)
 
-    def residency(self, decode, nsym, order, shift=10):
-        """(streams per CU, live lanes per wave, CUs) of the chain kernel for this kind of stream."""
+    def residency(self, decode, nsym, order, shift=10, kind=0):
+        """(streams per CU, live lanes per wave, CUs) of the chain kernel for this kind of stream.  kind: 0 the full
+        chip's rows, R4X16_RES_SHORT (2) the short-step kind, R4X16_RES_MID (4) the mid rows (include/rans4x16_hip.h)."""
         a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
-        if self.L.rans4x16_hip_residency(self.ctx.h, 1 if decode else 0, nsym, order, shift,
+        if self.L.rans4x16_hip_residency(self.ctx.h, (1 if decode else 0) | int(kind), nsym, order, shift,
                                          C.byref(a), C.byref(b), C.byref(c)) != 0:
             raise RuntimeError("residency query failed")
         return a.value, b.value, c.value

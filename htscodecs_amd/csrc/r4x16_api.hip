@@ -8,45 +8,49 @@
 extern "C" const char *rans4x16_hip_version(void) { return "rans4x16_hip 0.2 (gfx950)"; }
 
 // ---------------------------------------------------------------------------------------------
-// Options (include/rans4x16_hip.h part 2b).  {name, environment variable that provides the default, built-in default}.
+// Options (include/rans4x16_hip.h part 2b).
+// {name, environment variable that provides the default, built-in default, smallest and largest value set_option accepts}.
+// The ranges keep every value a launcher can be handed usable: a value outside them is refused (enc_qpw_cap = 0 would be a
+// division by zero on the host, a forced qpw beyond a wave's sixteen quads or the CU's LDS a launch that cannot run).
 // ---------------------------------------------------------------------------------------------
-static const struct { const char *name, *env; long dflt; } OPT_TAB[OPT_COUNT] = {
-    /* OPT_DEC_DIRECT        */ {"dec_direct", "R4X16_DEC_DIRECT", 1},
-    /* OPT_ENC_DIRECT        */ {"enc_direct", "R4X16_ENC_DIRECT", 1},
-    /* OPT_BACK_WG_PER_CU    */ {"back_wg_per_cu", "R4X16_BACK_WG_PER_CU", 0},
-    /* OPT_DEC_MID           */ {"dec_mid", "R4X16_DEC_MID", 0},
-    /* OPT_DEC_SHORT_RING    */ {"dec_short_ring", "R4X16_DEC_SHORT_RING", 0},
-    /* OPT_SCHED_SORT        */ {"sched_sort", "R4X16_SCHED_SORT", 1},
-    /* OPT_SCHED_CLAIM       */ {"sched_claim", "R4X16_SCHED_CLAIM", 1},
-    /* OPT_SCHED_CONCURRENT  */ {"sched_concurrent", "R4X16_SCHED_CONCURRENT", 1},
-    /* OPT_SCHED_TRACE       */ {"sched_trace", "R4X16_SCHED_TRACE", 0},
-    /* OPT_SCHED_LEARN       */ {"sched_learn", "R4X16_SCHED_LEARN", 2},
-    /* OPT_MAX_WS_MB         */ {"max_workspace_mb", "R4X16_MAX_WS_MB", 160 << 10},
-    /* OPT_HOST_STRIPE_DEV   */ {"host_stripe_dev", "R4X16_HOST_STRIPE_DEV", 1},
-    /* OPT_HOST_PIPE_MB      */ {"host_pipe_mb", "R4X16_HOST_PIPE_MB", 64},
-    /* OPT_HOST_THREADS      */ {"host_threads", "R4X16_HOST_THREADS", 8},
-    /* OPT_HOST_LANES        */ {"host_lanes", "R4X16_HOST_LANES", 2},
-    /* OPT_HOST_SLAB_MIN_MB  */ {"host_slab_min_mb", "R4X16_HOST_SLAB_MIN_MB", 32},
-    /* OPT_HOST_DEC_SLABS    */ {"host_dec_slabs", "R4X16_HOST_DEC_SLABS", 0},
-    /* OPT_HOST_ENC_SLABS    */ {"host_enc_slabs", "R4X16_HOST_ENC_SLABS", 0},
-    /* OPT_HOST_PACK         */ {"host_pack", "R4X16_HOST_PACK", 1},
-    /* OPT_HOST_TRACE        */ {"host_trace", "R4X16_HOST_TRACE", 0},
-    /* OPT_DEC_QPW           */ {"dec_qpw", "R4X16_DEC_QPW", 0},
-    /* OPT_DEC_QPW_SMALL     */ {"dec_qpw_small", "R4X16_DEC_QPW_SMALL", 0},
-    /* OPT_DEC_QPW_PK        */ {"dec_qpw_pk", "R4X16_DEC_QPW_PK", 0},
-    /* OPT_DEC_QPW_DIR       */ {"dec_qpw_dir", "R4X16_DEC_QPW_DIR", 0},
-    /* OPT_ENC_QPW           */ {"enc_qpw", "R4X16_ENC_QPW", 0},
-    /* OPT_ENC_WAVES         */ {"enc_waves", "R4X16_ENC_WAVES", 0},
-    /* OPT_ENC_QPW_REC       */ {"enc_qpw_rec", "R4X16_ENC_QPW_REC", 0},
-    /* OPT_ENC_QPW_CAP       */ {"enc_qpw_cap", "R4X16_ENC_QPW_CAP", 64},
-    /* OPT_FRONT_LDS         */ {"front_lds", "R4X16_FRONT_LDS", 0},
+static const struct { const char *name, *env; long dflt, lo, hi; } OPT_TAB[OPT_COUNT] = {
+    /* OPT_DEC_DIRECT        */ {"dec_direct", "R4X16_DEC_DIRECT", 1, 0, 1L << 16},
+    /* OPT_ENC_DIRECT        */ {"enc_direct", "R4X16_ENC_DIRECT", 1, 0, 1L << 16},
+    /* OPT_BACK_WG_PER_CU    */ {"back_wg_per_cu", "R4X16_BACK_WG_PER_CU", 0, 0, 1L << 20},
+    /* OPT_DEC_MID           */ {"dec_mid", "R4X16_DEC_MID", 0, 0, 1L << 16},
+    /* OPT_DEC_SHORT_RING    */ {"dec_short_ring", "R4X16_DEC_SHORT_RING", 0, 0, 1},
+    /* OPT_SCHED_SORT        */ {"sched_sort", "R4X16_SCHED_SORT", 1, 0, 1},
+    /* OPT_SCHED_CLAIM       */ {"sched_claim", "R4X16_SCHED_CLAIM", 1, 0, 1},
+    /* OPT_SCHED_CONCURRENT  */ {"sched_concurrent", "R4X16_SCHED_CONCURRENT", 1, 0, 1},
+    /* OPT_SCHED_TRACE       */ {"sched_trace", "R4X16_SCHED_TRACE", 0, 0, 1},
+    /* OPT_SCHED_LEARN       */ {"sched_learn", "R4X16_SCHED_LEARN", 2, 0, 3},
+    /* OPT_MAX_WS_MB         */ {"max_workspace_mb", "R4X16_MAX_WS_MB", 160 << 10, 0, 1L << 30},
+    /* OPT_HOST_STRIPE_DEV   */ {"host_stripe_dev", "R4X16_HOST_STRIPE_DEV", 1, 0, 1},
+    /* OPT_HOST_PIPE_MB      */ {"host_pipe_mb", "R4X16_HOST_PIPE_MB", 64, 0, 1L << 30},
+    /* OPT_HOST_THREADS      */ {"host_threads", "R4X16_HOST_THREADS", 8, 1, 32},
+    /* OPT_HOST_LANES        */ {"host_lanes", "R4X16_HOST_LANES", 2, 1, 16},
+    /* OPT_HOST_SLAB_MIN_MB  */ {"host_slab_min_mb", "R4X16_HOST_SLAB_MIN_MB", 32, 0, 1L << 20},
+    /* OPT_HOST_DEC_SLABS    */ {"host_dec_slabs", "R4X16_HOST_DEC_SLABS", 0, 0, 64},
+    /* OPT_HOST_ENC_SLABS    */ {"host_enc_slabs", "R4X16_HOST_ENC_SLABS", 0, 0, 64},
+    /* OPT_HOST_PACK         */ {"host_pack", "R4X16_HOST_PACK", 1, 0, 1},
+    /* OPT_HOST_TRACE        */ {"host_trace", "R4X16_HOST_TRACE", 0, 0, 1},
+    /* OPT_DEC_QPW           */ {"dec_qpw", "R4X16_DEC_QPW", 0, 0, 16},
+    /* OPT_DEC_QPW_SMALL     */ {"dec_qpw_small", "R4X16_DEC_QPW_SMALL", 0, 0, 16},
+    /* OPT_DEC_QPW_PK        */ {"dec_qpw_pk", "R4X16_DEC_QPW_PK", 0, 0, 16},
+    /* OPT_DEC_QPW_DIR       */ {"dec_qpw_dir", "R4X16_DEC_QPW_DIR", 0, 0, 16},
+    /* OPT_ENC_QPW           */ {"enc_qpw", "R4X16_ENC_QPW", 0, 0, 31},
+    /* OPT_ENC_WAVES         */ {"enc_waves", "R4X16_ENC_WAVES", 0, 0, 4},
+    /* OPT_ENC_QPW_REC       */ {"enc_qpw_rec", "R4X16_ENC_QPW_REC", 0, 0, 16},
+    /* OPT_ENC_QPW_CAP       */ {"enc_qpw_cap", "R4X16_ENC_QPW_CAP", 64, 1, 64},
+    /* OPT_FRONT_LDS         */ {"front_lds", "R4X16_FRONT_LDS", 0, 0, 65536},
+    /* OPT_ROUTE_COUNT       */ {"route_count", "R4X16_ROUTE_COUNT", 0, 0, 1},
     // process-wide (set with ctx == NULL before the first single-block call / multi-device call)
-    /* OPT_COMBINE           */ {"combine", "R4X16_COMBINE", 1},
-    /* OPT_COMBINE_WINDOW_US */ {"combine_window_us", "R4X16_COMBINE_WINDOW_US", -1},
-    /* OPT_COMBINE_MAX       */ {"combine_max", "R4X16_COMBINE_MAX", 256},
-    /* OPT_COMBINE_WORKERS   */ {"combine_workers", "R4X16_COMBINE_WORKERS", 1},
-    /* OPT_COMBINE_MAX_MB    */ {"combine_max_mb", "R4X16_COMBINE_MAX_MB", 2048},
-    /* OPT_NUMA              */ {"numa", "R4X16_NUMA", 1},
+    /* OPT_COMBINE           */ {"combine", "R4X16_COMBINE", 1, 0, 1},
+    /* OPT_COMBINE_WINDOW_US */ {"combine_window_us", "R4X16_COMBINE_WINDOW_US", -1, -1, 1000000},
+    /* OPT_COMBINE_MAX       */ {"combine_max", "R4X16_COMBINE_MAX", 256, 0, 1L << 20},
+    /* OPT_COMBINE_WORKERS   */ {"combine_workers", "R4X16_COMBINE_WORKERS", 1, 0, 4},
+    /* OPT_COMBINE_MAX_MB    */ {"combine_max_mb", "R4X16_COMBINE_MAX_MB", 2048, 0, 1L << 20},
+    /* OPT_NUMA              */ {"numa", "R4X16_NUMA", 1, 0, 1},
 };
 // the process-wide defaults: the environment is read here, once, and nowhere else
 static std::mutex g_opts_mu;
@@ -57,7 +61,8 @@ static R4Opts *opts_defaults_rw()
     std::call_once(once, [] {
         for (int i = 0; i < OPT_COUNT; i++) {
             const char *e = getenv(OPT_TAB[i].env);
-            d.v[i] = e && *e ? atol(e) : OPT_TAB[i].dflt;
+            const long v = e && *e ? atol(e) : OPT_TAB[i].dflt;
+            d.v[i] = v >= OPT_TAB[i].lo && v <= OPT_TAB[i].hi ? v : OPT_TAB[i].dflt;     // (out of range: the built-in default)
         }
     });
     return &d;
@@ -72,7 +77,7 @@ static int opt_index(const char *name)
 extern "C" int rans4x16_hip_set_option(rans4x16_hip_ctx *c, const char *name, long value)
 {
     const int i = opt_index(name);
-    if (i < 0) return -1;
+    if (i < 0 || value < OPT_TAB[i].lo || value > OPT_TAB[i].hi) return -1;
     if (!c) {                                                    // the defaults of contexts created from now on, the contexts
         R4Opts *d = opts_defaults_rw();                           // behind the five drop-in symbols, and the process-wide options
         std::lock_guard<std::mutex> g(g_opts_mu);
@@ -158,6 +163,7 @@ extern "C" void rans4x16_hip_destroy(rans4x16_hip_ctx *c)
     if (!c) return;
     r4x16_pipe_destroy(c->pipe);
     (void)hipSetDevice(c->device);
+    for (auto &r : c->route_pending) { (void)hipEventSynchronize(r.ev); (void)hipEventDestroy(r.ev); (void)hipHostFree(r.cnt); }
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (int w = 0; w < 2; w++)
         for (auto &t : c->timed[w]) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
@@ -207,6 +213,61 @@ extern "C" int rans4x16_hip_timing_read(rans4x16_hip_ctx *c, int which, double *
         c->timed[which].clear();
     }
     return 0;
+}
+
+// ---- route read-out (option route_count; include/rans4x16_hip.h) -------------------------------------------------
+// A chain launch's per-class stream counts (SchedWs.cnt[SCHED_COUNT + class], written by the scheduler's scan) are copied
+// behind it on its stream into pinned memory; the host folds them into per-kind sums when they are read (or when many
+// are waiting).  Off, none of this happens: no copy, no event, no synchronisation.
+extern "C" int r4x16_dec_route_kind(u32 ci);
+extern "C" int r4x16_enc_route_kind(u32 ci);
+static int route_fold(rans4x16_hip_ctx *c)
+{
+    int rc = 0;
+    for (auto &r : c->route_pending) {
+        if (hipEventSynchronize(r.ev) != hipSuccess) rc = -1;
+        else
+            for (u32 ci = 0; ci < CLS_MAX; ci++) {
+                const int k = r.which == 0 ? r4x16_enc_route_kind(ci) : r4x16_dec_route_kind(ci);
+                if (k >= 0 && r.cnt[ci]) c->route[r.which][k] += (long)r.cnt[ci];
+            }
+        (void)hipEventDestroy(r.ev);
+        (void)hipHostFree(r.cnt);
+    }
+    c->route_pending.clear();
+    return rc;
+}
+static int route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, hipStream_t s)
+{
+    if (c->route_pending.size() >= 64 && route_fold(c) != 0) { c->err = "route read-out: a counted launch failed"; return -1; }
+    RouteSnap r{which, nullptr, nullptr};
+    HIPCHK(c, hipHostMalloc((void **)&r.cnt, CLS_MAX * sizeof(u32), hipHostMallocDefault));
+    memset(r.cnt, 0, CLS_MAX * sizeof(u32));
+    if (hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(r.cnt); c->err = "route read-out: no event"; return -1; }
+    c->route_pending.push_back(r);
+    HIPCHK(c, hipMemcpyAsync(r.cnt, d_cnt + SCHED_COUNT, CLS_MAX * sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(r.ev, s));
+    return 0;
+}
+static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS};
+static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS, "route kinds");
+extern "C" int rans4x16_hip_route_read(rans4x16_hip_ctx *c, int which, long *counts, int n, int reset)
+{
+    if (!c || which < 0 || which >= ROUTE_WHICH || n < 0 || (n && !counts)) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    // the context's own launches and its pipeline lanes' (a lane works only inside its parent's calls)
+    std::vector<rans4x16_hip_ctx *> all{c};
+    for (int i = 0; rans4x16_hip_ctx *l = r4x16_pipe_lane(c->pipe, i); i++) all.push_back(l);
+    int rc = 0;
+    long sum[ROUTE_KINDS] = {};
+    for (auto *x : all) {
+        if (route_fold(x) != 0) rc = -1;
+        for (int k = 0; k < ROUTE_KINDS; k++) sum[k] += x->route[which][k];
+        if (reset) for (int k = 0; k < ROUTE_KINDS; k++) x->route[which][k] = 0;
+    }
+    if (rc != 0) { c->err = "route read-out: a counted launch failed"; return -1; }
+    for (int k = 0; k < n; k++) counts[k] = k < ROUTE_NKINDS[which] ? sum[k] : 0;
+    return ROUTE_NKINDS[which];
 }
 
 static int ensure_ws(rans4x16_hip_ctx *c, size_t bytes)
@@ -423,6 +484,10 @@ extern "C" int rans4x16_hip_compress_dev_sized(rans4x16_hip_ctx *c, int n,
         if (c->timing) time_begin(c, 0, s, t);
         r4x16_launch_enc_chain(&w, 3 * nb, s, fk, &c->opts, &c->hint[0]);
         if (c->timing) time_end(c, 0, s, t);
+        if (c->opts.v[OPT_ROUTE_COUNT]) {
+            if (route_snap(c, 0, w.sched.cnt, s) != 0) return -1;
+            c->route[3][fk ? R4X16_LAUNCH_SIDE_BY_SIDE : R4X16_LAUNCH_IN_ORDER]++;
+        }
         r4x16_launch_enc_finish(&a, &w, (int)base, nb, s);
     }
     HIPCHK(c, hipGetLastError());
@@ -517,7 +582,12 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
         if (c->timing) time_begin(c, 1, s, t);
         r4x16_launch_dec_chain(&w, 2 * nb, s, fk, &c->opts, &c->hint[1]);
         if (c->timing) time_end(c, 1, s, t);
-        r4x16_launch_dec_back(&a, &w, (int)base, nb, s, &c->opts);
+        if (c->opts.v[OPT_ROUTE_COUNT]) {
+            if (route_snap(c, 1, w.sched.cnt, s) != 0) return -1;
+            c->route[3][fk ? R4X16_LAUNCH_SIDE_BY_SIDE : R4X16_LAUNCH_IN_ORDER]++;
+        }
+        const int wg = r4x16_launch_dec_back(&a, &w, (int)base, nb, s, &c->opts);
+        if (c->opts.v[OPT_ROUTE_COUNT]) c->route[2][wg ? R4X16_EXPAND_WORKGROUP : R4X16_EXPAND_WAVE] += nb;
     }
     HIPCHK(c, hipGetLastError());
     return ws_order_end(c, s);
@@ -525,6 +595,8 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
 
 extern "C" int r4x16_dec_residency(u32 nsym, int order, u32 bits, int *streams_per_wave, int *waves_per_cu, int short_ring);
 extern "C" int r4x16_enc_residency(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu);
+extern "C" int r4x16_dec_residency_kind(u32 nsym, int order, u32 bits, bool short_step, int *streams_per_wave, int *waves_per_cu);
+extern "C" int r4x16_enc_residency_records(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu);
 extern "C" int r4x16_cu_count(void);
 
 extern "C" int rans4x16_hip_residency(rans4x16_hip_ctx *c, int decode, unsigned int nsym, int order, unsigned int shift,
@@ -533,7 +605,17 @@ extern "C" int rans4x16_hip_residency(rans4x16_hip_ctx *c, int decode, unsigned 
     if (!c) return -1;
     if (hipSetDevice(c->device) != hipSuccess) return -1;
     int spw = 0, wpc = 0, total = 0;
-    if (decode) {
+    const int kind = decode & (R4X16_RES_SHORT | R4X16_RES_MID);
+    if ((decode & ~(1 | R4X16_RES_SHORT | R4X16_RES_MID)) || kind == (R4X16_RES_SHORT | R4X16_RES_MID) || (kind == R4X16_RES_MID && !(decode & 1)))
+        return -1;
+    decode &= 1;
+    if (kind && decode) {
+        if (r4x16_dec_residency_kind(nsym, order & 1, shift, kind == R4X16_RES_SHORT, &spw, &wpc) != 0) return -1;
+        total = spw * wpc;
+    } else if (kind) {
+        total = r4x16_enc_residency_records(nsym, order & 1, &spw, &wpc);
+        if (total < 0) return -1;
+    } else if (decode) {
         if (r4x16_dec_residency(nsym, order & 1, shift, &spw, &wpc, c->opts.v[OPT_DEC_SHORT_RING] != 0) != 0) return -1;
         total = spw * wpc;
     } else {

@@ -2611,7 +2611,7 @@ static const struct { u32 bytes; int qpw; int lv; } DEC_CLASSES[] = {
     {3360, 16, 9},
     // mid rows (level 10; only batches of one partly filled round make such images, r4x16_dec_mid_budget): four streams
     // per wave - the loop is two LDS round trips per step, few lanes per access - and four waves per CU, one per SIMD:
-    // sixteen streams of up to 48 symbols (8,816 bytes) per CU, 4,096 per chip
+    // sixteen streams of up to 47 symbols (8,640 bytes with the word ring; 48 take 9,008) per CU, 4,096 per chip
     {8976, 4, 10},
 };
 // workgroups of `lds_bytes` each that one CU holds at once (1,280-byte LDS granules, 32 wave slots)
@@ -2858,15 +2858,61 @@ extern "C" int r4x16_dec_residency(u32 nsym, int order, u32 bits, int *streams_p
     *streams_per_wave = 16; *waves_per_cu = 8;              // tables in global memory: bounded by wave slots
     return 0;
 }
-extern "C" void r4x16_launch_dec_back(const BatchArgs *a, const DecWs *ws, int base, int nblk, hipStream_t s, const R4Opts *o)
+// The row kind of a class id of the chain decoder (its position in DEC_CLASSES, then the catch-alls of depths 2, 3, 4), as
+// the route read-out counts it (include/rans4x16_hip.h R4X16_DEC_*); -1 for ids beyond the catch-alls.
+extern "C" int r4x16_dec_route_kind(u32 ci)
+{
+    if (ci >= DEC_NCLS) return ci - DEC_NCLS < 3u ? 1 + (int)(ci - DEC_NCLS) : -1;
+    switch (DEC_CLASSES[ci].lv) {
+    case 1: return 0;
+    case 2: case 8: return 1;                    // (level 8: level 2's kernel for order-0 streams)
+    case 3: return 2;
+    case 4: return 3;
+    case 5: return 4;
+    case 6: case 7: return 5;                    // (level 7: level 6's kernel for order-0 streams)
+    case 10: return 6;
+    case 9: return 7;
+    }
+    return -1;
+}
+// Streams per CU of the class a stream of this kind lands in when the batch's budget admits it: the direct rows (short) /
+// the mid rows (!short).  Mirrors the front's choice (o1_tables, o0_front) and the class tables; -1 where the stream can
+// never take that kind.
+extern "C" int r4x16_dec_residency_kind(u32 nsym, int order, u32 bits, bool short_step, int *streams_per_wave, int *waves_per_cu)
+{
+    if (nsym == 0 || nsym > 256) return -1;
+    u32 need, lv;
+    if (short_step) {
+        if ((order && bits != 10 && bits != 12) || nsym > DIR_MAX_NSYM) return -1;
+        need = (order ? dir_img_bytes(nsym, nsym, bits) : dir_img_bytes(nsym, 1u, O0_BITS)) + RING_BYTES;
+        lv = 6u;
+    } else {
+        if (!order || bits != 10 || nsym < MID_MIN_NSYM || nsym > MID_MAX_NSYM) return -1;
+        need = mid_img_bytes(nsym) + RING_BYTES;
+        lv = 10u;
+    }
+    for (const auto &c : DEC_CLASSES) {
+        if ((u32)c.lv != lv || need > c.bytes) continue;
+        *streams_per_wave = c.qpw;
+        *waves_per_cu = resident_per_cu((size_t)c.qpw * c.bytes, 1);
+        return 0;
+    }
+    return -1;
+}
+// returns the expansion kernel it launched: 0 one wave per block, 1 a workgroup per block (R4X16_EXPAND_*)
+extern "C" int r4x16_launch_dec_back(const BatchArgs *a, const DecWs *ws, int base, int nblk, hipStream_t s, const R4Opts *o)
 {
     // One wave per block at every batch size since its trips became 256 literals of LDS-fed work (64 x 1 MiB q8 blocks with
     // X_RLE: step 38.0 ms either way; 1,024: 53.5 against 55.6; 2,048: 56.2 against 64.6); the workgroup-per-block
     // kernel, round 3's first answer to the old trip's fixed ~19 ms per MiB, stays selectable: R4X16_BACK_WG_PER_CU=N
     // takes it up to N blocks per CU.
     const int wg_per_cu = (int)o->v[OPT_BACK_WG_PER_CU];
-    if (nblk <= wg_per_cu * cu_count()) hipLaunchKernelGGL(k_dec_back<BACK_THREADS>, dim3(nblk), dim3(BACK_THREADS), 0, s, *a, *ws, base);
-    else hipLaunchKernelGGL(k_dec_back<WAVE>, dim3(nblk), dim3(WAVE), 0, s, *a, *ws, base);
+    if ((long)nblk <= (long)wg_per_cu * cu_count()) {
+        hipLaunchKernelGGL(k_dec_back<BACK_THREADS>, dim3(nblk), dim3(BACK_THREADS), 0, s, *a, *ws, base);
+        return 1;
+    }
+    hipLaunchKernelGGL(k_dec_back<WAVE>, dim3(nblk), dim3(WAVE), 0, s, *a, *ws, base);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

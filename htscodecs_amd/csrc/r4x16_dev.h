@@ -82,7 +82,7 @@ enum R4Opt {
     OPT_HOST_STRIPE_DEV, OPT_HOST_PIPE_MB, OPT_HOST_THREADS, OPT_HOST_LANES, OPT_HOST_SLAB_MIN_MB,
     OPT_HOST_DEC_SLABS, OPT_HOST_ENC_SLABS, OPT_HOST_PACK, OPT_HOST_TRACE,
     OPT_DEC_QPW, OPT_DEC_QPW_SMALL, OPT_DEC_QPW_PK, OPT_DEC_QPW_DIR,
-    OPT_ENC_QPW, OPT_ENC_WAVES, OPT_ENC_QPW_REC, OPT_ENC_QPW_CAP, OPT_FRONT_LDS,
+    OPT_ENC_QPW, OPT_ENC_WAVES, OPT_ENC_QPW_REC, OPT_ENC_QPW_CAP, OPT_FRONT_LDS, OPT_ROUTE_COUNT,
     OPT_COMBINE, OPT_COMBINE_WINDOW_US, OPT_COMBINE_MAX, OPT_COMBINE_WORKERS, OPT_COMBINE_MAX_MB, OPT_NUMA,
     OPT_COUNT
 };

@@ -199,6 +199,37 @@ extern "C" u32 r4x16_enc_direct_budget(int nblk, const R4Opts *o)
     }
     return best;
 }
+// The row kind of a class id of r4x16_launch_enc_chain's table (u16 classes, packed classes, record classes, then the
+// order-0 u16 class, the order-0 record class and the catch-all of images too large for LDS) as the route read-out counts
+// it (include/rans4x16_hip.h R4X16_ENC_*: 0 u16 rows, 1 packed rows, 2 symbol records); -1 beyond the table.
+extern "C" int r4x16_enc_route_kind(u32 ci)
+{
+    if (ci < ENC_NCLS) return 0;
+    ci -= ENC_NCLS;
+    if (ci < ENC_PK_NCLS) return 1;
+    ci -= ENC_PK_NCLS;
+    if (ci < ENC_REC_NCLS) return 2;
+    ci -= ENC_REC_NCLS;
+    return ci == 0 ? 0 : ci == 1 ? 2 : ci == 2 ? 0 : -1;
+}
+// Streams per CU of the record class a stream lands in when the batch's budget admits records (r4x16_enc_direct_budget and
+// the front's choice, r4x16_encode.hip); -1 where its image can never be records.
+extern "C" int r4x16_enc_residency_records(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu)
+{
+    if (nsym == 0 || nsym > 256) return -1;
+    const u32 img = order ? enc_rec_img_bytes(nsym, nsym) : enc_rec_img_bytes(256u, 1u);
+    if (img > ENC_IMG_MAIN) return -1;
+    for (const auto &c : ENC_REC_CLASSES) {
+        if (img + ENC_RING_BYTES > c.bytes) continue;
+        const long granules = ((long)c.qpw * c.bytes + 1279) / 1280;
+        long wgs = 128 / granules;
+        if (wgs > 32) wgs = 32;
+        *streams_per_wave = c.qpw;
+        *waves_per_cu = (int)wgs;
+        return (int)wgs * c.qpw;
+    }
+    return -1;
+}
 extern "C" int r4x16_enc_residency(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu)
 {
     if (nsym == 0 || nsym > 256) return -1;

@@ -23,7 +23,7 @@
 extern "C" {
 void r4x16_launch_dec_front(const BatchArgs *, const DecWs *, int, int, hipStream_t, const R4Opts *);
 void r4x16_launch_dec_chain(const DecWs *, int, hipStream_t, const R4Fork *, const R4Opts *, SchedHint *);
-void r4x16_launch_dec_back(const BatchArgs *, const DecWs *, int, int, hipStream_t, const R4Opts *);
+int  r4x16_launch_dec_back(const BatchArgs *, const DecWs *, int, int, hipStream_t, const R4Opts *);
 void r4x16_launch_enc_front(const BatchArgs *, const EncWs *, int, int, hipStream_t, const R4Opts *);
 void r4x16_launch_enc_tables(const BatchArgs *, const EncWs *, int, int, hipStream_t);
 void r4x16_launch_enc_chain(const EncWs *, int, hipStream_t, const R4Fork *, const R4Opts *, SchedHint *);
@@ -36,8 +36,14 @@ void r4x16_launch_stripe(const u8 *, u8 *, u32, u32, int, hipStream_t);
 }
 
 struct TimedLaunch { hipEvent_t a, b; };
+// route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
+struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
+#define ROUTE_WHICH 4
+#define ROUTE_KINDS 8
 struct HostPipe;
 void r4x16_pipe_destroy(HostPipe *);
+// the lane contexts of a context's host pipeline (nullptr past the last)
+struct rans4x16_hip_ctx *r4x16_pipe_lane(HostPipe *, int i);
 int r4x16_ensure_stage(rans4x16_hip_ctx *c, size_t bytes);
 void r4x16_trim(rans4x16_hip_ctx *c, size_t keep);
 // stream ordering of a context's arenas (workspace, stripe arena) between calls on different streams: r4x16_api.hip
@@ -85,6 +91,9 @@ struct rans4x16_hip_ctx {
     // host-buffer batches: this context's own stream, and the lane contexts large batches are pipelined over
     hipStream_t stream = nullptr;
     struct HostPipe *pipe = nullptr;
+    // route read-out (rans4x16_hip_route_read): counts folded so far, and the launches' copies not yet folded
+    long route[ROUTE_WHICH][ROUTE_KINDS] = {};
+    std::vector<RouteSnap> route_pending;
 };
 
 #define HIPCHK(ctx, call)                                                                   \

@@ -238,6 +238,8 @@ void r4x16_pipe_destroy(HostPipe *hp)
     delete hp;
 }
 
+rans4x16_hip_ctx *r4x16_pipe_lane(HostPipe *hp, int i) { return hp && i >= 0 && i < (int)hp->lanes.size() ? hp->lanes[(size_t)i] : nullptr; }
+
 static int pipe_prepare(rans4x16_hip_ctx *c, int threads, int nlanes, size_t nevents, size_t n, size_t nblocks)
 {
     if (!c->pipe) c->pipe = new HostPipe();
@@ -257,7 +259,6 @@ static int pipe_prepare(rans4x16_hip_ctx *c, int threads, int nlanes, size_t nev
             rans4x16_hip_ctx *l = rans4x16_hip_create(c->device);
             if (!l) { c->err = "host batch: cannot create a lane context"; return -1; }
             l->no_fork = true;          // (side streams of equal priority on two lanes would share a hardware queue)
-            l->opts = c->opts;
             // The runtime keeps one pool of hardware queues per stream priority and multiplexes the streams of
             // a priority onto it; two lane streams of equal priority were seen sharing a queue, which runs their
             // kernels one after the other.  Lanes therefore take different priorities: different queues.
@@ -276,6 +277,12 @@ static int pipe_prepare(rans4x16_hip_ctx *c, int threads, int nlanes, size_t nev
             }
             hp->lanes.push_back(l);
         }
+    }
+    // the lanes work for this context: its options as they are NOW, at every call (the parent's options change between
+    // calls - rans4x16_hip_set_option, the combiner's snapshot of the process-wide options per batch)
+    for (auto *l : hp->lanes) {
+        l->opts = c->opts;
+        l->max_ws = c->max_ws;
     }
     while (hp->events.size() < nevents) {
         hipEvent_t e;

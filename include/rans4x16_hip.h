@@ -198,6 +198,8 @@ int rans4x16_hip_set_dev_stripe_planes(rans4x16_hip_ctx *ctx, int planes, unsign
  *   host_trace            0     R4X16_HOST_TRACE         timeline of a pipelined host batch on stderr
  *   dec_qpw, dec_qpw_small, dec_qpw_pk, dec_qpw_dir, enc_qpw, enc_waves, enc_qpw_rec, enc_qpw_cap, front_lds
  *                                                        tuning aids: streams per wave / workgroup of single classes
+ *   route_count           0     R4X16_ROUTE_COUNT        1: keep the route read-out of rans4x16_hip_route_read (below); 0: nothing is
+ *                                                        copied or recorded for it
  *   process-wide (ctx == NULL, before the first single-block or multi-device call):
  *   combine               1     R4X16_COMBINE            the five drop-in symbols go through the combiner
  *   combine_window_us    -1     R4X16_COMBINE_WINDOW_US  fixed gathering window (-1: adaptive)
@@ -205,6 +207,17 @@ int rans4x16_hip_set_dev_stripe_planes(rans4x16_hip_ctx *ctx, int planes, unsign
  *   combine_workers       1     R4X16_COMBINE_WORKERS    worker threads per direction
  *   combine_max_mb     2048     R4X16_COMBINE_MAX_MB     buffer bytes per combined batch
  *   numa                  1     R4X16_NUMA               multi-device calls bind each device's worker to its NUMA node
+ *
+ * Every option has a range (0 keeps its meaning of "auto" / "never" where it has one; host_threads 1..32, host_lanes
+ * 1..16, the dec_qpw* and enc_qpw_rec knobs 0..16, enc_qpw 0..31, enc_waves 0..4, enc_qpw_cap 1..64, switches 0..1,
+ * sched_learn 0..3, combine_window_us -1..10^6, combine_workers 0..4; the counts and sizes 0 .. a large bound): a value
+ * outside it is refused with -1 and the option keeps its value.  An environment default outside it is ignored.
+ *
+ * Contexts the library makes for itself follow the options of the context they work for: the lane contexts of the
+ * host-batch pipeline take their parent's options (max_workspace_mb included) at every pipelined call, and the contexts
+ * behind the five drop-in symbols (the combiner's, the per-thread ones) take the process-wide options at every batch.
+ * The contexts of a rans4x16_hip_multi are the exception: they are made with the process-wide options of the moment of
+ * rans4x16_hip_multi_create and keep them (there is no call to change them).
  */
 int rans4x16_hip_set_option(rans4x16_hip_ctx *ctx, const char *name, long value);
 int rans4x16_hip_get_option(const rans4x16_hip_ctx *ctx, const char *name, long *value);
@@ -221,10 +234,44 @@ void rans4x16_hip_timing(rans4x16_hip_ctx *ctx, int enable);
 int  rans4x16_hip_timing_read(rans4x16_hip_ctx *ctx, int which /*0 enc chain, 1 dec chain*/,
                               double *ms_total, int *launches, int reset);
 
+/* Which routes a context's calls took (option route_count = 1; off, nothing is recorded).  The count of streams, blocks
+ * or calls of each kind since the last reset, over the context's own *_dev calls and everything its host batches ran -
+ * on the context itself or on its pipeline lanes.  `which` selects the list: */
+enum {
+    R4X16_ROUTE_ENCODE = 0,   /* encode chain: streams per row kind (R4X16_ENC_*)                                    */
+    R4X16_ROUTE_DECODE = 1,   /* decode chain: streams per row kind (R4X16_DEC_*)                                    */
+    R4X16_ROUTE_EXPAND = 2,   /* run-length expansion: blocks of the calls whose expansion kernel was that kind       */
+    R4X16_ROUTE_LAUNCH = 3    /* chain launches (encode and decode): in stream order, or classes side by side        */
+};
+enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
+    R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
+    R4X16_DEC_L2 = 1,         /* u16 rows, two reads (up to 50 symbols; order-0 streams of such alphabets included)    */
+    R4X16_DEC_L3 = 2,         /* u16 rows, three reads                                                                */
+    R4X16_DEC_L4 = 3,         /* u16 rows, four reads                                                                 */
+    R4X16_DEC_L5 = 4,         /* wide packed rows, 49..96 symbols                                                     */
+    R4X16_DEC_DIRECT = 5,     /* level 6: the short-step rows (order-0 streams of them included)                      */
+    R4X16_DEC_MID = 6,        /* level 10: mid rows                                                                   */
+    R4X16_DEC_SHORT_RING = 7, /* packed rows with the short word ring                                                 */
+    R4X16_DEC_KINDS = 8
+};
+enum { R4X16_ENC_U16 = 0, R4X16_ENC_PACKED = 1, R4X16_ENC_RECORDS = 2, R4X16_ENC_KINDS = 3 };    /* R4X16_ROUTE_ENCODE */
+enum { R4X16_EXPAND_WAVE = 0, R4X16_EXPAND_WORKGROUP = 1, R4X16_EXPAND_KINDS = 2 };               /* R4X16_ROUTE_EXPAND */
+enum { R4X16_LAUNCH_IN_ORDER = 0, R4X16_LAUNCH_SIDE_BY_SIDE = 1, R4X16_LAUNCH_KINDS = 2 };        /* R4X16_ROUTE_LAUNCH */
+/* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
+ * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
+int rans4x16_hip_route_read(rans4x16_hip_ctx *ctx, int which, long *counts, int n, int reset);
+
 /* How many streams of one kind the chain kernel of this build keeps resident per compute unit (the unit of
  * parallelism is the stream): `nsym` symbols in the alphabet, order 0 / 1, table precision `shift`
  * (10 or 12; ignored for order 0).  Host arithmetic on the kernels' LDS size classes; bench.py reports it next
- * to the measured step latency, and sizes its batch in whole rounds of it. */
+ * to the measured step latency, and sizes its batch in whole rounds of it.
+ * `decode` may carry one of the flags below: the residency of the kind a stream takes in a batch that leaves LDS to
+ * spare instead of the full chip's - R4X16_RES_SHORT: the short-step kind (decode: direct rows, encode: symbol records),
+ * R4X16_RES_MID: the decoder's mid rows.  A batch of n blocks gives such a stream its kind while
+ * ceil(n / (compute_units x dec_direct (enc_direct, dec_mid))) <= streams_per_cu.  Returns -1 if the stream can never
+ * take that kind (alphabet, table precision or image size). */
+#define R4X16_RES_SHORT 2
+#define R4X16_RES_MID   4
 int rans4x16_hip_residency(rans4x16_hip_ctx *ctx, int decode, unsigned int nsym, int order, unsigned int shift,
                            int *streams_per_cu, int *lanes_live_per_wave, int *compute_units);
 

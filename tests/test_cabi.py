@@ -151,6 +151,34 @@ def test_options_by_name_without_a_gpu():
     assert L.rans4x16_hip_set_option(None, b"no_such_option", 1) == -1
     assert L.rans4x16_hip_get_option(None, b"no_such_option", C.byref(v)) == -1
     assert L.rans4x16_hip_set_option(None, None, 1) == -1
+    # every option has a range (header part 2b): values outside it are refused and leave the option as it was, the
+    # bounds themselves are accepted; 0 keeps its meaning where it means "auto" / "never"
+    big = 1 << 16
+    ranges = {
+        "dec_direct": (0, big), "enc_direct": (0, big), "back_wg_per_cu": (0, 1 << 20), "dec_mid": (0, big),
+        "dec_short_ring": (0, 1), "sched_sort": (0, 1), "sched_claim": (0, 1), "sched_concurrent": (0, 1),
+        "sched_trace": (0, 1), "sched_learn": (0, 3), "max_workspace_mb": (0, 1 << 30), "host_stripe_dev": (0, 1),
+        "host_pipe_mb": (0, 1 << 30), "host_threads": (1, 32), "host_lanes": (1, 16), "host_slab_min_mb": (0, 1 << 20),
+        "host_dec_slabs": (0, 64), "host_enc_slabs": (0, 64), "host_pack": (0, 1), "host_trace": (0, 1),
+        "dec_qpw": (0, 16), "dec_qpw_small": (0, 16), "dec_qpw_pk": (0, 16), "dec_qpw_dir": (0, 16),
+        "enc_qpw": (0, 31), "enc_waves": (0, 4), "enc_qpw_rec": (0, 16), "enc_qpw_cap": (1, 64), "front_lds": (0, 65536),
+        "route_count": (0, 1), "combine": (0, 1), "combine_window_us": (-1, 10 ** 6), "combine_max": (0, 1 << 20),
+        "combine_workers": (0, 4), "combine_max_mb": (0, 1 << 20), "numa": (0, 1),
+    }
+    assert sorted(ranges) == sorted(names)
+    for n, (lo, hi) in ranges.items():
+        assert L.rans4x16_hip_get_option(None, n.encode(), C.byref(v)) == 0
+        before = v.value
+        assert lo <= before <= hi, (n, before)
+        for bad in (lo - 1, hi + 1, -(1 << 40), 1 << 40):
+            assert L.rans4x16_hip_set_option(None, n.encode(), bad) == -1, (n, bad)
+            assert L.rans4x16_hip_get_option(None, n.encode(), C.byref(v)) == 0 and v.value == before, (n, bad, v.value)
+        for good in (lo, hi, before):
+            assert L.rans4x16_hip_set_option(None, n.encode(), good) == 0, (n, good)
+            assert L.rans4x16_hip_get_option(None, n.encode(), C.byref(v)) == 0 and v.value == good, (n, good)
+    # the route read-out needs a context: NULL is refused, as are lists that do not exist
+    counts = (C.c_long * 8)()
+    assert L.rans4x16_hip_route_read(None, 1, counts, 8, 0) == -1
     # the library reads the environment in exactly one place
     n_getenv = 0
     for fn in os.listdir(os.path.join(ROOT, "htscodecs_amd", "csrc")):

@@ -26,11 +26,32 @@ def H(request):
     import htscodecs_amd
     htscodecs_amd.load()
     from conftest import _Options
+    from htscodecs_amd import codec
     o = _Options()
     for k in ("dec_direct", "enc_direct"):
         o.set(k, 1 if request.param == "short-step" else 0)
+    codec.set_option("route_count", 1)                     # the thread context's read-out: checked at the end of the pass
+    for w in ("encode", "decode"):
+        codec.route_read(w)
     yield htscodecs_amd
     o.restore()
+    try:
+        _route_pass_check(request.param, codec)
+    finally:
+        codec.set_option("route_count", 0)
+
+
+def _route_pass_check(param, codec):
+    """What the thread context's host batches of the module ran on (option route_count): the "compressed-rows" pass must
+    not have touched the short-step kinds, and must have run the compressed rows; the "short-step" pass must have run the
+    short-step rows."""
+    dec, enc = codec.route_read("decode"), codec.route_read("encode")
+    compressed_dec = dec["l1"] + dec["l2"] + dec["l3"] + dec["l4"] + dec["l5"]
+    if param == "compressed-rows":
+        assert dec["direct"] == 0 and enc["records"] == 0, (dec, enc)
+        assert compressed_dec > 0 and enc["u16"] + enc["packed"] > 0, (dec, enc)
+    else:
+        assert dec["direct"] > 0, dec
 
 
 ALL_ORDERS = [0, 1, 64, 65, 128, 129, 192, 193, 8, 9, 0x48, 0xc9, (2 << 8) | 9, 16 | 1, 32]

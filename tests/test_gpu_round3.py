@@ -21,12 +21,15 @@ def H():
     return htscodecs_amd
 
 
-def _dev_roundtrip(H, name, nblk, bs, order):
-    """nblk blocks through rans4x16_hip_{compress,uncompress}_dev; returns what the checks below need."""
+def _dev_roundtrip(H, name, nblk, bs, order, routes=None):
+    """nblk blocks through rans4x16_hip_{compress,uncompress}_dev; returns what the checks below need.  routes: a dict
+    that receives the calls' route read-out."""
     import torch
     sys.path.insert(0, ROOT)
     import bench
     dc = H.DeviceCodec(0)
+    if routes is not None:
+        dc.set_option("route_count", 1)
     dev = dc.dev
     d_in, in_off, in_size = bench.build_batch(torch, dev, name, nblk, bs, 0)
     cap = H.rans_compress_bound_4x16(bs, order)
@@ -45,6 +48,8 @@ def _dev_roundtrip(H, name, nblk, bs, order):
     assert int((st_enc != 0).sum()) == 0 and int((st_dec != 0).sum()) == 0
     assert torch.equal(back_size, in_size)
     assert torch.equal(d_back, d_in)
+    if routes is not None:
+        routes.update(encode=dc.route_read("encode"), decode=dc.route_read("decode"))
     return bench, d_in, d_comp, comp_size.cpu().numpy(), slot
 
 
@@ -78,7 +83,10 @@ def test_direct_rows_walk_several_rounds(H, oracle, opts):
     opts.set("dec_direct", 8)
     opts.set("enc_direct", 8)
     nblk, bs, order = 2100, 65536, 1
-    bench, d_in, d_comp, csz, slot = _dev_roundtrip(H, "q40+dir", nblk, bs, order)
+    routes = {}
+    bench, d_in, d_comp, csz, slot = _dev_roundtrip(H, "q40+dir", nblk, bs, order, routes)
+    assert routes["decode"]["direct"] == nblk, routes                 # every stream on the direct rows, over several rounds
+    assert routes["encode"]["records"] >= nblk, routes
     rs = np.random.RandomState(8)
     for b in sorted(set([0, 1023, 1024, 2047, 2048, nblk - 1] + [int(x) for x in rs.randint(0, nblk, size=40)])):
         raw = bench.block_bytes("q40+dir", bs, b, 0)
@@ -95,6 +103,7 @@ def test_small_batches_of_every_shape_both_row_kinds(H, oracle, opts, knob):
     opts.set("dec_direct", knob)
     opts.set("enc_direct", knob)
     dc = H.DeviceCodec(0)
+    dc.set_option("route_count", 1)
     dev = dc.dev
     for nblk, sizes in ((1, [1 << 20]), (3, [1 << 20, 777777, 5]), (64, [65536, 40001, 3, 131072])):
         for name, order in (("q40+dir", 1), ("q40+dir", 0), ("q8", 1), ("q4", 193), ("q8", 65), ("q4", 1)):
@@ -129,6 +138,13 @@ def test_small_batches_of_every_shape_both_row_kinds(H, oracle, opts, knob):
             dec = d_dec.cpu().numpy()
             for b, off in zip(blocks, in_off):
                 assert (dec[off:off + len(b)] == b).all(), (name, order, nblk)
+    # the row kinds this parameter names: the short-step kinds with knob 1, never with knob 0
+    denc, ddec = dc.route_read("encode"), dc.route_read("decode")
+    if knob:
+        assert ddec["direct"] > 0 and denc["records"] > 0, (denc, ddec)
+    else:
+        assert ddec["direct"] == 0 and denc["records"] == 0, (denc, ddec)
+        assert sum(ddec.values()) > 0 and denc["u16"] + denc["packed"] > 0, (denc, ddec)
 
 
 def test_direct_rows_alphabet_shapes(H, oracle, opts):
@@ -161,9 +177,12 @@ def test_direct_rows_alphabet_shapes(H, oracle, opts):
     add(datagen.weighted(1 << 18, [100000, 50000] + [1] * 100, 3), both=False)
     add(datagen.tile("q40+dir", 100001, 3))
     add(datagen.tile("q8", 99999, 4))
+    from htscodecs_amd import codec
+    opts.set("route_count", 1)
     for knob in (1, 0):
         opts.set("dec_direct", knob)
         opts.set("enc_direct", knob)
+        codec.route_read("decode")
         enc, st = H.compress_batch(datas, orders)
         assert all(s == 0 for s in st), st
         want = [oracle.compress(d, o) for d, o in zip(datas, orders)]
@@ -173,6 +192,12 @@ def test_direct_rows_alphabet_shapes(H, oracle, opts):
         assert all(s == 0 for s in st), (knob, st)
         bad = [(i, orders[i]) for i in range(len(datas)) if dec[i] != datas[i]]
         assert not bad, (knob, bad)
+        # knob 1: the direct rows, except for the 129-symbol alphabet (beyond their 7-bit index: u16 rows); knob 0: never
+        ddec = codec.route_read("decode")
+        if knob:
+            assert ddec["direct"] > 0 and ddec["l3"] >= 2, ddec
+        else:
+            assert ddec["direct"] == 0, ddec
     def shift_of(c):                                                        # flags, varint size, then shift << 4 | compressed
         i = 1
         while c[i] & 0x80:
@@ -249,7 +274,10 @@ def test_run_length_shapes(H, oracle, opts, route):
       * runs around 2^22 bytes (where a trip leaves its 32-bit sums for the plain route) and one of more than 2^24 in
         a 20 MiB block;
       * X_PACK in front (order 192 / 193) and quality-like data."""
+    from htscodecs_amd import codec
     opts.set("back_wg_per_cu", route)
+    opts.set("route_count", 1)
+    codec.route_read("expand")
     rs = np.random.RandomState(4242)
     datas, orders = [], []
     def add(a, os_=(64, 65)):
@@ -280,6 +308,9 @@ def test_run_length_shapes(H, oracle, opts, route):
     assert all(s == 0 for s in st), st
     bad = [(i, orders[i], len(datas[i])) for i in range(len(datas)) if dec[i] != datas[i]]
     assert not bad, bad
+    # every block went through the expansion kernel this parameter names (the batch is pipelined: on the lanes)
+    exp = codec.route_read("expand")
+    assert exp == ({"wave": len(datas), "workgroup": 0} if route == 0 else {"wave": 0, "workgroup": len(datas)}), exp
 
 
 def test_pack_widths(H, oracle):

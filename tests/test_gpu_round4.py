@@ -226,6 +226,7 @@ def test_mid_rows_alphabet_shapes_and_overflow_buckets(H, oracle):
     dc = H.DeviceCodec(0)
     dc.set_option("dec_direct", 0)
     dc.set_option("dec_mid", 8)
+    dc.set_option("route_count", 1)
     B = _Arena(H, dc, want, [len(b) for b in blocks])
     for rep in range(2):
         B.d_out.zero_(); B.out_size.zero_(); B.status.fill_(-1)
@@ -233,9 +234,13 @@ def test_mid_rows_alphabet_shapes_and_overflow_buckets(H, oracle):
         st, dec = B.results()
         bad = [(i, len(blocks[i]), int(st[i])) for i in range(len(blocks)) if st[i] != 0 or dec[i] != blocks[i].tobytes()]
         assert not bad, (rep, bad[:10])
+        # the mid rows took the 13 .. 64-symbol alphabets and the quality blocks; 12 and 65 .. 80 symbols kept their kinds
+        r = dc.route_read("decode")
+        assert r["direct"] == 0 and r["mid"] >= 2300 - 14 * 4 and r["mid"] < len(blocks), r
     # and as the budget rule picks them: 3,000 blocks (more than the direct rows hold, one round of the mid class)
     dc2 = H.DeviceCodec(0)
     dc2.set_option("dec_mid", 1)
+    dc2.set_option("route_count", 1)
     more = [np.ascontiguousarray(datagen.tile("q40+dir", 65536, i)) for i in range(3000)]
     wm = [oracle.compress(b.tobytes(), 1) for b in more[:40]]
     src = wm * 75
@@ -244,3 +249,4 @@ def test_mid_rows_alphabet_shapes_and_overflow_buckets(H, oracle):
     st, dec = B.results()
     assert not st.any()
     assert all(dec[i] == more[i % 40].tobytes() for i in range(3000))
+    assert dc2.route_read("decode")["mid"] == 3000
