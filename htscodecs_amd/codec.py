@@ -147,7 +147,7 @@ class _Ctx:
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3}
 ROUTE_KINDS = {
-    "encode": ("u16", "packed", "records"),
+    "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
     "expand": ("wave", "workgroup"),
     "launch": ("in_order", "side_by_side"),

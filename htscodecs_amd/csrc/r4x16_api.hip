@@ -133,15 +133,24 @@ extern "C" rans4x16_hip_ctx *rans4x16_hip_create(int device)
         return nullptr;
     }
     // reciprocal of every frequency 1..4096 (rANS_word.h:220-259); index 0 is never used
-    std::vector<u32> rcp(RCPTAB_ENTRIES, 0u);
+    std::vector<u32> rcp(RCPTAB_DWORDS, 0u);
     rcp[1] = ~0u;
     for (u32 f = 2; f < RCPTAB_ENTRIES; f++) {
         u32 shift = 0;
         while (f > (1u << shift)) shift++;
         rcp[f] = (u32)(((1ull << (shift + 31)) + f - 1) / f);
     }
-    if (hipMalloc((void **)&c->rcptab, RCPTAB_ENTRIES * 4) != hipSuccess ||
-        hipMemcpy(c->rcptab, rcp.data(), RCPTAB_ENTRIES * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    // the frequency table of the packed rows' short-index kind (r4x16_enc_chain.h, EncOutT::step_freq): per frequency
+    // f = 1..1024 of a 10-bit table {m, (1024 - f) | s << 24} with s = ceil(log2 f) and m = ceil(2^(32 + s) / f) - 2^32,
+    // the round-up reciprocal's low 32 bits: (mulhi(x, m) + x) >> s is x / f for every 32-bit x and every f, f = 1 included
+    for (u32 f = 1; f < ENC_FREQTAB_ENTRIES; f++) {
+        u32 s = 0;
+        while (f > (1u << s)) s++;
+        rcp[ENC_FREQTAB_OFF + 2 * f] = (u32)(((1ull << (32 + s)) + f - 1) / f - (1ull << 32));
+        rcp[ENC_FREQTAB_OFF + 2 * f + 1] = (1024u - f) | (s << 24);
+    }
+    if (hipMalloc((void **)&c->rcptab, RCPTAB_DWORDS * 4) != hipSuccess ||
+        hipMemcpy(c->rcptab, rcp.data(), RCPTAB_DWORDS * 4, hipMemcpyHostToDevice) != hipSuccess) {
         rans4x16_hip_destroy(c);
         return nullptr;
     }
@@ -220,7 +229,7 @@ extern "C" int rans4x16_hip_timing_read(rans4x16_hip_ctx *c, int which, double *
 // behind it on its stream into pinned memory; the host folds them into per-kind sums when they are read (or when many
 // are waiting).  Off, none of this happens: no copy, no event, no synchronisation.
 extern "C" int r4x16_dec_route_kind(u32 ci);
-extern "C" int r4x16_enc_route_kind(u32 ci);
+extern "C" int r4x16_enc_route_kind(u32 ci, int *freq_table);
 static int route_fold(rans4x16_hip_ctx *c)
 {
     int rc = 0;
@@ -228,8 +237,10 @@ static int route_fold(rans4x16_hip_ctx *c)
         if (hipEventSynchronize(r.ev) != hipSuccess) rc = -1;
         else
             for (u32 ci = 0; ci < CLS_MAX; ci++) {
-                const int k = r.which == 0 ? r4x16_enc_route_kind(ci) : r4x16_dec_route_kind(ci);
+                int freq_table = 0;
+                const int k = r.which == 0 ? r4x16_enc_route_kind(ci, &freq_table) : r4x16_dec_route_kind(ci);
                 if (k >= 0 && r.cnt[ci]) c->route[r.which][k] += (long)r.cnt[ci];
+                if (freq_table && r.cnt[ci]) c->route[0][R4X16_ENC_PACKED_FREQ] += (long)r.cnt[ci];
             }
         (void)hipEventDestroy(r.ev);
         (void)hipHostFree(r.cnt);

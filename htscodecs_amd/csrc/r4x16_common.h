@@ -278,6 +278,11 @@ struct DecDesc {
 #define ENC_IMG_META_BYTES 4352u                                  // one cumulative row, or 256 symbol records (enc_rec_img_bytes(256, 1))
 #define ENC_IMG_BYTES  (ENC_IMG_META + ENC_IMG_META_BYTES)        // 137,472 per block
 #define RCPTAB_ENTRIES 4097u
+// Behind the reciprocals, in the same device buffer: the frequency table of the packed rows' short-index kind (below),
+// one 8-byte entry per frequency 0..1024 of a 10-bit table - everything a coding step derives from the frequency alone.
+#define ENC_FREQTAB_ENTRIES 1025u
+#define ENC_FREQTAB_OFF     4100u                                     // first dword of entry 0 (8-byte aligned)
+#define RCPTAB_DWORDS       (ENC_FREQTAB_OFF + 2u * ENC_FREQTAB_ENTRIES)
 
 struct EncItem {
     u64 data;        // device address of the bytes to code
@@ -291,7 +296,8 @@ struct EncItem {
     u32 blk;
     u32 ns;          // symbols per image row (a row is ns+1 u16)
     u32 img_bytes;   // bytes of the image (what must sit in LDS)
-    u32 packed;      // 0: u16 rows, 1: rows are 11-bit bit streams (below), 2: 16-byte symbol records (further below)
+    u32 packed;      // 0: u16 rows, 1: rows are 11-bit bit streams (below), 2: 16-byte symbol records (further below),
+                     // ENC_KIND_PK_SHORT: packed rows behind a 128-byte index (below)
     u32 affine;      // symbol records: c + 1 when compact index = byte - c for every byte of the data (no idx_of[] look-up), else 0
 };
 // Packed encoder rows: order-1 streams with 10-bit tables and 20..64 symbols (the quality alphabets).  Row r is a
@@ -299,10 +305,17 @@ struct EncItem {
 // / 32) dwords per row.  A symbol's (start, next) pair is 22 bits out of two adjacent dwords (one ds_read2 at a
 // 4-byte aligned address and a funnel shift).  46 symbols: 68-byte rows instead of 94, 3.5 KB per stream instead
 // of 4.7: 45 streams per CU - the decoder's count, so that a batch is a whole number of rounds for both.
+// Short index (kind ENC_KIND_PK_SHORT): a block whose highest byte is below 128 - every quality alphabet - never looks
+// up idx_of[128..255], so its image starts with idx_of[0..127] and the rows follow at byte 128.  The 128 bytes a stream
+// saves pay, 45 streams to a CU, for a frequency table of 8-byte entries in place of the bare reciprocals (r4x16_enc_chain.h):
+// the classes of this kind are the packed classes less ENC_IMG_IDX - ENC_IMG_IDX_SHORT, and 8,208 + 45 x 3,408 bytes fit
+// where 4,112 + 45 x 3,536 did.
 #define ENC_PK_MIN_NS 20u
 #define ENC_PK_MAX_NS 64u
+#define ENC_IMG_IDX_SHORT 128u
+#define ENC_KIND_PK_SHORT 5u                               // (3 and 4 are the classifier's kinds of order-0 streams)
 static inline __host__ __device__ u32 enc_pk_row_dwords(u32 ns) { return (11u * (ns + 1u) + 31u) / 32u; }
-static inline __host__ __device__ u32 enc_pk_img_bytes(u32 ns) { return ENC_IMG_IDX + 4u * ns * enc_pk_row_dwords(ns) + 4u; }
+static inline __host__ __device__ u32 enc_pk_img_bytes(u32 ns, u32 idx_bytes = ENC_IMG_IDX) { return idx_bytes + 4u * ns * enc_pk_row_dwords(ns) + 4u; }
 
 // Symbol records ("kind 2"): the encoder's short-step route for batches that leave LDS to spare - the twin of the
 // decoder's direct rows.  The u16 / packed rows above make the coder derive start, freq, x_max, the reciprocal (one more
@@ -435,7 +448,7 @@ struct EncWs {
     u8 *tab;            // [nblk][TAB_BYTES]  table bytes as they go into the stream
     u8 *scratch;        // [nblk][scratch_stride]  backward-written states + words
     const double *logtab;   // [2][257]  log(1024+k), log(4096+k) from the host libm (:651-652)
-    const u32 *rcptab;      // [4097]    reciprocal by frequency (rANS_word.h:252), shared by all streams
+    const u32 *rcptab;      // [RCPTAB_DWORDS]  reciprocal by frequency (rANS_word.h:252), shared by all streams; then the frequency table
     u64 scratch_stride;
     // X_PACK / X_RLE staging: a region per block that asks for a transform, sized from the block's own length and laid
     // out on the device (enc_var_bytes, k_enc_voff): block b owns var[voff[b] .. voff[b + 1]) - bit-packed bytes, RLE

@@ -94,6 +94,9 @@ __device__ __forceinline__ u32 chain_encode(gcu8 *data, u32 n, gcu8 *image, u32 
 // 16-byte store (a completed half of the ring, or a dump slot nobody reads).
 // (ENC_RING_BYTES, r4x16_common.h: the ring + a 2-byte dump slot for lanes that do not emit, padded)
 #define ENC_LRCP_BYTES 16400u        // RCPTAB_ENTRIES dwords, padded to 16
+// the frequency table of the packed rows' short-index kind (k_enc_chain<true, true, true>)
+#define ENC_LFREQ_BYTES   8208u      // ENC_FREQTAB_ENTRIES 8-byte entries, padded to 16
+static_assert(ENC_LFREQ_BYTES >= 8u * ENC_FREQTAB_ENTRIES && ENC_LFREQ_BYTES % 16u == 0, "frequency table in LDS");
 // BYTE: rANS 4x8's renormalisation (rANS_byte.h:320-402: L = 2^23, up to TWO bytes per chain and step, 12-bit
 // frequencies) on the same pipeline, ring and flush - round 4; the unit of `written` / the ring is then the byte.
 template <bool BYTE>
@@ -109,6 +112,21 @@ struct EncOutT {
     u32x4 held;          // a half read out of the ring, stored one double-trip later
     gu8 *held_dst;
     static constexpr u32 HALF_SHIFT = BYTE ? 6u : 5u;    // units per 64-byte half, as a shift
+    // the 16-bit renormalisation of one step (rANS_word.h:300-306): the state's low word into the ring where x is over
+    // x_max; returns the state the step carries on with
+    __device__ __forceinline__ u32 emit16(u32 x, bool live, bool over)
+    {
+        // the compare's own lane mask, and-ed with the live lanes on the scalar side (a ballot of the
+        // combined predicate would be rebuilt through a select and a second compare)
+        const u64 m = __ballot(over) & __ballot(live);
+        const u32 em = (u32)(m >> (lane & ~3u)) & 0xfu;
+        const bool emit = live && over;
+        const u32 j = written + __popc(em >> (k + 1));
+        const u32 j63 = emit ? (j & 63u) : ~0u;                          // -1: the dump slot at ring + 128
+        *(LAS u16 *)(unsigned long)(ring126 - 2u * j63) = (u16)x;
+        written += __popc(em);
+        return emit ? x >> 16 : x;
+    }
     // rANS_word.h:281-321 for one symbol; x is this lane's state.  pk = start | freq << 16.
     // q = x / freq < 2^21 once x < x_max, so q * (M - freq) is a 24-bit multiply (mod 2^32).
     __device__ __forceinline__ void step(u32 &x, bool live, u32 rcp, u32 pk, u32 bits)
@@ -128,19 +146,7 @@ struct EncOutT {
             *(LAS u8 *)(unsigned long)(ring126 - j2) = (u8)(x >> 8);
             xs = emit2 ? x >> 16 : emit1 ? x >> 8 : x;
             written += __popc(e1) + __popc(e2);
-        } else {
-            // the compare's own lane mask, and-ed with the live lanes on the scalar side (a ballot of the
-            // combined predicate would be rebuilt through a select and a second compare)
-            const bool over = x >= (f << (31u - bits));
-            const u64 m = __ballot(over) & __ballot(live);
-            const u32 em = (u32)(m >> (lane & ~3u)) & 0xfu;
-            const bool emit = live && over;
-            const u32 j = written + __popc(em >> (k + 1));
-            const u32 j63 = emit ? (j & 63u) : ~0u;                          // -1: the dump slot at ring + 128
-            *(LAS u16 *)(unsigned long)(ring126 - 2u * j63) = (u16)x;
-            xs = emit ? x >> 16 : x;
-            written += __popc(em);
-        }
+        } else xs = emit16(x, live, x >= (f << (31u - bits)));
         // exact x / f: Alverson reciprocal for f >= 2; f == 1 has rcp = 2^32 - 1 and shift 0, which
         // gives x - 1: the compare's carry puts the 1 back (an add-with-carry, no select)
         const u32 fm1 = f - 1u;
@@ -148,6 +154,23 @@ struct EncOutT {
         const u32 q = (__umulhi(xs, rcp) >> rsh) + (fm1 == 0u ? 1u : 0u);
         const u32 cmpl = (1u << bits) - f;
         const u32 xn = __umul24(q, cmpl) + (xs + start);
+        x = live ? xn : xs;
+    }
+    // The step of the short-index packed rows (10-bit tables): {m, w} is the frequency table's entry of f (r4x16_api.hip),
+    // w = (1024 - f) | s << 24, and nothing is derived from f here but x_max.  The same x as step(), bit for bit:
+    // both compute xs + start + (xs / f) * (1024 - f) with the exact quotient of a state xs < 2^31.
+    //   q: m is the low word of the round-up reciprocal ceil(2^(32 + s) / f), s = ceil(log2 f), which lies in
+    //      [2^32, 2^33): (mulhi(xs, m) + xs) >> s = floor(xs * (2^32 + m) / 2^(32 + s)) = xs / f for every 32-bit xs; the
+    //      sum stays below 2^32 because mulhi(xs, m) < xs < 2^31.  step() has the reciprocal of shift s - 1, exact below 2^31.
+    //      f = 1: s = 0, m = 0, q = xs - what step() reaches with reciprocal 2^32 - 1, xs - 1 and the compare's carry.
+    //      f = 2 (any power of two): m = 0, q = xs >> s.      f = 3 (no power of two): m = ceil(2^(32 + s) / f) - 2^32 > 0.
+    //   q * (1024 - f): q < 2^21 and 1024 - f < 2^10, a 24-bit multiply that does not look at the shift in w's top byte
+    //      (the symbol records' trick, r4x16_common.h).  f = 1024: w's low bits are 0, the product is 0 and x = xs + start.
+    __device__ __forceinline__ void step_freq(u32 &x, bool live, u32 m, u32 w, u32 start, u32 f)
+    {
+        const u32 xs = emit16(x, live, x >= (f << 21));
+        const u32 q = (__umulhi(xs, m) + xs) >> ((w >> 24) & 31u);
+        const u32 xn = __umul24(q, w) + (xs + start);
         x = live ? xn : xs;
     }
     // conditional form: copy out the half that has just been completed, if any
@@ -200,13 +223,16 @@ struct EncOutT {
 typedef EncOutT<false> EncOut;
 
 // PK: packed rows (r4x16_common.h) and a reciprocal table of the 1,025 frequencies a 10-bit table can hold.
-template <bool PK, bool BYTE = false>
+// FT: the packed rows' short-index kind: idx_of[0..127] only, and `lrcp` is the frequency table (8-byte entries, read whole
+// where the reciprocal alone was read; EncOutT::step_freq).
+template <bool PK, bool BYTE = false, bool FT = false>
 __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, const u32 *lrcp, gcu8 *data, u32 n, u32 ns,
                                                    u32 bits, gcu8 *safe, gu8 *scratch_end, gu8 *dump, bool active, u32 lane)
 {
     const u32 k = lane & 3;
+    static_assert(!FT || (PK && !BYTE), "the frequency table serves the packed rows");
     const u8 *idx = img_lds;
-    const u8 *cumb = img_lds + ENC_IMG_IDX;
+    const u8 *cumb = img_lds + (FT ? ENC_IMG_IDX_SHORT : ENC_IMG_IDX);
     const u32 rs = PK ? 4u * enc_pk_row_dwords(ns) : ns + 1;       // bytes (packed) / u16 entries per context row
     const u32 cumb_lds = (u32)(unsigned long)(LAS const u8 *)cumb;
     // the (start, next) pair of symbol si in context ci.  u16 rows: start | next << 16, one dword read at a 2-byte
@@ -221,17 +247,38 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
         return *(LAS const u32 *)(cumb + 2u * (__umul24(ci, rs) + si));
     };
     const u32 rcp_last = PK ? 1024u : RCPTAB_ENTRIES - 1u;
-    auto rcpof = [&](u32 pk) -> u32 { const u32 f = pk >> 16; return lrcp[f < rcp_last ? f : rcp_last]; };   // (clamp: idle lanes hold garbage)
-    // pair -> start | freq << 16.  u16 rows: a shift and a subtract (the empty asm keeps it from becoming a
-    // quarter-rate multiply by 0xFFFF0001); packed rows: two field extractions, a subtract, a shift-or
-    auto topk = [&](u32 p) -> u32 {
-        if (PK) { const u32 st = p & 2047u; return st | ((__builtin_amdgcn_ubfe(p, 11, 11) - st) << 16); }
-        u32 hi = p << 16; asm("" : "+v"(hi)); return p - hi;
-    };
-    auto fetch = [&](u32 ci, u32 si) -> u32x2 {           // {rcp, start | freq << 16}
-        const u32 pk = topk(pair(ci, si));
-        u32x2 r = {rcpof(pk), pk};
+    // A symbol on its way to its step: pk = start | freq << 16; FT: pk = start and f = freq, apart as they come out of the row
+    // (every instruction of the loop is issue time, on the dependent path or off it: no packing that a step undoes again)
+    struct PF { u32 pk, f; };
+    // {reciprocal, 0}, or the frequency table's entry  (clamp: idle lanes hold garbage)
+    auto rcpof = [&](PF s) -> u32x2 {
+        if (FT) return ((const u32x2 *)lrcp)[s.f < rcp_last ? s.f : rcp_last];
+        const u32 f = s.pk >> 16;
+        u32x2 r = {lrcp[f < rcp_last ? f : rcp_last], 0u};
         return r;
+    };
+    // pair -> start | freq << 16.  u16 rows: a shift and a subtract (the empty asm keeps it from becoming a
+    // quarter-rate multiply by 0xFFFF0001); packed rows: two field extractions, a subtract, a shift-or (FT: none)
+    auto topk = [&](u32 p) -> PF {
+        if (PK) {
+            const u32 st = p & 2047u, f = __builtin_amdgcn_ubfe(p, 11, 11) - st;
+            PF r = {FT ? st : st | (f << 16), f};
+            return r;
+        }
+        u32 hi = p << 16; asm("" : "+v"(hi));
+        PF r = {p - hi, 0u};
+        return r;
+    };
+    struct Sym { u32 rcp, w; PF s; };                     // {reciprocal, second word of the frequency table, the symbol}
+    auto fetch = [&](u32 ci, u32 si) -> Sym {
+        const PF s = topk(pair(ci, si));
+        const u32x2 e = rcpof(s);
+        Sym r = {e.x, e.y, s};
+        return r;
+    };
+    auto step = [&](EncOutT<BYTE> &o, u32 &x, bool live, u32 rcp, u32 w, u32 pk, u32 f) {
+        if (FT) o.step_freq(x, live, rcp, w, pk, f);
+        else o.step(x, live, rcp, pk, bits);
     };
     EncOutT<BYTE> o{ring, (u32)(unsigned long)(LAS u8 *)ring + (BYTE ? 127u : 126u), scratch_end, dump, 0u, 0u, k, lane, active, {0, 0, 0, 0}, dump};
     u32 x = BYTE ? (1u << 23) : RANS_LOW;
@@ -243,14 +290,13 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
     if (active && k == 3 && tail) cur = idx[data[n - 1]];
     for (u32 s = 0; wave_any(s < tail); s++) {
         const bool live = k == 3 && s < tail;
-        u32 rcp = 0, pk = 0;
+        Sym e = {0, 0, {0, 0}};
         if (live) {
             const u32 ci = idx[data[n - 2 - s]];
-            const u32x2 e = fetch(ci, cur);
-            rcp = e.x; pk = e.y;
+            e = fetch(ci, cur);
             cur = ci;
         }
-        o.step(x, live, rcp, pk, bits);
+        step(o, x, live, e.rcp, e.w, e.s.pk, e.s.f);
     }
 
     // (B) backward walk over offsets q-1 .. 1 of each quarter (:813-829); chain k codes byte
@@ -279,17 +325,22 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             u32x4 r = {pair(c.c0, sym), pair(c.c1, c.c0), pair(c.c2, c.c1), pair(c.c3, c.c2)};
             return r;
         };
-        auto topk4 = [&](u32x4 p) -> u32x4 {
-            u32x4 r = {topk(p.x), topk(p.y), topk(p.z), topk(p.w)};
+        struct P4 { PF x, y, z, w; };
+        auto topk4 = [&](u32x4 p) -> P4 {
+            P4 r = {topk(p.x), topk(p.y), topk(p.z), topk(p.w)};
             return r;
         };
-        auto rcp4 = [&](u32x4 p) -> u32x4 {
-            u32x4 r = {rcpof(p.x), rcpof(p.y), rcpof(p.z), rcpof(p.w)};
+        struct R4 { u32x4 rcp, w; };
+        auto rcp4 = [&](const P4 &p) -> R4 {
+            const u32x2 a = rcpof(p.x), b = rcpof(p.y), c = rcpof(p.z), d = rcpof(p.w);
+            R4 r = {{a.x, b.x, c.x, d.x}, {a.y, b.y, c.y, d.y}};
             return r;
         };
         u32 cur1, cur2;
         I4 I2;
-        u32x4 P0, Praw, R0;
+        P4 P0;
+        u32x4 Praw;
+        R4 R0;
         // input pieces live in a ring of four register pairs, piece j in Q[j % 4]; the loop is unrolled
         // four double-trips so that no piece is ever copied (a copy would have to wait for the load)
         u32x2 Q0, Q1, Q2, Q3;
@@ -307,15 +358,15 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             const bool live = t < ntrip;
             const I4 In = idx4(wnext3);              // bytes of trip t+3
             const u32x4 Pn = cum4(I2, cur2);         // pairs of trip t+2
-            const u32x4 P1 = topk4(Praw);            // trip t+1, read during the previous trip
-            const u32x4 Rn = rcp4(P1);
+            const P4 P1 = topk4(Praw);               // trip t+1, read during the previous trip
+            const R4 Rn = rcp4(P1);
             // the look-ups above belong to later trips: keep the scheduler from pulling next trip's
             // (which depend on them) up behind them, which would put their latency on this trip
             __builtin_amdgcn_sched_barrier(0);
-            o.step(x, live, R0.x, P0.x, bits);
-            o.step(x, live, R0.y, P0.y, bits);
-            o.step(x, live, R0.z, P0.z, bits);
-            o.step(x, live, R0.w, P0.w, bits);
+            step(o, x, live, R0.rcp.x, R0.w.x, P0.x.pk, P0.x.f);
+            step(o, x, live, R0.rcp.y, R0.w.y, P0.y.pk, P0.y.f);
+            step(o, x, live, R0.rcp.z, R0.w.z, P0.z.pk, P0.z.f);
+            step(o, x, live, R0.rcp.w, R0.w.w, P0.w.pk, P0.w.f);
             if (live) cur = cur1;
             cur1 = cur2; cur2 = I2.c3;
             I2 = In; P0 = P1; Praw = Pn; R0 = Rn;
@@ -337,22 +388,21 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
     u32 r = r0 - 4 * ntrip, done = 4 * ntrip;
     for (; wave_any(done < main); ) {
         const bool live = done < main;
-        u32 rcp = 0, pk = 0;
+        Sym e = {0, 0, {0, 0}};
         if (live) {
             const u32 ci = idx[qbase[r - 1]];
-            const u32x2 e = fetch(ci, cur);
-            rcp = e.x; pk = e.y;
+            e = fetch(ci, cur);
             cur = ci; r--; done++;
         }
-        o.step(x, live, rcp, pk, bits);
+        step(o, x, live, e.rcp, e.w, e.s.pk, e.s.f);
         o.flush();
     }
     // (C) first byte of each quarter in context 0 (:831-834)
     {
         const bool live = active && q > 0;
-        u32 rcp = 0, pk = 0;
-        if (live) { const u32x2 e = fetch(0, cur); rcp = e.x; pk = e.y; }
-        o.step(x, live, rcp, pk, bits);
+        Sym e = {0, 0, {0, 0}};
+        if (live) e = fetch(0, cur);
+        step(o, x, live, e.rcp, e.w, e.s.pk, e.s.f);
     }
     return o.finish(x);
 }
@@ -471,8 +521,9 @@ __device__ __forceinline__ u32 chain_encode_o0_pipe(const u8 *img_lds, u8 *ring,
 // LDS_IMG: a workgroup of up to four waves shares one LDS copy of the reciprocal table; each quad
 // owns lds_per_item bytes (image, then the word ring).  Waves never meet again after the set-up.
 // PK: the class holds packed order-1 streams only (10-bit tables): a 1,025-entry reciprocal table suffices.
+// FT: the class holds packed streams of the short-index kind: the frequency table in place of the reciprocals.
 #define ENC_LRCP_PK_BYTES 4112u      // 1,025 dwords, padded to 16
-template <bool LDS_IMG, bool PK>
+template <bool LDS_IMG, bool PK, bool FT = false>
 __global__ __launch_bounds__(256) void k_enc_chain(EncItem *items, const u32 *rcptab_, u8 *dump_, const u32 *list, u32 *count,
                                                    int qpw, int spw, u32 lds_per_item, int dyn)
 {
@@ -517,8 +568,9 @@ __global__ __launch_bounds__(256) void k_enc_chain(EncItem *items, const u32 *rc
     u32 pay;
     if (LDS_IMG) {
         u32 *lrcp = (u32 *)lds;
-        u8 *slots = lds + (PK ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES);
-        for (u32 j = tid; j < (PK ? 1025u : RCPTAB_ENTRIES); j += blockDim.x) lrcp[j] = rcptab[j];
+        u8 *slots = lds + (FT ? ENC_LFREQ_BYTES : PK ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES);
+        if (FT) for (u32 j = tid; j < 2u * ENC_FREQTAB_ENTRIES; j += blockDim.x) lrcp[j] = rcptab[ENC_FREQTAB_OFF + j];
+        else for (u32 j = tid; j < (PK ? 1025u : RCPTAB_ENTRIES); j += blockDim.x) lrcp[j] = rcptab[j];
         // each wave copies the images of its own quads (16-byte pieces)
         const u64 my_img = active ? I->image : 0ull;
         const u32 wq0 = (tid >> 6) * (u32)spw;             // first stream slot of this wave
@@ -536,7 +588,7 @@ __global__ __launch_bounds__(256) void k_enc_chain(EncItem *items, const u32 *rc
         const u8 *im = slots + (u64)slot * lds_per_item;
         u8 *ring = slots + (u64)slot * lds_per_item + (lds_per_item - ENC_RING_BYTES);
         gu8 *dump = to_global(dump_) + 16u * ((blockIdx.x * blockDim.x + tid) & (ENC_DUMP_BYTES / 16u - 1u));
-        pay = chain_encode_o1_lds<PK>(im, ring, lrcp, data, n, ns, bits, (gcu8 *)rcptab, send, dump, order == 1, lane);
+        pay = chain_encode_o1_lds<PK, false, FT>(im, ring, lrcp, data, n, ns, bits, (gcu8 *)rcptab, send, dump, order == 1, lane);
         if (!PK) pay |= chain_encode_o0_pipe(im, ring, lrcp, data, n, bits, (gcu8 *)rcptab, send, dump, order == 0, lane);
     } else {
         gcu8 *im = (gcu8 *)I->image;

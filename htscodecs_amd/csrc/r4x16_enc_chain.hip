@@ -4,9 +4,9 @@
 // =============================================================================================
 #include "r4x16_enc_chain.h"
 
-// r4x16_enc_chain_pk.hip: k_enc_chain<true, true>
+// r4x16_enc_chain_pk.hip: k_enc_chain<true, true> / k_enc_chain<true, true, true>
 extern "C" void r4x16_enc_chain_pk_lds_limit(int bytes);
-extern "C" const void *r4x16_enc_chain_pk_kernel(void);
+extern "C" const void *r4x16_enc_chain_pk_kernel(int freq_table);
 
 // ---- host-callable launcher ----------------------------------------------------------------------
 extern "C" bool r4x16_first_on_device(u32 bit);                                          // r4x16_decode.hip
@@ -23,6 +23,11 @@ static const u32 ENC_CLASSES[] = {656, 1296, 2576, 4752, 6416, 12816, 16272, 244
 // packed rows (20..64 symbols, 10-bit tables): 46 symbols need 3,532 bytes -> 45 streams per CU beside the small
 // reciprocal table (3,536 is 80 mod 128: consecutive streams start 20 banks apart)
 static const u32 ENC_PK_CLASSES[] = {1168, 2064, 2832, 3536, 3728, 4752, 6416};
+// the short-index kind of the packed rows (r4x16_common.h: highest byte below 128): class k is packed class k less the
+// half of the index its images leave out - 46 symbols: 3,408 bytes, 45 streams per CU beside the 8,208-byte frequency
+// table (80 mod 128 like 3,536)
+#define ENC_PKS_LESS (ENC_IMG_IDX - ENC_IMG_IDX_SHORT)
+static u32 enc_pks_class(u32 k) { return ENC_PK_CLASSES[k] - ENC_PKS_LESS; }
 // symbol records (kind 2, r4x16_enc_chain_rec.hip; only batches that leave LDS to spare make such images): one wave
 // per workgroup, {LDS bytes per stream, streams per wave}; four workgroups per CU, then fewer
 struct EncRecClass { u32 bytes; int qpw; };
@@ -34,9 +39,11 @@ extern "C" void r4x16_enc_chain_rec_lds_limit(int bytes);
 extern "C" const void *r4x16_enc_chain_rec_kernel(void);
 #define ENC_NCLS    ((u32)(sizeof(ENC_CLASSES) / sizeof(ENC_CLASSES[0])))
 #define ENC_PK_NCLS ((u32)(sizeof(ENC_PK_CLASSES) / sizeof(ENC_PK_CLASSES[0])))
-static int enc_class_qpw(u32 bytes, bool pk, const R4Opts *o)
+// (kind: 0 u16 rows, 1 packed rows, ENC_KIND_PK_SHORT their short-index kind)
+static u32 enc_table_bytes(u32 kind) { return kind == ENC_KIND_PK_SHORT ? ENC_LFREQ_BYTES : kind == 1u ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES; }
+static int enc_class_qpw(u32 bytes, u32 kind, const R4Opts *o)
 {
-    const u32 room = 163840u - (pk ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES);
+    const u32 room = 163840u - enc_table_bytes(kind);
     const u32 fit = room / bytes;
     const int cap = (int)o->v[OPT_ENC_QPW_CAP];                  // tuning aid (default 64)
     return (int)(fit > (u32)cap ? (u32)cap : fit);
@@ -71,13 +78,14 @@ struct EncShape { int qpw, waves, spw; size_t ldsb; u32 bytes; };
 #define ENC_O0_ROWS_BYTES 1296u      // order-0 streams with u16 rows: a 770-byte image and the ring
 #define ENC_O0_REC_BYTES  8080u      // order-0 streams with symbol records: a 4,352-byte image and the ring
 #define ENC_O0_REC_QPW    5
+// (cls: u16 classes, then the packed ones, then the packed ones of the short-index kind)
 static EncShape enc_rows_shape(u32 cls, int nitems, const R4Opts *o, u32 bytes_o0 = 0)
 {
-    const bool pk = !bytes_o0 && cls >= ENC_NCLS;
-    const u32 bytes = bytes_o0 ? bytes_o0 : pk ? ENC_PK_CLASSES[cls - ENC_NCLS] : ENC_CLASSES[cls];
-    const u32 tuned = pk ? 3536u : 4752u;                // the class of the 46-symbol quality tables
+    const u32 kind = bytes_o0 || cls < ENC_NCLS ? 0u : cls < ENC_NCLS + ENC_PK_NCLS ? 1u : ENC_KIND_PK_SHORT;
+    const u32 bytes = bytes_o0 ? bytes_o0 : kind == 0u ? ENC_CLASSES[cls] : kind == 1u ? ENC_PK_CLASSES[cls - ENC_NCLS] : enc_pks_class(cls - ENC_NCLS - ENC_PK_NCLS);
+    const u32 tuned = kind == 0u ? 4752u : kind == 1u ? 3536u : 3536u - ENC_PKS_LESS;       // the class of the 46-symbol quality tables
     const int force_qpw = (int)o->v[OPT_ENC_QPW], force_waves = (int)o->v[OPT_ENC_WAVES];   // tuning aids
-    int qpw = (force_qpw && bytes == tuned) ? force_qpw : enc_class_qpw(bytes, pk, o);
+    int qpw = (force_qpw && bytes == tuned) ? force_qpw : enc_class_qpw(bytes, kind, o);
     // One workgroup per CU is the best shape (measured: 30 streams per CU as 1 x 32 beat 2 x 16 by a
     // third and half-filled 64s by a fifth), so a batch that cannot fill the class's workgroups on
     // every CU gets smaller ones (items [0, n/3) are the payload streams).
@@ -92,7 +100,7 @@ static EncShape enc_rows_shape(u32 cls, int nitems, const R4Opts *o, u32 bytes_o
     if (force_waves && bytes == tuned) waves = force_waves;
     EncShape sh;
     sh.qpw = qpw; sh.waves = waves; sh.spw = (qpw + waves - 1) / waves; sh.bytes = bytes;
-    sh.ldsb = (size_t)(pk ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES) + (size_t)qpw * bytes;
+    sh.ldsb = (size_t)enc_table_bytes(kind) + (size_t)qpw * bytes;
     return sh;
 }
 static EncShape enc_rec_shape(u32 r, const R4Opts *o, bool o0 = false)
@@ -117,7 +125,7 @@ extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t 
 {
     // classes side by side over the caller's stream and the side streams, each with its stream's share of the chip
     // (launch_dec_chain_of, r4x16_sched.h); class index ci = position in the classify table: u16 classes, packed
-    // classes, record classes
+    // classes, short-index packed classes, record classes
     const int nq = fk ? fk->n + 1 : 1;
     struct Launch { const void *kern; int grid; EncShape sh; u32 ci; };
     Launch todo[CLS_MAX];
@@ -138,7 +146,8 @@ extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t 
         todo[ntodo++] = Launch{kern, r4x16_resident_grid(sh.ldsb, sh.waves, (nitems + sh.qpw - 1) / sh.qpw), sh, ci};
     };
     for (u32 k = 0; k < ENC_NCLS; k++) add(0, ENC_CLASSES[k], enc_rows_shape(k, nitems, o), (const void *)k_enc_chain<true, false>);
-    for (u32 k = 0; k < ENC_PK_NCLS; k++) add(1, ENC_PK_CLASSES[k], enc_rows_shape(ENC_NCLS + k, nitems, o), r4x16_enc_chain_pk_kernel());
+    for (u32 k = 0; k < ENC_PK_NCLS; k++) add(1, ENC_PK_CLASSES[k], enc_rows_shape(ENC_NCLS + k, nitems, o), r4x16_enc_chain_pk_kernel(0));
+    for (u32 k = 0; k < ENC_PK_NCLS; k++) add(ENC_KIND_PK_SHORT, enc_pks_class(k), enc_rows_shape(ENC_NCLS + ENC_PK_NCLS + k, nitems, o), r4x16_enc_chain_pk_kernel(1));
     // (record classes: only batches that leave LDS to spare make such images)
     for (u32 k = 0; k < ENC_REC_NCLS; k++) add(2, ENC_REC_CLASSES[k].bytes, enc_rec_shape(k, o), ws->direct_budget ? r4x16_enc_chain_rec_kernel() : nullptr);
     add(3, ENC_O0_ROWS_BYTES, enc_rows_shape(0, nitems, o, ENC_O0_ROWS_BYTES), (const void *)k_enc_chain<true, false>);
@@ -199,15 +208,17 @@ extern "C" u32 r4x16_enc_direct_budget(int nblk, const R4Opts *o)
     }
     return best;
 }
-// The row kind of a class id of r4x16_launch_enc_chain's table (u16 classes, packed classes, record classes, then the
-// order-0 u16 class, the order-0 record class and the catch-all of images too large for LDS) as the route read-out counts
-// it (include/rans4x16_hip.h R4X16_ENC_*: 0 u16 rows, 1 packed rows, 2 symbol records); -1 beyond the table.
-extern "C" int r4x16_enc_route_kind(u32 ci)
+// The row kind of a class id of r4x16_launch_enc_chain's table (u16 classes, packed classes of both kinds, record classes,
+// then the order-0 u16 class, the order-0 record class and the catch-all of images too large for LDS) as the route read-out
+// counts it (include/rans4x16_hip.h R4X16_ENC_*: 0 u16 rows, 1 packed rows, 2 symbol records); -1 beyond the table.
+// *freq_table: the class is of the short-index kind (counted as R4X16_ENC_PACKED_FREQ as well).
+extern "C" int r4x16_enc_route_kind(u32 ci, int *freq_table)
 {
+    *freq_table = ci >= ENC_NCLS + ENC_PK_NCLS && ci < ENC_NCLS + 2u * ENC_PK_NCLS;
     if (ci < ENC_NCLS) return 0;
     ci -= ENC_NCLS;
-    if (ci < ENC_PK_NCLS) return 1;
-    ci -= ENC_PK_NCLS;
+    if (ci < 2u * ENC_PK_NCLS) return 1;
+    ci -= 2u * ENC_PK_NCLS;
     if (ci < ENC_REC_NCLS) return 2;
     ci -= ENC_REC_NCLS;
     return ci == 0 ? 0 : ci == 1 ? 2 : ci == 2 ? 0 : -1;
@@ -234,13 +245,15 @@ extern "C" int r4x16_enc_residency(u32 nsym, int order, int *streams_per_wave, i
 {
     if (nsym == 0 || nsym > 256) return -1;
     // (the packed rows need a 10-bit table: what every BASELINE text chooses; a 12-bit stream keeps the u16 rows)
+    // (of the packed rows' two kinds the full index: what any alphabet of that size can take; the short-index classes
+    //  hold as many streams or more)
     const bool pk = order && nsym >= ENC_PK_MIN_NS && nsym <= ENC_PK_MAX_NS;
     const u32 need = (pk ? enc_pk_img_bytes(nsym) : order ? ENC_IMG_IDX + 2u * nsym * (nsym + 1) : ENC_IMG_IDX + 2u * 257u) + ENC_RING_BYTES;
     for (u32 cls = 0; cls < ENC_NCLS + ENC_PK_NCLS; cls++) {
         if ((cls >= ENC_NCLS) != pk) continue;
         const u32 bytes = pk ? ENC_PK_CLASSES[cls - ENC_NCLS] : ENC_CLASSES[cls];
         if (need > bytes) continue;
-        const int qpw = enc_class_qpw(bytes, pk, r4x16_opts_defaults());
+        const int qpw = enc_class_qpw(bytes, pk ? 1u : 0u, r4x16_opts_defaults());
         int waves = (qpw + 7) / 8;
         if (waves > 4) waves = 4;
         *streams_per_wave = (qpw + waves - 1) / waves;

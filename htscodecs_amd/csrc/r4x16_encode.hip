@@ -1475,13 +1475,17 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
 
     TPROF(3);
     // ---- encoder image: scale each row up to 1<<bits (:756) and build entries (:759-762) -----------
-    for (u32 j = lane; j < 256; j += WAVE) img[j] = S.present[j] ? S.idx_of[j] : (u8)0;
     u16 *cumimg = (u16 *)(img + ENC_IMG_IDX);            // cum[r][0..ns]
     // a batch that leaves LDS to spare takes symbol records (the short step); else quality-sized 10-bit tables pack
     const bool recs = enc_rec_img_bytes(ns, ns) + ENC_RING_BYTES <= ws.direct_budget && enc_rec_img_bytes(ns, ns) <= ENC_IMG_MAIN &&
                       n >= enc_rec_img_bytes(ns, ns) / 4u;
     const bool packed = !recs && bits == 10 && ns >= ENC_PK_MIN_NS && ns <= ENC_PK_MAX_NS;
     const u32 W = enc_pk_row_dwords(ns);
+    // packed rows of an alphabet below byte 128: the short index, rows from byte ENC_IMG_IDX_SHORT on (r4x16_common.h)
+    bool high = false;
+    for (u32 j = ENC_IMG_IDX_SHORT + lane; j < 256; j += WAVE) high |= S.present[j] != 0;
+    const u32 idxb = packed && !__ballot(high) ? ENC_IMG_IDX_SHORT : ENC_IMG_IDX;
+    for (u32 j = lane; j < idxb; j += WAVE) img[j] = S.present[j] ? S.idx_of[j] : (u8)0;
     // one context row per lane, serial over its ns entries (a row per wave with a scan per 64 entries and two
     // barriers per packed row took 98 us per block for 46 rows)
     for (u32 rb = 0; rb < ns; rb += WAVE) {
@@ -1500,7 +1504,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
             row[ns] = (u16)x;
         } else {
             // packed row (r4x16_common.h): entry j at bit 11 j of the row's bit stream
-            u32 *row = (u32 *)(img + ENC_IMG_IDX) + r * W;
+            u32 *row = (u32 *)(img + idxb) + r * W;
             u64 acc = 0;                                  // bits not yet written, `have` of them
             u32 have = 0, wi = 0;
             for (u32 j = 0; j <= ns; j++) {
@@ -1512,7 +1516,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
             if (wi < W) row[wi] = (u32)acc;
         }
     }
-    if (packed && lane == 0) ((u32 *)(img + ENC_IMG_IDX))[ns * W] = 0;      // the pair window's second dword past the last row
+    if (packed && lane == 0) ((u32 *)(img + idxb))[ns * W] = 0;      // the pair window's second dword past the last row
     wsync();
 
     TPROF(4);
@@ -1553,8 +1557,8 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
     if (lane == 0) {
         D->tab_len = final_len;
         I0->data = (u64)data; I0->n = n; I0->image = (u64)img; I0->bits = bits; I0->order = 1;
-        I0->ns = ns; I0->img_bytes = recs ? enc_rec_img_bytes(ns, ns) : packed ? enc_pk_img_bytes(ns) : ENC_IMG_IDX + 2u * ns * (ns + 1);
-        I0->packed = recs ? 2u : packed ? 1u : 0u;
+        I0->ns = ns; I0->img_bytes = recs ? enc_rec_img_bytes(ns, ns) : packed ? enc_pk_img_bytes(ns, idxb) : ENC_IMG_IDX + 2u * ns * (ns + 1);
+        I0->packed = recs ? 2u : !packed ? 0u : idxb == ENC_IMG_IDX_SHORT ? ENC_KIND_PK_SHORT : 1u;
         I0->affine = aff;
         I0->scratch_end = (u64)scratch_end;
         I0->active = 1;

@@ -254,7 +254,12 @@ enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) 
     R4X16_DEC_SHORT_RING = 7, /* packed rows with the short word ring                                                 */
     R4X16_DEC_KINDS = 8
 };
-enum { R4X16_ENC_U16 = 0, R4X16_ENC_PACKED = 1, R4X16_ENC_RECORDS = 2, R4X16_ENC_KINDS = 3 };    /* R4X16_ROUTE_ENCODE */
+enum {   /* R4X16_ROUTE_ENCODE: the encoder's row kinds */
+    R4X16_ENC_U16 = 0, R4X16_ENC_PACKED = 1, R4X16_ENC_RECORDS = 2,
+    R4X16_ENC_PACKED_FREQ = 3,/* those of the packed streams (counted there too) whose highest byte is below 128: the image  */
+                              /* with the 128-byte index, coded from the 8-byte frequency table                              */
+    R4X16_ENC_KINDS = 4
+};
 enum { R4X16_EXPAND_WAVE = 0, R4X16_EXPAND_WORKGROUP = 1, R4X16_EXPAND_KINDS = 2 };               /* R4X16_ROUTE_EXPAND */
 enum { R4X16_LAUNCH_IN_ORDER = 0, R4X16_LAUNCH_SIDE_BY_SIDE = 1, R4X16_LAUNCH_KINDS = 2 };        /* R4X16_ROUTE_LAUNCH */
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
