@@ -369,6 +369,32 @@ class DeviceCodec:
         if rc != 0:
             raise RuntimeError("compress_dev: " + self.ctx.error())
 
+    def set_stripe_encode(self, max_planes):
+        """rans4x16_hip_set_dev_stripe_encode: `compress` with d_order encodes X_STRIPE blocks of up to max_planes
+        planes (0: off, such blocks report UNSUPPORTED)."""
+        if self.L.rans4x16_hip_set_dev_stripe_encode(self.ctx.h, int(max_planes)) != 0:
+            raise ValueError(f"set_stripe_encode: {max_planes!r} is outside 0..255")
+
+    def compress_best(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status, methods,
+                      max_in_size, chosen=None, total_in_size=0):
+        """rans4x16_hip_compress_best_dev: every block with each of `methods` (a list of order values), the smallest
+        result in its output slot, the winning method in `chosen` (int32 tensor, optional).  Enqueues only."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
+        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert chosen is None or chosen.dtype == t.int32
+        n = in_off.numel()
+        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        rc = self.L.rans4x16_hip_compress_best_dev(
+            self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(),
+            status.data_ptr(), len(methods), meth, chosen.data_ptr() if chosen is not None else None,
+            int(max_in_size), int(total_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("compress_best_dev: " + self.ctx.error())
+
     def uncompress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status,
                    max_in_size, max_out_cap, total_out_cap=0):
         t = self.torch

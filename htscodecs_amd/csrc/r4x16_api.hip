@@ -198,6 +198,13 @@ extern "C" int rans4x16_hip_set_dev_stripe_planes(rans4x16_hip_ctx *c, int plane
     return 0;
 }
 
+extern "C" int rans4x16_hip_set_dev_stripe_encode(rans4x16_hip_ctx *c, int max_planes)
+{
+    if (!c || max_planes < 0 || max_planes > 255) return -1;
+    c->dev_stripe_enc = max_planes;
+    return 0;
+}
+
 extern "C" const char *rans4x16_hip_last_error(const rans4x16_hip_ctx *c) { return c ? c->err.c_str() : "no context"; }
 extern "C" size_t rans4x16_hip_workspace_bytes(const rans4x16_hip_ctx *c) { return c ? c->ws_bytes : 0; }
 
@@ -318,6 +325,18 @@ static size_t plan_chunk(rans4x16_hip_ctx *c, size_t n, F bytes)
     return (n + rounds - 1) / rounds;
 }
 
+// What the arenas of one call may take together: plan_chunk's cap, for callers that hold a second arena (r4x16_best.hip)
+size_t r4x16_ws_room(rans4x16_hip_ctx *c)
+{
+    size_t cap = c->max_ws;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        const size_t room = (free_b + c->ws_bytes + c->xs_bytes) / 4 * 3;
+        if (room < cap) cap = room;
+    }
+    return cap;
+}
+
 // The side streams of the chain kernels' class launches (R4Fork, r4x16_dev.h); nullptr where they are switched off
 // (option sched_concurrent = 0), cannot be made, or the context is a lane of the host pipeline.
 extern "C" int r4x16_cu_count(void);
@@ -418,6 +437,13 @@ static size_t enc_ws_layout(u8 *base, size_t nblk, u64 scratch_stride, u64 var_b
     return align_up(cv.off, 256);
 }
 
+// workspace of one encode chunk of nitems blocks with per-block orders that hold total_in bytes together
+size_t r4x16_enc_ws_bytes(size_t nitems, u32 max_in_size, u64 total_in)
+{
+    EncWs w;
+    return enc_ws_layout(nullptr, nitems, ENC_F_BYTES, enc_var_bound(nitems, std::min<u64>(total_in, (u64)nitems * max_in_size)), &w) + 4096;
+}
+
 extern "C" int rans4x16_hip_compress_dev(rans4x16_hip_ctx *c, int n,
                                          const unsigned char *d_in, const uint64_t *d_in_off,
                                          const uint32_t *d_in_size,
@@ -452,6 +478,13 @@ extern "C" int rans4x16_hip_compress_dev_sized(rans4x16_hip_ctx *c, int n,
         sa.out = d_out; sa.out_off = d_out_off; sa.out_cap = d_out_cap; sa.out_size = d_out_size;
         sa.status = d_status; sa.d_order = nullptr; sa.order = order; sa.n = n;
         return r4x16_stripe_compress_dev(c, n, sa, order, max_in_size, s);
+    }
+    if (d_order && c->dev_stripe_enc > 0 && !c->in_stripe) {   // per-block orders that may ask for X_STRIPE: N and the methods are read on the device
+        BatchArgs sa;
+        sa.in = d_in; sa.in_off = d_in_off; sa.in_size = d_in_size;
+        sa.out = d_out; sa.out_off = d_out_off; sa.out_cap = d_out_cap; sa.out_size = d_out_size;
+        sa.status = d_status; sa.d_order = d_order; sa.order = order; sa.n = n;
+        return r4x16_orders_stripe_compress_dev(c, n, sa, max_in_size, total_in_size, s);
     }
 
     // Per block the workspace holds fixed-size records, tables and images, 256 KB for the pair counters and the nested

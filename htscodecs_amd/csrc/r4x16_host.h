@@ -50,6 +50,11 @@ void r4x16_trim(rans4x16_hip_ctx *c, size_t keep);
 int r4x16_ws_order_begin(rans4x16_hip_ctx *c, hipStream_t s);
 int r4x16_ws_order_end(rans4x16_hip_ctx *c, hipStream_t s);
 int r4x16_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, int order, uint32_t max_in_size, hipStream_t s);
+// best-of-k and X_STRIPE under per-block orders (r4x16_best.hip); what they ask of r4x16_api.hip
+int r4x16_orders_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint64_t total_in_size,
+                                     hipStream_t s);
+size_t r4x16_ws_room(rans4x16_hip_ctx *c);
+size_t r4x16_enc_ws_bytes(size_t nitems, u32 max_in_size, u64 total_in);
 int r4x16_stripe_uncompress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint32_t max_out_cap,
                                 uint32_t max_stripe_out, hipStream_t s);
 int r4x16_run_host_batch(rans4x16_hip_ctx *c, int n, bool decode,
@@ -78,7 +83,8 @@ struct rans4x16_hip_ctx {
     size_t xs_bytes = 0;
     int dev_stripe_planes = 0;
     unsigned int dev_stripe_out = 0;        // largest uncompressed stripe block such a batch may hold
-    bool in_stripe = false;
+    int dev_stripe_enc = 0;                 // encode with per-block orders: planes a block reserves (rans4x16_hip_set_dev_stripe_encode)
+    bool in_stripe = false;                 // inside the recursive call over the internal items
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;

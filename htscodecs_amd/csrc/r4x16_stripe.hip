@@ -174,8 +174,14 @@ int r4x16_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, in
     // before the previous call's last kernel is done, and the event recorded after the finishing kernel covers it
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
     hipLaunchKernelGGL(k_stripe_enc_prepare, dim3(n), dim3(256), 0, s, a, w, e);
-    if (rans4x16_hip_compress_dev(c, (int)((size_t)n * P), w.planes, w.in_off, w.in_size, w.out, w.out_off, w.out_cap, w.out_size,
-                                  w.status, 0, w.order, item_max, s) != 0) return -1;
+    // (in_stripe: the internal items carry per-item orders, and must not be taken for a caller's batch of per-block
+    //  orders that may hold stripes - rans4x16_hip_set_dev_stripe_encode - which would lay its own items out in this arena)
+    const bool keep_in = c->in_stripe;
+    c->in_stripe = true;
+    const int rc = rans4x16_hip_compress_dev(c, (int)((size_t)n * P), w.planes, w.in_off, w.in_size, w.out, w.out_off, w.out_cap, w.out_size,
+                                             w.status, 0, w.order, item_max, s);
+    c->in_stripe = keep_in;
+    if (rc != 0) return -1;
     hipLaunchKernelGGL(k_stripe_enc_pick, dim3(n), dim3(WAVE), 0, s, a, w, e);
     HIPCHK(c, hipGetLastError());
     return r4x16_ws_order_end(c, s);

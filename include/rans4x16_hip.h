@@ -114,7 +114,8 @@ int rans4x16_hip_compress_best_batch(rans4x16_hip_ctx *ctx, int n,
  * `stream` is a hipStream_t (NULL = default stream).  The call only enqueues work.
  * X_STRIPE (0x08), device-resident: encode accepts it when all blocks share one `order` (d_order == NULL): the
  * planes, the N x K candidate encodings, the choice of the smallest per plane and the header are all produced on the
- * device (rANS_static4x16pr.c:1154-1216); with per-block orders a stripe block reports UNSUPPORTED.  Decode accepts
+ * device (rANS_static4x16pr.c:1154-1216); with per-block orders a stripe block is encoded the same way after
+ * rans4x16_hip_set_dev_stripe_encode (below) and reports UNSUPPORTED without it.  Decode accepts
  * stripe blocks after rans4x16_hip_set_dev_stripe_planes (below); without it they report UNSUPPORTED.  The host
  * entry points handle stripes in every case.
  * Returns 0 if enqueued, -1 on argument / allocation / launch errors. */
@@ -160,6 +161,46 @@ int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *ctx, int n,
  * with more planes, or larger than that, reports UNSUPPORTED; like the reference (:1379) a stripe block must be given
  * an output capacity equal to its stored size.  planes == 0 (the default) switches it off.  Returns 0, -1 on bad arguments. */
 int rans4x16_hip_set_dev_stripe_planes(rans4x16_hip_ctx *ctx, int planes, unsigned int max_block_size);
+
+/* Device-resident encode of X_STRIPE blocks under per-block orders (d_order != NULL): N and the candidate methods of a
+ * block are then known to the device only, so every block of such a call reserves max_planes x 4 internal items.
+ * A stripe block with N <= max_planes is encoded byte for byte like rans_compress_to_4x16(.., d_order[b]); one with more
+ * planes reports UNSUPPORTED and leaves its neighbours alone; blocks without the flag, and blocks of at most 20 bytes,
+ * are encoded with their own order as before.  max_planes 0..255; 0 (the default) switches it off: a stripe block under
+ * d_order reports UNSUPPORTED.  Calls with one `order` for all blocks are not affected.
+ * Cost: the plane count of a block is not known to the host, so the reservation is made for the worst case - per block
+ * four output slots of a whole block's bound and max_planes x 4 - 4 slots of half a block's bound (each at least the
+ * 198 KB of an order-1 table), and as many items of workspace.  Set max_planes to the largest N the batches really
+ * use (4 for the default N), not to 255.  Returns 0, -1 on bad arguments. */
+int rans4x16_hip_set_dev_stripe_encode(rans4x16_hip_ctx *ctx, int max_planes);
+
+/* rans4x16_hip_compress_best_batch for device-resident blocks: the arrays of rans4x16_hip_compress_dev_sized, the
+ * semantics of the host call.  Block i is encoded with methods[0..k) (a HOST array, 1 <= k <= 32) in that order and
+ * d_out + d_out_off[i] receives exactly the bytes of rans_compress_to_4x16(in, size, .., methods[j]) for the smallest
+ * result; of equal sizes the earlier method wins (tokenise_name3.c:1281-1284).  d_chosen[i] (device, may be NULL) is that
+ * methods[j] as given, -1 if no candidate succeeded.
+ *   - A method with X_STRIPE (0x08) is skipped for a block whose size is no multiple of 4 (:1270-1271); on a block of at
+ *     most 20 bytes it is a plain encode with the flag dropped (rANS_static4x16pr.c:1151).
+ *   - A candidate that fails is skipped: one whose own rans_compress_bound_4x16(size, methods[j]) exceeds d_out_cap[i]
+ *     (CAPACITY).  The block fails only if no candidate succeeded: d_out_size[i] = 0, d_chosen[i] = -1 and
+ *     d_status[i] is the status of the first candidate that was tried, UNSUPPORTED if none was.  Other blocks are not affected.
+ *   - A stripe method with more than 255 planes (methods[j] >> 8) makes the call return -1.
+ * The choice is made on the device: the call only enqueues on `stream`, reads nothing back and does not synchronise; it
+ * is ordered against the context's other calls like every *_dev call.  Every candidate is encoded in full into a
+ * bound-sized slot of an internal arena (a stripe method as N x K plane encodings, the planes transposed once per
+ * distinct N); the batch is walked in chunks of blocks so that this arena and the workspace together stay under the
+ * option max_workspace_mb.  max_in_size / total_in_size (0 = unknown) as in rans4x16_hip_compress_dev_sized.
+ * As with the workspace of every *_dev call, the arena grows on demand and is kept: a call that has to enlarge it (the
+ * first one, or a larger batch) waits for the device once while it reallocates, and what a large call allocated stays
+ * with the context until it is destroyed - max_workspace_mb bounds what one call plans for, not what earlier calls left.
+ * Returns 0 if enqueued, -1 on argument / allocation / launch errors. */
+int rans4x16_hip_compress_best_dev(rans4x16_hip_ctx *ctx, int n,
+                                   const unsigned char *d_in, const uint64_t *d_in_off,
+                                   const uint32_t *d_in_size,
+                                   unsigned char *d_out, const uint64_t *d_out_off,
+                                   const uint32_t *d_out_cap, uint32_t *d_out_size,
+                                   int32_t *d_status, int k, const int *methods, int32_t *d_chosen,
+                                   uint32_t max_in_size, uint64_t total_in_size, void *stream);
 
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
