@@ -82,7 +82,8 @@ int r4x16_run_host_batch(rans4x16_hip_ctx *c, int n, bool decode,
         if (rc < 0) return -1;
         for (size_t k = 0; k < striped.size(); k++) {
             const int i = striped[k];
-            if (status) status[i] = sst[k] ? R4X16_E_SIZE : 0;
+            // decode: the status a device-resident call reports (a plane's own verdict included); encode: SIZE as before
+            if (status) status[i] = !sst[k] ? 0 : decode ? sst[k] : R4X16_E_SIZE;
             if (sst[k]) { out_size[i] = 0; failed++; }
         }
     }
@@ -810,7 +811,7 @@ static int stripe_many_dev(rans4x16_hip_ctx *c, bool decode, const std::vector<i
     u32 max_planes = 0, max_ulen = 0;
     for (size_t k = 0; k < nb; k++) {
         const int i = which[k];
-        fail[k] = 1;
+        fail[k] = R4X16_E_SIZE;                              // decode: the block's status; encode: failed or not
         if (!decode) {
             const int o = order ? order[i] : 0;
             int N = o >> 8; if (N == 0) N = 4;
@@ -823,7 +824,7 @@ static int stripe_many_dev(rans4x16_hip_ctx *c, bool decode, const std::vector<i
             hdr += var_get_host(p + hdr, end, &ulen);
             if (hdr >= in_size[i]) continue;                               // :1367
             const u32 N = p[hdr++];
-            if (ulen != out_size[i]) continue;                             // :1379 (caller sized the buffer)
+            if (ulen != out_size[i]) { fail[k] = R4X16_E_CAPACITY; continue; }   // :1379 (caller sized the buffer)
             if (N == 0) { if (ulen == 0) { fail[k] = 0; out_size[i] = 0; } continue; }   // the reference spins forever here
             u64 ctot = 0;
             bool good = true;
@@ -922,7 +923,7 @@ static int stripe_many_dev(rans4x16_hip_ctx *c, bool decode, const std::vector<i
         for (int e = 0; e < m; e++) {
             const size_t k = g[e];
             const int i = which[k];
-            if (st[e] != 0) continue;                                          // fail[k] stays 1
+            if (st[e] != 0) { if (decode) fail[k] = st[e]; continue; }         // (encode: fail[k] stays set)
             if (decode) {
                 if (osz[e] != cap[e]) continue;
                 if (osz[e]) memcpy(out[i], host.data() + out_off[e], osz[e]);
@@ -1087,13 +1088,13 @@ static int stripe_uncompress_many(rans4x16_hip_ctx *c, const std::vector<int> &w
     for (size_t k = 0; k < nb; k++) {
         const int i = which[k];
         Blk &b = B[k];
-        b.ok = false; fail[k] = 1; b.item0 = (int)items; b.boff = in_tot; b.poff = pl_tot; b.N = 0;
+        b.ok = false; fail[k] = R4X16_E_SIZE; b.item0 = (int)items; b.boff = in_tot; b.poff = pl_tot; b.N = 0;
         const unsigned char *p = in[i], *end = p + in_size[i];
         u32 ulen, hdr = 1;
         hdr += var_get_host(p + hdr, end, &ulen);
         if (hdr >= in_size[i]) continue;                               // :1367
         const u32 N = p[hdr++];
-        if (ulen != out_size[i]) continue;                             // :1379 (caller sized the buffer)
+        if (ulen != out_size[i]) { fail[k] = R4X16_E_CAPACITY; continue; }   // :1379 (caller sized the buffer)
         if (N == 0) { if (ulen == 0) { fail[k] = 0; out_size[i] = 0; } continue; }   // the reference spins forever here
         u64 ctot = 0;
         bool good = true;
@@ -1158,8 +1159,10 @@ static int stripe_uncompress_many(rans4x16_hip_ctx *c, const std::vector<int> &w
     for (size_t k = 0; k < nb; k++) {
         Blk &b = B[k];
         if (!b.ok) continue;
-        for (u32 j = 0; j < b.N; j++)
-            if (st[(size_t)b.item0 + j] != 0 || osz[(size_t)b.item0 + j] != cap[(size_t)b.item0 + j]) b.ok = false;   // :1419-1420
+        for (u32 j = 0; j < b.N && b.ok; j++) {                            // :1419-1420: the first failing plane's verdict
+            if (st[(size_t)b.item0 + j] != 0) { b.ok = false; fail[k] = st[(size_t)b.item0 + j]; }
+            else if (osz[(size_t)b.item0 + j] != cap[(size_t)b.item0 + j]) b.ok = false;
+        }
         if (!b.ok) continue;
         r4x16_launch_stripe(d_pl + b.poff, d_out + b.poff, b.ulen, b.N, 1, s);
         any = true;

@@ -78,7 +78,10 @@ const char       *rans4x16_hip_last_error(const rans4x16_hip_ctx *ctx);
 /* Host-buffer batches: n independent blocks, semantics of n calls of the functions in part 1
  * with caller-provided output buffers (out[i] != NULL, out_size[i] = capacity in / size out).
  * Returns the number of failed blocks (their out_size[i] is set to 0 and status[i] != 0 if
- * status is not NULL), or -1 if the batch could not be run at all. */
+ * status is not NULL), or -1 if the batch could not be run at all.
+ * An X_STRIPE block that fails on decode reports what rans4x16_hip_uncompress_dev reports for it: CAPACITY where the
+ * stored size is not out_size[i] (:1379), SIZE for an inconsistent header, else the status of its first failing plane
+ * (UNSUPPORTED for a plane that is itself a stripe stream; CONTEXT / RLE in the stricter cases above). */
 int rans4x16_hip_compress_batch(rans4x16_hip_ctx *ctx, int n,
                                 const unsigned char *const *in, const unsigned int *in_size,
                                 unsigned char *const *out, unsigned int *out_size,
