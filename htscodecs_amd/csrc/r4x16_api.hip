@@ -235,8 +235,6 @@ extern "C" int rans4x16_hip_timing_read(rans4x16_hip_ctx *c, int which, double *
 // A chain launch's per-class stream counts (SchedWs.cnt[SCHED_COUNT + class], written by the scheduler's scan) are copied
 // behind it on its stream into pinned memory; the host folds them into per-kind sums when they are read (or when many
 // are waiting).  Off, none of this happens: no copy, no event, no synchronisation.
-extern "C" int r4x16_dec_route_kind(u32 ci);
-extern "C" int r4x16_enc_route_kind(u32 ci, int *freq_table);
 static int route_fold(rans4x16_hip_ctx *c)
 {
     int rc = 0;
@@ -339,7 +337,6 @@ size_t r4x16_ws_room(rans4x16_hip_ctx *c)
 
 // The side streams of the chain kernels' class launches (R4Fork, r4x16_dev.h); nullptr where they are switched off
 // (option sched_concurrent = 0), cannot be made, or the context is a lane of the host pipeline.
-extern "C" int r4x16_cu_count(void);
 #define FORK_ONE_BLOCK_BYTES (256u << 10)
 static const R4Fork *fork_for(rans4x16_hip_ctx *c)
 {
@@ -637,12 +634,6 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
     return ws_order_end(c, s);
 }
 
-extern "C" int r4x16_dec_residency(u32 nsym, int order, u32 bits, int *streams_per_wave, int *waves_per_cu, int short_ring);
-extern "C" int r4x16_enc_residency(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu);
-extern "C" int r4x16_dec_residency_kind(u32 nsym, int order, u32 bits, bool short_step, int *streams_per_wave, int *waves_per_cu);
-extern "C" int r4x16_enc_residency_records(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu);
-extern "C" int r4x16_cu_count(void);
-
 extern "C" int rans4x16_hip_residency(rans4x16_hip_ctx *c, int decode, unsigned int nsym, int order, unsigned int shift,
                                       int *streams_per_cu, int *lanes_live_per_wave, int *compute_units)
 {
@@ -936,11 +927,6 @@ extern "C" unsigned char *rans_uncompress_4x16(unsigned char *in, unsigned int i
 // rANS 4x8 (CRAM 3.0): include/rans4x8_hip.h.  Same context, same workspace; kernels at the end of
 // r4x16_encode.hip / r4x16_decode.hip.
 // =============================================================================================
-extern "C" size_t r4x8_dec_ws_bytes(size_t nblk);
-extern "C" void r4x8_launch_decode(const BatchArgs *, u8 *, int, int, hipStream_t);
-extern "C" void r4x8_launch_encode(const BatchArgs *, const EncWs *, int, int, hipStream_t);
-extern "C" u32 r4x8_compress_bound(u32);
-
 extern "C" unsigned int rans4x8_hip_compress_bound(unsigned int size) { return r4x8_compress_bound(size); }
 
 extern "C" int rans4x8_hip_compress_dev(rans4x16_hip_ctx *c, int n,

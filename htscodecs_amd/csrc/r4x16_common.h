@@ -17,7 +17,6 @@ typedef uint64_t u64;
 typedef int32_t  i32;
 
 // container flag bits, rANS_static4x16pr.c:38-43
-#define X_ORDER  0x01
 #define X_STRIPE 0x08
 #define X_NOSZ   0x10
 #define X_CAT    0x20

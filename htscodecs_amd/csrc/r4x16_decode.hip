@@ -12,10 +12,10 @@
 //                 and status.  Replaces :1578-1629, rle.c:142-187, pack.c:211-348.
 #include <stdlib.h>
 #include <stdio.h>
-#include <mutex>
 #include <type_traits>
 #include "r4x16_dev.h"
 #include "r4x16_sched.h"
+#include "r4x16_host.h"
 
 static inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -2614,51 +2614,6 @@ static const struct { u32 bytes; int qpw; int lv; } DEC_CLASSES[] = {
     // sixteen streams of up to 47 symbols (8,640 bytes with the word ring; 48 take 9,008) per CU, 4,096 per chip
     {8976, 4, 10},
 };
-// workgroups of `lds_bytes` each that one CU holds at once (1,280-byte LDS granules, 32 wave slots)
-static int resident_per_cu(size_t lds_bytes, int waves_per_wg)
-{
-    const int granules = (int)((lds_bytes + 1279) / 1280);
-    int n = granules ? 128 / granules : 32;
-    if (n * waves_per_wg > 32) n = 32 / waves_per_wg;
-    return n < 1 ? 1 : n;
-}
-// Per-device state of the launchers: a process may hold contexts on several devices, on several host threads.
-#define MAX_DEVICES 64
-static std::mutex g_dev_mu;
-static int g_cu_count[MAX_DEVICES];
-static u32 g_setup_done[MAX_DEVICES];
-static int cu_count()
-{
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= MAX_DEVICES) return 256;
-    std::lock_guard<std::mutex> g(g_dev_mu);
-    int &n = g_cu_count[dev];
-    if (!n && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)) n = 256;
-    return n;
-}
-extern "C" int r4x16_cu_count(void) { return cu_count(); }
-// true exactly once per (current device, bit): kernel attributes such as the dynamic-LDS limit are per device
-extern "C" bool r4x16_first_on_device(u32 bit)
-{
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= MAX_DEVICES) return true;
-    std::lock_guard<std::mutex> g(g_dev_mu);
-    if (g_setup_done[dev] & bit) return false;
-    g_setup_done[dev] |= bit;
-    return true;
-}
-static void lds_limit(const void *kernel, int bytes)
-{
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) fprintf(stderr, "rans4x16_hip: cannot raise a kernel's dynamic LDS limit to %d bytes: %s\n", bytes, hipGetErrorString(e));
-}
-extern "C" int r4x16_resident_grid(size_t lds_bytes, int waves_per_wg, int wanted)
-{
-    const int cap = cu_count() * resident_per_cu(lds_bytes, waves_per_wg);
-    return wanted < cap ? wanted : cap;
-}
 // ---- streams -> classes, on the device ---------------------------------------------------------
 // class ids: index into DEC_CLASSES, then one catch-all per tree depth (images too large for LDS)
 #define DEC_NCLS ((u32)(sizeof(DEC_CLASSES) / sizeof(DEC_CLASSES[0])))
@@ -2712,7 +2667,7 @@ __global__ __launch_bounds__(256) void k_cls_scatter(const u32 *cls, int nitems,
     if (c != CLS_NONE) list[base[c] + rank] = (u32)i;
 }
 
-// positions and lists from per-item classes and per-class counts (also used by the encoder's launcher)
+// positions and lists from per-item classes and per-class counts (r4x16_sched.h; also used by the 4x8 encoder's launcher)
 extern "C" void r4x16_launch_cls_zero(u32 *count, hipStream_t s)     // (a kernel, not hipMemsetAsync: the runtime's first
 {                                                                      //  memset on a stream cost 0.5 s once per process)
     hipLaunchKernelGGL(k_cls_zero, dim3(1), dim3(64), 0, s, count);
@@ -2736,14 +2691,9 @@ static int dec_class_qpw(u32 ci, const R4Opts *o)
 // one_row_only: the items are order-0 streams (one-row images): only the classes such an image can fall into are launched
 static void launch_dec_chain_of(const DecWs *ws, const DecItem *items, int nitems, bool one_row_only, hipStream_t s0, const R4Fork *fk, const R4Opts *o, SchedHint *hint)
 {
-    // Classes side by side (r4x16_sched.h, PLAN): the class launches are dealt out over the caller's stream and the side
-    // streams (fk), and the device-written plan gives each class its stream's share of the chip.  Without side streams
-    // (a lane of the host pipeline, option sched_concurrent = 0) the launches go out in stream order, every class with
-    // the whole chip - as up to round 3.
-    const int nq = fk ? fk->n + 1 : 1;
+    // the classes go out side by side or in stream order: sched_launch_classes (r4x16_sched.hip)
     typedef void (*chain_fn)(const DecItem *, DecDesc *, const u32 *, u32 *, int, u32, int);
-    struct Launch { chain_fn kern; int grid, qpw; size_t ldsb; u32 ci, bytes; };
-    Launch todo[CLS_MAX];
+    SchedLaunch todo[CLS_MAX];
     int ntodo = 0;
     SchedPlan plan;
     DecClassTab tab;
@@ -2751,16 +2701,17 @@ static void launch_dec_chain_of(const DecWs *ws, const DecItem *items, int nitem
     tab.split_o0 = fk != nullptr;           // (launches in stream order: a wave takes both kinds, 4,096 x 1 MiB q8 with X_RLE 26.7 against 28.2 ms)
     tab.sort = o->v[OPT_SCHED_SORT] != 0;
     tab.short_ring = o->v[OPT_DEC_SHORT_RING] != 0;
-    plan.ncls = DEC_NCLS; plan.concurrent = nq > 1 ? (u32)o->v[OPT_SCHED_CONCURRENT] : 0u; plan.claim = o->v[OPT_SCHED_CLAIM] != 0; plan.pad = 0;
-    for (u32 ci = 0; ci < CLS_MAX; ci++) { plan.qpw[ci] = 16; plan.wgs_full[ci] = 0; plan.queue[ci] = 0xff; plan.rate[ci] = 0.f; }
+    sched_plan_init(plan, fk ? fk->n + 1 : 1, o);
+    plan.ncls = DEC_NCLS;
+    const int cus = r4x16_cu_count();
     for (u32 ci = 0; ci < DEC_NCLS; ci++) {
         const auto &c = DEC_CLASSES[ci];
         tab.bytes[ci] = c.bytes; tab.lv[ci] = (u32)c.lv;
         const int qpw = dec_class_qpw(ci, o);
         const size_t ldsb = (size_t)qpw * c.bytes;
         plan.qpw[ci] = (u16)qpw;
-        plan.wgs_full[ci] = (u16)(cu_count() * resident_per_cu(ldsb, 1));
-        plan.rate[ci] = sched_rate(qpw, 1, resident_per_cu(ldsb, 1), cu_count());
+        plan.wgs_full[ci] = (u16)(cus * sched_resident_per_cu(ldsb, 1));
+        plan.rate[ci] = sched_rate(qpw, 1, sched_resident_per_cu(ldsb, 1), cus);
         // (an order-0 image: at most IMG_O0_BYTES; depth 4 only as the lone row of an alphabet beyond 150 symbols)
         const bool skip = (c.lv == 9 && !tab.short_ring) || (c.lv == 10 && !ws->mid_budget) ||
                           (one_row_only && (c.lv == 1 || c.lv == 2 || (c.lv >= 5 && c.lv != 8) || c.bytes > (c.lv == 4 ? 22528u : IMG_O0_BYTES + RING_BYTES + 128u))) ||
@@ -2769,51 +2720,28 @@ static void launch_dec_chain_of(const DecWs *ws, const DecItem *items, int nitem
         chain_fn kern =
             c.lv == 10 ? k_dec_chain<true, 10> : c.lv == 9 ? k_dec_chain<true, 1, 4> : c.lv == 1 ? k_dec_chain<true, 1> : c.lv == 5 ? k_dec_chain<true, 5> : (c.lv == 2 || c.lv == 8) ? k_dec_chain<true, 2> : c.lv == 3 ? k_dec_chain<true, 3> :
             (c.lv == 6 || c.lv == 7) ? k_dec_chain<true, 6> : k_dec_chain<true, 4>;
-        todo[ntodo++] = Launch{kern, r4x16_resident_grid(ldsb, 1, (nitems + qpw - 1) / qpw), qpw, ldsb, ci, c.bytes};
+        todo[ntodo++] = SchedLaunch{(const void *)kern, r4x16_resident_grid(ldsb, 1, (nitems + qpw - 1) / qpw), WAVE, ldsb, ci, qpw, qpw, c.bytes};
     }
-    u8 qof[CLS_MAX];
-    int lorder[CLS_MAX];
-    {
-        int cls_of[CLS_MAX];
-        for (int k = 0; k < ntodo; k++) cls_of[k] = (int)todo[k].ci;
-        if (hint) hint->learn = (o->v[OPT_SCHED_LEARN] & 2) != 0;
-        sched_assign_queues(plan, cls_of, ntodo, nq, hint, qof, lorder, (hint && hint->work && o->v[OPT_SCHED_TRACE]) ? "decode" : nullptr);
-        for (int k = 0; k < ntodo; k++) plan.queue[todo[k].ci] = qof[k];
-    }
-    r4x16_sched_zero(&ws->sched, s0);
-    hipLaunchKernelGGL(k_dec_classify, dim3((nitems + 255) / 256), dim3(256), 0, s0, items, nitems, tab, ws->sched);
-    r4x16_sched_group(&ws->sched, nitems, &plan, s0);
-    if (r4x16_first_on_device(1u)) {
-        lds_limit((const void *)k_dec_chain<true, 1>, 163840);
-        lds_limit((const void *)k_dec_chain<true, 1, 4>, 163840);
-        lds_limit((const void *)k_dec_chain<true, 10>, 163840);
-        lds_limit((const void *)k_dec_chain<true, 5>, 163840);
-        lds_limit((const void *)k_dec_chain<true, 2>, 163840);
-        lds_limit((const void *)k_dec_chain<true, 3>, 163840);
-        lds_limit((const void *)k_dec_chain<true, 4>, 163840);
-        lds_limit((const void *)k_dec_chain<true, 6>, 163840);
-    }
-    const int dyn = o->v[OPT_SCHED_CLAIM] != 0;
-    auto go = [&](const Launch &L, hipStream_t s) {
-        DecDesc *desc = ws->desc;
-        const u32 *list = ws->sched.list;
-        u32 *cnt = ws->sched.cnt + L.ci;
-        int qpw = L.qpw, dyn_ = dyn;
-        u32 bytes = L.bytes;
-        void *args[] = {(void *)&items, (void *)&desc, (void *)&list, (void *)&cnt, (void *)&qpw, (void *)&bytes, (void *)&dyn_};
-        r4x16_sched_launch((const void *)L.kern, dim3(L.grid), dim3(WAVE), args, L.ldsb, s);
-    };
-    unsigned used = 0;
-    for (int k = 0; k < ntodo; k++) used |= 1u << (qof[k] % (unsigned)nq);
-    if (fk) fk->begin(s0, used);
-    for (int j = 0; j < ntodo; j++) { const int k = lorder[j]; go(todo[k], fk ? fk->pick(s0, (unsigned)qof[k]) : s0); }
-    if (fk) { fk->end(s0, used); r4x16_sched_hint_save(&ws->sched, hint, s0); }
-    if (one_row_only) return;                 // (such an image always fits a class)
-    // images that fit no LDS class: tables stay in global memory (L2); after the join, in stream order
+    if (r4x16_first_on_device(FIRST_DEC_CHAIN))
+        for (chain_fn k : std::initializer_list<chain_fn>{k_dec_chain<true, 1>, k_dec_chain<true, 1, 4>, k_dec_chain<true, 10>, k_dec_chain<true, 5>,
+                                                          k_dec_chain<true, 2>, k_dec_chain<true, 3>, k_dec_chain<true, 4>, k_dec_chain<true, 6>})
+            sched_lds_limit((const void *)k, 163840);
+    // images that fit no LDS class: tables stay in global memory (L2); one catch-all per tree depth
+    // (one_row_only: such an image always fits a class)
     const int grid = (nitems + 15) / 16;
-    go(Launch{k_dec_chain<false, 2>, grid, 16, 0, DEC_NCLS + 0, 0u}, s0);
-    go(Launch{k_dec_chain<false, 3>, grid, 16, 0, DEC_NCLS + 1, 0u}, s0);
-    go(Launch{k_dec_chain<false, 4>, grid, 16, 0, DEC_NCLS + 2, 0u}, s0);
+    const SchedLaunch tail[3] = {
+        {(const void *)(chain_fn)k_dec_chain<false, 2>, grid, WAVE, 0, DEC_NCLS + 0, 16, 16, 0u},
+        {(const void *)(chain_fn)k_dec_chain<false, 3>, grid, WAVE, 0, DEC_NCLS + 1, 16, 16, 0u},
+        {(const void *)(chain_fn)k_dec_chain<false, 4>, grid, WAVE, 0, DEC_NCLS + 2, 16, 16, 0u},
+    };
+    DecDesc *desc = ws->desc;
+    const u32 *list = ws->sched.list;
+    u32 *cnt, bytes;
+    int qpw, dyn = o->v[OPT_SCHED_CLAIM] != 0;
+    void *args[] = {(void *)&items, (void *)&desc, (void *)&list, (void *)&cnt, (void *)&qpw, (void *)&bytes, (void *)&dyn};
+    sched_launch_classes(plan, SchedBatch{&ws->sched, nitems, s0, fk, o, hint, 2u, "decode"}, todo, ntodo, tail, one_row_only ? 0 : 3,
+        [&] { hipLaunchKernelGGL(k_dec_classify, dim3((nitems + 255) / 256), dim3(256), 0, s0, items, nitems, tab, ws->sched); },
+        [&](const SchedLaunch &L) { cnt = ws->sched.cnt + L.ci; qpw = L.qpw; bytes = L.bytes; return args; });
 }
 // LDS bytes a stream may spend on direct blocks (level 6) when `nblk` streams are to be resident at once: the largest
 // direct class that still holds the batch in ONE round of the chip (0: none does - the batch is large enough to be
@@ -2823,11 +2751,11 @@ extern "C" u32 r4x16_dec_direct_budget(int nblk, const R4Opts *o)
 {
     const int rounds = (int)o->v[OPT_DEC_DIRECT];
     if (rounds <= 0 || nblk <= 0) return 0u;
-    const long cus = cu_count();
+    const long cus = r4x16_cu_count();
     const long per_cu = (nblk + cus * rounds - 1) / (cus * rounds);
     u32 best = 0;
     for (const auto &c : DEC_CLASSES)
-        if (c.lv == 6 && (long)resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw >= per_cu && c.bytes > best) best = c.bytes;
+        if (c.lv == 6 && (long)sched_resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw >= per_cu && c.bytes > best) best = c.bytes;
     return best;
 }
 // LDS bytes a stream may spend on mid rows (level 10): the mid class's, if `nblk` streams fit `dec_mid` rounds of it
@@ -2837,7 +2765,7 @@ extern "C" u32 r4x16_dec_mid_budget(int nblk, const R4Opts *o)
     const long rounds = o->v[OPT_DEC_MID];
     if (rounds <= 0 || nblk <= 0) return 0u;
     for (const auto &c : DEC_CLASSES)
-        if (c.lv == 10 && (long)nblk <= rounds * cu_count() * resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw) return c.bytes;
+        if (c.lv == 10 && (long)nblk <= rounds * r4x16_cu_count() * sched_resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw) return c.bytes;
     return 0u;
 }
 // Streams of one kind that a CU holds at once in the chain decoder (host arithmetic on the class table above).
@@ -2852,7 +2780,7 @@ extern "C" int r4x16_dec_residency(u32 nsym, int order, u32 bits, int *streams_p
     for (const auto &c : DEC_CLASSES) {
         if ((u32)c.lv != lv || need > c.bytes) continue;
         *streams_per_wave = c.qpw;
-        *waves_per_cu = resident_per_cu((size_t)c.qpw * c.bytes, 1);
+        *waves_per_cu = sched_resident_per_cu((size_t)c.qpw * c.bytes, 1);
         return 0;
     }
     *streams_per_wave = 16; *waves_per_cu = 8;              // tables in global memory: bounded by wave slots
@@ -2894,7 +2822,7 @@ extern "C" int r4x16_dec_residency_kind(u32 nsym, int order, u32 bits, bool shor
     for (const auto &c : DEC_CLASSES) {
         if ((u32)c.lv != lv || need > c.bytes) continue;
         *streams_per_wave = c.qpw;
-        *waves_per_cu = resident_per_cu((size_t)c.qpw * c.bytes, 1);
+        *waves_per_cu = sched_resident_per_cu((size_t)c.qpw * c.bytes, 1);
         return 0;
     }
     return -1;
@@ -2907,7 +2835,7 @@ extern "C" int r4x16_launch_dec_back(const BatchArgs *a, const DecWs *ws, int ba
     // kernel, round 3's first answer to the old trip's fixed ~19 ms per MiB, stays selectable: R4X16_BACK_WG_PER_CU=N
     // takes it up to N blocks per CU.
     const int wg_per_cu = (int)o->v[OPT_BACK_WG_PER_CU];
-    if ((long)nblk <= (long)wg_per_cu * cu_count()) {
+    if ((long)nblk <= (long)wg_per_cu * r4x16_cu_count()) {
         hipLaunchKernelGGL(k_dec_back<BACK_THREADS>, dim3(nblk), dim3(BACK_THREADS), 0, s, *a, *ws, base);
         return 1;
     }
@@ -2966,7 +2894,6 @@ extern "C" void r4x16_launch_stripe(const u8 *src, u8 *dst, u32 n, u32 N, int jo
 // =============================================================================================
 #define X8_LOW   (1u << 23)
 #define X8_BITS  12u
-#define IMG8_MAX_NSYM 257u                                // 256 symbols + the flagged one
 #define IMG8_SLOT ((528u + 257u * 832u + 255u) & ~255u)   // alpha[257] + 257 four-level rows
 
 struct X8Item {
@@ -3230,140 +3157,13 @@ __device__ __forceinline__ u32 chain_decode8(GImg img, u32 nsym, gcu8 *bytes, u3
     return bad;
 }
 
-// The same loop with the image and a 256-byte window of the stream's bytes in LDS (as k_dec_chain has them for 4x16):
-// the first version read its tables through L2 and fetched every renormalisation byte with a load that depended on the
-// step before (19-25 GB/s).  Ring: quarters h, h+1, h+2 of the stream are resident while the cursor is in quarter h (a
-// trip of eight steps moves it by at most 64 bytes), quarter h+3 waits in registers.
+// LDS bytes of a stream's byte ring beside its image (k8_dec_chain<true>): as RING_BYTES, a 256-byte window of the
+// stream with the mirror of its head
 #define X8_RING 272u
-#define X8_TRIP 8
-template <int ORDER, int LV>
-__device__ __forceinline__ u32 chain_decode8_lds(const u8 *img_lds, u32 nsym, u8 *ring, gcu8 *bytes, u32 bytes_len, gu8 *out, u32 out_sz,
-                                                 u32 x, bool active, u32 lane)
-{
-    const LImg img{lds_addr(img_lds)};
-    const u32 k = lane & 3;
-    const u32 rows = img_alpha_bytes(nsym), roww = img_row_bytes(nsym);
-    const u32 below = (1u << k) - 1u;
-    u32 count, pos;
-    if (ORDER == 0) { count = (out_sz + 3 - k) >> 2; pos = k; }
-    else { const u32 q = out_sz >> 2; count = q + (k == 3 ? out_sz - 4 * q : 0); pos = k * q; }
-    if (!active) count = 0;
-    // stream bytes relative to the 16-byte aligned address below `bytes`
-    gcu8 *abase = (gcu8 *)((u64)bytes & ~15ull);
-    const u32 off0 = (u32)((u64)bytes & 15ull);
-    const u32 avail = off0 + bytes_len;
-    const u32 lastc = avail ? (avail - 1u) >> 4 : 0u;
-    const bool loadable = active && avail != 0;
-    auto load_chunk = [&](u32 c) -> u32x4 {
-        u32x4 v = {0, 0, 0, 0};
-        if (loadable) v = *(gcu32x4 *)(abase + 16ull * (c < lastc ? c : lastc));   // past the input the last chunk repeats: never taken
-        return v;
-    };
-    if (active) {
-        const u32x4 c0 = load_chunk(k);
-        *(u32x4 *)(ring + 16 * k) = c0;
-        *(u32x4 *)(ring + 64 + 16 * k) = load_chunk(k + 4);
-        *(u32x4 *)(ring + 128 + 16 * k) = load_chunk(k + 8);
-        if (k == 0) *(u32x2 *)(ring + 256) = c0.xy;           // the first 8 bytes once more behind the ring: no wrap inside a window
-    }
-    u32x4 pend = load_chunk(12 + k);
-    u32 half = 0;
-    __syncthreads();
-    const u32 rbase = lds_addr(ring);
-    u32 row = rows, cursor = 0, bad = 0, t = 0;
-    u32x2 root = LV == 2 ? img.ld64(row) : u32x2{0u, 0u};
-    if (ORDER == 1 && count) bad = img.ld16(0) & ROW_EMPTY;
-    // Output: a trip's bytes are gathered in registers and leave at the top of the NEXT trip - the wave's vector-memory
-    // counter retires in order, so a store issued just before the ring refill would make the refill's wait for its
-    // prefetched chunk a wait for that store's acknowledgement (byte stores every step: 330 ns per step instead of 250).
-    // Order 1: a chain's eight consecutive bytes, one 8-byte store.  Order 0: step T puts byte 4T + k on chain k; the
-    // quad transposes four steps' bytes (k_dec_chain's scheme) and each lane stores the dword of one step.
-    u32 accA = 0, accB = 0, pendA = 0, pendB = 0;
-    u64 pend_at = 0;
-    bool pending = false;
-    const u32 qcount = ORDER == 0 ? (out_sz >> 2) : 0u;       // order 0: steps in which all four chains produce a byte
-    while (wave_any(t < count)) {
-        if (pending) {
-            if (ORDER == 1) *(GAS u32x2_unaligned *)(out + pend_at) = u32x2{pendA, pendB};
-            else { *(GAS u32_unaligned *)(out + pend_at) = pendA; *(GAS u32_unaligned *)(out + pend_at + 16) = pendB; }
-            pending = false;
-        }
-        // gathered route for this trip: every step of it produces a byte on this chain (order 1) / on all four chains
-        const bool whole = active && (ORDER == 1 ? t + X8_TRIP <= count : t + X8_TRIP <= qcount);   // (idle quads point at another's item)
-#pragma unroll
-        for (int u = 0; u < X8_TRIP; u++) {
-            const bool live = t + (u32)u < count;
-            // the eight bytes at the quad's cursor - all it can take in one step - are requested before the table
-            // look-ups, as three aligned dwords (k_dec_chain does the same with its words)
-            const u32 P0 = off0 + cursor, ra = rbase + (P0 & 252u);
-            const u32 d0 = *(LAS const volatile u32 *)(unsigned long)ra, d1 = *(LAS const volatile u32 *)(unsigned long)(ra + 4u),
-                      d2 = *(LAS const volatile u32 *)(unsigned long)(ra + 8u);
-            u32 xn = x;
-            const u32 s = lookup_step<LV>(img, row, X8_BITS, 4095u, xn, LV == 2 ? &root : nullptr);
-            // the next row's root: requested as soon as the symbol is known, used at the top of the next step
-            const u32 rown = ORDER == 1 ? rows + __umul24(s, roww) : row;
-            const u32x2 rootn = (LV == 2 && ORDER == 1) ? img.ld64_now(rown) : root;
-            const u32 al = img.ld16(2 * s);
-            x = live ? xn : x;
-            bad |= live ? (al & ROW_BAD) : 0u;
-            if (ORDER == 1) {
-                row = live ? rown : row;
-                root.x = live ? rootn.x : root.x;
-                root.y = live ? rootn.y : root.y;
-                bad |= (t + (u32)u + 1 < count) ? (al & ROW_EMPTY) : 0u;
-            }
-            if (live && !whole) { out[pos] = (u8)al; pos += ORDER == 0 ? 4 : 1; }
-            if (u < 4) accA = __builtin_amdgcn_alignbit(al, accA, 8); else accB = __builtin_amdgcn_alignbit(al, accB, 8);
-            // a chain takes one byte if x < 2^23 and a second one if x < 2^15; chains are served in the order 0..3, and
-            // nothing is read past the end (rANS_byte.h:541-551)
-            const bool w1 = live && x < X8_LOW, w2 = live && x < (1u << 15);
-            const u32 m1 = quad_ballot(w1, lane), m2 = quad_ballot(w2, lane);
-            const u32 pre = __popc(m1 & below) + __popc(m2 & below);        // bytes the chains before this one take: 0..6
-            const u32 at = cursor + pre;
-            const u32 want = (w1 ? 1u : 0u) + (w2 ? 1u : 0u);
-            const u32 room = at < bytes_len ? bytes_len - at : 0u;
-            const u32 take = want < room ? want : room;
-            const u32 wlo = __builtin_amdgcn_alignbyte(d1, d0, P0), whi = __builtin_amdgcn_alignbyte(d2, d1, P0);
-            const u64 win = (((u64)whi << 32) | wlo) >> (8u * pre);
-            const u32 b0 = (u32)win & 0xffu, b1 = ((u32)win >> 8) & 0xffu;
-            const u32 x1 = (x << 8) | b0, x2 = (x1 << 8) | b1;
-            x = take > 1 ? x2 : take ? x1 : x;
-            cursor += __popc(m1) + __popc(m2);
-        }
-        if (ORDER == 1) {
-            if (whole) { pendA = accA; pendB = accB; pend_at = pos; pos += X8_TRIP; pending = true; }
-        } else {
-            // (uniform over a quad: out_sz is) 4 x 4 byte transposes: lane j gets the dword of step t + j / t + 4 + j
-            const u32 sel = k | ((4u + k) << 8);
-            const u32 A0 = quad_bcast0(accA), A1 = quad_bcast1(accA), A2 = quad_bcast2(accA), A3 = quad_bcast3(accA);
-            const u32 B0 = quad_bcast0(accB), B1 = quad_bcast1(accB), B2 = quad_bcast2(accB), B3 = quad_bcast3(accB);
-            const u32 dA = __builtin_amdgcn_perm(__builtin_amdgcn_perm(A3, A2, sel), __builtin_amdgcn_perm(A1, A0, sel), 0x05040100u);
-            const u32 dB = __builtin_amdgcn_perm(__builtin_amdgcn_perm(B3, B2, sel), __builtin_amdgcn_perm(B1, B0, sel), 0x05040100u);
-            if (whole) { pendA = dA; pendB = dB; pend_at = 4ull * (t + k); pos += 4 * X8_TRIP; pending = true; }
-        }
-        t += X8_TRIP;
-        const u32 nh = (off0 + cursor) >> 6;
-        if (wave_any(active && nh != half)) {
-            if (active && nh != half) {
-                const u32 slot = ((nh + 2) & 3u) * 64u + 16u * k;
-                *(u32x4 *)(ring + slot) = pend;
-                if (slot == 0) *(u32x2 *)(ring + 256) = pend.xy;
-                pend = load_chunk(4 * (nh + 3) + k);
-                half = nh;
-            }
-            __syncthreads();
-        }
-    }
-    if (pending) {
-        if (ORDER == 1) *(GAS u32x2_unaligned *)(out + pend_at) = u32x2{pendA, pendB};
-        else { *(GAS u32_unaligned *)(out + pend_at) = pendA; *(GAS u32_unaligned *)(out + pend_at + 16) = pendB; }
-    }
-    return bad;
-}
 
 // streams grouped by LDS need (k_cls_scan / k_cls_scatter as for 4x16): class 0 - one-row images (order 0), 16 per
-// wave; class 1 - images up to X8_SLOT1 (order 1, up to 50 symbols: the quality alphabets), 12 per wave; class 2 - the
-// rest, tables through L2
+// wave; class 1 - images up to X8_SLOT1A (order 1, up to 47 symbols), 15 per wave; class 2 - images up to X8_SLOT1
+// (order 1, up to 50 symbols: the quality alphabets), 12 per wave; class 3 - the rest, tables through L2
 #define X8_SLOT0 (IMG_O0_BYTES + X8_RING)
 #define X8_SLOT1A 5456u      // round 4: up to 47 symbols (the 45-46 of the quality alphabets and the flagged extra one) - fifteen per wave, two waves per CU (30 streams)
 #define X8_SLOT1 6416u
@@ -3415,8 +3215,8 @@ __global__ __launch_bounds__(WAVE) void k8_dec_chain(const X8Item *items, BatchA
         __syncthreads();
         const u8 *im = lds + (u64)quad * slot_bytes;
         u8 *ring = lds + (u64)quad * slot_bytes + (slot_bytes - X8_RING);
-        // (round 4: the 4x16 decoder's loop with rANS 4x8's byte renormalisation - full trips without liveness selects,
-        //  speculative roots, gathered stores - instead of round 2's chain_decode8_lds)
+        // (the 4x16 decoder's loop with rANS 4x8's byte renormalisation: full trips without liveness selects,
+        //  speculative roots, gathered stores)
 #define X8_RUN(O, L) bad |= chain_decode_lds<O, L, TRIP_STEPS, true>(im, nsym, ring, bytes, blen, out, osz, x0, X8_BITS, active && order == O && lv == L, lane)
         X8_RUN(0, 2); X8_RUN(0, 3); X8_RUN(0, 4);
         X8_RUN(1, 2);                                          // (X8_SLOT1 holds 2-read images only: up to 50 symbols)
@@ -3449,7 +3249,7 @@ extern "C" void r4x8_launch_decode(const BatchArgs *a, u8 *ws, int base, int nbl
     r4x16_launch_cls_zero(cls_count, s);
     hipLaunchKernelGGL(k8_classify, dim3((nblk + 255) / 256), dim3(256), 0, s, (const X8Item *)items, nblk, cls, cls_count);
     r4x16_launch_cls_group(cls, nblk, cls_count, cls_list, s);
-    if (r4x16_first_on_device(16u)) lds_limit((const void *)k8_dec_chain<true>, 163840);
+    if (r4x16_first_on_device(FIRST_DEC8_CHAIN)) sched_lds_limit((const void *)k8_dec_chain<true>, 163840);
     // (measured with the shape as a launch parameter, gpurun_out/r04_ab_x8*.txt, 11,520 x 1 MiB q40: a round takes ~58 ms whatever the wave holds - 12, 14 or 15 streams in
     //  each of two waves per CU: 100 GB/s; 8 x 3 waves: 87; 10 per wave does NOT make three waves: 54,560 bytes round up
     //  past a third of the LDS - so the class holds as many streams as two waves can: 2 x 15 x 5,456 = 163,680 bytes)

@@ -1,15 +1,20 @@
 // =============================================================================================
-// r4x16_enc_chain.hip - launcher of k_enc_chain (r4x16_enc_chain.h), the LDS size classes, and the instantiations for
-// u16 images.  The packed-row instantiation lives in r4x16_enc_chain_pk.hip.
+// r4x16_enc_chain.hip - the encoder's LDS size classes, their classify kernel and the table of launches that
+// r4x16_launch_enc_chain hands to the class launcher (sched_launch_classes, r4x16_sched.hip); the residency and route
+// queries over the same tables; the instantiations of k_enc_chain (r4x16_enc_chain.h) for u16 images, and the rANS 4x8
+// chain kernel.  The packed-row instantiation lives in r4x16_enc_chain_pk.hip, the record kernel in
+// r4x16_enc_chain_rec.hip: their kernels are reached through the accessors declared below.
 // =============================================================================================
 #include "r4x16_enc_chain.h"
+#include "r4x16_host.h"
 
-// r4x16_enc_chain_pk.hip: k_enc_chain<true, true> / k_enc_chain<true, true, true>
+// r4x16_enc_chain_pk.hip: k_enc_chain<true, true> / k_enc_chain<true, true, true>; r4x16_enc_chain_rec.hip: k_enc_chain_rec
 extern "C" void r4x16_enc_chain_pk_lds_limit(int bytes);
 extern "C" const void *r4x16_enc_chain_pk_kernel(int freq_table);
+extern "C" void r4x16_enc_chain_rec_lds_limit(int bytes);
+extern "C" const void *r4x16_enc_chain_rec_kernel(void);
 
 // ---- host-callable launcher ----------------------------------------------------------------------
-extern "C" bool r4x16_first_on_device(u32 bit);                                          // r4x16_decode.hip
 // {LDS bytes per stream, streams per wave}; LDS is allocated in 1,280-byte granules.
 // q4/q8 images are ~0.4 KB, an order-0 row 0.8 KB, q40 4.6 KB (16 x 4,800 = 60 granules: 2 waves, 32 streams per CU — fuller waves measured faster than more waves)
 // LDS size classes: bytes per stream (image + word ring).  A workgroup takes as many streams as
@@ -35,8 +40,6 @@ static const EncRecClass ENC_REC_CLASSES[] = {
     {2576, 15}, {4112, 9}, {8080, 5}, {13584, 3}, {20368, 2}, {32000, 1}, {40960, 1}, {53760, 1}, {81920, 1}, {163840, 1},
 };
 #define ENC_REC_NCLS ((u32)(sizeof(ENC_REC_CLASSES) / sizeof(ENC_REC_CLASSES[0])))
-extern "C" void r4x16_enc_chain_rec_lds_limit(int bytes);
-extern "C" const void *r4x16_enc_chain_rec_kernel(void);
 #define ENC_NCLS    ((u32)(sizeof(ENC_CLASSES) / sizeof(ENC_CLASSES[0])))
 #define ENC_PK_NCLS ((u32)(sizeof(ENC_PK_CLASSES) / sizeof(ENC_PK_CLASSES[0])))
 // (kind: 0 u16 rows, 1 packed rows, ENC_KIND_PK_SHORT their short-index kind)
@@ -48,8 +51,6 @@ static int enc_class_qpw(u32 bytes, u32 kind, const R4Opts *o)
     const int cap = (int)o->v[OPT_ENC_QPW_CAP];                  // tuning aid (default 64)
     return (int)(fit > (u32)cap ? (u32)cap : fit);
 }
-extern "C" int r4x16_resident_grid(size_t lds_bytes, int waves_per_wg, int wanted);      // r4x16_decode.hip
-extern "C" int r4x16_cu_count(void);
 struct EncClassTab { u32 n; u32 sort; u32 bytes[CLS_MAX]; u32 pk[CLS_MAX]; };     // classes: u16 images, then packed ones, then records
 __global__ __launch_bounds__(256) void k_enc_classify(const EncItem *items, int nitems, EncClassTab tab, SchedWs sw)
 {
@@ -114,36 +115,27 @@ static EncShape enc_rec_shape(u32 r, const R4Opts *o, bool o0 = false)
     sh.ldsb = (size_t)sh.qpw * c.bytes;
     return sh;
 }
-static int enc_wgs_per_cu(const EncShape &sh)
-{
-    const long granules = ((long)sh.ldsb + 1279) / 1280;      // LDS is allocated in 1,280-byte granules
-    long wgs = granules ? 128 / granules : 32;
-    if (wgs * sh.waves > 32) wgs = 32 / sh.waves;
-    return wgs < 1 ? 1 : (int)wgs;
-}
 extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t s0, const R4Fork *fk, const R4Opts *o, SchedHint *hint)
 {
-    // classes side by side over the caller's stream and the side streams, each with its stream's share of the chip
-    // (launch_dec_chain_of, r4x16_sched.h); class index ci = position in the classify table: u16 classes, packed
-    // classes, short-index packed classes, record classes
-    const int nq = fk ? fk->n + 1 : 1;
-    struct Launch { const void *kern; int grid; EncShape sh; u32 ci; };
-    Launch todo[CLS_MAX];
+    // the classes go out side by side or in stream order: sched_launch_classes (r4x16_sched.hip); class index ci =
+    // position in the classify table: u16 classes, packed classes, short-index packed classes, record classes
+    SchedLaunch todo[CLS_MAX];
     int ntodo = 0;
     EncClassTab tab;
     tab.n = 0;
     tab.sort = o->v[OPT_SCHED_SORT] != 0;
     SchedPlan plan;
-    plan.concurrent = nq > 1 ? (u32)o->v[OPT_SCHED_CONCURRENT] : 0u; plan.claim = o->v[OPT_SCHED_CLAIM] != 0; plan.pad = 0;
-    for (u32 ci = 0; ci < CLS_MAX; ci++) { plan.qpw[ci] = 16; plan.wgs_full[ci] = 0; plan.queue[ci] = 0xff; plan.rate[ci] = 0.f; }
+    sched_plan_init(plan, fk ? fk->n + 1 : 1, o);
     const int cus = r4x16_cu_count();
+    // (kern == nullptr: the class keeps its id and its plan entry, and gets no launch)
     auto add = [&](u32 pk, u32 bytes, const EncShape &sh, const void *kern) {
         const u32 ci = tab.n++;
         tab.pk[ci] = pk; tab.bytes[ci] = bytes;
-        plan.qpw[ci] = (u16)sh.qpw; plan.wgs_full[ci] = (u16)(cus * enc_wgs_per_cu(sh));
-        plan.rate[ci] = sched_rate(sh.qpw, sh.waves, enc_wgs_per_cu(sh), cus);
+        const int wgs = sched_resident_per_cu(sh.ldsb, sh.waves);
+        plan.qpw[ci] = (u16)sh.qpw; plan.wgs_full[ci] = (u16)(cus * wgs);
+        plan.rate[ci] = sched_rate(sh.qpw, sh.waves, wgs, cus);
         if (!kern) return;
-        todo[ntodo++] = Launch{kern, r4x16_resident_grid(sh.ldsb, sh.waves, (nitems + sh.qpw - 1) / sh.qpw), sh, ci};
+        todo[ntodo++] = SchedLaunch{kern, r4x16_resident_grid(sh.ldsb, sh.waves, (nitems + sh.qpw - 1) / sh.qpw), WAVE * sh.waves, sh.ldsb, ci, sh.qpw, sh.spw, sh.bytes};
     };
     for (u32 k = 0; k < ENC_NCLS; k++) add(0, ENC_CLASSES[k], enc_rows_shape(k, nitems, o), (const void *)k_enc_chain<true, false>);
     for (u32 k = 0; k < ENC_PK_NCLS; k++) add(1, ENC_PK_CLASSES[k], enc_rows_shape(ENC_NCLS + k, nitems, o), r4x16_enc_chain_pk_kernel(0));
@@ -153,43 +145,23 @@ extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t 
     add(3, ENC_O0_ROWS_BYTES, enc_rows_shape(0, nitems, o, ENC_O0_ROWS_BYTES), (const void *)k_enc_chain<true, false>);
     add(4, ENC_O0_REC_BYTES, enc_rec_shape(0, o, true), ws->direct_budget ? r4x16_enc_chain_rec_kernel() : nullptr);
     plan.ncls = tab.n;
-    u8 qof[CLS_MAX];
-    int lorder[CLS_MAX];
-    {
-        int cls_of[CLS_MAX];
-        for (int k = 0; k < ntodo; k++) cls_of[k] = (int)todo[k].ci;
-        if (hint) hint->learn = (o->v[OPT_SCHED_LEARN] & 1) != 0;
-        sched_assign_queues(plan, cls_of, ntodo, nq, hint, qof, lorder, (hint && hint->work && o->v[OPT_SCHED_TRACE]) ? "encode" : nullptr);
-        for (int k = 0; k < ntodo; k++) plan.queue[todo[k].ci] = qof[k];
-    }
-    r4x16_sched_zero(&ws->sched, s0);
-    hipLaunchKernelGGL(k_enc_classify, dim3((nitems + 255) / 256), dim3(256), 0, s0, (const EncItem *)ws->items, nitems, tab, ws->sched);
-    r4x16_sched_group(&ws->sched, nitems, &plan, s0);
-    if (r4x16_first_on_device(4u)) {
-        (void)hipFuncSetAttribute((const void *)k_enc_chain<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    if (r4x16_first_on_device(FIRST_ENC_CHAIN)) {
+        sched_lds_limit((const void *)k_enc_chain<true, false>, 163840);
         r4x16_enc_chain_pk_lds_limit(163840);
         r4x16_enc_chain_rec_lds_limit(163840);
     }
-    const int dyn = o->v[OPT_SCHED_CLAIM] != 0;
-    auto go = [&](const Launch &L, hipStream_t s) {
-        EncItem *items = ws->items;
-        const u32 *rcptab = ws->rcptab;
-        u8 *dump = ws->dump;
-        const u32 *list = ws->sched.list;
-        u32 *cnt = ws->sched.cnt + L.ci;
-        int qpw = L.sh.qpw, spw = L.sh.spw, dyn_ = dyn;
-        u32 bytes = L.sh.bytes;
-        void *args[] = {(void *)&items, (void *)&rcptab, (void *)&dump, (void *)&list, (void *)&cnt, (void *)&qpw, (void *)&spw, (void *)&bytes, (void *)&dyn_};
-        r4x16_sched_launch(L.kern, dim3(L.grid), dim3(WAVE * L.sh.waves), args, L.sh.ldsb, s);
-    };
-    unsigned used = 0;
-    for (int k = 0; k < ntodo; k++) used |= 1u << (qof[k] % (unsigned)nq);
-    if (fk) fk->begin(s0, used);
-    for (int j = 0; j < ntodo; j++) { const int k = lorder[j]; go(todo[k], fk ? fk->pick(s0, (unsigned)qof[k]) : s0); }
-    if (fk) { fk->end(s0, used); r4x16_sched_hint_save(&ws->sched, hint, s0); }
-    EncShape sh;
-    sh.qpw = 16; sh.waves = 1; sh.spw = 16; sh.bytes = 0u; sh.ldsb = 0;
-    go(Launch{(const void *)k_enc_chain<false, false>, (nitems + 15) / 16, sh, tab.n}, s0);     // images too large for LDS
+    // images too large for LDS
+    const SchedLaunch tail = {(const void *)k_enc_chain<false, false>, (nitems + 15) / 16, WAVE, 0, tab.n, 16, 16, 0u};
+    EncItem *items = ws->items;
+    const u32 *rcptab = ws->rcptab;
+    u8 *dump = ws->dump;
+    const u32 *list = ws->sched.list;
+    u32 *cnt, bytes;
+    int qpw, spw, dyn = o->v[OPT_SCHED_CLAIM] != 0;
+    void *args[] = {(void *)&items, (void *)&rcptab, (void *)&dump, (void *)&list, (void *)&cnt, (void *)&qpw, (void *)&spw, (void *)&bytes, (void *)&dyn};
+    sched_launch_classes(plan, SchedBatch{&ws->sched, nitems, s0, fk, o, hint, 1u, "encode"}, todo, ntodo, &tail, 1,
+        [&] { hipLaunchKernelGGL(k_enc_classify, dim3((nitems + 255) / 256), dim3(256), 0, s0, (const EncItem *)ws->items, nitems, tab, ws->sched); },
+        [&](const SchedLaunch &L) { cnt = ws->sched.cnt + L.ci; qpw = L.qpw; spw = L.spw; bytes = L.bytes; return args; });
 }
 // LDS bytes a stream may spend on symbol records when `nblk` streams are to be resident at once: the largest record
 // class that still holds the batch in one round of the chip (0: none).  R4X16_ENC_DIRECT=0 never; =N up to N rounds.
@@ -200,12 +172,8 @@ extern "C" u32 r4x16_enc_direct_budget(int nblk, const R4Opts *o)
     const long cus = r4x16_cu_count();
     const long per_cu = (nblk + cus * rounds - 1) / (cus * rounds);
     u32 best = 0;
-    for (const auto &c : ENC_REC_CLASSES) {
-        const long granules = ((long)c.qpw * c.bytes + 1279) / 1280;      // LDS is allocated in 1,280-byte granules
-        long wgs = 128 / granules;
-        if (wgs > 32) wgs = 32;
-        if (wgs * c.qpw >= per_cu && c.bytes > best) best = c.bytes;
-    }
+    for (const auto &c : ENC_REC_CLASSES)       // (one wave per workgroup)
+        if ((long)sched_resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw >= per_cu && c.bytes > best) best = c.bytes;
     return best;
 }
 // The row kind of a class id of r4x16_launch_enc_chain's table (u16 classes, packed classes of both kinds, record classes,
@@ -232,12 +200,10 @@ extern "C" int r4x16_enc_residency_records(u32 nsym, int order, int *streams_per
     if (img > ENC_IMG_MAIN) return -1;
     for (const auto &c : ENC_REC_CLASSES) {
         if (img + ENC_RING_BYTES > c.bytes) continue;
-        const long granules = ((long)c.qpw * c.bytes + 1279) / 1280;
-        long wgs = 128 / granules;
-        if (wgs > 32) wgs = 32;
+        const int wgs = sched_resident_per_cu((size_t)c.qpw * c.bytes, 1);      // (one wave per workgroup)
         *streams_per_wave = c.qpw;
-        *waves_per_cu = (int)wgs;
-        return (int)wgs * c.qpw;
+        *waves_per_cu = wgs;
+        return wgs * c.qpw;
     }
     return -1;
 }
@@ -316,8 +282,7 @@ __global__ __launch_bounds__(256) void k8_enc_chain_pipe(EncItem *items, const u
 extern "C" void r4x8_enc_chain_launch(EncItem *items, const u32 *rcptab, u8 *dump, const u32 *list, const u32 *count, int nblk, u32 slot_bytes,
                                       int qpw, int spw, hipStream_t s)
 {
-    if (r4x16_first_on_device(32u))
-        (void)hipFuncSetAttribute((const void *)k8_enc_chain_pipe, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    if (r4x16_first_on_device(FIRST_ENC8_CHAIN)) sched_lds_limit((const void *)k8_enc_chain_pipe, 163840);
     const int waves = (qpw + spw - 1) / spw;
     hipLaunchKernelGGL(k8_enc_chain_pipe, dim3((nblk + qpw - 1) / qpw), dim3(WAVE * waves), ENC_LRCP_BYTES + (size_t)qpw * slot_bytes, s,
                        items, rcptab, dump, list, count, slot_bytes, qpw, spw);

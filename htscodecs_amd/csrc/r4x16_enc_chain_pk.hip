@@ -10,8 +10,8 @@
 
 extern "C" void r4x16_enc_chain_pk_lds_limit(int bytes)
 {
-    (void)hipFuncSetAttribute((const void *)k_enc_chain<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute((const void *)k_enc_chain<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    sched_lds_limit((const void *)k_enc_chain<true, true>, bytes);
+    sched_lds_limit((const void *)k_enc_chain<true, true, true>, bytes);
 }
 extern "C" const void *r4x16_enc_chain_pk_kernel(int freq_table)
 {

@@ -350,6 +350,6 @@ __global__ __launch_bounds__(WAVE) void k_enc_chain_rec(EncItem *items, const u3
 
 extern "C" void r4x16_enc_chain_rec_lds_limit(int bytes)
 {
-    (void)hipFuncSetAttribute((const void *)k_enc_chain_rec, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    sched_lds_limit((const void *)k_enc_chain_rec, bytes);
 }
 extern "C" const void *r4x16_enc_chain_rec_kernel(void) { return (const void *)k_enc_chain_rec; }

@@ -15,6 +15,7 @@
 #include "r4x16_dev.h"
 #include "r4x16_sched.h"
 #include "r4x16_enc_step.h"
+#include "r4x16_host.h"
 
 #define FRONT_DYN_LDS  36864u                           // LDS counters: alphabets up to 96 symbols (three workgroups per CU;
                                                         // 61,440 bytes / two per CU: +4 % on PACK|RLE blocks, +2 % on 64 KiB ones)
@@ -818,15 +819,6 @@ struct PieceOut {
         p += cnt; cnt = 0;
     }
 };
-
-// var_put_u32 (varint.h:85-104) through a global-address-space pointer (see wg_pack on FLAT accesses)
-__device__ __forceinline__ u32 var_put_g(gu8 *cp, u32 v)
-{
-    u32 groups = 1;
-    for (u32 t = v >> 7; t; t >>= 7) groups++;
-    for (u32 g = groups; g-- > 0; ) *cp++ = (u8)(((v >> (7 * g)) & 0x7f) | (g ? 0x80 : 0));
-    return groups;
-}
 
 // bytes whose flag in an LDS table of 256 bytes is set
 __device__ __forceinline__ u32 flag_mask16(u32x4 v, const u8 *flags)
@@ -1702,7 +1694,6 @@ __global__ __launch_bounds__(256) void k_enc_vsize(BatchArgs a, int base, int nb
 }
 
 // ---- host-callable launchers -------------------------------------------------------------------
-extern "C" bool r4x16_first_on_device(u32 bit);                                          // r4x16_decode.hip
 extern "C" void r4x16_launch_enc_front(const BatchArgs *a, const EncWs *ws, int base, int nblk, hipStream_t s, const R4Opts *o)
 {
     if (ws->var) {
@@ -1710,8 +1701,7 @@ extern "C" void r4x16_launch_enc_front(const BatchArgs *a, const EncWs *ws, int 
         r4x16_voff_scan(ws->voff, nblk, s);
     }
     // static + dynamic LDS exceeds the 64 KB default; gfx950 has 160 KB per CU
-    if (r4x16_first_on_device(2u))
-        (void)hipFuncSetAttribute((const void *)k_enc_front, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    if (r4x16_first_on_device(FIRST_ENC_FRONT)) sched_lds_limit((const void *)k_enc_front, 65536);
     const u32 dynb0 = o->v[OPT_FRONT_LDS] > 0 ? (u32)o->v[OPT_FRONT_LDS] : FRONT_DYN_LDS;  // tuning aid
     const u32 dynb = dynb0 < RLE_LDS_BYTES ? RLE_LDS_BYTES : dynb0 > 65536u - 8192u ? 65536u - 8192u : dynb0;   // (the run-length split's slots; wg_hist8's 16 x 257 counters are smaller)
     hipLaunchKernelGGL(k_enc_front, dim3(nblk), dim3(FRONT_THREADS), dynb, s, *a, *ws, base, dynb);
@@ -2064,14 +2054,9 @@ __global__ __launch_bounds__(FINISH_THREADS) void k8_enc_finish(BatchArgs a, Enc
     if (tid == 0) { a.status[i] = ST_OK; a.out_size[i] = total; }
 }
 
-extern "C" void r4x16_launch_cls_group(const u32 *cls, int nitems, u32 *count, u32 *list, hipStream_t s);   // r4x16_decode.hip
-extern "C" void r4x16_launch_cls_zero(u32 *count, hipStream_t s);
-extern "C" void r4x8_enc_chain_launch(EncItem *items, const u32 *rcptab, u8 *dump, const u32 *list, const u32 *count, int nblk, u32 slot_bytes,
-                                      int qpw, int spw, hipStream_t s);    // r4x16_enc_chain.hip
 extern "C" void r4x8_launch_encode(const BatchArgs *a, const EncWs *ws, int base, int nblk, hipStream_t s)
 {
-    if (r4x16_first_on_device(8u))
-        (void)hipFuncSetAttribute((const void *)k8_enc_front, hipFuncAttributeMaxDynamicSharedMemorySize, FRONT_DYN_LDS);
+    if (r4x16_first_on_device(FIRST_ENC8_FRONT)) sched_lds_limit((const void *)k8_enc_front, FRONT_DYN_LDS);
     const u32 room = (u32)(ws->scratch_stride > 0xffffffffull ? 0xffffffffu : ws->scratch_stride);
     hipLaunchKernelGGL(k8_enc_front, dim3(nblk), dim3(FRONT_THREADS), FRONT_DYN_LDS, s, *a, *ws, base);
     // (the 4x16 encoder's grouping arrays, with round 2's plain grouping by class: key = class, cnt = count / start / cursor)

@@ -1,5 +1,7 @@
-// r4x16_host.h - what the two host-side translation units of librans4x16_hip.so share: the context, the error
+// r4x16_host.h - what the host-side translation units of librans4x16_hip.so share: the context, the error
 // macro and the entry points of the host-buffer batch machinery (r4x16_host.hip) used by the C ABI (r4x16_api.hip).
+// It is also the one place that declares the launchers and queries the kernel units define: those units include it,
+// so that a definition that drifts from its declaration does not compile.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -33,6 +35,21 @@ u32  r4x16_dec_direct_budget(int nblk, const R4Opts *);
 u32  r4x16_dec_mid_budget(int nblk, const R4Opts *);
 u32  r4x16_enc_direct_budget(int nblk, const R4Opts *);
 void r4x16_launch_stripe(const u8 *, u8 *, u32, u32, int, hipStream_t);
+// streams per CU of the chain kernels, by host arithmetic on the class tables (rans4x16_hip_residency), and the row kind
+// of a class id as the route read-out counts it
+int  r4x16_dec_residency(u32 nsym, int order, u32 bits, int *streams_per_wave, int *waves_per_cu, int short_ring);
+int  r4x16_dec_residency_kind(u32 nsym, int order, u32 bits, bool short_step, int *streams_per_wave, int *waves_per_cu);
+int  r4x16_enc_residency(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu);
+int  r4x16_enc_residency_records(u32 nsym, int order, int *streams_per_wave, int *waves_per_cu);
+int  r4x16_dec_route_kind(u32 ci);
+int  r4x16_enc_route_kind(u32 ci, int *freq_table);
+// rANS 4x8
+size_t r4x8_dec_ws_bytes(size_t nblk);
+void r4x8_launch_decode(const BatchArgs *, u8 *ws, int base, int nblk, hipStream_t);
+void r4x8_launch_encode(const BatchArgs *, const EncWs *, int base, int nblk, hipStream_t);
+void r4x8_enc_chain_launch(EncItem *items, const u32 *rcptab, u8 *dump, const u32 *list, const u32 *count, int nblk, u32 slot_bytes,
+                           int qpw, int spw, hipStream_t);
+u32  r4x8_compress_bound(u32 size);
 }
 
 struct TimedLaunch { hipEvent_t a, b; };

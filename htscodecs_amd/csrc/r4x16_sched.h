@@ -16,7 +16,11 @@
 //   * PLAN   the classes of a batch run SIDE BY SIDE: the class launches are dealt out over six streams (R4Fork), every
 //            class is launched with the grid it would need alone, and a device-written plan gives it `seats` workgroups -
 //            its stream's share of the chip by work (bytes / resident streams) - the others leave at once.
+// Also declared here, defined in r4x16_sched.hip, for every unit that launches kernels: the residency rule
+// (sched_resident_per_cu), the per-device state (CU count, once-per-device setup, dynamic-LDS limits), and the one
+// class launcher of both chain directions (sched_launch_classes) - at the end of this file.
 #pragma once
+#include <functional>
 #include "r4x16_dev.h"
 
 // what the host knows about each class: streams per workgroup and the workgroups a full chip holds
@@ -171,16 +175,35 @@ struct SchedHint {
 };                // pinned, [2 * CLS_MAX]: sums, then longest - and behind them the SCHED_CNT_WORDS
                                                 // dwords of SchedWs.cnt (counts, seats: for the trace); nullptr: no hint kept
 #define SCHED_HINT_BYTES (2 * CLS_MAX * sizeof(u64) + SCHED_CNT_WORDS * sizeof(u32))
-// launch_order: the order in which the launches should go out - the classes the last batch used first (an EMPTY class's
-// launch still has to get its workgroups through the dispatcher, which on a chip full of seated persistent workgroups
-// takes until LDS frees up: 18 ms were seen - anything queued behind it on its stream waits that long)
-void sched_assign_queues(SchedPlan &plan, const int *todo_cls, int ntodo, int nq, SchedHint *hint, u8 *queue_of_todo,
-                         int *launch_order, const char *trace = nullptr);
-
 extern "C" {
-void r4x16_sched_hint_save(const SchedWs *w, SchedHint *hint, hipStream_t s);
 void r4x16_voff_scan(u64 *v, int n, hipStream_t s);
-void r4x16_sched_zero(const SchedWs *w, hipStream_t s);
-void r4x16_sched_group(const SchedWs *w, int nitems, const SchedPlan *plan, hipStream_t s);
-void r4x16_sched_launch(const void *kernel, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t s);
+// the older grouping of rANS 4x8: lists from per-item classes and per-class counts (r4x16_decode.hip)
+void r4x16_launch_cls_zero(u32 *count, hipStream_t s);
+void r4x16_launch_cls_group(const u32 *cls, int nitems, u32 *count, u32 *list, hipStream_t s);
+// The chip, and the launchers' per-device state (a process may hold contexts on several devices, on several threads).
+int r4x16_cu_count(void);                    // of the current device
+// true exactly once per (current device, bit): kernel attributes such as the dynamic-LDS limit are per device
+bool r4x16_first_on_device(u32 bit);
+enum : u32 { FIRST_DEC_CHAIN = 1u, FIRST_ENC_FRONT = 2u, FIRST_ENC_CHAIN = 4u, FIRST_ENC8_FRONT = 8u, FIRST_DEC8_CHAIN = 16u, FIRST_ENC8_CHAIN = 32u };
+int r4x16_resident_grid(size_t lds_bytes, int waves_per_wg, int wanted);     // min(wanted, what the chip holds at once)
 }
+// workgroups of `lds_bytes` and `waves_per_wg` waves each that one CU holds at once: LDS is allocated in 1,280-byte
+// granules, 128 per CU; 32 wave slots; at least 1
+int sched_resident_per_cu(size_t lds_bytes, int waves_per_wg);
+// raises a kernel's dynamic-LDS limit; a failure is reported on stderr
+void sched_lds_limit(const void *kernel, int bytes);
+
+// One launcher for the classes of a batch, both chain directions.  sched_plan_init: the defaults of a plan for `nq`
+// streams (every class 16 streams per workgroup, no figures, not launched); the caller sets ncls and its classes' figures.
+void sched_plan_init(SchedPlan &plan, int nq, const R4Opts *o);
+// one launch of a chain kernel: its class (counters: SchedWs.cnt + ci) and the shape the kernel is told (streams per
+// workgroup, per wave, LDS bytes per stream)
+struct SchedLaunch { const void *kern; int grid, block; size_t ldsb; u32 ci; int qpw, spw; u32 bytes; };
+// fk: the side streams (nullptr: all in stream order on s0); learn_bit: of option sched_learn (1 encode, 2 decode);
+// name: for option sched_trace
+struct SchedBatch { const SchedWs *ws; int nitems; hipStream_t s0; const R4Fork *fk; const R4Opts *o; SchedHint *hint; u32 learn_bit; const char *name; };
+// Enqueues on s0: zero, the caller's classify kernel, group; then the launches of `todo` - dealt out over the streams by
+// sched_assign_queues, in its launch order, between fork and join - the hint's copy, and the `tail` launches (streams
+// that fit no LDS class) in stream order.  `args_of`: a launch's kernel arguments, read before it is called again.
+void sched_launch_classes(SchedPlan &plan, const SchedBatch &b, const SchedLaunch *todo, int ntodo, const SchedLaunch *tail, int ntail,
+                          const std::function<void()> &classify, const std::function<void **(const SchedLaunch &)> &args_of);

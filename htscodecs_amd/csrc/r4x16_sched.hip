@@ -1,6 +1,8 @@
-// r4x16_sched.hip - the device-side grouping, ordering and launch plan of the chain kernels' streams (r4x16_sched.h).
+// r4x16_sched.hip - the device-side grouping, ordering and launch plan of the chain kernels' streams (r4x16_sched.h),
+// the chip arithmetic and per-device state every launcher shares, and the one class launcher of both chain directions.
 #include "r4x16_sched.h"
 #include <algorithm>
+#include <mutex>
 #include <stdio.h>
 
 __global__ __launch_bounds__(256) void k_sched_zero(SchedWs w)
@@ -95,22 +97,21 @@ __global__ __launch_bounds__(256) void k_sched_scatter(SchedWs w, int nitems)
     if (has) w.list[w.bins[key] + rank] = (u32)i;
 }
 
-extern "C" void r4x16_sched_zero(const SchedWs *w, hipStream_t s)
+static void r4x16_sched_zero(const SchedWs *w, hipStream_t s)
 {
     hipLaunchKernelGGL(k_sched_zero, dim3((2u * SCHED_BINS + 255u) / 256u), dim3(256), 0, s, *w);
 }
-extern "C" void r4x16_sched_group(const SchedWs *w, int nitems, const SchedPlan *plan, hipStream_t s)
+static void r4x16_sched_group(const SchedWs *w, int nitems, const SchedPlan *plan, hipStream_t s)
 {
     hipLaunchKernelGGL(k_sched_scan, dim3(1), dim3(1024), 0, s, *w, *plan);
     hipLaunchKernelGGL(k_sched_scatter, dim3((nitems + 255) / 256), dim3(256), 0, s, *w, nitems);
 }
-extern "C" void r4x16_sched_launch(const void *kernel, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t s)
-{
-    (void)hipLaunchKernel(kernel, grid, block, args, lds, s);
-}
 
-void sched_assign_queues(SchedPlan &plan, const int *todo_cls, int ntodo, int nq, SchedHint *hint, u8 *queue_of_todo,
-                         int *launch_order, const char *trace)
+// launch_order: the order in which the launches should go out - the classes the last batch used first (an EMPTY class's
+// launch still has to get its workgroups through the dispatcher, which on a chip full of seated persistent workgroups
+// takes until LDS frees up: 18 ms were seen - anything queued behind it on its stream waits that long)
+static void sched_assign_queues(SchedPlan &plan, const int *todo_cls, int ntodo, int nq, SchedHint *hint, u8 *queue_of_todo,
+                                int *launch_order, const char *trace)
 {
     double load[R4_FORK_STREAMS + 1] = {0}, floor_q[R4_FORK_STREAMS + 1] = {0};
     double t[CLS_MAX], tl[CLS_MAX], fl[CLS_MAX];
@@ -191,12 +192,86 @@ void sched_assign_queues(SchedPlan &plan, const int *todo_cls, int ntodo, int nq
         }
     }
 }
-extern "C" void r4x16_sched_hint_save(const SchedWs *w, SchedHint *hint, hipStream_t s)
+static void r4x16_sched_hint_save(const SchedWs *w, SchedHint *hint, hipStream_t s)
 {
     if (hint && hint->work) {
         (void)hipMemcpyAsync(hint->work, w->work, 2 * CLS_MAX * sizeof(u64), hipMemcpyDeviceToHost, s);
         (void)hipMemcpyAsync(hint->work + 2 * CLS_MAX, w->cnt, SCHED_CNT_WORDS * sizeof(u32), hipMemcpyDeviceToHost, s);
     }
+}
+
+// ---- the chip, and the per-device state of the launchers ----------------------------------------
+int sched_resident_per_cu(size_t lds_bytes, int waves_per_wg)
+{
+    const int granules = (int)((lds_bytes + 1279) / 1280);
+    int n = granules ? 128 / granules : 32;
+    if (n * waves_per_wg > 32) n = 32 / waves_per_wg;
+    return n < 1 ? 1 : n;
+}
+#define MAX_DEVICES 64
+static std::mutex g_dev_mu;
+static int g_cu_count[MAX_DEVICES];
+static u32 g_setup_done[MAX_DEVICES];
+extern "C" int r4x16_cu_count(void)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= MAX_DEVICES) return 256;
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    int &n = g_cu_count[dev];
+    if (!n && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)) n = 256;
+    return n;
+}
+extern "C" bool r4x16_first_on_device(u32 bit)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= MAX_DEVICES) return true;
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    if (g_setup_done[dev] & bit) return false;
+    g_setup_done[dev] |= bit;
+    return true;
+}
+void sched_lds_limit(const void *kernel, int bytes)
+{
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) fprintf(stderr, "rans4x16_hip: cannot raise a kernel's dynamic LDS limit to %d bytes: %s\n", bytes, hipGetErrorString(e));
+}
+extern "C" int r4x16_resident_grid(size_t lds_bytes, int waves_per_wg, int wanted)
+{
+    const int cap = r4x16_cu_count() * sched_resident_per_cu(lds_bytes, waves_per_wg);
+    return wanted < cap ? wanted : cap;
+}
+
+void sched_plan_init(SchedPlan &plan, int nq, const R4Opts *o)
+{
+    plan.ncls = 0; plan.concurrent = nq > 1 ? (u32)o->v[OPT_SCHED_CONCURRENT] : 0u; plan.claim = o->v[OPT_SCHED_CLAIM] != 0; plan.pad = 0;
+    for (u32 ci = 0; ci < CLS_MAX; ci++) { plan.qpw[ci] = 16; plan.wgs_full[ci] = 0; plan.queue[ci] = 0xff; plan.rate[ci] = 0.f; }
+}
+// Classes side by side (r4x16_sched.h, PLAN): dealt out over the caller's stream and the side streams (fk), each with its
+// stream's share of the chip by the device-written plan.  Without side streams (a lane of the host pipeline, option
+// sched_concurrent = 0) the launches go out in stream order, every class with the whole chip - as up to round 3.
+void sched_launch_classes(SchedPlan &plan, const SchedBatch &b, const SchedLaunch *todo, int ntodo, const SchedLaunch *tail, int ntail,
+                          const std::function<void()> &classify, const std::function<void **(const SchedLaunch &)> &args_of)
+{
+    const R4Fork *fk = b.fk;
+    const int nq = fk ? fk->n + 1 : 1;
+    u8 qof[CLS_MAX];
+    int lorder[CLS_MAX], cls_of[CLS_MAX];
+    for (int k = 0; k < ntodo; k++) cls_of[k] = (int)todo[k].ci;
+    if (b.hint) b.hint->learn = (b.o->v[OPT_SCHED_LEARN] & b.learn_bit) != 0;
+    sched_assign_queues(plan, cls_of, ntodo, nq, b.hint, qof, lorder, (b.hint && b.hint->work && b.o->v[OPT_SCHED_TRACE]) ? b.name : nullptr);
+    for (int k = 0; k < ntodo; k++) plan.queue[todo[k].ci] = qof[k];
+    r4x16_sched_zero(b.ws, b.s0);
+    classify();
+    r4x16_sched_group(b.ws, b.nitems, &plan, b.s0);
+    auto go = [&](const SchedLaunch &L, hipStream_t s) { (void)hipLaunchKernel(L.kern, dim3(L.grid), dim3(L.block), args_of(L), L.ldsb, s); };
+    unsigned used = 0;
+    for (int k = 0; k < ntodo; k++) used |= 1u << (qof[k] % (unsigned)nq);
+    if (fk) fk->begin(b.s0, used);
+    for (int j = 0; j < ntodo; j++) { const int k = lorder[j]; go(todo[k], fk ? fk->pick(b.s0, (unsigned)qof[k]) : b.s0); }
+    if (fk) { fk->end(b.s0, used); r4x16_sched_hint_save(b.ws, b.hint, b.s0); }
+    for (int k = 0; k < ntail; k++) go(tail[k], b.s0);     // after the join, in stream order
 }
 
 // Exclusive prefix sum, in place, of the n u64 entries of v (the sizes of the blocks' staging regions, written by a
