@@ -133,8 +133,8 @@ class _Ctx:
         return v.value
 
     def route_read(self, which, reset=True):
-        """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch") since the
-        last reset; needs option route_count = 1 while the calls run."""
+        """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
+        "result") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -145,12 +145,13 @@ class _Ctx:
 
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
-ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3}
+ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
     "expand": ("wave", "workgroup"),
     "launch": ("in_order", "side_by_side"),
+    "result": ("in_slot", "dense", "gathered"),
 }
 
 _tls = threading.local()
@@ -406,3 +407,72 @@ class DeviceCodec:
             status.data_ptr(), int(max_in_size), int(max_out_cap), int(total_out_cap), self._stream())
         if rc != 0:
             raise RuntimeError("uncompress_dev: " + self.ctx.error())
+
+    # ---- packed calls (include/rans4x16_hip.h part 2a): one dense arena, offsets written by the device ----------
+    def _packed_args(self, d_in, in_off, in_size, d_out, out_off, out_size, status):
+        t = self.torch
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == in_off.numel() + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+
+    def compress_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, order, max_in_size,
+                        d_order=None, total_in_size=0, out_capacity=None):
+        """rans4x16_hip_compress_packed_dev: block i at d_out[out_off[i]:out_off[i + 1]]; out_off (int64, n + 1 entries) is
+        written by the call, out_off[n] is what the batch needs.  out_capacity defaults to d_out's size."""
+        self._packed_args(d_in, in_off, in_size, d_out, out_off, out_size, status)
+        cap = d_out.numel() if out_capacity is None else int(out_capacity)
+        assert cap <= d_out.numel()
+        rc = self.L.rans4x16_hip_compress_packed_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), int(order),
+            d_order.data_ptr() if d_order is not None else None, int(max_in_size), int(total_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("compress_packed_dev: " + self.ctx.error())
+
+    def compress_best_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size,
+                             chosen=None, total_in_size=0, out_capacity=None):
+        """rans4x16_hip_compress_best_packed_dev: compress_best with the winners back to back in d_out."""
+        self._packed_args(d_in, in_off, in_size, d_out, out_off, out_size, status)
+        assert chosen is None or chosen.dtype == self.torch.int32
+        cap = d_out.numel() if out_capacity is None else int(out_capacity)
+        assert cap <= d_out.numel()
+        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        rc = self.L.rans4x16_hip_compress_best_packed_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), len(methods), meth,
+            chosen.data_ptr() if chosen is not None else None, int(max_in_size), int(total_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("compress_best_packed_dev: " + self.ctx.error())
+
+    def peek(self, d_in, in_off, in_size, fmt, raw_size, status, max_in_size):
+        """rans4x16_hip_peek_dev: first byte (fmt, int32) and stored uncompressed size (raw_size, int32 holding the
+        unsigned value; -1 = the stream carries none) of every block."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and in_off.dtype == t.int64 and in_size.dtype == t.int32
+        assert fmt.dtype == t.int32 and raw_size.dtype == t.int32 and status.dtype == t.int32
+        rc = self.L.rans4x16_hip_peek_dev(self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+                                          fmt.data_ptr(), raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("peek_dev: " + self.ctx.error())
+
+    def uncompress_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, max_in_size, max_out_size,
+                          nosz_size=None, out_capacity=None):
+        """rans4x16_hip_uncompress_packed_dev: every block decoded to d_out[out_off[i]:out_off[i + 1]], the sizes taken from
+        the streams (nosz_size: int32 tensor with the sizes of X_NOSZ blocks, optional).  in_off may have n or n + 1
+        entries (compress_packed's out_off goes straight in); the block count is in_size's."""
+        t = self.torch
+        n = in_size.numel()
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and in_off.numel() >= n and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == n + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert nosz_size is None or (nosz_size.dtype == t.int32 and nosz_size.numel() == n)
+        cap = d_out.numel() if out_capacity is None else int(out_capacity)
+        assert cap <= d_out.numel()
+        rc = self.L.rans4x16_hip_uncompress_packed_dev(
+            self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            nosz_size.data_ptr() if nosz_size is not None else None, int(max_in_size), int(max_out_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("uncompress_packed_dev: " + self.ctx.error())

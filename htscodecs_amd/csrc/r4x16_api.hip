@@ -184,6 +184,7 @@ extern "C" void rans4x16_hip_destroy(rans4x16_hip_ctx *c)
     if (c->ws_done) (void)hipEventDestroy(c->ws_done);
     if (c->ws) (void)hipFree(c->ws);
     if (c->xs) (void)hipFree(c->xs);
+    if (c->ps) (void)hipFree(c->ps);
     if (c->stage) (void)hipFree(c->stage);
     if (c->logtab) (void)hipFree(c->logtab);
     if (c->rcptab) (void)hipFree(c->rcptab);
@@ -265,7 +266,7 @@ static int route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, hipStrea
     HIPCHK(c, hipEventRecord(r.ev, s));
     return 0;
 }
-static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS};
+static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS, R4X16_RESULT_KINDS};
 static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS, "route kinds");
 extern "C" int rans4x16_hip_route_read(rans4x16_hip_ctx *c, int which, long *counts, int n, int reset)
 {
@@ -304,13 +305,14 @@ static int ensure_ws(rans4x16_hip_ctx *c, size_t bytes)
 // Blocks per workspace chunk: as many as the cap allows (the context's ceiling, and three quarters of what the device has
 // free right now - other contexts and other processes share the card), in equal chunks rather than full ones and a rest.
 // bytes(nb) = workspace of a chunk of nb blocks, monotone in nb.
+// held: bytes of other arenas of the context that bytes(nb) counts as well (they are not free, but the call reuses them).
 template <class F>
-static size_t plan_chunk(rans4x16_hip_ctx *c, size_t n, F bytes)
+static size_t plan_chunk(rans4x16_hip_ctx *c, size_t n, F bytes, size_t held = 0)
 {
     size_t cap = c->max_ws;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const size_t room = (free_b + c->ws_bytes) / 4 * 3;
+        const size_t room = (free_b + c->ws_bytes + held) / 4 * 3;
         if (room < cap) cap = room;
     }
     if (bytes(n) <= cap) return n;
@@ -324,12 +326,13 @@ static size_t plan_chunk(rans4x16_hip_ctx *c, size_t n, F bytes)
 }
 
 // What the arenas of one call may take together: plan_chunk's cap, for callers that hold a second arena (r4x16_best.hip)
-size_t r4x16_ws_room(rans4x16_hip_ctx *c)
+// held: an arena the caller keeps next to these and plans for itself (the packed calls' slots)
+size_t r4x16_ws_room(rans4x16_hip_ctx *c, size_t held)
 {
     size_t cap = c->max_ws;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const size_t room = (free_b + c->ws_bytes + c->xs_bytes) / 4 * 3;
+        const size_t room = (free_b + c->ws_bytes + c->xs_bytes + held) / 4 * 3;
         if (room < cap) cap = room;
     }
     return cap;
@@ -469,6 +472,7 @@ extern "C" int rans4x16_hip_compress_dev_sized(rans4x16_hip_ctx *c, int n,
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
+    if (c->opts.v[OPT_ROUTE_COUNT] && !c->in_stripe && !c->in_packed) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_IN_SLOT] += n;
     if (!d_order && (order & X_STRIPE)) {                 // one order for all blocks: N and the candidate methods are host knowledge
         BatchArgs sa;
         sa.in = d_in; sa.in_off = d_in_off; sa.in_size = d_in_size;
@@ -484,9 +488,25 @@ extern "C" int rans4x16_hip_compress_dev_sized(rans4x16_hip_ctx *c, int n,
         return r4x16_orders_stripe_compress_dev(c, n, sa, max_in_size, total_in_size, s);
     }
 
+    BatchArgs a;
+    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
+    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
+    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
+    return r4x16_enc_run(c, a, max_in_size, total_in_size, s, nullptr);
+}
+
+// The plain encode pipeline over a batch, in chunks of blocks under the workspace ceiling.  pk == nullptr: into the
+// caller's slots (a.out / a.out_off / a.out_cap).  pk != nullptr (rans4x16_hip_compress_packed_dev, dense route): the
+// slots are the context's own, a chunk's worth in the packed arena next to the workspace, and the finish writes every
+// stream at pk->out + pk->off[i]; a.out_size / a.status are the caller's arrays either way.
+int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64_t total_in_size, hipStream_t s, const PackedOut *pk)
+{
+    const int n = a.n;
+    const int order = a.order;
+    const int32_t *d_order = a.d_order;
     // Per block the workspace holds fixed-size records, tables and images, 256 KB for the pair counters and the nested
     // table stream, and - only for blocks that ask for X_PACK / X_RLE - a staging region sized from the block's own length
-    // and laid out on the device (enc_var_layout).  The payload itself is written into the caller's slot (k_enc_tables).
+    // and laid out on the device (enc_var_layout).  The payload itself is written into the block's slot (k_enc_tables).
     // The host only needs a bound for the staging regions together: from total_in_size when the caller gave it, from
     // n x max_in_size otherwise (per-block orders: every block may ask).
     const u64 scratch_stride = ENC_F_BYTES;
@@ -494,22 +514,26 @@ extern "C" int rans4x16_hip_compress_dev_sized(rans4x16_hip_ctx *c, int n,
     const u64 total_in = total_in_size ? total_in_size : (u64)n * max_in_size;
     auto var_for = [&](size_t nb) -> u64 { return xf ? enc_var_bound(nb, std::min<u64>(total_in, (u64)nb * max_in_size)) : 0; };
     EncWs w;
-    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w) + 4096; });
+    PackedSlots p = {};
+    const u64 slot_stride = pk ? r4x16_packed_stride(max_in_size, order, d_order != nullptr) : 0;
+    auto slots_for = [&](size_t nb) -> size_t { return pk ? r4x16_packed_carve(&p, nullptr, (size_t)n, nb, slot_stride) : 0; };
+    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w) + 4096 + slots_for(nb); },
+                              pk ? c->ps_bytes : 0);
     if (ws_order_begin(c, s) != 0) return -1;
     for (;;) {                                     // out of memory: walk the batch in smaller chunks
         const size_t need = enc_ws_layout(nullptr, chunk, scratch_stride, var_for(chunk), &w);
-        if (ensure_ws(c, need) == 0) break;
+        if (ensure_ws(c, need) == 0 && (!pk || r4x16_ensure_ps(c, slots_for(chunk)) == 0)) break;
         if (chunk == 1) return -1;
         chunk = (chunk + 1) / 2;
     }
     enc_ws_layout(c->ws, chunk, scratch_stride, var_for(chunk), &w);
     w.logtab = c->logtab;
     w.rcptab = c->rcptab;
-
-    BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
+    if (pk) {
+        r4x16_packed_carve(&p, c->ps, (size_t)n, chunk, slot_stride);
+        r4x16_launch_packed_slots(&a, &p, n, chunk, max_in_size, s);
+        a.out = p.slots; a.out_off = p.slot_off; a.out_cap = p.slot_cap;
+    }
 
     for (size_t base = 0; base < (size_t)n; base += chunk) {
         const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
@@ -528,8 +552,10 @@ extern "C" int rans4x16_hip_compress_dev_sized(rans4x16_hip_ctx *c, int n,
         if (c->opts.v[OPT_ROUTE_COUNT]) {
             if (route_snap(c, 0, w.sched.cnt, s) != 0) return -1;
             c->route[3][fk ? R4X16_LAUNCH_SIDE_BY_SIDE : R4X16_LAUNCH_IN_ORDER]++;
+            if (pk) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_DENSE] += nb;
         }
-        r4x16_launch_enc_finish(&a, &w, (int)base, nb, s);
+        if (pk) r4x16_launch_enc_finish_dense(&a, &w, (int)base, nb, pk, s);
+        else r4x16_launch_enc_finish(&a, &w, (int)base, nb, s);
     }
     HIPCHK(c, hipGetLastError());
     return ws_order_end(c, s);

@@ -380,6 +380,7 @@ extern "C" int rans4x16_hip_compress_best_dev(rans4x16_hip_ctx *c, int n,
     }
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->opts.v[OPT_ROUTE_COUNT] && !c->in_packed) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_IN_SLOT] += n;
     BatchArgs a;
     a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
     a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;

@@ -104,6 +104,14 @@ struct BatchArgs {
     int        n;
 };
 
+// Where the results of a packed call go (rans4x16_hip_compress_packed_dev): block i at out + off[i], off[i + 1] behind
+// its last byte; a block that would end beyond `capacity` is not written.
+struct PackedOut {
+    u8  *out;
+    u64 *off;        // [n + 1], written on the device (k_pk_scan, r4x16_packed.hip)
+    u64  capacity;
+};
+
 // ---------------------------------------------------------------------------------------------
 // Sequential byte reader for the single lane that parses headers and tables.  Keeps an
 // 8-byte window so that a run of dependent byte reads costs one global load per 8 bytes.

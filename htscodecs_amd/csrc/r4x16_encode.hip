@@ -1589,8 +1589,14 @@ __device__ __forceinline__ void slot_move(u8 *dst, const u8 *src, u32 n, u32 t)
     }
 }
 
-__global__ __launch_bounds__(FINISH_THREADS) void k_enc_finish(BatchArgs a, EncWs ws, int base)
+// DENSE (the packed calls): the slot is the context's own, the stream is assembled at pk.out + pk.off[i] - what
+// k_enc_size and the scan made of it - and nothing of it lies in the slot it is read from: every move is a group_copy.
+// The slot instantiation's last argument is an empty struct: it compiles to the code it was before the mode existed.
+struct SlotOut {};
+template <class PK>
+__global__ __launch_bounds__(FINISH_THREADS) void k_enc_finish(BatchArgs a, EncWs ws, int base, PK pk)
 {
+    constexpr bool DENSE = sizeof(PK) == sizeof(PackedOut);
     __shared__ u8 vbuf[16];
     __shared__ u32 vlen;
     const u32 lane = threadIdx.x;
@@ -1600,7 +1606,18 @@ __global__ __launch_bounds__(FINISH_THREADS) void k_enc_finish(BatchArgs a, EncW
     const EncItem *I0 = &ws.items[b], *I1 = &ws.items[gridDim.x + b], *I2 = &ws.items[2 * gridDim.x + b];
     u8 *out = a.out + a.out_off[i];
     const i32 st = D->status;
-    if (st != ST_OK) {
+    if constexpr (DENSE) {
+        // size and status are k_enc_size's: a block that failed there has no range, one that ends beyond the capacity is
+        // not written
+        const u64 at = pk.off[i], end = pk.off[i + 1];
+        if (end == at) return;
+        if (end > pk.capacity) {
+            if (lane == 0) { a.status[i] = ST_CAPACITY; a.out_size[i] = 0; }
+            return;
+        }
+        out = pk.out + at;
+    }
+    if (!DENSE && st != ST_OK) {
         if (lane == 0) { a.status[i] = st; a.out_size[i] = 0; }
         return;
     }
@@ -1673,16 +1690,58 @@ __global__ __launch_bounds__(FINISH_THREADS) void k_enc_finish(BatchArgs a, EncW
             // and table were written below `pos`, which the reference's own layout keeps below the payload's start
             // (the same bytes in a buffer of the same bound); a stream that did not would have been cut: reported.
             const u8 *psrc = (const u8 *)I0->scratch_end - pay;
-            if (out + pos > psrc) { if (lane == 0) { a.status[i] = ST_CAPACITY; a.out_size[i] = 0; } return; }
-            slot_move<FINISH_THREADS>(out + pos, psrc, pay, lane);
+            if (!DENSE && out + pos > psrc) { if (lane == 0) { a.status[i] = ST_CAPACITY; a.out_size[i] = 0; } return; }
+            if constexpr (DENSE) group_copy<FINISH_THREADS>(out + pos, psrc, pay, lane);      // (k_enc_size has made that check)
+            else slot_move<FINISH_THREADS>(out + pos, psrc, pay, lane);
             pos += pay;
         }
     }
     if (lane == 0) {
         out[0] = (u8)flags;
-        a.status[i] = ST_OK;
+        a.status[i] = ST_OK;                                          // (DENSE: what k_enc_size wrote)
         a.out_size[i] = pos;
     }
+}
+
+// The length of every stream of a chunk and its status, by k_enc_finish's arithmetic, without moving a byte: header,
+// run-length meta (compressed or raw), table (as serialised or nested), payload, the CAT fall-back at plen >= dlen, and
+// the "header would reach the payload" verdict against the block's internal slot.  One thread per block.
+__global__ __launch_bounds__(256) void k_enc_size(BatchArgs a, EncWs ws, int base, int nblk)
+{
+    const int b = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (b >= nblk) return;
+    const int i = base + b;
+    const EncDesc *D = &ws.desc[b];
+    const EncItem *I0 = &ws.items[b], *I1 = &ws.items[nblk + b], *I2 = &ws.items[2 * nblk + b];
+    i32 st = D->status;
+    u32 pos = 0;
+    if (st == ST_OK) {
+        pos = D->hdr_len;
+        const u32 dlen = D->dlen;
+        if (D->cat) pos += dlen;
+        else {
+            if (D->rle_on) {                                              // :1294-1310
+                const u32 mlen = D->rle_mlen;
+                const u32 clen = D->meta_tab_len + I1->pay_len;
+                const bool comp = clen < mlen;
+                pos += var_len(comp ? mlen * 2 : mlen * 2 + 1) + var_len(D->rle_lits) + (comp ? var_len(clen) + clen : mlen);
+            }
+            const u32 pay = I0->active ? I0->pay_len : 0;
+            u32 tab_len = D->tab_len;
+            const u32 tlen = tab_len - 1;
+            const u32 nlen = D->nest_tab_len + (D->nest_on ? I2->pay_len : 0);
+            if (D->nest_on && nlen + 6 < tab_len) tab_len = 1 + var_len(tlen) + var_len(nlen) + nlen;     // :772
+            if (tab_len + pay >= dlen) pos += dlen;                       // :1332-1337
+            else {
+                pos += tab_len;
+                const u8 *slot = a.out + a.out_off[i];
+                if (slot + pos > (const u8 *)I0->scratch_end - pay) { st = ST_CAPACITY; pos = 0; }
+                else pos += pay;
+            }
+        }
+    } else if (st == ST_CAPACITY && a.out_cap[i] == 0) st = ST_UNSUPPORTED;      // a block the slots were not sized for (k_pk_slots)
+    a.status[i] = st;
+    a.out_size[i] = st == ST_OK ? pos : 0u;
 }
 
 // The size of each block's staging region for the transforms (enc_var_layout); r4x16_voff_scan turns the sizes into
@@ -1712,7 +1771,13 @@ extern "C" void r4x16_launch_enc_tables(const BatchArgs *a, const EncWs *ws, int
 }
 extern "C" void r4x16_launch_enc_finish(const BatchArgs *a, const EncWs *ws, int base, int nblk, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_enc_finish, dim3(nblk), dim3(FINISH_THREADS), 0, s, *a, *ws, base);
+    hipLaunchKernelGGL(k_enc_finish<SlotOut>, dim3(nblk), dim3(FINISH_THREADS), 0, s, *a, *ws, base, SlotOut{});
+}
+extern "C" void r4x16_launch_enc_finish_dense(const BatchArgs *a, const EncWs *ws, int base, int nblk, const PackedOut *pk, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_enc_size, dim3((nblk + 255) / 256), dim3(256), 0, s, *a, *ws, base, nblk);
+    r4x16_launch_packed_scan(a->out_size, pk->off, base, nblk, s);
+    hipLaunchKernelGGL(k_enc_finish<PackedOut>, dim3(nblk), dim3(FINISH_THREADS), 0, s, *a, *ws, base, *pk);
 }
 extern "C" u32 r4x16_compress_bound(u32 size, int order) { return compress_bound(size, order); }
 

@@ -30,6 +30,9 @@ void r4x16_launch_enc_front(const BatchArgs *, const EncWs *, int, int, hipStrea
 void r4x16_launch_enc_tables(const BatchArgs *, const EncWs *, int, int, hipStream_t);
 void r4x16_launch_enc_chain(const EncWs *, int, hipStream_t, const R4Fork *, const R4Opts *, SchedHint *);
 void r4x16_launch_enc_finish(const BatchArgs *, const EncWs *, int, int, hipStream_t);
+// the packed calls' finish: sizes, offsets, then every stream assembled at out + off[i] (r4x16_encode.hip, r4x16_packed.hip)
+void r4x16_launch_enc_finish_dense(const BatchArgs *, const EncWs *, int, int, const PackedOut *, hipStream_t);
+void r4x16_launch_packed_scan(const u32 *size, u64 *off, int base, int nb, hipStream_t);
 u32  r4x16_compress_bound(u32 size, int order);
 u32  r4x16_dec_direct_budget(int nblk, const R4Opts *);
 u32  r4x16_dec_mid_budget(int nblk, const R4Opts *);
@@ -55,7 +58,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 4
+#define ROUTE_WHICH 5
 #define ROUTE_KINDS 8
 struct HostPipe;
 void r4x16_pipe_destroy(HostPipe *);
@@ -70,10 +73,18 @@ int r4x16_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, in
 // best-of-k and X_STRIPE under per-block orders (r4x16_best.hip); what they ask of r4x16_api.hip
 int r4x16_orders_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint64_t total_in_size,
                                      hipStream_t s);
-size_t r4x16_ws_room(rans4x16_hip_ctx *c);
+size_t r4x16_ws_room(rans4x16_hip_ctx *c, size_t held = 0);
 size_t r4x16_enc_ws_bytes(size_t nitems, u32 max_in_size, u64 total_in);
 int r4x16_stripe_uncompress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint32_t max_out_cap,
                                 uint32_t max_stripe_out, hipStream_t s);
+// the packed calls (r4x16_packed.hip): the internal bound-sized slots of a chunk of blocks in the context's packed arena,
+// and the plain encode pipeline of r4x16_api.hip with either finish (pk == nullptr: into the caller's slots)
+struct PackedSlots { u64 *slot_off; u32 *slot_cap; u8 *slots; u64 stride; };     // slot_off / slot_cap: [n], block i in slot i % chunk
+int r4x16_ensure_ps(rans4x16_hip_ctx *c, size_t bytes);
+size_t r4x16_packed_carve(PackedSlots *p, u8 *base, size_t n, size_t chunk, u64 stride);
+u64 r4x16_packed_stride(u32 max_in_size, int order, bool any_order);
+void r4x16_launch_packed_slots(const BatchArgs *a, const PackedSlots *p, int n, size_t chunk, u32 max_in_size, hipStream_t s);
+int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64_t total_in_size, hipStream_t s, const PackedOut *pk);
 int r4x16_run_host_batch(rans4x16_hip_ctx *c, int n, bool decode,
                           const unsigned char *const *in, const unsigned int *in_size,
                           unsigned char *const *out, unsigned int *out_size, const int *order, int *status);
@@ -102,6 +113,10 @@ struct rans4x16_hip_ctx {
     unsigned int dev_stripe_out = 0;        // largest uncompressed stripe block such a batch may hold
     int dev_stripe_enc = 0;                 // encode with per-block orders: planes a block reserves (rans4x16_hip_set_dev_stripe_encode)
     bool in_stripe = false;                 // inside the recursive call over the internal items
+    // the packed calls (r4x16_packed.hip): the arena of their internal bound-sized slots and layout arrays
+    u8 *ps = nullptr;
+    size_t ps_bytes = 0;
+    bool in_packed = false;                 // inside a packed call's slot call over its internal slots
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;

@@ -53,6 +53,18 @@ SIGNATURES = {
     "rans4x16_hip_compress_best_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    # the packed device-resident calls: (ctx, n, d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, ..)
+    "rans4x16_hip_compress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "rans4x16_hip_compress_best_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "rans4x16_hip_peek_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rans4x16_hip_uncompress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rans4x16_hip_device_clock_khz": (C.c_int, [C.c_void_p]),
     "rans4x16_hip_residency": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_uint, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]),

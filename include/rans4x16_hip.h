@@ -205,6 +205,76 @@ int rans4x16_hip_compress_best_dev(rans4x16_hip_ctx *ctx, int n,
                                    int32_t *d_status, int k, const int *methods, int32_t *d_chosen,
                                    uint32_t max_in_size, uint64_t total_in_size, void *stream);
 
+/* ---- 2a. packed device-resident calls -------------------------------------------------------
+ * The calls above give every block a slot of its bound (an order-1 bound is 198 KB plus the data: 262,144 blocks of 4 KiB
+ * need 53 GB of slots for 1 GiB of input) and need the output sizes of a decode on the host.  The packed calls produce
+ * and consume ONE dense byte arena: block i's bytes at d_out + d_out_off[i], the next block right behind them.
+ * d_out_off is a device array of n + 1 entries that the call WRITES; out_capacity (host) is what d_out holds.
+ * All of them only enqueue on `stream`, read nothing back, are ordered against the context's other calls like every *_dev
+ * call, and walk the batch in chunks under max_workspace_mb and three quarters of the free device memory.  The
+ * bound-sized slots the encoder works in are the context's own (an arena of a chunk's worth, kept like the workspace).
+ *
+ * rans4x16_hip_compress_packed_dev: the arguments of rans4x16_hip_compress_dev_sized, with out_capacity and the written
+ * d_out_off in place of the slot arrays.
+ *   - The bytes of block i, d_out_size[i] and d_status[i] are what the slot call gives for a slot of exactly
+ *     rans_compress_bound_4x16(d_in_size[i], order of block i) bytes: d_order, X_STRIPE with one `order`, and X_STRIPE
+ *     under d_order after rans4x16_hip_set_dev_stripe_encode included.  (A block larger than max_in_size, or one whose
+ *     bound exceeds that of the largest order byte with 255 planes, reports UNSUPPORTED.)
+ *   - d_out_off[0] = 0 and d_out_off[i + 1] = d_out_off[i] + the size of block i, a block that failed to encode counting
+ *     0.  The sums are taken BEFORE the capacity rule: d_out_off[n] is the capacity the batch needs even if it did not fit.
+ *   - Capacity rule: a block with d_out_off[i + 1] > out_capacity reports R4X16_E_CAPACITY with size 0 and nothing of it
+ *     is written; its neighbours are not affected.  No byte at or beyond out_capacity and no byte outside the blocks'
+ *     ranges is written.
+ *   - Routes (R4X16_ROUTE_RESULT below): without stripe machinery - one `order` without X_STRIPE, or d_order with
+ *     rans4x16_hip_set_dev_stripe_encode off - every stream is assembled at its final place (dense: each result byte
+ *     moves once); where the stripe routes run, the blocks are encoded into the internal slots and copied out (gathered).
+ *
+ * rans4x16_hip_compress_best_packed_dev: rans4x16_hip_compress_best_dev with the same substitution.  A candidate is
+ * tried when its own bound fits the internal slot, which holds the largest bound of the methods - every candidate the
+ * slot call tries with full capacity; skip rules, tie rule and d_chosen as there.  Gathered route.
+ *
+ * rans4x16_hip_peek_dev: per block d_format[i] = the first byte of the stream (-1 if there is none) and d_raw_size[i] =
+ * the stored uncompressed size - the varint at byte 1, present for X_STRIPE streams and for streams without X_NOSZ
+ * (rANS_static4x16pr.c:1360-1366, :1435-1448) - or 0xFFFFFFFF where the stream carries none.  d_status[i]: R4X16_E_EMPTY
+ * for a zero-length block, R4X16_E_TRUNCATED where the varint runs past the block, R4X16_E_UNSUPPORTED for a block
+ * larger than max_in_size (it is not read).
+ *
+ * rans4x16_hip_uncompress_packed_dev: the input arrays of rans4x16_hip_uncompress_dev; the output sizes come from the
+ * streams themselves.
+ *   - Every block claims its stored size (as peek reads it); an X_NOSZ block claims d_nosz_size[i] (device array, may be
+ *     NULL: such a block then reports R4X16_E_SIZE and takes 0 bytes).  A claim above max_out_size is hostile or
+ *     unannounced: the block reports R4X16_E_UNSUPPORTED and takes 0 bytes; so does what peek refuses, with its status.
+ *   - d_out_off is the exclusive scan of the claimed sizes, d_out_off[n] their total.  A block whose range ends beyond
+ *     out_capacity reports R4X16_E_CAPACITY and is not decoded.
+ *   - The other blocks are decoded with a capacity of exactly the claimed size - what X_STRIPE blocks need (:1379; they
+ *     are decoded after rans4x16_hip_set_dev_stripe_planes, as in the slot call).  A block that fails while decoding keeps
+ *     its range, reports size 0, and the bytes inside its own range are unspecified.  Nothing outside the ranges is written.
+ *   - max_out_size also sizes the stage buffers of X_PACK / X_RLE blocks (max_out_cap of the slot call).
+ * Returns 0 if enqueued, -1 on argument / allocation / launch errors. */
+int rans4x16_hip_compress_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                     const unsigned char *d_in, const uint64_t *d_in_off,
+                                     const uint32_t *d_in_size,
+                                     unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                     uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
+                                     uint32_t max_in_size, uint64_t total_in_size, void *stream);
+int rans4x16_hip_compress_best_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                          const unsigned char *d_in, const uint64_t *d_in_off,
+                                          const uint32_t *d_in_size,
+                                          unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                          uint32_t *d_out_size, int32_t *d_status,
+                                          int k, const int *methods, int32_t *d_chosen,
+                                          uint32_t max_in_size, uint64_t total_in_size, void *stream);
+int rans4x16_hip_peek_dev(rans4x16_hip_ctx *ctx, int n,
+                          const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                          int32_t *d_format, uint32_t *d_raw_size, int32_t *d_status,
+                          uint32_t max_in_size, void *stream);
+int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                       const unsigned char *d_in, const uint64_t *d_in_off,
+                                       const uint32_t *d_in_size,
+                                       unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                       uint32_t *d_out_size, int32_t *d_status, const uint32_t *d_nosz_size,
+                                       uint32_t max_in_size, uint32_t max_out_size, void *stream);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
@@ -285,7 +355,8 @@ enum {
     R4X16_ROUTE_ENCODE = 0,   /* encode chain: streams per row kind (R4X16_ENC_*)                                    */
     R4X16_ROUTE_DECODE = 1,   /* decode chain: streams per row kind (R4X16_DEC_*)                                    */
     R4X16_ROUTE_EXPAND = 2,   /* run-length expansion: blocks of the calls whose expansion kernel was that kind       */
-    R4X16_ROUTE_LAUNCH = 3    /* chain launches (encode and decode): in stream order, or classes side by side        */
+    R4X16_ROUTE_LAUNCH = 3,   /* chain launches (encode and decode): in stream order, or classes side by side        */
+    R4X16_ROUTE_RESULT = 4    /* encode results: blocks per way they reached the caller's memory (R4X16_RESULT_*)     */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -306,6 +377,12 @@ enum {   /* R4X16_ROUTE_ENCODE: the encoder's row kinds */
 };
 enum { R4X16_EXPAND_WAVE = 0, R4X16_EXPAND_WORKGROUP = 1, R4X16_EXPAND_KINDS = 2 };               /* R4X16_ROUTE_EXPAND */
 enum { R4X16_LAUNCH_IN_ORDER = 0, R4X16_LAUNCH_SIDE_BY_SIDE = 1, R4X16_LAUNCH_KINDS = 2 };        /* R4X16_ROUTE_LAUNCH */
+enum {   /* R4X16_ROUTE_RESULT: device-resident encode calls, counted in blocks */
+    R4X16_RESULT_IN_SLOT = 0, /* the slot calls (a host batch's own included): assembled in the bound-sized slot given       */
+    R4X16_RESULT_DENSE = 1,   /* packed call, dense finish: assembled at its final offset, every byte moved once              */
+    R4X16_RESULT_GATHERED = 2,/* packed call over the stripe / best-of-k routes: encoded into an internal slot, then copied    */
+    R4X16_RESULT_KINDS = 3
+};
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
 int rans4x16_hip_route_read(rans4x16_hip_ctx *ctx, int which, long *counts, int n, int reset);
