@@ -111,6 +111,7 @@ struct EncOutT {
     bool active;
     u32x4 held;          // a half read out of the ring, stored one double-trip later
     gu8 *held_dst;
+    u32 above = (0xeu << k) & 0xfu;                      // the quad's lanes that write before this one (chains k + 1 .. 3)
     static constexpr u32 HALF_SHIFT = BYTE ? 6u : 5u;    // units per 64-byte half, as a shift
     // the 16-bit renormalisation of one step (rANS_word.h:300-306): the state's low word into the ring where x is over
     // x_max; returns the state the step carries on with
@@ -127,8 +128,29 @@ struct EncOutT {
         written += __popc(em);
         return emit ? x >> 16 : x;
     }
+    // emit16 for the packed rows.  The same words at the same places, in fewer instructions: the lanes above this one are
+    // counted through a per-lane mask and straight onto `written` (one and + one bit count with accumulate, no second shift
+    // and no add), and the ring address is one multiply-add of the slot (-1: the dump slot, as above).
+    // ALL: every lane's step is real or codes a neutral symbol (chain_encode_o1_lds), so there is no `live` to and in -
+    // a neutral symbol has x_max = 2^31 and never emits.
+    template <bool ALL>
+    __device__ __forceinline__ u32 emit16q(u32 x, bool live, bool over)
+    {
+        const u64 m = ALL ? __ballot(over) : __ballot(over) & __ballot(live);
+        const u32 em = (u32)(m >> (lane & ~3u));
+        const bool emit = ALL ? over : live && over;
+        const u32 j = written + __popc(em & above);
+        const u32 j63 = emit ? (j & 63u) : ~0u;
+        u32 a;
+        asm("v_mad_i32_i24 %0, %1, -2, %2" : "=v"(a) : "v"(j63), "v"(ring126));   // (as shift + subtract otherwise)
+        *(LAS u16 *)(unsigned long)a = (u16)x;
+        written += __popc(em & 0xfu);
+        return emit ? x >> 16 : x;
+    }
     // rANS_word.h:281-321 for one symbol; x is this lane's state.  pk = start | freq << 16.
     // q = x / freq < 2^21 once x < x_max, so q * (M - freq) is a 24-bit multiply (mod 2^32).
+    // Q: the packed rows' emit16q; ALL: no idle lanes (emit16q)
+    template <bool Q = false, bool ALL = false>
     __device__ __forceinline__ void step(u32 &x, bool live, u32 rcp, u32 pk, u32 bits)
     {
         const u32 f = pk >> 16, start = pk & 0xffffu;
@@ -146,7 +168,7 @@ struct EncOutT {
             *(LAS u8 *)(unsigned long)(ring126 - j2) = (u8)(x >> 8);
             xs = emit2 ? x >> 16 : emit1 ? x >> 8 : x;
             written += __popc(e1) + __popc(e2);
-        } else xs = emit16(x, live, x >= (f << (31u - bits)));
+        } else xs = Q ? emit16q<ALL>(x, live, x >= (f << (31u - bits))) : emit16(x, live, x >= (f << (31u - bits)));
         // exact x / f: Alverson reciprocal for f >= 2; f == 1 has rcp = 2^32 - 1 and shift 0, which
         // gives x - 1: the compare's carry puts the 1 back (an add-with-carry, no select)
         const u32 fm1 = f - 1u;
@@ -154,7 +176,7 @@ struct EncOutT {
         const u32 q = (__umulhi(xs, rcp) >> rsh) + (fm1 == 0u ? 1u : 0u);
         const u32 cmpl = (1u << bits) - f;
         const u32 xn = __umul24(q, cmpl) + (xs + start);
-        x = live ? xn : xs;
+        x = ALL || live ? xn : xs;
     }
     // The step of the short-index packed rows (10-bit tables): {m, w} is the frequency table's entry of f (r4x16_api.hip),
     // w = (1024 - f) | s << 24, and nothing is derived from f here but x_max.  The same x as step(), bit for bit:
@@ -166,12 +188,13 @@ struct EncOutT {
     //      f = 2 (any power of two): m = 0, q = xs >> s.      f = 3 (no power of two): m = ceil(2^(32 + s) / f) - 2^32 > 0.
     //   q * (1024 - f): q < 2^21 and 1024 - f < 2^10, a 24-bit multiply that does not look at the shift in w's top byte
     //      (the symbol records' trick, r4x16_common.h).  f = 1024: w's low bits are 0, the product is 0 and x = xs + start.
+    template <bool ALL = false>
     __device__ __forceinline__ void step_freq(u32 &x, bool live, u32 m, u32 w, u32 start, u32 f)
     {
-        const u32 xs = emit16(x, live, x >= (f << 21));
+        const u32 xs = emit16q<ALL>(x, live, x >= (f << 21));
         const u32 q = (__umulhi(xs, m) + xs) >> ((w >> 24) & 31u);
         const u32 xn = __umul24(q, w) + (xs + start);
-        x = live ? xn : xs;
+        x = ALL || live ? xn : xs;
     }
     // conditional form: copy out the half that has just been completed, if any
     __device__ __forceinline__ void flush()
@@ -231,30 +254,50 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
 {
     const u32 k = lane & 3;
     static_assert(!FT || (PK && !BYTE), "the frequency table serves the packed rows");
+    if (PK) bits = 10u;              // what packed rows are made for - and what a lane WITHOUT a stream must code its neutral symbols with
     const u8 *idx = img_lds;
     const u8 *cumb = img_lds + (FT ? ENC_IMG_IDX_SHORT : ENC_IMG_IDX);
     const u32 rs = PK ? 4u * enc_pk_row_dwords(ns) : ns + 1;       // bytes (packed) / u16 entries per context row
     const u32 cumb_lds = (u32)(unsigned long)(LAS const u8 *)cumb;
     // the (start, next) pair of symbol si in context ci.  u16 rows: start | next << 16, one dword read at a 2-byte
     // aligned LDS address.  Packed rows: 22 bits at bit 11 si of the row, from two aligned dwords and a funnel shift.
-    auto pair = [&](u32 ci, u32 si) -> u32 {
-        if (PK) {
-            const u32 b = __umul24(si, 11u);
-            const u32 a = cumb_lds + __umul24(ci, rs) + ((b >> 5) << 2);
-            const u32x2 d = *(LAS const u32x2_a4 *)(unsigned long)a;
-            return __builtin_amdgcn_alignbit(d.y, d.x, b);                   // (the shift uses the low five bits of b)
-        }
-        return *(LAS const u32 *)(cumb + 2u * (__umul24(ci, rs) + si));
+    // Packed rows: everything a look-up takes from a compact index j comes out of ONE multiply-add, the index's word
+    //     11 j  |  (dword address of row j) << 16         (11 j <= 693; an LDS dword address is below 2^16)
+    // - an index is the symbol of one step and the context of the next (cum4), so it used to be multiplied twice.  The pair of
+    // symbol si in context ci starts at dword word(ci) >> 16 + (11 si >> 5), bit 11 si & 31.  u16 rows: the word is the index.
+    const u32 wmul = PK ? 11u | (rs >> 2) << 16 : 1u, wadd = PK ? (cumb_lds >> 2) << 16 : 0u;
+    auto word = [&](u32 j) -> u32 {
+        if (!PK) return j;
+        u32 w = __umul24(j, wmul) + wadd;
+        asm("" : "+v"(w));               // one word: without this the low half is multiplied a second time, without the add
+        return w;
     };
-    const u32 rcp_last = PK ? 1024u : RCPTAB_ENTRIES - 1u;
+    auto pairw = [&](u32 wc, u32 ws) -> u32 {
+        if (PK) {
+            const u32 a = ((wc >> 16) + __builtin_amdgcn_ubfe(ws, 5, 5)) << 2;
+            const u32x2 d = *(LAS const u32x2_a4 *)(unsigned long)a;
+            return __builtin_amdgcn_alignbit(d.y, d.x, ws);                  // (the shift uses the low five bits of ws)
+        }
+        return *(LAS const u32 *)(cumb + 2u * (__umul24(wc, rs) + ws));
+    };
+    auto pair = [&](u32 ci, u32 si) -> u32 { return pairw(word(ci), word(si)); };
+    // Packed rows: the pair of a NEUTRAL symbol, {start 0, next 1 << bits} (their tables have 10 bits): frequency 1,024 has
+    // x_max = 2^31, which no state reaches, and 1024 - f = 0, so a step that codes it leaves x and the ring as they are.
+    // The pipelined loop hands it to every lane that has no symbol to code in a trip, and therefore
+    //  - its steps need no `live` (EncOutT::emit16q<ALL>), and
+    //  - every pair that reaches rcpof() is this one or a pair of the stream's own bytes in the stream's own rows, whose
+    //    entries ascend from 0 to 1,024: 0 <= f <= 1,024 and the table index stays inside the table with no clamp.  The
+    //    other phases fetch() for live lanes only.
+    const u32 neutral = 1024u << 11;
+    const u32 rcp_last = RCPTAB_ENTRIES - 1u;
     // A symbol on its way to its step: pk = start | freq << 16; FT: pk = start and f = freq, apart as they come out of the row
     // (every instruction of the loop is issue time, on the dependent path or off it: no packing that a step undoes again)
     struct PF { u32 pk, f; };
-    // {reciprocal, 0}, or the frequency table's entry  (clamp: idle lanes hold garbage)
+    // {reciprocal, 0}, or the frequency table's entry  (u16 rows clamp: their idle lanes hold garbage; packed rows: above)
     auto rcpof = [&](PF s) -> u32x2 {
-        if (FT) return ((const u32x2 *)lrcp)[s.f < rcp_last ? s.f : rcp_last];
+        if (FT) return ((const u32x2 *)lrcp)[s.f];
         const u32 f = s.pk >> 16;
-        u32x2 r = {lrcp[f < rcp_last ? f : rcp_last], 0u};
+        u32x2 r = {lrcp[PK ? f : f < rcp_last ? f : rcp_last], 0u};
         return r;
     };
     // pair -> start | freq << 16.  u16 rows: a shift and a subtract (the empty asm keeps it from becoming a
@@ -278,7 +321,11 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
     };
     auto step = [&](EncOutT<BYTE> &o, u32 &x, bool live, u32 rcp, u32 w, u32 pk, u32 f) {
         if (FT) o.step_freq(x, live, rcp, w, pk, f);
-        else o.step(x, live, rcp, pk, bits);
+        else o.template step<PK>(x, live, rcp, pk, bits);
+    };
+    auto step_all = [&](EncOutT<BYTE> &o, u32 &x, u32 rcp, u32 w, u32 pk, u32 f) {        // packed rows, pipelined loop
+        if (FT) o.template step_freq<true>(x, true, rcp, w, pk, f);
+        else o.template step<true, true>(x, true, rcp, pk, bits);
     };
     EncOutT<BYTE> o{ring, (u32)(unsigned long)(LAS u8 *)ring + (BYTE ? 127u : 126u), scratch_end, dump, 0u, 0u, k, lane, active, {0, 0, 0, 0}, dump};
     u32 x = BYTE ? (1u << 23) : RANS_LOW;
@@ -312,17 +359,31 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
         // Software pipeline, every access issued at least one trip before its first use:
         //   input piece of double-trip D+3 (HBM, 8 bytes)   byte -> compact index of trip t+3 (LDS)
         //   cumulative pair of trip t+2 (LDS)               reciprocal of trip t+1 (LDS)      trip t: 4 state updates
+        // Pieces are asked for in order, j = 0, 1, 2 ..: a saturating offset walks down the quarter and stops at its
+        // start, so a lane past its last double trip reads the quarter's first eight bytes again (npair > 0: the quarter
+        // has nine or more) and a lane with no double trip at all reads `safe`.  Their trips code neutral symbols.
+        gcu8 *lbase = npair ? qbase : safe;
+        u32 loff = npair ? r0 : 0u;
         auto load8 = [&](u32 j) -> u32x2 {       // bytes r0-8j-8 .. r0-8j-1: .y = contexts of trip 2j, .x = of trip 2j+1
-            gcu8 *p = j < npair ? qbase + (r0 - 8 * j) - 8 : safe;
-            return *(GAS const u32x2_unaligned *)p;
+            if (!PK) {
+                gcu8 *p = j < npair ? qbase + (r0 - 8 * j) - 8 : safe;
+                return *(GAS const u32x2_unaligned *)p;
+            }
+            loff = __builtin_elementwise_sub_sat(loff, 8u);
+            return *(GAS const u32x2_unaligned *)(lbase + loff);
         };
-        struct I4 { u32 c0, c1, c2, c3; };
+        struct I4 { u32 c0, c1, c2, c3; };       // the words of four compact indices
         auto idx4 = [&](u32 ww) -> I4 {
-            I4 r = {idx[ww >> 24], idx[(ww >> 16) & 0xff], idx[(ww >> 8) & 0xff], idx[ww & 0xff]};
+            I4 r = {word(idx[ww >> 24]), word(idx[(ww >> 16) & 0xff]), word(idx[(ww >> 8) & 0xff]), word(idx[ww & 0xff])};
             return r;
         };
         auto cum4 = [&](const I4 &c, u32 sym) -> u32x4 {     // raw pairs start | next << 16
-            u32x4 r = {pair(c.c0, sym), pair(c.c1, c.c0), pair(c.c2, c.c1), pair(c.c3, c.c2)};
+            u32x4 r = {pairw(c.c0, sym), pairw(c.c1, c.c0), pairw(c.c2, c.c1), pairw(c.c3, c.c2)};
+            return r;
+        };
+        auto real4 = [&](u32x4 p, bool live) -> u32x4 {      // packed rows: neutral symbols for a lane without a trip
+            if (!PK) return p;
+            u32x4 r = {live ? p.x : neutral, live ? p.y : neutral, live ? p.z : neutral, live ? p.w : neutral};
             return r;
         };
         struct P4 { PF x, y, z, w; };
@@ -348,7 +409,7 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             Q0 = load8(0); Q1 = load8(1); Q2 = load8(2); Q3 = load8(3);
             const I4 i0 = idx4(Q0.y), i1 = idx4(Q0.x);
             I2 = idx4(Q1.y);
-            P0 = topk4(cum4(i0, cur));
+            P0 = topk4(real4(cum4(i0, word(cur)), 0 < ntrip));
             Praw = cum4(i1, i0.c3);
             cur1 = i0.c3; cur2 = i1.c3;
             R0 = rcp4(P0);
@@ -358,16 +419,23 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             const bool live = t < ntrip;
             const I4 In = idx4(wnext3);              // bytes of trip t+3
             const u32x4 Pn = cum4(I2, cur2);         // pairs of trip t+2
-            const P4 P1 = topk4(Praw);               // trip t+1, read during the previous trip
+            const P4 P1 = topk4(real4(Praw, t + 1 < ntrip));     // trip t+1, read during the previous trip
             const R4 Rn = rcp4(P1);
             // the look-ups above belong to later trips: keep the scheduler from pulling next trip's
             // (which depend on them) up behind them, which would put their latency on this trip
             __builtin_amdgcn_sched_barrier(0);
-            step(o, x, live, R0.rcp.x, R0.w.x, P0.x.pk, P0.x.f);
-            step(o, x, live, R0.rcp.y, R0.w.y, P0.y.pk, P0.y.f);
-            step(o, x, live, R0.rcp.z, R0.w.z, P0.z.pk, P0.z.f);
-            step(o, x, live, R0.rcp.w, R0.w.w, P0.w.pk, P0.w.f);
-            if (live) cur = cur1;
+            if (PK) {
+                step_all(o, x, R0.rcp.x, R0.w.x, P0.x.pk, P0.x.f);
+                step_all(o, x, R0.rcp.y, R0.w.y, P0.y.pk, P0.y.f);
+                step_all(o, x, R0.rcp.z, R0.w.z, P0.z.pk, P0.z.f);
+                step_all(o, x, R0.rcp.w, R0.w.w, P0.w.pk, P0.w.f);
+            } else {
+                step(o, x, live, R0.rcp.x, R0.w.x, P0.x.pk, P0.x.f);
+                step(o, x, live, R0.rcp.y, R0.w.y, P0.y.pk, P0.y.f);
+                step(o, x, live, R0.rcp.z, R0.w.z, P0.z.pk, P0.z.f);
+                step(o, x, live, R0.rcp.w, R0.w.w, P0.w.pk, P0.w.f);
+                if (live) cur = cur1;
+            }
             cur1 = cur2; cur2 = I2.c3;
             I2 = In; P0 = P1; Praw = Pn; R0 = Rn;
             t++;
@@ -383,6 +451,8 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
         }
         o.flush_drain();
         o.flush();                               // fewer than 32 words may stay in the ring from here on
+        // (packed rows: the loop does not carry the symbol that follows its last live trip - it is read again)
+        if (PK) cur = (active && q) ? idx[qbase[r0 - 4 * ntrip]] : 0u;
     }
     // (B') remaining walk steps, one at a time
     u32 r = r0 - 4 * ntrip, done = 4 * ntrip;
