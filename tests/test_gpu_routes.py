@@ -86,10 +86,14 @@ def _toggle_data(option):
         return [datagen.tile("q8", 65536, b) for b in range(40)], 65, {}
     if option == "dec_mid":
         return [datagen.tile("q40+dir", 65536, b) for b in range(40)], 1, {"dec_direct": 0}
+    if option == "dec_short_ring":                         # 44 symbols with byte 0, 10-bit tables: an image of 3,168 bytes, which
+        # fits the class of sixteen streams per wave with the short ring only (k_dec_classify; 45 and more fit neither way)
+        return [datagen.rand(65536, 1 + b, 43, 33) for b in range(40)], 1, {"dec_direct": 0}
     return [datagen.tile("q40+dir", 65536, b) for b in range(40)], 1, {}
 
 
-TOGGLES = {"dec_direct": (1, 0), "enc_direct": (1, 0), "back_wg_per_cu": (0, 99999), "dec_mid": (0, 8), "sched_concurrent": (1, 0)}
+TOGGLES = {"dec_direct": (1, 0), "enc_direct": (1, 0), "back_wg_per_cu": (0, 99999), "dec_mid": (0, 8), "sched_concurrent": (1, 0),
+           "dec_short_ring": (0, 1)}
 
 
 def _check_route(option, value, path, enc, dec, exp, launch, nblk):
@@ -115,6 +119,13 @@ def _check_route(option, value, path, enc, dec, exp, launch, nblk):
             assert dec["mid"] == nblk and compressed_dec == 0, dec
         else:
             assert dec["mid"] == 0 and compressed_dec == nblk, dec
+    elif option == "dec_short_ring":
+        # every payload stream (the launch that decodes nested order-1 tables is not counted)
+        assert dec["direct"] == 0 and dec["mid"] == 0, dec
+        if value:
+            assert dec["short_ring"] == nblk and dec["l1"] == 0, dec
+        else:
+            assert dec["l1"] == nblk and dec["short_ring"] == 0, dec
     elif option == "sched_concurrent":
         # the classes of a call side by side on the context's side streams; a pipeline lane has none (its lanes are the
         # pipeline's concurrency), so a pipelined batch is in stream order either way
