@@ -476,3 +476,109 @@ class DeviceCodec:
             nosz_size.data_ptr() if nosz_size is not None else None, int(max_in_size), int(max_out_size), self._stream())
         if rc != 0:
             raise RuntimeError("uncompress_packed_dev: " + self.ctx.error())
+
+    # ---- rANS 4x8 (CRAM 3.0), include/rans4x8_hip.h part 2a: the same surface, every result assembled in place -------
+    def compress_packed_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, order, max_in_size,
+                            d_order=None, out_capacity=None):
+        """rans4x8_hip_compress_packed_dev: block i at d_out[out_off[i]:out_off[i + 1]]; out_off (int64, n + 1 entries) is
+        written by the call, out_off[n] is what the batch needs.  out_capacity defaults to d_out's size."""
+        self._packed_args(d_in, in_off, in_size, d_out, out_off, out_size, status)
+        cap = d_out.numel() if out_capacity is None else int(out_capacity)
+        assert cap <= d_out.numel()
+        rc = self.L.rans4x8_hip_compress_packed_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), int(order),
+            d_order.data_ptr() if d_order is not None else None, int(max_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("rans4x8 compress_packed_dev: " + self.ctx.error())
+
+    def compress_best_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size,
+                          chosen=None, packed=False, out_cap=None, out_capacity=None):
+        """Every block with each of `methods` (one or two of 0 / 1), the smaller result kept, the first on a tie; `chosen`
+        (int32 tensor, optional) gets the winner's index into `methods`, -1 for a failed block.
+        packed=False: rans4x8_hip_compress_best_dev, the winner in its slot (out_off: n entries, read; out_cap: int32).
+        packed=True: rans4x8_hip_compress_best_packed_dev, the winners back to back (out_off: n + 1 entries, written)."""
+        t = self.torch
+        assert chosen is None or chosen.dtype == t.int32
+        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        ch = chosen.data_ptr() if chosen is not None else None
+        if packed:
+            self._packed_args(d_in, in_off, in_size, d_out, out_off, out_size, status)
+            cap = d_out.numel() if out_capacity is None else int(out_capacity)
+            assert cap <= d_out.numel()
+            rc = self.L.rans4x8_hip_compress_best_packed_dev(
+                self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+                d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), len(methods), meth, ch,
+                int(max_in_size), self._stream())
+        else:
+            assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+            assert in_off.dtype == t.int64 and out_off.dtype == t.int64 and out_off.numel() == in_off.numel()
+            assert in_size.dtype == t.int32 and out_cap is not None and out_cap.dtype == t.int32
+            assert out_size.dtype == t.int32 and status.dtype == t.int32
+            rc = self.L.rans4x8_hip_compress_best_dev(
+                self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+                d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+                len(methods), meth, ch, int(max_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("rans4x8 compress_best%s_dev: " % ("_packed" if packed else "") + self.ctx.error())
+
+    def peek_4x8(self, d_in, in_off, in_size, fmt, raw_size, status, max_in_size):
+        """rans4x8_hip_peek_dev: byte 0 (fmt, int32; -1 = none) and bytes 5..8 (raw_size, int32 holding the unsigned value;
+        -1 = fewer than 9 bytes) of every block."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and in_off.dtype == t.int64 and in_size.dtype == t.int32
+        assert fmt.dtype == t.int32 and raw_size.dtype == t.int32 and status.dtype == t.int32
+        rc = self.L.rans4x8_hip_peek_dev(self.ctx.h, in_size.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+                                         fmt.data_ptr(), raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("rans4x8 peek_dev: " + self.ctx.error())
+
+    def uncompress_packed_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, max_in_size, max_out_size,
+                              out_capacity=None):
+        """rans4x8_hip_uncompress_packed_dev: every block decoded to d_out[out_off[i]:out_off[i + 1]], the sizes taken from
+        the streams.  in_off may have n or n + 1 entries (compress_packed_4x8's out_off goes straight in); the block
+        count is in_size's."""
+        t = self.torch
+        n = in_size.numel()
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and in_off.numel() >= n and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == n + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        cap = d_out.numel() if out_capacity is None else int(out_capacity)
+        assert cap <= d_out.numel()
+        rc = self.L.rans4x8_hip_uncompress_packed_dev(
+            self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            int(max_in_size), int(max_out_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("rans4x8 uncompress_packed_dev: " + self.ctx.error())
+
+    def compress_4x8(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status, order, max_in_size, d_order=None):
+        """rans4x8_hip_compress_dev: the slot call (out_off: n entries, read; out_cap: int32, what each slot holds)."""
+        t = self.torch
+        n = in_off.numel()
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and out_off.dtype == t.int64 and out_off.numel() == n
+        assert in_size.dtype == t.int32 and in_size.numel() == n and out_cap.dtype == t.int32 and out_cap.numel() == n
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert d_order is None or (d_order.dtype == t.int32 and d_order.numel() == n)
+        rc = self.L.rans4x8_hip_compress_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(), int(order),
+            d_order.data_ptr() if d_order is not None else None, int(max_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("rans4x8 compress_dev: " + self.ctx.error())
+
+    def uncompress_4x8(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status):
+        """rans4x8_hip_uncompress_dev: the slot call (in_off may have more than n entries; the block count is in_size's)."""
+        t = self.torch
+        n = in_size.numel()
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and in_off.numel() >= n and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == n and out_cap.dtype == t.int32 and out_cap.numel() == n
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        rc = self.L.rans4x8_hip_uncompress_dev(
+            self.ctx.h, in_size.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError("rans4x8 uncompress_dev: " + self.ctx.error())

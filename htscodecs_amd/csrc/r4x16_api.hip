@@ -968,26 +968,61 @@ extern "C" int rans4x8_hip_compress_dev(rans4x16_hip_ctx *c, int n,
     }
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const u64 scratch_stride = align_up(std::max((size_t)r4x8_compress_bound(max_in_size) + 64, (size_t)ENC_F_BYTES), 256);
-    EncWs w;
-    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return enc_ws_layout(nullptr, nb, scratch_stride, 0, &w) + 4096; });
-    if (ws_order_begin(c, s) != 0) return -1;
-    for (;;) {
-        if (ensure_ws(c, enc_ws_layout(nullptr, chunk, scratch_stride, 0, &w)) == 0) break;
-        if (chunk == 1) return -1;
-        chunk = (chunk + 1) / 2;
-    }
-    enc_ws_layout(c->ws, chunk, scratch_stride, 0, &w);
-    w.logtab = c->logtab;
-    w.rcptab = c->rcptab;
     BatchArgs a;
     a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
     a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
     a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
+    return r4x8_enc_run(c, a, max_in_size, (hipStream_t)stream, nullptr, nullptr);
+}
+
+// The items' arrays of the packed and best-of-two calls, a chunk's worth in the context's packed arena.
+static size_t enc8_items_carve(Enc8Items *w, u8 *base, size_t nitems, size_t nb)
+{
+    Carver cv(base);
+    w->in_off = cv.take<u64>(nitems);
+    w->in_size = cv.take<u32>(nitems);
+    w->cap = cv.take<u32>(nitems);
+    w->order = cv.take<i32>(nitems);
+    w->pick = cv.take<i32>(nb);
+    return align_up(cv.off, 256);
+}
+
+// The 4x8 encode pipeline over a batch, in chunks of blocks under the workspace ceiling (r4x16_host.h).  The slot call
+// keeps its launch sequence.  The packed and best-of-two forms run k items per block - the chunk is planned for that -
+// and need no output slots of their own: the payload sits in the workspace scratch until the finish moves it, once.
+int r4x8_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, hipStream_t s, const PackedOut *pk, const Enc8Sel *sel)
+{
+    const int n = a.n;
+    const bool slot_call = !pk && !sel;
+    const size_t k = sel && sel->k ? (size_t)sel->k : 1;
+    const u64 scratch_stride = align_up(std::max((size_t)r4x8_compress_bound(max_in_size) + 64, (size_t)ENC_F_BYTES), 256);
+    EncWs w;
+    Enc8Items it = {};
+    auto items_for = [&](size_t nb) -> size_t { return slot_call ? 0 : enc8_items_carve(&it, nullptr, k * nb, nb); };
+    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w) + 4096 + items_for(nb); },
+                              slot_call ? 0 : c->ps_bytes);
+    chunk = std::min(chunk, (size_t)INT_MAX / k);      // item indices (j * nb + b < k * nb) and the item count stay inside an int
+    if (ws_order_begin(c, s) != 0) return -1;
+    for (;;) {
+        if (ensure_ws(c, enc_ws_layout(nullptr, k * chunk, scratch_stride, 0, &w)) == 0 &&
+            (slot_call || r4x16_ensure_ps(c, items_for(chunk)) == 0)) break;
+        if (chunk == 1) return -1;
+        chunk = (chunk + 1) / 2;
+    }
+    enc_ws_layout(c->ws, k * chunk, scratch_stride, 0, &w);
+    w.logtab = c->logtab;
+    w.rcptab = c->rcptab;
+    if (!slot_call) enc8_items_carve(&it, c->ps, k * chunk, chunk);
     for (size_t base = 0; base < (size_t)n; base += chunk) {
         const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
-        r4x8_launch_encode(&a, &w, (int)base, nb, s);
+        if (slot_call) { r4x8_launch_encode(&a, &w, (int)base, nb, s); continue; }
+        r4x8_launch_enc_items(&a, (int)base, nb, sel ? sel->k : 0, sel ? sel->m : nullptr, max_in_size, &it, s);
+        BatchArgs ia = a;                              // the items: the same input bytes, their own offsets, sizes, orders and slots
+        ia.in_off = it.in_off; ia.in_size = it.in_size; ia.out_cap = it.cap; ia.d_order = it.order; ia.n = (int)k * nb;
+        r4x8_launch_enc_front(&ia, &w, 0, (int)k * nb, s);
+        const Pick8Out po = {pk ? *pk : PackedOut{nullptr, nullptr, 0}, it.pick, sel ? sel->d_chosen : nullptr};
+        r4x8_launch_enc_finish_pick(&a, &w, (int)base, nb, (int)k, &po, s);
+        if (c->opts.v[OPT_ROUTE_COUNT]) c->route[R4X16_ROUTE_RESULT][pk ? R4X16_RESULT_DENSE : R4X16_RESULT_IN_SLOT] += nb;
     }
     HIPCHK(c, hipGetLastError());
     return ws_order_end(c, s);

@@ -112,6 +112,14 @@ struct PackedOut {
     u64  capacity;
 };
 
+// rANS 4x8's packed and best-of-two calls (include/rans4x8_hip.h; k8_enc_items / k8_enc_size / k8_enc_finish,
+// r4x16_encode.hip): a block of a chunk of nb blocks is k internal items over the same input, candidate j of block b
+// being item j * nb + b; a chunk holds at most INT_MAX / k blocks (r4x8_enc_run), so an item's index fits an int.
+// Enc8Items: what the front end reads per item.  Pick8Out: where the winner goes - pk.off == nullptr: into the caller's
+// slot -, the winner's candidate per block of the chunk (-1: none), and the caller's d_chosen (or nullptr).
+struct Enc8Items { u64 *in_off; u32 *in_size; u32 *cap; i32 *order; i32 *pick; };      // [k * nb] each, pick: [nb]
+struct Pick8Out { PackedOut pk; i32 *pick; i32 *chosen; };
+
 // ---------------------------------------------------------------------------------------------
 // Sequential byte reader for the single lane that parses headers and tables.  Keeps an
 // 8-byte window so that a run of dependent byte reads costs one global load per 8 bytes.

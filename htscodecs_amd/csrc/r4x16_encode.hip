@@ -12,6 +12,7 @@
 //   k_enc_finish : one wave per block.  Chooses CAT fall-back (:1332-1337), assembles
 //                  header + table + payload into the caller's slot, writes size and status.
 #include <stdlib.h>
+#include <type_traits>
 #include "r4x16_dev.h"
 #include "r4x16_sched.h"
 #include "r4x16_enc_step.h"
@@ -1790,7 +1791,12 @@ extern "C" u32 r4x16_compress_bound(u32 size, int order) { return compress_bound
 //   k8_enc_chain  : a quad per block; the general-form chain loop with BYTE renormalisation: a chain emits
 //                   (x >= x_max) + (x >> 8 >= x_max) bytes, low byte first, on the quad's descending pointer,
 //                   chains served in the order 3, 2, 1, 0 (rANS_byte.h:320-402).
-//   k8_enc_finish : header (order, sizes), table, payload into the caller's slot.
+//   k8_enc_finish : header (order, sizes), table, payload into the caller's slot - or, for the packed and best-of-two
+//                   calls (include/rans4x8_hip.h), the winner of a block's candidates at its place in the dense arena,
+//                   after k8_enc_items (a block as k items over the same input), k8_enc_size (verdicts, sizes, winner)
+//                   and the packed calls' scan.
+// Loops of the three new kernels: k8_enc_items and k8_enc_size run k <= 2 trips, a launch argument; k8_enc_finish
+// copies tab_len <= TAB_BYTES and pay_len <= room bytes, both checked by k8_enc_size before (room is a launch argument).
 // Plain first version (tables through L2, byte stores); in_size == 0 is refused (the reference divides by zero).
 // =============================================================================================
 #define X8_LOW_E (1u << 23)
@@ -2095,31 +2101,108 @@ __global__ __launch_bounds__(WAVE) void k8_enc_chain_gm(EncItem *items, const u3
     if (active && (lane & 3) == 0) I->pay_len = pay;
 }
 
-__global__ __launch_bounds__(FINISH_THREADS) void k8_enc_finish(BatchArgs a, EncWs ws, int base, u32 room)
+// PK = SlotOut: into the caller's slot; it compiles to the code it was before the template existed.
+// PK = Pick8Out (the packed and best-of-two calls, r4x16_packed.hip): a block owns k items - candidate j of block b is
+// item j * gridDim.x + b - and k8_enc_size has left status and size in the caller's arrays and the winner in pk.pick[b],
+// -1 for a block with nothing to finish (this kernel reads none of the output arrays it writes); the winner is assembled
+// at pk.pk.out + pk.pk.off[i] (packed) or in the caller's slot (pk.pk.off == nullptr).  Header, table and payload come
+// from the workspace either way: every result byte moves once.
+template <class PK>
+__global__ __launch_bounds__(FINISH_THREADS) void k8_enc_finish(BatchArgs a, EncWs ws, int base, u32 room, PK pk)
 {
     const u32 tid = threadIdx.x;
     const u32 b = blockIdx.x;
     const int i = base + (int)b;
-    const EncItem *I0 = &ws.items[b];
-    const i32 st = ws.desc[b].status;
-    if (st != ST_OK || !I0->active || I0->pay_len > room) {
-        if (tid == 0) { a.status[i] = st != ST_OK ? st : ST_CAPACITY; a.out_size[i] = 0; }
-        return;
+    static_assert(std::is_same<PK, SlotOut>::value || std::is_same<PK, Pick8Out>::value, "k8_enc_finish: SlotOut or Pick8Out");
+    u32 it = b;
+    u8 *out;
+    if constexpr (std::is_same<PK, Pick8Out>::value) {
+        const i32 win = pk.pick[b];
+        if (win < 0) return;                                                     // failed, or too large for the caller's slot
+        it = (u32)win * gridDim.x + b;
+        if (pk.pk.off) {
+            const u64 at = pk.pk.off[i], end = pk.pk.off[i + 1];
+            if (end > pk.pk.capacity) {                                          // the capacity rule: nothing of it is written
+                if (tid == 0) { a.status[i] = ST_CAPACITY; a.out_size[i] = 0; if (pk.chosen) pk.chosen[i] = -1; }
+                return;
+            }
+            out = pk.pk.out + at;
+        } else out = a.out + a.out_off[i];
     }
-    u8 *out = a.out + a.out_off[i];
-    const u32 tab_len = ws.desc[b].tab_len, pay = I0->pay_len, total = 9 + tab_len + pay;
+    const EncItem *I0 = &ws.items[it];
+    if constexpr (std::is_same<PK, SlotOut>::value) {                            // the verdict is this kernel's own
+        const i32 st = ws.desc[it].status;
+        if (st != ST_OK || !I0->active || I0->pay_len > room) {
+            if (tid == 0) { a.status[i] = st != ST_OK ? st : ST_CAPACITY; a.out_size[i] = 0; }
+            return;
+        }
+        out = a.out + a.out_off[i];
+    }
+    const u32 tab_len = ws.desc[it].tab_len, pay = I0->pay_len, total = 9 + tab_len + pay;
     if (tid == 0) {                                                              // :204-214, :593-605
         const u32 csz = total - 9, n = I0->n;
         out[0] = (u8)I0->order;
         out[1] = (u8)csz; out[2] = (u8)(csz >> 8); out[3] = (u8)(csz >> 16); out[4] = (u8)(csz >> 24);
         out[5] = (u8)n; out[6] = (u8)(n >> 8); out[7] = (u8)(n >> 16); out[8] = (u8)(n >> 24);
     }
-    group_copy<FINISH_THREADS>(out + 9, ws.tab + (u64)b * TAB_BYTES, tab_len, tid);
+    group_copy<FINISH_THREADS>(out + 9, ws.tab + (u64)it * TAB_BYTES, tab_len, tid);
     group_copy<FINISH_THREADS>(out + 9 + tab_len, (const u8 *)I0->scratch_end - pay, pay, tid);
     if (tid == 0) { a.status[i] = ST_OK; a.out_size[i] = total; }
 }
 
-extern "C" void r4x8_launch_encode(const BatchArgs *a, const EncWs *ws, int base, int nblk, hipStream_t s)
+// The packed and best-of-two calls run every block as k internal items that view the same input (nothing is copied):
+// candidate j of block b of the chunk is item j * nb + b, with its own order.  The slot the front end asks for is the
+// block's bound - the candidates are what the slot call gives for a slot of exactly that - or 0 for a block larger than
+// the call announced, which the front end then refuses without reading it.  k == 0: one item, the call's order / d_order.
+__global__ __launch_bounds__(256) void k8_enc_items(BatchArgs a, int base, int nb, int k, int m0, int m1, u32 max_in, Enc8Items w)
+{
+    const int b = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (b >= nb) return;
+    const int i = base + b;
+    const u32 sz = a.in_size[i];
+    const u64 off = a.in_off[i];
+    const u32 cap = sz > max_in ? 0u : compress_bound8(sz);
+    if (k == 0) { k = 1; m0 = a.d_order ? a.d_order[i] : a.order; }
+    for (int j = 0; j < k; j++) {
+        const int it = j * nb + b;
+        w.in_off[it] = off; w.in_size[it] = sz; w.cap[it] = cap; w.order[it] = j ? m1 : m0;
+    }
+}
+
+// Verdict, size and winner of every block of a chunk, by k8_enc_finish's arithmetic and without moving a byte; one
+// thread per block.  A candidate the front end refused for its slot is a block larger than the call announced
+// (k8_enc_items): UNSUPPORTED.  The smallest candidate wins, the first on a tie; failed ones are passed over, and a
+// block without any reports the status of the first.  Sizes are written before the packed calls' capacity rule (the
+// scan needs them; k8_enc_finish applies the rule); the slot form's capacity is checked here.
+__global__ __launch_bounds__(256) void k8_enc_size(BatchArgs a, EncWs ws, int base, int nblk, int k, u32 room, Pick8Out pk)
+{
+    const int b = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (b >= nblk) return;
+    const int i = base + b;
+    i32 first = ST_OK;
+    int best = -1;
+    u32 bsz = 0;
+    for (int j = 0; j < k; j++) {
+        const int it = j * nblk + b;
+        const EncItem *I0 = &ws.items[it];
+        i32 st = ws.desc[it].status;
+        if (st == ST_CAPACITY) st = ST_UNSUPPORTED;
+        else if (st == ST_OK && (!I0->active || I0->pay_len > room)) st = ST_CAPACITY;
+        if (j == 0) first = st;
+        if (st != ST_OK) continue;
+        const u32 total = 9 + ws.desc[it].tab_len + I0->pay_len;
+        if (best < 0 || total < bsz) { best = j; bsz = total; }
+    }
+    i32 st = best >= 0 ? ST_OK : first;
+    if (best >= 0 && !pk.pk.off && bsz > a.out_cap[i]) { st = ST_CAPACITY; best = -1; bsz = 0; }
+    a.status[i] = st;
+    a.out_size[i] = bsz;
+    pk.pick[b] = best;                                                           // -1: k8_enc_finish leaves the block alone
+    if (pk.chosen) pk.chosen[i] = best;
+}
+
+// front end, classes and chains over `nitems` items (a[base + b] is item b's block)
+extern "C" void r4x8_launch_enc_front(const BatchArgs *a, const EncWs *ws, int base, int nblk, hipStream_t s)
 {
     if (r4x16_first_on_device(FIRST_ENC8_FRONT)) sched_lds_limit((const void *)k8_enc_front, FRONT_DYN_LDS);
     const u32 room = (u32)(ws->scratch_stride > 0xffffffffull ? 0xffffffffu : ws->scratch_stride);
@@ -2134,5 +2217,34 @@ extern "C" void r4x8_launch_encode(const BatchArgs *a, const EncWs *ws, int base
     r4x8_enc_chain_launch(ws->items, ws->rcptab, ws->dump, ws->sched.list, ws->sched.cnt + 1, nblk, X8E_SLOT1, 30, 8, s);
     hipLaunchKernelGGL(k8_enc_chain_gm, dim3((nblk + 15) / 16), dim3(WAVE), 0, s, ws->items, ws->rcptab,
                        (const u32 *)ws->sched.list, (const u32 *)(ws->sched.cnt + 2), room);
-    hipLaunchKernelGGL(k8_enc_finish, dim3(nblk), dim3(FINISH_THREADS), 0, s, *a, *ws, base, room);
+}
+
+extern "C" void r4x8_launch_enc_finish(const BatchArgs *a, const EncWs *ws, int base, int nblk, hipStream_t s)
+{
+    const u32 room = (u32)(ws->scratch_stride > 0xffffffffull ? 0xffffffffu : ws->scratch_stride);
+    hipLaunchKernelGGL(k8_enc_finish<SlotOut>, dim3(nblk), dim3(FINISH_THREADS), 0, s, *a, *ws, base, room, SlotOut{});
+}
+
+extern "C" void r4x8_launch_encode(const BatchArgs *a, const EncWs *ws, int base, int nblk, hipStream_t s)
+{
+    r4x8_launch_enc_front(a, ws, base, nblk, s);
+    r4x8_launch_enc_finish(a, ws, base, nblk, s);
+}
+
+extern "C" void r4x8_launch_enc_items(const BatchArgs *a, int base, int nb, int k, const int *m, u32 max_in_size, const Enc8Items *w,
+                                      hipStream_t s)
+{
+    hipLaunchKernelGGL(k8_enc_items, dim3((nb + 255) / 256), dim3(256), 0, s, *a, base, nb, k, k > 0 ? m[0] : 0, k > 1 ? m[1] : 0,
+                       max_in_size, *w);
+}
+
+// the finish of the packed and best-of-two calls over a chunk of nblk blocks of k items each: verdicts, sizes and
+// winners, for the packed forms the offsets (carried on from the previous chunk), then every winner at its final place
+extern "C" void r4x8_launch_enc_finish_pick(const BatchArgs *a, const EncWs *ws, int base, int nblk, int k, const Pick8Out *pk,
+                                            hipStream_t s)
+{
+    const u32 room = (u32)(ws->scratch_stride > 0xffffffffull ? 0xffffffffu : ws->scratch_stride);
+    hipLaunchKernelGGL(k8_enc_size, dim3((nblk + 255) / 256), dim3(256), 0, s, *a, *ws, base, nblk, k, room, *pk);
+    if (pk->pk.off) r4x16_launch_packed_scan(a->out_size, pk->pk.off, base, nblk, s);
+    hipLaunchKernelGGL(k8_enc_finish<Pick8Out>, dim3(nblk), dim3(FINISH_THREADS), 0, s, *a, *ws, base, room, *pk);
 }

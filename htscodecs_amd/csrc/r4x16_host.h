@@ -50,6 +50,13 @@ int  r4x16_enc_route_kind(u32 ci, int *freq_table);
 size_t r4x8_dec_ws_bytes(size_t nblk);
 void r4x8_launch_decode(const BatchArgs *, u8 *ws, int base, int nblk, hipStream_t);
 void r4x8_launch_encode(const BatchArgs *, const EncWs *, int base, int nblk, hipStream_t);
+// the same in its two halves (front end, classes and chains over nblk items; the finish into the callers' slots), and
+// what the packed and best-of-two calls put around the first half: a block as k items, then verdicts / sizes / winners,
+// offsets and the winners at their final place (r4x16_encode.hip)
+void r4x8_launch_enc_front(const BatchArgs *, const EncWs *, int base, int nblk, hipStream_t);
+void r4x8_launch_enc_finish(const BatchArgs *, const EncWs *, int base, int nblk, hipStream_t);
+void r4x8_launch_enc_items(const BatchArgs *, int base, int nb, int k, const int *m, u32 max_in_size, const Enc8Items *, hipStream_t);
+void r4x8_launch_enc_finish_pick(const BatchArgs *, const EncWs *, int base, int nblk, int k, const Pick8Out *, hipStream_t);
 void r4x8_enc_chain_launch(EncItem *items, const u32 *rcptab, u8 *dump, const u32 *list, const u32 *count, int nblk, u32 slot_bytes,
                            int qpw, int spw, hipStream_t);
 u32  r4x8_compress_bound(u32 size);
@@ -85,6 +92,11 @@ size_t r4x16_packed_carve(PackedSlots *p, u8 *base, size_t n, size_t chunk, u64 
 u64 r4x16_packed_stride(u32 max_in_size, int order, bool any_order);
 void r4x16_launch_packed_slots(const BatchArgs *a, const PackedSlots *p, int n, size_t chunk, u32 max_in_size, hipStream_t s);
 int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64_t total_in_size, hipStream_t s, const PackedOut *pk);
+// rANS 4x8: the encode pipeline of r4x16_api.hip over a batch in chunks.  pk == nullptr && sel == nullptr: the slot call.
+// pk: results back to back at pk->out + pk->off[i].  sel: best-of-k, k <= 2 candidates per block (sel->k == 0: one, the
+// call's order / d_order), the winner into the caller's slot (pk == nullptr) or the dense arena.
+struct Enc8Sel { int k; int m[2]; i32 *d_chosen; };
+int r4x8_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, hipStream_t s, const PackedOut *pk, const Enc8Sel *sel);
 int r4x16_run_host_batch(rans4x16_hip_ctx *c, int n, bool decode,
                           const unsigned char *const *in, const unsigned int *in_size,
                           unsigned char *const *out, unsigned int *out_size, const int *order, int *status);

@@ -14,8 +14,17 @@
 // k_unpk_admit withdraws the blocks that may not run (their input length becomes 0 for the inner call), the existing
 // decode runs with capacity = claimed size, and k_unpk_verdict restores the withdrawn blocks' statuses.
 //
+//
+// rANS 4x8 (include/rans4x8_hip.h, the five calls at the end of this file) has the same surface on the same kernels.
+// Its encoder leaves the payload in workspace scratch and its finish only copies header, table and payload out, so the
+// packed encode and best-of-two are all dense and hold no slots at all: a block runs as k <= 2 internal items over the
+// same input, k8_enc_size picks the winner and sizes it, k_pk_scan lays the winners out and k8_enc_finish assembles
+// each at its place (r4x16_encode.hip; r4x8_enc_run in r4x16_api.hip).  Its decode is the sequence above around
+// rans4x8_hip_uncompress_dev, with peek_one8 reading the size field (bytes 5..8).
+//
 // Loops: every trip count is a launch argument (n, nb, k <= 32) or a block size checked against the host's max_in_size
-// first (the size field's varint is read inside the block's in_size <= max_in_size bytes).
+// first (the size field's varint is read inside the block's in_size <= max_in_size bytes; rANS 4x8's is at a fixed place
+// and read only from blocks of 9 bytes or more).
 #include "r4x16_host.h"
 
 #define PK_MAX_K 32
@@ -118,13 +127,28 @@ static __device__ __forceinline__ i32 peek_one(const u8 *in, u32 in_size, u32 ma
     return ST_OK;
 }
 
+// The same for a rANS 4x8 stream (rANS_static.c:934-943): the order byte, and the uncompressed size in bytes 5..8; a
+// stream of fewer than 9 bytes has none (:938).  Nothing else is judged here: the decoder does that.
+static __device__ __forceinline__ i32 peek_one8(const u8 *in, u32 in_size, u32 max_in, i32 *format, u32 *raw)
+{
+    *format = -1; *raw = PK_NO_SIZE;
+    if (in_size == 0) return ST_EMPTY;
+    if (in_size > max_in) return ST_UNSUPPORTED;
+    *format = (i32)in[0];
+    if (in_size < 9) return ST_TRUNCATED;
+    *raw = (u32)in[5] | ((u32)in[6] << 8) | ((u32)in[7] << 16) | ((u32)in[8] << 24);
+    return ST_OK;
+}
+
+// X8: the blocks are rANS 4x8 streams
+template <bool X8>
 __global__ __launch_bounds__(256) void k_peek(const u8 *in, const u64 *in_off, const u32 *in_size, i32 *format, u32 *raw_size,
                                               i32 *status, int n, u32 max_in)
 {
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= n) return;
     i32 f; u32 r;
-    status[i] = peek_one(in + in_off[i], in_size[i], max_in, &f, &r);
+    status[i] = X8 ? peek_one8(in + in_off[i], in_size[i], max_in, &f, &r) : peek_one(in + in_off[i], in_size[i], max_in, &f, &r);
     format[i] = f; raw_size[i] = r;
 }
 
@@ -132,14 +156,16 @@ __global__ __launch_bounds__(256) void k_peek(const u8 *in, const u64 *in_off, c
 struct UnpkWs { u32 *claim, *in_size; i32 *pre; };   // [n] each, in the context's packed arena
 
 // what block i asks for: its stored size, or the caller's for an X_NOSZ stream; 0 and a status where it may not run
+// (X8: a rANS 4x8 stream always carries its size)
+template <bool X8>
 __global__ __launch_bounds__(256) void k_unpk_claim(const u8 *in, const u64 *in_off, const u32 *in_size, const u32 *nosz_size,
                                                     UnpkWs w, int n, u32 max_in, u32 max_out)
 {
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= n) return;
     i32 f; u32 claim;
-    i32 st = peek_one(in + in_off[i], in_size[i], max_in, &f, &claim);
-    if (st == ST_OK && !(f & X_STRIPE) && (f & X_NOSZ)) {                            // the stream carries no size: the caller's
+    i32 st = X8 ? peek_one8(in + in_off[i], in_size[i], max_in, &f, &claim) : peek_one(in + in_off[i], in_size[i], max_in, &f, &claim);
+    if (!X8 && st == ST_OK && !(f & X_STRIPE) && (f & X_NOSZ)) {                            // the stream carries no size: the caller's
         if (nosz_size) claim = nosz_size[i]; else st = ST_SIZE;
     }
     if (st == ST_OK && claim > max_out) st = ST_UNSUPPORTED;                          // hostile, or larger than announced
@@ -333,10 +359,42 @@ extern "C" int rans4x16_hip_peek_dev(rans4x16_hip_ctx *c, int n,
     }
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_peek, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_in, d_in_off, d_in_size, d_format, d_raw_size,
+    hipLaunchKernelGGL(k_peek<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_in, d_in_off, d_in_size, d_format, d_raw_size,
                        d_status, n, max_in_size);
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+// The packed decode of either codec: claims, offsets, admission, the slot call with capacity = claim, verdicts.
+template <bool X8>
+static int unpack_run(rans4x16_hip_ctx *c, int n, const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                      unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off, uint32_t *d_out_size, int32_t *d_status,
+                      const uint32_t *d_nosz_size, uint32_t max_in_size, uint32_t max_out_size, hipStream_t s)
+{
+    // the layout's own arrays: 12 bytes per block in the packed arena (ordered between streams like the workspace)
+    size_t off = 0;
+    auto take = [&](u8 *base, size_t bytes) { u8 *q = base ? base + off : nullptr; off = align_up(off + bytes, 256); return q; };
+    if (r4x16_ensure_ps(c, 3 * align_up((size_t)n * 4, 256)) != 0) return -1;
+    UnpkWs w;
+    w.claim = (u32 *)take(c->ps, (size_t)n * 4); w.in_size = (u32 *)take(c->ps, (size_t)n * 4); w.pre = (i32 *)take(c->ps, (size_t)n * 4);
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    const PackedOut pk = {d_out, d_out_off, out_capacity};
+    const dim3 grid((n + 255) / 256), wg(256);
+    hipLaunchKernelGGL(k_unpk_claim<X8>, grid, wg, 0, s, d_in, d_in_off, d_in_size, d_nosz_size, w, n, max_in_size, max_out_size);
+    hipLaunchKernelGGL(k_pk_scan, dim3(1), dim3(1024), 0, s, (const u32 *)w.claim, d_out_off, 0, n);
+    hipLaunchKernelGGL(k_unpk_admit, grid, wg, 0, s, d_in_size, w, pk, n);
+    // every admitted block ends inside the capacity, so the capacities of the transformed blocks together do too
+    const u64 total = std::max<u64>(std::min<u64>(out_capacity, (u64)n * max_out_size), 1);
+    // rANS 4x8's sizing pass (no arena, capacity 0): only blocks that claim 0 bytes are admitted and nothing is written,
+    // but the slot call wants a pointer - the packed arena's own
+    unsigned char *out8 = d_out ? d_out : c->ps;
+    const int rc = X8 ? rans4x8_hip_uncompress_dev(c, n, d_in, d_in_off, w.in_size, out8, d_out_off, w.claim, d_out_size, d_status, s)
+                      : rans4x16_hip_uncompress_dev_sized(c, n, d_in, d_in_off, w.in_size, d_out, d_out_off, w.claim, d_out_size, d_status,
+                                                          max_in_size, max_out_size, total, s);
+    if (rc != 0) return -1;
+    hipLaunchKernelGGL(k_unpk_verdict, grid, wg, 0, s, w, d_out_size, d_status, n);
+    HIPCHK(c, hipGetLastError());
+    return r4x16_ws_order_end(c, s);
 }
 
 extern "C" int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *c, int n,
@@ -353,24 +411,123 @@ extern "C" int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *c, int n,
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
-    // the layout's own arrays: 12 bytes per block in the packed arena (ordered between streams like the workspace)
-    size_t off = 0;
-    auto take = [&](u8 *base, size_t bytes) { u8 *q = base ? base + off : nullptr; off = align_up(off + bytes, 256); return q; };
-    if (r4x16_ensure_ps(c, 3 * align_up((size_t)n * 4, 256)) != 0) return -1;
-    UnpkWs w;
-    w.claim = (u32 *)take(c->ps, (size_t)n * 4); w.in_size = (u32 *)take(c->ps, (size_t)n * 4); w.pre = (i32 *)take(c->ps, (size_t)n * 4);
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    return unpack_run<false>(c, n, d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, d_nosz_size,
+                             max_in_size, max_out_size, s);
+}
+
+// ---- rANS 4x8 (include/rans4x8_hip.h) --------------------------------------------------------------------------
+static int pick8_methods(rans4x16_hip_ctx *c, int k, const int *methods, Enc8Sel *sel, const char *who)
+{
+    if (k < 1 || k > 2 || !methods) { c->err = std::string(who) + ": k must be 1 or 2"; return -1; }
+    sel->k = k;
+    for (int j = 0; j < k; j++) {
+        if (methods[j] != 0 && methods[j] != 1) { c->err = std::string(who) + ": a method must be 0 or 1"; return -1; }
+        sel->m[j] = methods[j];
+    }
+    return 0;
+}
+
+static BatchArgs enc8_args(int n, const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size, uint32_t *d_out_size,
+                           int32_t *d_status, int order, const int32_t *d_order)
+{
+    BatchArgs a;
+    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
+    a.out = nullptr; a.out_off = nullptr; a.out_cap = nullptr; a.out_size = d_out_size;
+    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
+    return a;
+}
+
+extern "C" int rans4x8_hip_compress_packed_dev(rans4x16_hip_ctx *c, int n,
+                                               const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                               unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                               uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
+                                               uint32_t max_in_size, void *stream)
+{
+    if (!c) return -1;
+    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
+        c->err = "rans4x8 compress_packed_dev: bad arguments";
+        return -1;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
     const PackedOut pk = {d_out, d_out_off, out_capacity};
-    const dim3 grid((n + 255) / 256), wg(256);
-    hipLaunchKernelGGL(k_unpk_claim, grid, wg, 0, s, d_in, d_in_off, d_in_size, d_nosz_size, w, n, max_in_size, max_out_size);
-    hipLaunchKernelGGL(k_pk_scan, dim3(1), dim3(1024), 0, s, (const u32 *)w.claim, d_out_off, 0, n);
-    hipLaunchKernelGGL(k_unpk_admit, grid, wg, 0, s, d_in_size, w, pk, n);
-    // every admitted block ends inside the capacity, so the capacities of the transformed blocks together do too
-    const u64 total = std::max<u64>(std::min<u64>(out_capacity, (u64)n * max_out_size), 1);
-    const int rc = rans4x16_hip_uncompress_dev_sized(c, n, d_in, d_in_off, w.in_size, d_out, d_out_off, w.claim, d_out_size, d_status,
-                                                     max_in_size, max_out_size, total, s);
-    if (rc != 0) return -1;
-    hipLaunchKernelGGL(k_unpk_verdict, grid, wg, 0, s, w, d_out_size, d_status, n);
+    return r4x8_enc_run(c, enc8_args(n, d_in, d_in_off, d_in_size, d_out_size, d_status, order, d_order), max_in_size, s, &pk, nullptr);
+}
+
+extern "C" int rans4x8_hip_compress_best_dev(rans4x16_hip_ctx *c, int n,
+                                             const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                             unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                             uint32_t *d_out_size, int32_t *d_status,
+                                             int k, const int *methods, int32_t *d_chosen, uint32_t max_in_size, void *stream)
+{
+    if (!c) return -1;
+    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
+        c->err = "rans4x8 compress_best_dev: bad arguments";
+        return -1;
+    }
+    Enc8Sel sel = {};
+    if (pick8_methods(c, k, methods, &sel, "rans4x8 compress_best_dev") != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    sel.d_chosen = d_chosen;
+    BatchArgs a = enc8_args(n, d_in, d_in_off, d_in_size, d_out_size, d_status, 0, nullptr);
+    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap;
+    return r4x8_enc_run(c, a, max_in_size, (hipStream_t)stream, nullptr, &sel);
+}
+
+extern "C" int rans4x8_hip_compress_best_packed_dev(rans4x16_hip_ctx *c, int n,
+                                                    const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                                    unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                                    uint32_t *d_out_size, int32_t *d_status,
+                                                    int k, const int *methods, int32_t *d_chosen, uint32_t max_in_size, void *stream)
+{
+    if (!c) return -1;
+    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
+        c->err = "rans4x8 compress_best_packed_dev: bad arguments";
+        return -1;
+    }
+    Enc8Sel sel = {};
+    if (pick8_methods(c, k, methods, &sel, "rans4x8 compress_best_packed_dev") != 0) return -1;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
+    sel.d_chosen = d_chosen;
+    const PackedOut pk = {d_out, d_out_off, out_capacity};
+    return r4x8_enc_run(c, enc8_args(n, d_in, d_in_off, d_in_size, d_out_size, d_status, 0, nullptr), max_in_size, s, &pk, &sel);
+}
+
+extern "C" int rans4x8_hip_peek_dev(rans4x16_hip_ctx *c, int n,
+                                    const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                    int32_t *d_format, uint32_t *d_raw_size, int32_t *d_status, uint32_t max_in_size, void *stream)
+{
+    if (!c) return -1;
+    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_format || !d_raw_size || !d_status))) {
+        c->err = "rans4x8 peek_dev: bad arguments";
+        return -1;
+    }
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_peek<true>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_in, d_in_off, d_in_size, d_format,
+                       d_raw_size, d_status, n, max_in_size);
     HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+    return 0;
+}
+
+extern "C" int rans4x8_hip_uncompress_packed_dev(rans4x16_hip_ctx *c, int n,
+                                                 const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                                 unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                                 uint32_t *d_out_size, int32_t *d_status,
+                                                 uint32_t max_in_size, uint32_t max_out_size, void *stream)
+{
+    if (!c) return -1;
+    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
+        c->err = "rans4x8 uncompress_packed_dev: bad arguments";
+        return -1;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
+    return unpack_run<true>(c, n, d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, nullptr,
+                            max_in_size, max_out_size, s);
 }
