@@ -307,6 +307,22 @@ def uncompress_batch(blocks, caps):
     return _host_batch(blocks, True, caps=caps)
 
 
+def tok3_scan(container, max_columns=0, max_col_size=0):
+    """rans4x16_hip_tok3_scan: walk one tok3 column container (bytes) on the host.  Returns (status, info): status 0 or the
+    R4X16_E_* code the device walk gives, info a dict with last_start, nreads, ndesc, ncol, total_col_size, largest_col
+    and largest_stream (after a failure: of the columns accepted before it).  Needs no GPU."""
+    L = _lib.load()
+    buf = bytes(container)
+    u32 = [C.c_uint32(0) for _ in range(6)]
+    total = C.c_uint64(0)
+    rc = L.rans4x16_hip_tok3_scan(buf, len(buf), int(max_columns), int(max_col_size), C.byref(u32[0]), C.byref(u32[1]),
+                                  C.byref(u32[2]), C.byref(u32[3]), C.byref(total), C.byref(u32[4]), C.byref(u32[5]))
+    if rc < 0:
+        raise ValueError("tok3_scan: bad arguments")
+    return rc, {"last_start": u32[0].value, "nreads": u32[1].value, "ndesc": u32[2].value, "ncol": u32[3].value,
+                "total_col_size": total.value, "largest_col": u32[4].value, "largest_stream": u32[5].value}
+
+
 class DeviceCodec:
     """Device-resident batches on torch tensors (torch is used for device memory and streams
     only).  All tensors must live on the context's device."""
@@ -476,6 +492,57 @@ class DeviceCodec:
             nosz_size.data_ptr() if nosz_size is not None else None, int(max_in_size), int(max_out_size), self._stream())
         if rc != 0:
             raise RuntimeError("uncompress_packed_dev: " + self.ctx.error())
+
+    # ---- tok3 column containers (include/rans4x16_hip.h part 2c) -------------------------------------------------
+    def tok3_pack(self, blk_first, d_in, col_off, col_size, col_id, last_start, nreads, d_out, out_off, out_size, status,
+                  methods, max_col_size, chosen=None, total_col_size=0, out_capacity=None):
+        """rans4x16_hip_tok3_pack_dev: the columns col_off / col_size / col_id (int64 / int32 / int32) of the blocks
+        blk_first (int32, nblk + 1 entries) compressed with the best of `methods` and framed into one container per block
+        at d_out[out_off[b]:out_off[b + 1]].  d_out None: the sizing pass."""
+        t = self.torch
+        nblk, n = blk_first.numel() - 1, col_off.numel()
+        assert blk_first.dtype == t.int32 and col_off.dtype == t.int64 and col_size.dtype == t.int32 and col_id.dtype == t.int32
+        assert col_size.numel() == n and col_id.numel() == n
+        assert last_start.dtype == t.int32 and nreads.dtype == t.int32 and last_start.numel() == nblk and nreads.numel() == nblk
+        assert out_off.dtype == t.int64 and out_off.numel() == nblk + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32 and out_size.numel() == nblk and status.numel() == nblk
+        assert chosen is None or (chosen.dtype == t.int32 and chosen.numel() == n)
+        assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
+        cap = (d_out.numel() if d_out is not None else 0) if out_capacity is None else int(out_capacity)
+        assert cap <= (d_out.numel() if d_out is not None else 0)
+        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        rc = self.L.rans4x16_hip_tok3_pack_dev(
+            self.ctx.h, nblk, n, blk_first.data_ptr(), d_in.data_ptr(), col_off.data_ptr(), col_size.data_ptr(),
+            col_id.data_ptr(), last_start.data_ptr(), nreads.data_ptr(), d_out.data_ptr() if d_out is not None else None, cap,
+            out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), len(methods), meth,
+            chosen.data_ptr() if chosen is not None else None, int(max_col_size), int(total_col_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("tok3_pack_dev: " + self.ctx.error())
+
+    def tok3_unpack(self, d_in, in_off, in_size, d_out, out_off, out_size, status, ncol, last_start, nreads,
+                    col_id, col_off, col_size, max_columns, max_in_size, max_col_size, out_capacity=None):
+        """rans4x16_hip_tok3_unpack_dev: every container walked and its columns decoded back to back into
+        d_out[out_off[b]:out_off[b + 1]]; col_id / col_off / col_size (int32 / int64 / int32, nblk x max_columns) are the
+        directory of the columns.  d_out None: the sizing pass."""
+        t = self.torch
+        nblk = in_size.numel()
+        assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
+        assert in_off.dtype == t.int64 and in_off.numel() >= nblk and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == nblk + 1
+        for x in (out_size, status, ncol, last_start, nreads):
+            assert x.dtype == t.int32 and x.numel() == nblk
+        assert col_id.dtype == t.int32 and col_off.dtype == t.int64 and col_size.dtype == t.int32
+        for x in (col_id, col_off, col_size):
+            assert x.numel() == nblk * int(max_columns)
+        cap = (d_out.numel() if d_out is not None else 0) if out_capacity is None else int(out_capacity)
+        assert cap <= (d_out.numel() if d_out is not None else 0)
+        rc = self.L.rans4x16_hip_tok3_unpack_dev(
+            self.ctx.h, nblk, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            ncol.data_ptr(), last_start.data_ptr(), nreads.data_ptr(), col_id.data_ptr(), col_off.data_ptr(), col_size.data_ptr(),
+            int(max_columns), int(max_in_size), int(max_col_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("tok3_unpack_dev: " + self.ctx.error())
 
     # ---- rANS 4x8 (CRAM 3.0), include/rans4x8_hip.h part 2a: the same surface, every result assembled in place -------
     def compress_packed_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, order, max_in_size,

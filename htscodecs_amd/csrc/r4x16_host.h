@@ -129,6 +129,9 @@ struct rans4x16_hip_ctx {
     u8 *ps = nullptr;
     size_t ps_bytes = 0;
     bool in_packed = false;                 // inside a packed call's slot call over its internal slots
+    // the tok3 container calls (r4x16_tok3.hip): the winners waiting to be framed / the directory of the columns to decode
+    u8 *t3 = nullptr;
+    size_t t3_bytes = 0;
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;

@@ -275,6 +275,102 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
                                        uint32_t *d_out_size, int32_t *d_status, const uint32_t *d_nosz_size,
                                        uint32_t max_in_size, uint32_t max_out_size, void *stream);
 
+/* ---- 2c. tok3 column containers ---------------------------------------------------------------
+ * The CRAM 3.1 name tokeniser (htscodecs tokenise_name3.c) turns a block of read names into token columns, compresses
+ * each with the best of a method list and frames them into one container (encode_names, :1431-1531); decode_names
+ * (:1546-1669) walks the container and decodes the columns before it rebuilds the names.  These calls do the column
+ * half of both on the device, rANS flavour (use_arith = 0); the tokeniser itself - trie, encode_name / decode_name -
+ * is serial per name and stays with the caller.
+ *
+ * A container: last_start (4 bytes, little endian), nreads (4), use_arith (1), then per column a type byte
+ * (type | 128 on the first column of a token position, | 64 for a duplicate) followed by var_put_u32(clen) and the
+ * rANS 4x16 stream, or - duplicate - by id >> 4, id & 15 of the earlier column it repeats.  A column's id is
+ * tnum << 4 | type, tnum below 128.
+ *
+ * rans4x16_hip_tok3_scan: walks one container in HOST memory.  Pure host arithmetic, usable without a GPU, like
+ * rans4x16_hip_partition.  Reports the header's last_start and nreads, the number of descriptors, the number of columns
+ * they give (descriptors plus synthesised type columns, below), the total and the largest column size and the largest
+ * stream (any of the pointers may be NULL), and returns 0 or the R4X16_E_* status the walk of
+ * rans4x16_hip_tok3_unpack_dev gives with the same max_columns / max_col_size (0 = no limit: 2048 / 2^32 - 1); -1 on bad
+ * arguments.  After a failure the counts and sizes are those of the columns accepted before it.
+ *
+ * rans4x16_hip_tok3_pack_dev: nblk name blocks with n columns in all.  Every array is a DEVICE array.
+ *   d_blk_first[nblk + 1]       first column of each block; d_blk_first[0] = 0, d_blk_first[nblk] = n
+ *   d_in + d_col_off[i]         column i, d_col_size[i] bytes
+ *   d_col_id[i]                 tnum << 4 | type; strictly ascending inside a block
+ *   d_last_start, d_nreads      [nblk], the header values
+ *   k, methods, d_chosen        as in rans4x16_hip_compress_best_dev, per column; a column written as a duplicate still
+ *                               reports its method
+ *   max_col_size, total_col_size  largest column / sum of the columns (0 = unknown), host
+ *   d_out, out_capacity, d_out_off[nblk + 1], d_out_size, d_status: one dense arena as in
+ *   rans4x16_hip_compress_packed_dev - offsets written by the call, sums before the capacity rule, d_out == NULL with
+ *   out_capacity 0 as a sizing pass; a block that ends beyond out_capacity reports R4X16_E_CAPACITY and size 0.
+ * Block b's bytes are what :1498-1531 writes: the header with use_arith = 0, then per column the type byte and either
+ * var_put_u32(clen) and the winner's stream - the winner of rans4x16_hip_compress_best_dev's rules, X_STRIPE skip and
+ * first-listed-wins included - or the three bytes of a duplicate.  A column is a duplicate of the first earlier column
+ * of its block whose varint + stream has the same length, more than 4 bytes, and the same bytes (:1461-1477); columns
+ * that were themselves written as duplicates are candidates too; if that first match has id 0 the column is written in
+ * full (the reference tests `if (dup_from)`).  d_out_size is the bytes really written (the reference's own figure comes
+ * out too small after a duplicate).
+ * A block with a zero-length column, with ids that do not ascend or are outside 0 .. 2047, or with an inconsistent
+ * d_blk_first (first > next, next > n, a start below the start of an earlier block, d_blk_first[0] != 0 for block 0,
+ * d_blk_first[nblk] != n for the last) reports
+ * R4X16_E_SIZE and size 0; one with a column above max_col_size (or more bytes than total_col_size announced)
+ * R4X16_E_UNSUPPORTED; one with a column that no method could encode that column's status.  Its neighbours are not
+ * affected.  The call only enqueues and reads nothing back.  The columns are encoded in chunks under max_workspace_mb like
+ * the packed calls; the winners of the whole batch wait in an arena of the context until their blocks are framed (about
+ * 1.05 x the columns plus 800 bytes per column where the list has an order-0 method), so no block's columns are ever
+ * split; a batch whose winners do not fit half of max_workspace_mb is refused with -1: split it.
+ *
+ * rans4x16_hip_tok3_unpack_dev: nblk containers at d_in + d_in_off[b], d_in_size[b] bytes (at most max_in_size).
+ *   max_columns (1..2048)  descriptors per block the directory holds; nblk x max_columns sizes the internal decode batch
+ *   max_col_size           largest column
+ *   d_out, out_capacity, d_out_off[nblk + 1]: the dense arena; a block's columns lie back to back in descriptor order,
+ *   a synthesised type column (below) right in front of the column whose descriptor opened its position.
+ *   d_col_id / d_col_off / d_col_size [nblk x max_columns]: entry b * max_columns + c is the column of descriptor c of
+ *   block b - its id, where it starts in d_out, its size (id -1, size 0 past the block's last descriptor).  An id with
+ *   R4X16_TOK3_TYPE_COLUMN set says that the type column of its position (id & ~15 & 2047, nreads bytes) lies at
+ *   d_col_off - nreads.
+ *   d_ncol (descriptors), d_last_start, d_nreads, d_out_size (bytes of all columns), d_status [nblk].
+ * The walk (the statuses are those of rans4x16_hip_tok3_scan):
+ *   - fewer than 9 bytes: TRUNCATED; use_arith != 0: UNSUPPORTED; last_start negative as an int or above
+ *     INT_MAX - 1024: SIZE (:1555); a container above max_in_size: UNSUPPORTED, not read.
+ *   - a | 128 descriptor opens the next tnum; the 128th: SIZE.  If its type is not 0 the position's type column (id
+ *     tnum << 4) is synthesised first: nreads bytes, the type and then N_MATCH (10) repeated (:1581-1591, :1619-1629);
+ *     nreads == 0: SIZE, nreads > max_col_size: UNSUPPORTED.  A descriptor before the first | 128: SIZE.
+ *   - a duplicate needs its two bytes and one more inside the container (the reference's own test, :1570, which refuses
+ *     a duplicate that is the last descriptor): else TRUNCATED; its j must be below its own id: else SIZE.  It is a
+ *     copy of column j; a j that never appeared gives a column of 0 bytes.
+ *   - a plain descriptor reads clen, then the stored size at the stream's byte 1 as rans4x16_hip_peek_dev does, claims
+ *     that many bytes and is decoded, with in_size = clen, exactly as rans4x16_hip_uncompress_packed_dev decodes a block
+ *     with that claim; a claim above max_col_size: UNSUPPORTED.
+ *   Stricter than the reference, never reached by encoder output: ids that do not strictly ascend: UNSUPPORTED (this
+ *   bounds the walk at 2048 descriptors); more descriptors than max_columns: UNSUPPORTED; a stream with X_NOSZ (and
+ *   without X_STRIPE): SIZE; a clen that does not end, or reaches beyond the container: TRUNCATED; clen == 0: EMPTY.
+ * A block fails as a whole, as the reference returns NULL: d_status is the walk's status, else R4X16_E_CAPACITY if its
+ * range ends beyond out_capacity (it is not decoded), else the status of its first column that failed to decode (SIZE
+ * for one that decoded to another size than it claimed, where the reference trips its assert at :1655);
+ * d_ncol = 0, d_out_size = 0, its directory sizes are 0, the bytes inside its own range are unspecified (a block the walk
+ * refuses has no range).  Nothing outside the ranges is written.  The call only enqueues and reads nothing back. */
+#define R4X16_TOK3_TYPE_COLUMN 0x10000   /* d_col_id flag of rans4x16_hip_tok3_unpack_dev, above */
+int rans4x16_hip_tok3_scan(const unsigned char *in, size_t size, uint32_t max_columns, uint32_t max_col_size,
+                           uint32_t *last_start, uint32_t *nreads, uint32_t *ndesc, uint32_t *ncol,
+                           uint64_t *total_col_size, uint32_t *largest_col, uint32_t *largest_stream);
+int rans4x16_hip_tok3_pack_dev(rans4x16_hip_ctx *ctx, int nblk, int n, const uint32_t *d_blk_first,
+                               const unsigned char *d_in, const uint64_t *d_col_off, const uint32_t *d_col_size,
+                               const int32_t *d_col_id, const uint32_t *d_last_start, const uint32_t *d_nreads,
+                               unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                               uint32_t *d_out_size, int32_t *d_status,
+                               int k, const int *methods, int32_t *d_chosen,
+                               uint32_t max_col_size, uint64_t total_col_size, void *stream);
+int rans4x16_hip_tok3_unpack_dev(rans4x16_hip_ctx *ctx, int nblk,
+                                 const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                 unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                 uint32_t *d_out_size, int32_t *d_status,
+                                 uint32_t *d_ncol, uint32_t *d_last_start, uint32_t *d_nreads,
+                                 int32_t *d_col_id, uint64_t *d_col_off, uint32_t *d_col_size,
+                                 uint32_t max_columns, uint32_t max_in_size, uint32_t max_col_size, void *stream);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
