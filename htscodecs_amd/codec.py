@@ -544,6 +544,61 @@ class DeviceCodec:
         if rc != 0:
             raise RuntimeError("tok3_unpack_dev: " + self.ctx.error())
 
+    # ---- tok3 name decoding (include/rans4x16_hip.h part 2d) ---------------------------------------------------------
+    def _names_out(self, nblk, d_out, out_off, out_size, nnames, status, name_start, max_names, out_capacity):
+        t = self.torch
+        assert d_out is None or d_out.dtype == t.uint8
+        assert out_off.dtype == t.int64 and out_off.numel() == nblk + 1
+        for x in (out_size, nnames, status):
+            assert x.dtype == t.int32 and x.numel() == nblk
+        assert name_start is None or (name_start.dtype == t.int32 and name_start.numel() == nblk * int(max_names))
+        cap = (d_out.numel() if d_out is not None else 0) if out_capacity is None else int(out_capacity)
+        assert cap <= (d_out.numel() if d_out is not None else 0)
+        return cap
+
+    def tok3_names(self, d_cols, col_id, col_off, col_size, ncol, last_start, nreads, d_out, out_off, out_size, nnames, status,
+                   max_columns, max_names, max_tokens=128, blk_status=None, name_start=None, out_capacity=None):
+        """rans4x16_hip_tok3_names_dev: the columns tok3_unpack left in d_cols (its directory col_id / col_off / col_size and
+        ncol / last_start / nreads go straight in, its status as blk_status) decoded to NUL-separated read names at
+        d_out[out_off[b]:out_off[b + 1]]; name_start (int32, nblk x max_names, optional): where every name starts inside
+        its block.  d_out None: the sizing pass."""
+        t = self.torch
+        nblk = ncol.numel()
+        assert d_cols.dtype == t.uint8
+        assert col_id.dtype == t.int32 and col_off.dtype == t.int64 and col_size.dtype == t.int32
+        for x in (col_id, col_off, col_size):
+            assert x.numel() == nblk * int(max_columns)
+        for x in (ncol, last_start, nreads):
+            assert x.dtype == t.int32 and x.numel() == nblk
+        assert blk_status is None or (blk_status.dtype == t.int32 and blk_status.numel() == nblk)
+        cap = self._names_out(nblk, d_out, out_off, out_size, nnames, status, name_start, max_names, out_capacity)
+        rc = self.L.rans4x16_hip_tok3_names_dev(
+            self.ctx.h, nblk, d_cols.data_ptr(), d_cols.numel(), col_id.data_ptr(), col_off.data_ptr(), col_size.data_ptr(),
+            ncol.data_ptr(), last_start.data_ptr(), nreads.data_ptr(), blk_status.data_ptr() if blk_status is not None else None,
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), nnames.data_ptr(),
+            status.data_ptr(), name_start.data_ptr() if name_start is not None else None,
+            int(max_columns), int(max_names), int(max_tokens), self._stream())
+        if rc != 0:
+            raise RuntimeError("tok3_names_dev: " + self.ctx.error())
+
+    def tok3_decode_names(self, d_in, in_off, in_size, d_out, out_off, out_size, nnames, status, max_columns, max_in_size,
+                          max_col_size, max_names, max_tokens=128, total_col_size=0, name_start=None, out_capacity=None):
+        """rans4x16_hip_tok3_decode_names_dev: every container walked, its columns decoded and its read names written,
+        NUL-separated, at d_out[out_off[b]:out_off[b + 1]] - tok3_unpack and tok3_names in one call, the columns kept in an
+        arena of the context (total_col_size: their bytes, 0 = unknown).  d_out None: the sizing pass."""
+        t = self.torch
+        nblk = in_size.numel()
+        assert d_in.dtype == t.uint8 and in_off.dtype == t.int64 and in_off.numel() >= nblk and in_size.dtype == t.int32
+        cap = self._names_out(nblk, d_out, out_off, out_size, nnames, status, name_start, max_names, out_capacity)
+        rc = self.L.rans4x16_hip_tok3_decode_names_dev(
+            self.ctx.h, nblk, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), nnames.data_ptr(),
+            status.data_ptr(), name_start.data_ptr() if name_start is not None else None,
+            int(max_columns), int(max_in_size), int(max_col_size), int(max_names), int(max_tokens), int(total_col_size),
+            self._stream())
+        if rc != 0:
+            raise RuntimeError("tok3_decode_names_dev: " + self.ctx.error())
+
     # ---- rANS 4x8 (CRAM 3.0), include/rans4x8_hip.h part 2a: the same surface, every result assembled in place -------
     def compress_packed_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, order, max_in_size,
                             d_order=None, out_capacity=None):

@@ -186,6 +186,7 @@ extern "C" void rans4x16_hip_destroy(rans4x16_hip_ctx *c)
     if (c->xs) (void)hipFree(c->xs);
     if (c->ps) (void)hipFree(c->ps);
     if (c->t3) (void)hipFree(c->t3);
+    if (c->tn) (void)hipFree(c->tn);
     if (c->stage) (void)hipFree(c->stage);
     if (c->logtab) (void)hipFree(c->logtab);
     if (c->rcptab) (void)hipFree(c->rcptab);

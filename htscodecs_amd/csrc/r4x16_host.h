@@ -132,6 +132,9 @@ struct rans4x16_hip_ctx {
     // the tok3 container calls (r4x16_tok3.hip): the winners waiting to be framed / the directory of the columns to decode
     u8 *t3 = nullptr;
     size_t t3_bytes = 0;
+    // tok3 name decoding (r4x16_tok3_names.hip): the names' histories; for the one-call form the columns in front of them
+    u8 *tn = nullptr;
+    size_t tn_bytes = 0;
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;

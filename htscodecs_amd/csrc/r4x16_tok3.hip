@@ -1,6 +1,6 @@
 // r4x16_tok3.hip - the tok3 column container on the device (include/rans4x16_hip.h part 2c): what encode_names
 // (htscodecs tokenise_name3.c:1431-1531) does with a name block's token columns once they are filled, and what
-// decode_names (:1546-1669) does before it reads them.  The tokeniser itself stays with the caller.
+// decode_names (:1546-1669) does before it reads them (the names themselves: r4x16_tok3_names.hip).
 //
 // Pack.   rans4x16_hip_compress_best_packed_dev over all columns of the batch leaves the winners back to back in an
 //         arena of the context (`t3`); then

@@ -279,8 +279,8 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
  * The CRAM 3.1 name tokeniser (htscodecs tokenise_name3.c) turns a block of read names into token columns, compresses
  * each with the best of a method list and frames them into one container (encode_names, :1431-1531); decode_names
  * (:1546-1669) walks the container and decodes the columns before it rebuilds the names.  These calls do the column
- * half of both on the device, rANS flavour (use_arith = 0); the tokeniser itself - trie, encode_name / decode_name -
- * is serial per name and stays with the caller.
+ * half of both on the device, rANS flavour (use_arith = 0); part 2d turns the decoded columns into names (decode_name).
+ * The encoding tokeniser - trie, encode_name - is serial per name and stays with the caller.
  *
  * A container: last_start (4 bytes, little endian), nreads (4), use_arith (1), then per column a type byte
  * (type | 128 on the first column of a token position, | 64 for a duplicate) followed by var_put_u32(clen) and the
@@ -370,6 +370,83 @@ int rans4x16_hip_tok3_unpack_dev(rans4x16_hip_ctx *ctx, int nblk,
                                  uint32_t *d_ncol, uint32_t *d_last_start, uint32_t *d_nreads,
                                  int32_t *d_col_id, uint64_t *d_col_off, uint32_t *d_col_size,
                                  uint32_t max_columns, uint32_t max_in_size, uint32_t max_col_size, void *stream);
+
+/* ---- 2d. tok3 name decoding ---------------------------------------------------------------------
+ * The second half of decode_names (htscodecs tokenise_name3.c:1546-1694): the token columns of a name block become its
+ * read names, NUL-separated, on the device - decode_name (:1018-1189) and the loop around it (:1671-1689).  rANS flavour
+ * (use_arith = 0) only; the encoding direction is not built.
+ *
+ * rans4x16_hip_tok3_names_dev: the stage.  Its inputs are what rans4x16_hip_tok3_unpack_dev wrote, DEVICE arrays all:
+ *   d_cols, col_capacity         the column arena and its size in bytes; a column that does not lie inside it fails its
+ *                                block with R4X16_E_SIZE, nothing outside it is read
+ *   d_col_id / d_col_off / d_col_size  [nblk x max_columns], the directory, R4X16_TOK3_TYPE_COLUMN flags included
+ *   d_ncol, d_last_start, d_nreads     [nblk]
+ *   d_blk_status                 [nblk] or NULL (all good): a block with a non-zero entry is skipped, reports that status
+ *                                and claims nothing
+ *   max_names                    names per block the call is sized for (host)
+ *   max_tokens                   token positions per block, 1..128 (host)
+ * Its outputs are one dense arena as in the packed calls:
+ *   d_out, out_capacity, d_out_off[nblk + 1]  block b's names at d_out + d_out_off[b]; the offsets are written by the call
+ *                                as sums before the capacity rule; d_out == NULL with out_capacity 0 is a sizing pass.
+ *                                A block's claim is its last_start (0 for a skipped block); a block that ends beyond
+ *                                out_capacity reports R4X16_E_CAPACITY and size 0
+ *   d_out_size, d_nnames, d_status [nblk]     bytes written (= last_start), names written, R4X16_OK or the failure
+ *   d_name_start                 [nblk x max_names] or NULL: where name i of block b starts, relative to d_out_off[b];
+ *                                entries [0, d_nnames[b]) of a block are written
+ * Encoder output decodes byte for byte as the reference decodes it.  The rules, with the reference's lines:
+ *   Framing.  A block holds as many names as its column id 0 has bytes (the reference stops when that column runs out,
+ *   :1019-1027).  nreads == 0, more names than nreads, or last_start above INT_MAX - 1024: SIZE.  More token positions
+ *   (largest id >> 4, plus 1) than max_tokens, or more names than max_names: UNSUPPORTED.  A column of 2^28 bytes or more:
+ *   UNSUPPORTED.  A name that ends beyond last_start, or a decoded size other than last_start: SIZE (the reference uses
+ *   the field as a capacity with 1,024 bytes of slack; encoder output satisfies equality, and it is what lets the arena be
+ *   dense without a sizing decode).
+ *   Position 0.  The type must be N_DUP (5) or N_DIFF (6): else SIZE (the reference reads a distance out of whatever
+ *   column that number names).  dist: 4 bytes, little endian, of column id 5 / 6; a column that runs out: TRUNCATED;
+ *   dist above the name's index, or N_DUP with dist 0: SIZE.  A N_DUP name is the bytes of name index - dist and takes
+ *   its token state; it may itself be repeated and matched against.
+ *   Positions 1 and up.  The type comes from column position << 4; a missing or exhausted type column, and every value
+ *   outside {1, 2, 3, 7, 8, 9, 10, 11}, is N_END (:1175); no end before position min(128, positions of the block): SIZE.
+ *   N_CHAR one byte; N_ALPHA the bytes up to a NUL; N_DIGITS0 the N_DZLEN byte vl and a 32-bit value written as
+ *   append_uint32_fixed does; N_DIGITS a 32-bit value written as append_uint32_var does - 0 writes no byte at all
+ *   (:284-302); N_DDELTA / N_DDELTA0 one byte added to the earlier name's value at that position, modulo 2^32; N_NOP
+ *   nothing; N_MATCH repeats the earlier name's token of that position.  N_MATCH, N_DDELTA, N_DDELTA0 at or beyond the
+ *   earlier name's end position (0 for dist 0, :1061), and N_MATCH of a N_NOP: SIZE.  A value column that runs out:
+ *   TRUNCATED.  Of several failing positions of one name the lowest decides.
+ *   Kept from the reference: a fixed-width value that needs more digits than vl has the byte v / 10^(vl - 1) + '0',
+ *   truncated to 8 bits, in front.
+ *   Stricter than the reference, never reached by encoder output: N_DDELTA on a token that is not N_DIGITS, N_DDELTA0 on
+ *   one that is not N_DIGITS0: SIZE (the reference adds to whatever integer sits there); vl above 9: SIZE (the reference
+ *   advances over bytes it never wrote); a N_ALPHA string without its NUL inside the column: TRUNCATED (the reference drops
+ *   its last byte).  A N_CHAR of 0 or a truncated fixed-width byte of 0 stays a byte of the name, also where the name is
+ *   repeated (the reference's strcpy would cut it there).
+ * A block fails as a whole, as the reference returns NULL: its status, size 0, d_nnames 0; the bytes inside its own range
+ * are unspecified; its neighbours are not affected.  Nothing outside the blocks' ranges is written.
+ * Every name keeps 8 bytes per token position and 16 bytes of its own in a history arena of the context, laid out on the
+ * device from each block's own names x positions (rounded up to 16 bytes, in batch order) and bounded on the host by
+ * nblk x max_names x (8 x max_tokens + 16) and by half of max_workspace_mb; a block whose history ends beyond that
+ * reports R4X16_E_UNSUPPORTED (before the capacity rule).  One wave decodes one block: a batch of few blocks leaves the chip idle.
+ *
+ * rans4x16_hip_tok3_decode_names_dev: decode_names as one call - rans4x16_hip_tok3_unpack_dev into a column arena of the
+ * context, then the stage.  It takes the unpack's arguments and limits, the stage's outputs and limits, and
+ * total_col_size: the bytes of all columns of the batch, synthesised type columns included (rans4x16_hip_tok3_scan's
+ * total_col_size, summed), 0 for unknown (then nblk x max_columns x 2 x max_col_size is reserved).  A block the unpack
+ * refuses - a block that ends beyond total_col_size is one, with R4X16_E_CAPACITY - reports the unpack's status.  A batch
+ * whose column arena plus histories do not fit half of max_workspace_mb is refused with -1: split it.
+ * Both calls only enqueue and read nothing back; -1 on bad arguments (a NULL context included). */
+int rans4x16_hip_tok3_names_dev(rans4x16_hip_ctx *ctx, int nblk,
+                                const unsigned char *d_cols, uint64_t col_capacity,
+                                const int32_t *d_col_id, const uint64_t *d_col_off, const uint32_t *d_col_size,
+                                const uint32_t *d_ncol, const uint32_t *d_last_start, const uint32_t *d_nreads,
+                                const int32_t *d_blk_status,
+                                unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                uint32_t *d_out_size, uint32_t *d_nnames, int32_t *d_status, uint32_t *d_name_start,
+                                uint32_t max_columns, uint32_t max_names, uint32_t max_tokens, void *stream);
+int rans4x16_hip_tok3_decode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
+                                       const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                       unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                       uint32_t *d_out_size, uint32_t *d_nnames, int32_t *d_status, uint32_t *d_name_start,
+                                       uint32_t max_columns, uint32_t max_in_size, uint32_t max_col_size,
+                                       uint32_t max_names, uint32_t max_tokens, uint64_t total_col_size, void *stream);
 
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
