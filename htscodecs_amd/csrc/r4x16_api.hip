@@ -108,6 +108,63 @@ extern "C" int rans4x16_hip_get_option(const rans4x16_hip_ctx *c, const char *na
 }
 extern "C" const char *rans4x16_hip_option_name(int index) { return index >= 0 && index < OPT_COUNT ? OPT_TAB[index].name : nullptr; }
 
+// ---- the context's arenas (r4x16_host.h) -----------------------------------------------------------------------
+static const char *const ARENA_NAME[A_COUNT] = {"workspace", "staging arena", "stripe / candidate arena", "packed calls' slot arena",
+                                                "tok3 arena", "tok3 names arena"};
+
+static void arena_release(rans4x16_hip_ctx *c, unsigned mask)
+{
+    for (int a = 0; a < A_COUNT; a++)
+        if ((mask & A_BIT(a)) && c->arena[a].p) { (void)hipFree(c->arena[a].p); c->arena[a].p = nullptr; c->arena[a].bytes = 0; }
+}
+
+int r4x16_ensure(rans4x16_hip_ctx *c, R4Arena which, size_t bytes, bool refuse_above_half_free)
+{
+    auto &ar = c->arena[which];
+    if (bytes <= ar.bytes) return 0;
+    if (ar.p) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(ar.p)); ar.p = nullptr; ar.bytes = 0; }
+    const std::string what = std::string(ARENA_NAME[which]) + " (" + std::to_string(bytes >> 20) + " MiB)";
+    size_t free_b = 0, total_b = 0;
+    if (refuse_above_half_free && hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b / 2) {
+        c->err = "the " + what + " exceeds half of the free device memory";
+        return -1;
+    }
+    const hipError_t e = hipMalloc((void **)&ar.p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();                   // not sticky: the caller retries with a smaller chunk
+        ar.p = nullptr;
+        c->err = "hipMalloc of the " + what + ": " + hipGetErrorString(e);
+        return -1;
+    }
+    ar.bytes = bytes;
+    return 0;
+}
+
+// (The slot calls of this file count the workspace, and the packed arena where they lay slots out in it; not the stripe
+//  arena: when they run as the inner call of r4x16_stripe.hip / r4x16_best.hip it holds that call's items.)
+size_t r4x16_room(rans4x16_hip_ctx *c, unsigned reuse_mask)
+{
+    size_t cap = c->max_ws;
+    size_t have = 0, total_b = 0;
+    if (hipMemGetInfo(&have, &total_b) == hipSuccess) {
+        for (int a = 0; a < A_COUNT; a++) if (reuse_mask & A_BIT(a)) have += c->arena[a].bytes;
+        if (have / 4 * 3 < cap) cap = have / 4 * 3;
+    }
+    return cap;
+}
+
+// Give back device memory above `keep` bytes (the single-block entry points call this after an unusually large
+// block, so that one call - or one hostile size field - does not pin gigabytes to the calling thread for good).
+void r4x16_trim(rans4x16_hip_ctx *c, size_t keep)
+{
+    if (!c || c->arena[A_STAGE].bytes + c->arena[A_WS].bytes <= keep) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    // (the packed and tok3 arenas are not touched by the single-block entry points)
+    arena_release(c, A_BIT(A_STAGE) | A_BIT(A_WS) | A_BIT(A_XS));
+    c->ws_busy = false;
+}
+
 extern "C" rans4x16_hip_ctx *rans4x16_hip_create(int device)
 {
     int ndev = 0;
@@ -182,12 +239,7 @@ extern "C" void rans4x16_hip_destroy(rans4x16_hip_ctx *c)
     }
     for (int w = 0; w < 2; w++) if (c->hint[w].work) (void)hipHostFree(c->hint[w].work);
     if (c->ws_done) (void)hipEventDestroy(c->ws_done);
-    if (c->ws) (void)hipFree(c->ws);
-    if (c->xs) (void)hipFree(c->xs);
-    if (c->ps) (void)hipFree(c->ps);
-    if (c->t3) (void)hipFree(c->t3);
-    if (c->tn) (void)hipFree(c->tn);
-    if (c->stage) (void)hipFree(c->stage);
+    arena_release(c, ~0u);
     if (c->logtab) (void)hipFree(c->logtab);
     if (c->rcptab) (void)hipFree(c->rcptab);
     delete c;
@@ -209,7 +261,7 @@ extern "C" int rans4x16_hip_set_dev_stripe_encode(rans4x16_hip_ctx *c, int max_p
 }
 
 extern "C" const char *rans4x16_hip_last_error(const rans4x16_hip_ctx *c) { return c ? c->err.c_str() : "no context"; }
-extern "C" size_t rans4x16_hip_workspace_bytes(const rans4x16_hip_ctx *c) { return c ? c->ws_bytes : 0; }
+extern "C" size_t rans4x16_hip_workspace_bytes(const rans4x16_hip_ctx *c) { return c ? c->arena[A_WS].bytes : 0; }
 
 extern "C" void rans4x16_hip_timing(rans4x16_hip_ctx *c, int enable) { if (c) c->timing = enable; }
 
@@ -289,57 +341,6 @@ extern "C" int rans4x16_hip_route_read(rans4x16_hip_ctx *c, int which, long *cou
     return ROUTE_NKINDS[which];
 }
 
-static int ensure_ws(rans4x16_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->ws_bytes) return 0;
-    if (c->ws) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->ws)); c->ws = nullptr; c->ws_bytes = 0; }
-    const hipError_t e = hipMalloc((void **)&c->ws, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();                   // not sticky: the caller retries with a smaller chunk
-        c->ws = nullptr;
-        c->err = std::string("hipMalloc of the workspace (") + std::to_string(bytes >> 20) + " MiB): " + hipGetErrorString(e);
-        return -1;
-    }
-    c->ws_bytes = bytes;
-    return 0;
-}
-
-// Blocks per workspace chunk: as many as the cap allows (the context's ceiling, and three quarters of what the device has
-// free right now - other contexts and other processes share the card), in equal chunks rather than full ones and a rest.
-// bytes(nb) = workspace of a chunk of nb blocks, monotone in nb.
-// held: bytes of other arenas of the context that bytes(nb) counts as well (they are not free, but the call reuses them).
-template <class F>
-static size_t plan_chunk(rans4x16_hip_ctx *c, size_t n, F bytes, size_t held = 0)
-{
-    size_t cap = c->max_ws;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const size_t room = (free_b + c->ws_bytes + held) / 4 * 3;
-        if (room < cap) cap = room;
-    }
-    if (bytes(n) <= cap) return n;
-    size_t lo = 1, hi = n;                         // the largest chunk that fits: bytes(lo) <= cap < bytes(hi)
-    while (lo + 1 < hi) {
-        const size_t mid = lo + (hi - lo) / 2;
-        if (bytes(mid) <= cap) lo = mid; else hi = mid;
-    }
-    const size_t rounds = (n + lo - 1) / lo;
-    return (n + rounds - 1) / rounds;
-}
-
-// What the arenas of one call may take together: plan_chunk's cap, for callers that hold a second arena (r4x16_best.hip)
-// held: an arena the caller keeps next to these and plans for itself (the packed calls' slots)
-size_t r4x16_ws_room(rans4x16_hip_ctx *c, size_t held)
-{
-    size_t cap = c->max_ws;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const size_t room = (free_b + c->ws_bytes + c->xs_bytes + held) / 4 * 3;
-        if (room < cap) cap = room;
-    }
-    return cap;
-}
-
 // The side streams of the chain kernels' class launches (R4Fork, r4x16_dev.h); nullptr where they are switched off
 // (option sched_concurrent = 0), cannot be made, or the context is a lane of the host pipeline.
 #define FORK_ONE_BLOCK_BYTES (256u << 10)
@@ -360,18 +361,14 @@ static const R4Fork *fork_for(rans4x16_hip_ctx *c)
     return c->fork.n ? &c->fork : nullptr;
 }
 
-static int ws_order_begin(rans4x16_hip_ctx *c, hipStream_t s);
-static int ws_order_end(rans4x16_hip_ctx *c, hipStream_t s);
 // A context has ONE workspace: calls on different streams must not overlap on it.  Every *_dev call ends with an
 // event on its stream; a call on another stream first waits for the previous call's event.
-int r4x16_ws_order_begin(rans4x16_hip_ctx *c, hipStream_t s) { return ws_order_begin(c, s); }
-int r4x16_ws_order_end(rans4x16_hip_ctx *c, hipStream_t s) { return ws_order_end(c, s); }
-static int ws_order_begin(rans4x16_hip_ctx *c, hipStream_t s)
+int r4x16_ws_order_begin(rans4x16_hip_ctx *c, hipStream_t s)
 {
     if (c->ws_busy && s != c->ws_stream) HIPCHK(c, hipStreamWaitEvent(s, c->ws_done, 0));
     return 0;
 }
-static int ws_order_end(rans4x16_hip_ctx *c, hipStream_t s)
+int r4x16_ws_order_end(rans4x16_hip_ctx *c, hipStream_t s)
 {
     if (!c->ws_done) HIPCHK(c, hipEventCreateWithFlags(&c->ws_done, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ws_done, s));
@@ -379,18 +376,6 @@ static int ws_order_end(rans4x16_hip_ctx *c, hipStream_t s)
     c->ws_busy = true;
     return 0;
 }
-
-// carve helper
-struct Carver {
-    u8 *p; size_t off = 0;
-    explicit Carver(u8 *base) : p(base) {}
-    template <class T> T *take(size_t count, size_t elem = sizeof(T)) {
-        off = align_up(off, 256);
-        T *r = (T *)(p ? p + off : nullptr);
-        off += count * elem;
-        return r;
-    }
-};
 
 static void sched_layout(Carver &cv, size_t nitems, SchedWs *w)
 {
@@ -436,7 +421,7 @@ static size_t enc_ws_layout(u8 *base, size_t nblk, u64 scratch_stride, u64 var_b
     w->direct_budget = 0;
     w->meta_records = 0;
     w->pad = 0;
-    return align_up(cv.off, 256);
+    return cv.total();
 }
 
 // workspace of one encode chunk of nitems blocks with per-block orders that hold total_in bytes together
@@ -519,20 +504,18 @@ int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64
     PackedSlots p = {};
     const u64 slot_stride = pk ? r4x16_packed_stride(max_in_size, order, d_order != nullptr) : 0;
     auto slots_for = [&](size_t nb) -> size_t { return pk ? r4x16_packed_carve(&p, nullptr, (size_t)n, nb, slot_stride) : 0; };
-    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w) + 4096 + slots_for(nb); },
-                              pk ? c->ps_bytes : 0);
-    if (ws_order_begin(c, s) != 0) return -1;
-    for (;;) {                                     // out of memory: walk the batch in smaller chunks
-        const size_t need = enc_ws_layout(nullptr, chunk, scratch_stride, var_for(chunk), &w);
-        if (ensure_ws(c, need) == 0 && (!pk || r4x16_ensure_ps(c, slots_for(chunk)) == 0)) break;
-        if (chunk == 1) return -1;
-        chunk = (chunk + 1) / 2;
-    }
-    enc_ws_layout(c->ws, chunk, scratch_stride, var_for(chunk), &w);
+    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS) | (pk ? A_BIT(A_PS) : 0)),
+                                   [&](size_t nb) { return enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w) + 4096 + slots_for(nb); });
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, [&](size_t nb) {
+            return r4x16_ensure(c, A_WS, enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w), false) == 0 &&
+                   (!pk || r4x16_ensure(c, A_PS, slots_for(nb), false) == 0) ? 0 : -1;
+        }) != 0) return -1;
+    enc_ws_layout(c->at(A_WS), chunk, scratch_stride, var_for(chunk), &w);
     w.logtab = c->logtab;
     w.rcptab = c->rcptab;
     if (pk) {
-        r4x16_packed_carve(&p, c->ps, (size_t)n, chunk, slot_stride);
+        r4x16_packed_carve(&p, c->at(A_PS), (size_t)n, chunk, slot_stride);
         r4x16_launch_packed_slots(&a, &p, n, chunk, max_in_size, s);
         a.out = p.slots; a.out_off = p.slot_off; a.out_cap = p.slot_cap;
     }
@@ -560,7 +543,7 @@ int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64
         else r4x16_launch_enc_finish(&a, &w, (int)base, nb, s);
     }
     HIPCHK(c, hipGetLastError());
-    return ws_order_end(c, s);
+    return r4x16_ws_order_end(c, s);
 }
 
 // var_bytes: the staging regions of the blocks that carry X_PACK / X_RLE, together (0: the batch has none)
@@ -580,7 +563,7 @@ static size_t dec_ws_layout(u8 *base, size_t nblk, u64 var_bytes, u32 max_out_ca
     sched_layout(cv, 2 * nblk, &w->sched);
     w->direct_budget = 0;
     w->mid_budget = 0;
-    return align_up(cv.off, 256);
+    return cv.total();
 }
 
 extern "C" int rans4x16_hip_uncompress_dev(rans4x16_hip_ctx *c, int n,
@@ -626,15 +609,12 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
     const u64 total_out = total_out_cap ? total_out_cap : (u64)n * max_out_cap;
     auto var_for = [&](size_t nb) -> u64 { return max_out_cap ? dec_var_bound(nb, std::min<u64>(total_out, (u64)nb * max_out_cap)) : 0; };
     DecWs w;
-    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return dec_ws_layout(nullptr, nb, var_for(nb), max_out_cap, &w) + 4096; });
-    if (ws_order_begin(c, s) != 0) return -1;
-    for (;;) {                                     // out of memory: walk the batch in smaller chunks
-        const size_t need = dec_ws_layout(nullptr, chunk, var_for(chunk), max_out_cap, &w);
-        if (ensure_ws(c, need) == 0) break;
-        if (chunk == 1) return -1;
-        chunk = (chunk + 1) / 2;
-    }
-    dec_ws_layout(c->ws, chunk, var_for(chunk), max_out_cap, &w);
+    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS)),
+                                   [&](size_t nb) { return dec_ws_layout(nullptr, nb, var_for(nb), max_out_cap, &w) + 4096; });
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_WS, dec_ws_layout(nullptr, nb, var_for(nb), max_out_cap, &w), false); }) != 0)
+        return -1;
+    dec_ws_layout(c->at(A_WS), chunk, var_for(chunk), max_out_cap, &w);
 
     BatchArgs a;
     a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
@@ -659,7 +639,7 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
         if (c->opts.v[OPT_ROUTE_COUNT]) c->route[2][wg ? R4X16_EXPAND_WORKGROUP : R4X16_EXPAND_WAVE] += nb;
     }
     HIPCHK(c, hipGetLastError());
-    return ws_order_end(c, s);
+    return r4x16_ws_order_end(c, s);
 }
 
 extern "C" int rans4x16_hip_residency(rans4x16_hip_ctx *c, int decode, unsigned int nsym, int order, unsigned int shift,
@@ -986,7 +966,7 @@ static size_t enc8_items_carve(Enc8Items *w, u8 *base, size_t nitems, size_t nb)
     w->cap = cv.take<u32>(nitems);
     w->order = cv.take<i32>(nitems);
     w->pick = cv.take<i32>(nb);
-    return align_up(cv.off, 256);
+    return cv.total();
 }
 
 // The 4x8 encode pipeline over a batch, in chunks of blocks under the workspace ceiling (r4x16_host.h).  The slot call
@@ -1001,20 +981,18 @@ int r4x8_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, hipStre
     EncWs w;
     Enc8Items it = {};
     auto items_for = [&](size_t nb) -> size_t { return slot_call ? 0 : enc8_items_carve(&it, nullptr, k * nb, nb); };
-    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w) + 4096 + items_for(nb); },
-                              slot_call ? 0 : c->ps_bytes);
-    chunk = std::min(chunk, (size_t)INT_MAX / k);      // item indices (j * nb + b < k * nb) and the item count stay inside an int
-    if (ws_order_begin(c, s) != 0) return -1;
-    for (;;) {
-        if (ensure_ws(c, enc_ws_layout(nullptr, k * chunk, scratch_stride, 0, &w)) == 0 &&
-            (slot_call || r4x16_ensure_ps(c, items_for(chunk)) == 0)) break;
-        if (chunk == 1) return -1;
-        chunk = (chunk + 1) / 2;
-    }
-    enc_ws_layout(c->ws, k * chunk, scratch_stride, 0, &w);
+    // (INT_MAX / k: item indices j * nb + b < k * nb and the item count stay inside an int)
+    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / k, r4x16_room(c, A_BIT(A_WS) | (slot_call ? 0 : A_BIT(A_PS))),
+                                   [&](size_t nb) { return enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w) + 4096 + items_for(nb); });
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, [&](size_t nb) {
+            return r4x16_ensure(c, A_WS, enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w), false) == 0 &&
+                   (slot_call || r4x16_ensure(c, A_PS, items_for(nb), false) == 0) ? 0 : -1;
+        }) != 0) return -1;
+    enc_ws_layout(c->at(A_WS), k * chunk, scratch_stride, 0, &w);
     w.logtab = c->logtab;
     w.rcptab = c->rcptab;
-    if (!slot_call) enc8_items_carve(&it, c->ps, k * chunk, chunk);
+    if (!slot_call) enc8_items_carve(&it, c->at(A_PS), k * chunk, chunk);
     for (size_t base = 0; base < (size_t)n; base += chunk) {
         const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
         if (slot_call) { r4x8_launch_encode(&a, &w, (int)base, nb, s); continue; }
@@ -1027,7 +1005,7 @@ int r4x8_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, hipStre
         if (c->opts.v[OPT_ROUTE_COUNT]) c->route[R4X16_ROUTE_RESULT][pk ? R4X16_RESULT_DENSE : R4X16_RESULT_IN_SLOT] += nb;
     }
     HIPCHK(c, hipGetLastError());
-    return ws_order_end(c, s);
+    return r4x16_ws_order_end(c, s);
 }
 
 extern "C" int rans4x8_hip_uncompress_dev(rans4x16_hip_ctx *c, int n,
@@ -1043,23 +1021,19 @@ extern "C" int rans4x8_hip_uncompress_dev(rans4x16_hip_ctx *c, int n,
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    size_t chunk = plan_chunk(c, (size_t)n, [&](size_t nb) { return r4x8_dec_ws_bytes(nb) + 4096; });
-    if (ws_order_begin(c, s) != 0) return -1;
-    for (;;) {
-        if (ensure_ws(c, r4x8_dec_ws_bytes(chunk)) == 0) break;
-        if (chunk == 1) return -1;
-        chunk = (chunk + 1) / 2;
-    }
+    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS)), [&](size_t nb) { return r4x8_dec_ws_bytes(nb) + 4096; });
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_WS, r4x8_dec_ws_bytes(nb), false); }) != 0) return -1;
     BatchArgs a;
     a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
     a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
     a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
     for (size_t base = 0; base < (size_t)n; base += chunk) {
         const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
-        r4x8_launch_decode(&a, c->ws, (int)base, nb, s);
+        r4x8_launch_decode(&a, c->at(A_WS), (int)base, nb, s);
     }
     HIPCHK(c, hipGetLastError());
-    return ws_order_end(c, s);
+    return r4x16_ws_order_end(c, s);
 }
 
 // host buffers: one staging pass (copy in, kernels, sizes back, copy out) on the context's stream
@@ -1085,8 +1059,8 @@ static int run_host8(rans4x16_hip_ctx *c, int n, bool decode,
         ord[i] = order ? order[i] : 0;
     }
     const size_t arr = align_up((size_t)n * 8, 256);
-    if (r4x16_ensure_stage(c, in_tot + out_tot + 6 * arr) != 0) return -1;
-    u8 *d_in = c->stage, *d_out = d_in + in_tot, *meta = d_out + out_tot;
+    if (r4x16_ensure(c, A_STAGE, in_tot + out_tot + 6 * arr, true) != 0) return -1;
+    u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
     u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
     u32 *d_in_size = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
     i32 *d_status = (i32 *)(meta + 5 * arr), *d_order = (i32 *)(meta + 5 * arr + arr / 2);

@@ -241,28 +241,13 @@ __global__ __launch_bounds__(256) void k_best_pick(BatchArgs a, BestWs w, BestAr
 static size_t best_carve(BestWs *w, u8 *base, size_t nb, const BestArgs &e)
 {
     const size_t M = nb * e.P;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { u8 *p = base ? base + off : nullptr; off = align_up(off + bytes, 256); return p; };
-    w->planes = take(nb * (size_t)e.nsets * e.pl_stride + 256);
-    w->in_off = (u64 *)take(M * 8); w->out_off = (u64 *)take(M * 8);
-    w->in_size = (u32 *)take(M * 4); w->out_cap = (u32 *)take(M * 4); w->out_size = (u32 *)take(M * 4);
-    w->status = (i32 *)take(M * 4); w->order = (i32 *)take(M * 4);
-    w->out = take(nb * e.blk_bytes + 256);
-    return off;
-}
-
-static int best_arena(rans4x16_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->xs_bytes) return 0;
-    if (c->xs) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->xs)); c->xs = nullptr; c->xs_bytes = 0; }
-    if (hipMalloc((void **)&c->xs, bytes) != hipSuccess) {
-        (void)hipGetLastError();                   // not sticky: the caller retries with a smaller chunk
-        c->xs = nullptr;
-        c->err = "hipMalloc of the candidate arena (" + std::to_string(bytes >> 20) + " MiB) failed";
-        return -1;
-    }
-    c->xs_bytes = bytes;
-    return 0;
+    Carver cv(base);
+    w->planes = cv.take<u8>(nb * (size_t)e.nsets * e.pl_stride + 256);
+    w->in_off = cv.take<u64>(M); w->out_off = cv.take<u64>(M);
+    w->in_size = cv.take<u32>(M); w->out_cap = cv.take<u32>(M); w->out_size = cv.take<u32>(M);
+    w->status = cv.take<i32>(M); w->order = cv.take<i32>(M);
+    w->out = cv.take<u8>(nb * e.blk_bytes + 256);
+    return cv.total();
 }
 
 // Lays the methods out (items, slots, plane sets) and runs the batch in chunks.  e->k, e->by_order, e->max_planes and
@@ -318,24 +303,13 @@ static int best_run(rans4x16_hip_ctx *c, int n, const BatchArgs &a, BestArgs *e,
     auto inner_total = [&](size_t nb) { return (u64)fan * std::min<u64>(total_in, (u64)nb * max_in_size); };
     BestWs w;
     auto bytes = [&](size_t nb) { return best_carve(&w, nullptr, nb, *e) + r4x16_enc_ws_bytes(nb * P, max_in_size, inner_total(nb)); };
-    const size_t room = r4x16_ws_room(c);
-    size_t chunk = std::min((size_t)n, (size_t)INT_MAX / P);          // the inner call counts its items in an int
-    if (chunk < (size_t)n || bytes(chunk) > room) {
-        size_t lo = 1, hi = chunk + 1;             // the largest chunk that fits (one block if none does): bytes(lo) <= room < bytes(hi)
-        while (lo + 1 < hi) {
-            const size_t mid = lo + (hi - lo) / 2;
-            if (bytes(mid) <= room) lo = mid; else hi = mid;
-        }
-        const size_t rounds = ((size_t)n + lo - 1) / lo;
-        chunk = ((size_t)n + rounds - 1) / rounds;
-    }
+    // (INT_MAX / P: the inner call counts its items in an int)
+    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / P, r4x16_room(c, A_BIT(A_WS) | A_BIT(A_XS)), bytes);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    for (;;) {                                     // out of memory: smaller chunks
-        if (best_arena(c, best_carve(&w, nullptr, chunk, *e)) == 0) break;
-        if (chunk == 1) return -1;
-        chunk = (chunk + 1) / 2;
-    }
-    best_carve(&w, c->xs, chunk, *e);
+    // (no refusal above half of the free memory here, unlike r4x16_stripe.hip on the same arena: the chunk was planned
+    //  under r4x16_room a moment ago, and a chunk that does not fit after all is halved, not refused)
+    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_XS, best_carve(&w, nullptr, nb, *e), false); }) != 0) return -1;
+    best_carve(&w, c->at(A_XS), chunk, *e);
     for (size_t base = 0; base < (size_t)n; base += chunk) {
         const size_t nb = std::min(chunk, (size_t)n - base);
         hipLaunchKernelGGL(k_best_prepare, dim3((u32)nb), dim3(256), 0, s, a, w, *e, (int)base);

@@ -21,6 +21,7 @@
 #include "../../include/rans4x8_hip.h"
 #include "r4x16_dev.h"
 #include "r4x16_sched.h"
+#include "r4x16_plan.h"
 
 extern "C" {
 void r4x16_launch_dec_front(const BatchArgs *, const DecWs *, int, int, hipStream_t, const R4Opts *);
@@ -71,7 +72,25 @@ struct HostPipe;
 void r4x16_pipe_destroy(HostPipe *);
 // the lane contexts of a context's host pipeline (nullptr past the last)
 struct rans4x16_hip_ctx *r4x16_pipe_lane(HostPipe *, int i);
-int r4x16_ensure_stage(rans4x16_hip_ctx *c, size_t bytes);
+// The context's device arenas, each growing on demand and kept between calls (r4x16_api.hip).  One routine grows them,
+// one says what a call may take, and the layouts inside them are Carver's (r4x16_plan.h).
+enum R4Arena {
+    A_WS,        // the workspace of the slot calls' pipelines
+    A_STAGE,     // staging for the host-buffer entry points
+    A_XS,        // the internal items of X_STRIPE blocks (r4x16_stripe.hip) and of best-of-k candidates (r4x16_best.hip)
+    A_PS,        // the packed calls' internal bound-sized slots and layout arrays (r4x16_packed.hip)
+    A_T3,        // tok3 containers: the winners waiting to be framed / the directory of the columns to decode (r4x16_tok3.hip)
+    A_TN,        // tok3 names: the names' histories; for the one-call form the columns in front of them (r4x16_tok3_names.hip)
+    A_COUNT
+};
+#define A_BIT(a) (1u << (a))
+// At least `bytes` in arena `which`: growing synchronizes the device, frees and allocates anew (contents are not kept).
+// refuse_above_half_free: for sizes that come from a caller's arrays or a stream's own size fields - never more than
+// half of what the card has free.  -1 with err set; an allocation failure is not sticky, the caller may ask for less.
+int r4x16_ensure(rans4x16_hip_ctx *c, R4Arena which, size_t bytes, bool refuse_above_half_free);
+// What the arenas of one call may take together: the context's ceiling (max_ws), and three quarters of the card's free
+// memory plus the arenas in reuse_mask - those the call is about to reuse are not free, but they are the call's to fill.
+size_t r4x16_room(rans4x16_hip_ctx *c, unsigned reuse_mask);
 void r4x16_trim(rans4x16_hip_ctx *c, size_t keep);
 // stream ordering of a context's arenas (workspace, stripe arena) between calls on different streams: r4x16_api.hip
 int r4x16_ws_order_begin(rans4x16_hip_ctx *c, hipStream_t s);
@@ -80,14 +99,12 @@ int r4x16_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, in
 // best-of-k and X_STRIPE under per-block orders (r4x16_best.hip); what they ask of r4x16_api.hip
 int r4x16_orders_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint64_t total_in_size,
                                      hipStream_t s);
-size_t r4x16_ws_room(rans4x16_hip_ctx *c, size_t held = 0);
 size_t r4x16_enc_ws_bytes(size_t nitems, u32 max_in_size, u64 total_in);
 int r4x16_stripe_uncompress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint32_t max_out_cap,
                                 uint32_t max_stripe_out, hipStream_t s);
 // the packed calls (r4x16_packed.hip): the internal bound-sized slots of a chunk of blocks in the context's packed arena,
 // and the plain encode pipeline of r4x16_api.hip with either finish (pk == nullptr: into the caller's slots)
 struct PackedSlots { u64 *slot_off; u32 *slot_cap; u8 *slots; u64 stride; };     // slot_off / slot_cap: [n], block i in slot i % chunk
-int r4x16_ensure_ps(rans4x16_hip_ctx *c, size_t bytes);
 size_t r4x16_packed_carve(PackedSlots *p, u8 *base, size_t n, size_t chunk, u64 stride);
 u64 r4x16_packed_stride(u32 max_in_size, int order, bool any_order);
 void r4x16_launch_packed_slots(const BatchArgs *a, const PackedSlots *p, int n, size_t chunk, u32 max_in_size, hipStream_t s);
@@ -105,36 +122,21 @@ struct rans4x16_hip_ctx {
     int device = 0;
     std::string err;
     R4Opts opts = {};                       // rans4x16_hip_set_option; defaults from the environment, read once per process
-    // one growing device workspace
-    u8 *ws = nullptr;
-    size_t ws_bytes = 0;
+    struct { u8 *p = nullptr; size_t bytes = 0; } arena[A_COUNT];
+    u8 *at(R4Arena a) const { return arena[a].p; }
     double *logtab = nullptr;
     u32 *rcptab = nullptr;
-    // staging for the host-buffer entry points
-    u8 *stage = nullptr;
-    size_t stage_bytes = 0;
     // timing hook
     int timing = 0;
     std::vector<TimedLaunch> timed[2];
-    size_t max_ws = (size_t)160 << 30;       // ceiling for one chunk of blocks (plan_chunk also looks at free memory)
-    // X_STRIPE in the device-resident calls (r4x16_stripe.hip): the arena of the internal items, and how many planes a
-    // device-resident decode batch reserves per block (0: stripe blocks report UNSUPPORTED there)
-    u8 *xs = nullptr;
-    size_t xs_bytes = 0;
+    size_t max_ws = (size_t)160 << 30;       // ceiling for one chunk of blocks (r4x16_room also looks at free memory)
+    // X_STRIPE in the device-resident calls (r4x16_stripe.hip): how many planes a device-resident decode batch reserves
+    // per block (0: stripe blocks report UNSUPPORTED there)
     int dev_stripe_planes = 0;
     unsigned int dev_stripe_out = 0;        // largest uncompressed stripe block such a batch may hold
     int dev_stripe_enc = 0;                 // encode with per-block orders: planes a block reserves (rans4x16_hip_set_dev_stripe_encode)
     bool in_stripe = false;                 // inside the recursive call over the internal items
-    // the packed calls (r4x16_packed.hip): the arena of their internal bound-sized slots and layout arrays
-    u8 *ps = nullptr;
-    size_t ps_bytes = 0;
-    bool in_packed = false;                 // inside a packed call's slot call over its internal slots
-    // the tok3 container calls (r4x16_tok3.hip): the winners waiting to be framed / the directory of the columns to decode
-    u8 *t3 = nullptr;
-    size_t t3_bytes = 0;
-    // tok3 name decoding (r4x16_tok3_names.hip): the names' histories; for the one-call form the columns in front of them
-    u8 *tn = nullptr;
-    size_t tn_bytes = 0;
+    bool in_packed = false;                 // inside a packed call's slot call over its internal slots (r4x16_packed.hip)
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;
@@ -160,6 +162,3 @@ struct rans4x16_hip_ctx {
             return -1;                                                                      \
         }                                                                                   \
     } while (0)
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-

@@ -7,41 +7,8 @@
 // ---------------------------------------------------------------------------------------------
 // host-buffer batches: stage through one device arena, run the *_dev path, copy results back.
 // ---------------------------------------------------------------------------------------------
-int r4x16_ensure_stage(rans4x16_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->stage_bytes) return 0;
-    if (c->stage) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
-    // never more than half of what the card has free: sizes come from the caller's arrays, and through the
-    // out == NULL decode entry from a size field of the stream itself (hostile input must not exhaust the device)
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b / 2) {
-        c->err = "host batch: staging of " + std::to_string(bytes >> 20) + " MiB exceeds half of the free device memory";
-        return -1;
-    }
-    const hipError_t e = hipMalloc((void **)&c->stage, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->stage = nullptr;
-        c->err = std::string("hipMalloc of the staging arena: ") + hipGetErrorString(e);
-        return -1;
-    }
-    c->stage_bytes = bytes;
-    return 0;
-}
-
-// Give back device memory above `keep` bytes (the single-block entry points call this after an unusually large
-// block, so that one call - or one hostile size field - does not pin gigabytes to the calling thread for good).
-void r4x16_trim(rans4x16_hip_ctx *c, size_t keep)
-{
-    if (!c || c->stage_bytes + c->ws_bytes <= keep) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    if (c->stage) { (void)hipFree(c->stage); c->stage = nullptr; c->stage_bytes = 0; }
-    if (c->ws) { (void)hipFree(c->ws); c->ws = nullptr; c->ws_bytes = 0; }
-    if (c->xs) { (void)hipFree(c->xs); c->xs = nullptr; c->xs_bytes = 0; }
-    c->ws_busy = false;
-}
-
+// (staging sizes come from the caller's arrays, and through the out == NULL decode entry from a size field of the stream
+//  itself: r4x16_ensure refuses more than half of the free memory - hostile input must not exhaust the device)
 static int stripe_compress_many(rans4x16_hip_ctx *, const std::vector<int> &, const unsigned char *const *, const unsigned int *,
                                 unsigned char *const *, unsigned int *, const int *, int *);
 static int stripe_uncompress_many(rans4x16_hip_ctx *, const std::vector<int> &, const unsigned char *const *, const unsigned int *,
@@ -137,8 +104,8 @@ static int run_slab(rans4x16_hip_ctx *c, int n, bool decode,
     }
     const size_t arr = align_up((size_t)n * 8, 256);
     const size_t total = in_tot + out_tot + 6 * arr;
-    if (r4x16_ensure_stage(c, total) != 0) return -1;
-    u8 *d_in = c->stage, *d_out = d_in + in_tot, *meta = d_out + out_tot;
+    if (r4x16_ensure(c, A_STAGE, total, true) != 0) return -1;
+    u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
     u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
     u32 *d_in_size = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
     i32 *d_status = (i32 *)(meta + 5 * arr);
@@ -352,8 +319,8 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
     }
     const size_t arr = align_up(ni * 8, 256);
     const size_t pk_bytes = align_up((size_t)n * sizeof(PackDesc), 256);
-    if (r4x16_ensure_stage(c, in_tot + out_tot + 6 * arr + pk_bytes) != 0) return -1;
-    u8 *d_in = c->stage, *d_out = d_in + in_tot, *meta = d_out + out_tot;
+    if (r4x16_ensure(c, A_STAGE, in_tot + out_tot + 6 * arr + pk_bytes, true) != 0) return -1;
+    u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
     u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
     u32 *d_in_size = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
     i32 *d_status = (i32 *)(meta + 5 * arr);
@@ -849,8 +816,8 @@ static int stripe_many_dev(rans4x16_hip_ctx *c, bool decode, const std::vector<i
             if (cap[e] > max_cap) max_cap = cap[e];
         }
         const size_t arr = align_up((size_t)m * 8, 256);
-        if (r4x16_ensure_stage(c, in_tot + out_tot + 6 * arr) != 0) return -1;
-        u8 *d_in = c->stage, *d_out = d_in + in_tot, *meta = d_out + out_tot;
+        if (r4x16_ensure(c, A_STAGE, in_tot + out_tot + 6 * arr, true) != 0) return -1;
+        u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
         u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
         u32 *d_isz = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
         i32 *d_st = (i32 *)(meta + 5 * arr);
@@ -976,8 +943,8 @@ static int stripe_compress_many(rans4x16_hip_ctx *c, const std::vector<int> &whi
         }
     }
     const size_t arr = align_up(items * 8, 256), pk_bytes = align_up(items * sizeof(PackDesc), 256);
-    if (r4x16_ensure_stage(c, 2 * in_tot + out_tot + 6 * arr + pk_bytes) != 0) return -1;
-    u8 *d_in = c->stage, *d_pl = d_in + in_tot, *d_out = d_pl + in_tot, *meta = d_out + out_tot;
+    if (r4x16_ensure(c, A_STAGE, 2 * in_tot + out_tot + 6 * arr + pk_bytes, true) != 0) return -1;
+    u8 *d_in = c->at(A_STAGE), *d_pl = d_in + in_tot, *d_out = d_pl + in_tot, *meta = d_out + out_tot;
     u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
     u32 *d_isz = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
     i32 *d_st = (i32 *)(meta + 5 * arr), *d_ord = (i32 *)(meta + 5 * arr + arr / 2);
@@ -1123,8 +1090,8 @@ static int stripe_uncompress_many(rans4x16_hip_ctx *c, const std::vector<int> &w
         }
     }
     const size_t arr = align_up(items * 8, 256);
-    if (r4x16_ensure_stage(c, in_tot + 2 * pl_tot + 6 * arr) != 0) return -1;
-    u8 *d_in = c->stage, *d_pl = d_in + in_tot, *d_out = d_pl + pl_tot, *meta = d_out + pl_tot;
+    if (r4x16_ensure(c, A_STAGE, in_tot + 2 * pl_tot + 6 * arr, true) != 0) return -1;
+    u8 *d_in = c->at(A_STAGE), *d_pl = d_in + in_tot, *d_out = d_pl + pl_tot, *meta = d_out + pl_tot;
     u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
     u32 *d_isz = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
     i32 *d_st = (i32 *)(meta + 5 * arr);

@@ -193,29 +193,14 @@ __global__ __launch_bounds__(256) void k_unpk_verdict(UnpkWs w, u32 *out_size, i
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------
-int r4x16_ensure_ps(rans4x16_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->ps_bytes) return 0;
-    if (c->ps) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->ps)); c->ps = nullptr; c->ps_bytes = 0; }
-    if (hipMalloc((void **)&c->ps, bytes) != hipSuccess) {
-        (void)hipGetLastError();                   // not sticky: the caller retries with a smaller chunk
-        c->ps = nullptr;
-        c->err = "hipMalloc of the packed calls' slot arena (" + std::to_string(bytes >> 20) + " MiB) failed";
-        return -1;
-    }
-    c->ps_bytes = bytes;
-    return 0;
-}
-
 size_t r4x16_packed_carve(PackedSlots *p, u8 *base, size_t n, size_t chunk, u64 stride)
 {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { u8 *q = base ? base + off : nullptr; off = align_up(off + bytes, 256); return q; };
-    p->slot_off = (u64 *)take(n * 8);
-    p->slot_cap = (u32 *)take(n * 4);
-    p->slots = take(chunk * stride + 256);
+    Carver cv(base);
+    p->slot_off = cv.take<u64>(n);
+    p->slot_cap = cv.take<u32>(n);
+    p->slots = cv.take<u8>(chunk * stride + 256);
     p->stride = stride;
-    return off;
+    return cv.total();
 }
 
 u64 r4x16_packed_stride(u32 max_in_size, int order, bool any_order)
@@ -249,19 +234,12 @@ static int gathered(rans4x16_hip_ctx *c, int n, const BatchArgs &a, const Packed
         for (int j = 0; j < pm.k; j++) stride = std::max(stride, r4x16_packed_stride(max_in_size, pm.m[j], false));
     PackedSlots p;
     const size_t keep_ws = c->max_ws;
-    const size_t room = r4x16_ws_room(c, c->ps_bytes);       // (the arena this call is about to reuse counts as room)
-    const size_t fixed = r4x16_packed_carve(&p, nullptr, (size_t)n, 0, stride);
-    size_t chunk = room / 4 > fixed + stride ? (room / 4 - fixed) / stride : 1;
-    if (chunk > (size_t)n) chunk = (size_t)n;
-    const size_t rounds = ((size_t)n + chunk - 1) / chunk;
-    chunk = ((size_t)n + rounds - 1) / rounds;
+    auto slots_for = [&](size_t nb) { return r4x16_packed_carve(&p, nullptr, (size_t)n, nb, stride); };
+    const size_t room = r4x16_room(c, A_BIT(A_WS) | A_BIT(A_XS) | A_BIT(A_PS));
+    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, room / 4, slots_for);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    for (;;) {                                     // out of memory: smaller chunks
-        if (r4x16_ensure_ps(c, r4x16_packed_carve(&p, nullptr, (size_t)n, chunk, stride)) == 0) break;
-        if (chunk == 1) return -1;
-        chunk = (chunk + 1) / 2;
-    }
-    const size_t arena = r4x16_packed_carve(&p, c->ps, (size_t)n, chunk, stride);
+    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_PS, slots_for(nb), false); }) != 0) return -1;
+    const size_t arena = r4x16_packed_carve(&p, c->at(A_PS), (size_t)n, chunk, stride);
     hipLaunchKernelGGL(k_pk_slots, dim3((n + 255) / 256), dim3(256), 0, s, a.in_size, a.d_order, a.order, pm, n, (u32)chunk, stride,
                        max_in_size, p.slot_off, p.slot_cap);
     int rc = 0;
@@ -372,11 +350,10 @@ static int unpack_run(rans4x16_hip_ctx *c, int n, const unsigned char *d_in, con
                       const uint32_t *d_nosz_size, uint32_t max_in_size, uint32_t max_out_size, hipStream_t s)
 {
     // the layout's own arrays: 12 bytes per block in the packed arena (ordered between streams like the workspace)
-    size_t off = 0;
-    auto take = [&](u8 *base, size_t bytes) { u8 *q = base ? base + off : nullptr; off = align_up(off + bytes, 256); return q; };
-    if (r4x16_ensure_ps(c, 3 * align_up((size_t)n * 4, 256)) != 0) return -1;
+    if (r4x16_ensure(c, A_PS, 3 * align_up((size_t)n * 4, 256), false) != 0) return -1;
+    Carver cv(c->at(A_PS));
     UnpkWs w;
-    w.claim = (u32 *)take(c->ps, (size_t)n * 4); w.in_size = (u32 *)take(c->ps, (size_t)n * 4); w.pre = (i32 *)take(c->ps, (size_t)n * 4);
+    w.claim = cv.take<u32>(n); w.in_size = cv.take<u32>(n); w.pre = cv.take<i32>(n);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
     const PackedOut pk = {d_out, d_out_off, out_capacity};
     const dim3 grid((n + 255) / 256), wg(256);
@@ -387,7 +364,7 @@ static int unpack_run(rans4x16_hip_ctx *c, int n, const unsigned char *d_in, con
     const u64 total = std::max<u64>(std::min<u64>(out_capacity, (u64)n * max_out_size), 1);
     // rANS 4x8's sizing pass (no arena, capacity 0): only blocks that claim 0 bytes are admitted and nothing is written,
     // but the slot call wants a pointer - the packed arena's own
-    unsigned char *out8 = d_out ? d_out : c->ps;
+    unsigned char *out8 = d_out ? d_out : c->at(A_PS);
     const int rc = X8 ? rans4x8_hip_uncompress_dev(c, n, d_in, d_in_off, w.in_size, out8, d_out_off, w.claim, d_out_size, d_status, s)
                       : rans4x16_hip_uncompress_dev_sized(c, n, d_in, d_in_off, w.in_size, d_out, d_out_off, w.claim, d_out_size, d_status,
                                                           max_in_size, max_out_size, total, s);

@@ -124,32 +124,17 @@ __global__ __launch_bounds__(WAVE) void k_stripe_enc_pick(BatchArgs a, StripeArr
     if (lane == 0) { a.status[b] = ST_OK; a.out_size[b] = hdr_len + woff[255]; }
 }
 
-static int ensure_xs(rans4x16_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->xs_bytes) return 0;
-    if (c->xs) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->xs)); c->xs = nullptr; c->xs_bytes = 0; }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b / 2) {
-        c->err = "stripe staging of " + std::to_string(bytes >> 20) + " MiB exceeds half of the free device memory";
-        return -1;
-    }
-    if (hipMalloc((void **)&c->xs, bytes) != hipSuccess) { (void)hipGetLastError(); c->xs = nullptr; c->err = "hipMalloc of the stripe arena failed"; return -1; }
-    c->xs_bytes = bytes;
-    return 0;
-}
-
 static size_t carve(StripeArrays *w, u8 *base, size_t n, size_t P, u64 pl_stride, u64 oslot)
 {
     const size_t M = n * P;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { u8 *p = base ? base + off : nullptr; off = align_up(off + bytes, 256); return p; };
-    w->planes = take(n * pl_stride); w->pl_stride = pl_stride;
-    w->in_off = (u64 *)take(M * 8); w->out_off = (u64 *)take(M * 8);
-    w->in_size = (u32 *)take(M * 4); w->out_cap = (u32 *)take(M * 4); w->out_size = (u32 *)take(M * 4);
-    w->status = (i32 *)take(M * 4); w->order = (i32 *)take(M * 4);
-    w->blk = (u32 *)take(n * 16);
-    w->out = take(M * oslot); w->oslot = oslot;
-    return off;
+    Carver cv(base);
+    w->planes = cv.take<u8>(n * pl_stride); w->pl_stride = pl_stride;
+    w->in_off = cv.take<u64>(M); w->out_off = cv.take<u64>(M);
+    w->in_size = cv.take<u32>(M); w->out_cap = cv.take<u32>(M); w->out_size = cv.take<u32>(M);
+    w->status = cv.take<i32>(M); w->order = cv.take<i32>(M);
+    w->blk = cv.take<u32>(4 * n);
+    w->out = cv.take<u8>(M * oslot); w->oslot = oslot;
+    return cv.total();
 }
 
 int r4x16_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, int order, uint32_t max_in_size, hipStream_t s)
@@ -168,8 +153,9 @@ int r4x16_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, in
     const size_t P = (size_t)e.N * e.K;
     if ((size_t)n * P > (size_t)INT_MAX) { c->err = "compress_dev: too many stripe candidates"; return -1; }
     StripeArrays w;
-    if (ensure_xs(c, carve(&w, nullptr, (size_t)n, P, pl_stride, oslot)) != 0) return -1;
-    carve(&w, c->xs, (size_t)n, P, pl_stride, oslot);
+    // (the whole batch's items at once, sized from the caller's max_in_size: never more than half of the free memory)
+    if (r4x16_ensure(c, A_XS, carve(&w, nullptr, (size_t)n, P, pl_stride, oslot), true) != 0) return -1;
+    carve(&w, c->at(A_XS), (size_t)n, P, pl_stride, oslot);
     // the stripe arena is ordered between calls on different streams like the workspace: nothing of this call touches it
     // before the previous call's last kernel is done, and the event recorded after the finishing kernel covers it
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
@@ -275,8 +261,8 @@ int r4x16_stripe_uncompress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, 
     if ((size_t)n * P > (size_t)INT_MAX) { c->err = "uncompress_dev: too many stripe planes"; return -1; }
     const u64 pl_stride = align_up((size_t)max_stripe_out + 64, 256);
     StripeArrays w;
-    if (ensure_xs(c, carve(&w, nullptr, (size_t)n, P, pl_stride, 0)) != 0) return -1;
-    carve(&w, c->xs, (size_t)n, P, pl_stride, 0);
+    if (r4x16_ensure(c, A_XS, carve(&w, nullptr, (size_t)n, P, pl_stride, 0), true) != 0) return -1;       // (as in r4x16_stripe_compress_dev)
+    carve(&w, c->at(A_XS), (size_t)n, P, pl_stride, 0);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;          // (as in r4x16_stripe_compress_dev)
     hipLaunchKernelGGL(k_stripe_dec_prepare, dim3(n), dim3(WAVE), 0, s, a, w, (u32)P);
     // the internal items: inputs relative to the caller's input arena, outputs relative to the plane buffer

@@ -28,25 +28,6 @@
 typedef u64 u64_unaligned __attribute__((aligned(1)));
 #define T3_KIND_NONE 3u
 
-static int ensure_t3(rans4x16_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->t3_bytes) return 0;
-    if (c->t3) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->t3)); c->t3 = nullptr; c->t3_bytes = 0; }
-    if (hipMalloc((void **)&c->t3, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->t3 = nullptr;
-        c->err = "hipMalloc of the tok3 arena (" + std::to_string(bytes >> 20) + " MiB) failed";
-        return -1;
-    }
-    c->t3_bytes = bytes;
-    return 0;
-}
-
-struct Carver {
-    u8 *base; size_t off;
-    template <class T> T *take(size_t count) { T *q = base ? (T *)(base + off) : nullptr; off = align_up(off + count * sizeof(T), 256); return q; }
-};
-
 // ---- unpack --------------------------------------------------------------------------------------------------
 // [nblk * max_columns] each (off: one more), entry b * max_columns + d is descriptor d of block b; pre: [nblk].
 // An entry claims lead + size bytes at off: the type column synthesised in front of it, then its own column at col_off.
@@ -56,13 +37,13 @@ struct T3Items {
 
 static size_t t3_items_carve(T3Items *w, u8 *base, size_t nitems, size_t nblk)
 {
-    Carver cv = {base, 0};
+    Carver cv(base);
     w->in_off = cv.take<u64>(nitems); w->clen = cv.take<u32>(nitems); w->in_size = cv.take<u32>(nitems);
     w->claim = cv.take<u32>(nitems); w->size = cv.take<u32>(nitems); w->lead = cv.take<u32>(nitems);
     w->cap = cv.take<u32>(nitems); w->kind_a = cv.take<u32>(nitems);
     w->off = cv.take<u64>(nitems + 1); w->col_off = cv.take<u64>(nitems); w->out_size = cv.take<u32>(nitems); w->status = cv.take<i32>(nitems);
     w->pre = cv.take<i32>(nblk);
-    return cv.off;
+    return cv.total();
 }
 
 struct DevDir {
@@ -225,8 +206,8 @@ extern "C" int rans4x16_hip_tok3_unpack_dev(rans4x16_hip_ctx *c, int nblk,
     hipStream_t s = (hipStream_t)stream;
     if (nblk == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
     T3Items w;
-    if (ensure_t3(c, t3_items_carve(&w, nullptr, (size_t)nitems, (size_t)nblk)) != 0) return -1;
-    const size_t arena = t3_items_carve(&w, c->t3, (size_t)nitems, (size_t)nblk);
+    if (r4x16_ensure(c, A_T3, t3_items_carve(&w, nullptr, (size_t)nitems, (size_t)nblk), false) != 0) return -1;
+    const size_t arena = t3_items_carve(&w, c->at(A_T3), (size_t)nitems, (size_t)nblk);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
     const dim3 per_item((u32)((nitems + 255) / 256));
     hipLaunchKernelGGL(k_t3_walk, dim3((u32)nblk), dim3(64), 0, s, d_in, d_in_off, d_in_size, w, d_col_id, d_ncol, d_last_start, d_nreads,
@@ -238,7 +219,7 @@ extern "C" int rans4x16_hip_tok3_unpack_dev(rans4x16_hip_ctx *c, int nblk,
     c->max_ws = keep_ws > arena + ((size_t)1 << 20) ? keep_ws - arena : (size_t)1 << 20;
     // the sizing pass (no arena, capacity 0): only blocks that claim 0 bytes are admitted and nothing is written, but the
     // slot call wants a pointer - the tok3 arena's own
-    unsigned char *out = d_out ? d_out : c->t3;
+    unsigned char *out = d_out ? d_out : c->at(A_T3);
     const int rc = rans4x16_hip_uncompress_dev_sized(c, (int)nitems, d_in, w.in_off, w.in_size, out, w.col_off, w.cap, w.out_size, w.status,
                                                      max_in_size, max_col_size, total, s);
     c->max_ws = keep_ws;
@@ -258,12 +239,12 @@ struct T3Cols {
 
 static size_t t3_cols_carve(T3Cols *w, u8 *base, size_t n, size_t nblk, u64 stream_bytes)
 {
-    Carver cv = {base, 0};
+    Carver cv(base);
     w->s_off = cv.take<u64>(n + 1); w->s_size = cv.take<u32>(n); w->s_status = cv.take<i32>(n);
     w->hash = cv.take<u64>(n); w->rel = cv.take<u32>(n); w->dup = cv.take<i32>(n);
     w->pmax = cv.take<u32>(nblk);
     w->streams = cv.take<u8>((size_t)stream_bytes + 256);
-    return cv.off;
+    return cv.total();
 }
 
 __device__ __forceinline__ u64 t3_mix(u64 x)                              // splitmix64's finaliser
@@ -447,14 +428,14 @@ extern "C" int rans4x16_hip_tok3_pack_dev(rans4x16_hip_ctx *c, int nblk, int n, 
     if (nblk == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
     T3Cols w;
     const size_t need = t3_cols_carve(&w, nullptr, (size_t)n, (size_t)nblk, stream_bytes);
-    if (need > r4x16_ws_room(c, c->t3_bytes) / 2) {
+    if (need > r4x16_room(c, A_BIT(A_WS) | A_BIT(A_XS) | A_BIT(A_T3)) / 2) {
         // (the winners of the whole batch wait in one arena until their blocks are framed; the best-of-k call in front of
         //  it walks the columns in chunks of its own)
         c->err = "tok3_pack_dev: the winners of this batch (" + std::to_string(need >> 20) + " MiB) do not fit half of max_workspace_mb: split the batch";
         return -1;
     }
-    if (ensure_t3(c, need) != 0) return -1;
-    const size_t arena = t3_cols_carve(&w, c->t3, (size_t)n, (size_t)nblk, stream_bytes);
+    if (r4x16_ensure(c, A_T3, need, false) != 0) return -1;
+    const size_t arena = t3_cols_carve(&w, c->at(A_T3), (size_t)n, (size_t)nblk, stream_bytes);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
     if (n) {
         const size_t keep_ws = c->max_ws;

@@ -39,25 +39,6 @@ enum { TN_ALPHA = 1, TN_CHAR = 2, TN_DIGITS0 = 3, TN_DZLEN = 4, TN_DUP = 5, TN_D
 #define TN_MAX_COLUMN (1u << 28)
 #define TN_NONE 0xffffffffu
 
-static int ensure_tn(rans4x16_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->tn_bytes) return 0;
-    if (c->tn) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->tn)); c->tn = nullptr; c->tn_bytes = 0; }
-    if (hipMalloc((void **)&c->tn, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->tn = nullptr;
-        c->err = "hipMalloc of the tok3 names arena (" + std::to_string(bytes >> 20) + " MiB) failed";
-        return -1;
-    }
-    c->tn_bytes = bytes;
-    return 0;
-}
-
-struct TnCarver {
-    u8 *base; size_t off;
-    template <class T> T *take(size_t count) { T *q = base ? (T *)(base + off) : nullptr; off = align_up(off + count * sizeof(T), 256); return q; }
-};
-
 // what rans4x16_hip_tok3_unpack_dev wrote
 struct TnIn {
     const u8 *cols; u64 col_capacity;
@@ -71,12 +52,12 @@ struct TnOut { u8 *out; u64 capacity; const u64 *off; u32 *out_size, *nnames; i3
 
 static size_t tn_carve(TnWs *w, u8 *base, size_t at, size_t nblk, size_t hist_bytes)
 {
-    TnCarver cv = {base, at};
+    Carver cv(base, at);
     w->hclaim = cv.take<u32>(nblk); w->hoff = cv.take<u64>(nblk + 1); w->oclaim = cv.take<u32>(nblk);
     w->count = cv.take<u32>(nblk); w->npos = cv.take<u32>(nblk); w->pre = cv.take<i32>(nblk);
     w->hist = cv.take<u8>(hist_bytes + 16);
     w->hist_bytes = hist_bytes;
-    return cv.off;
+    return cv.total();
 }
 
 __device__ __forceinline__ u32 tn_wave_max(u32 v)
@@ -474,6 +455,8 @@ __global__ __launch_bounds__(64) void k_tn_decode(TnIn in, TnWs w, TnOut o)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
+// the arenas a names call may fill: its own, the unpack's in front of it, and what the unpack's inner call reuses
+#define TN_REUSE (A_BIT(A_WS) | A_BIT(A_XS) | A_BIT(A_T3) | A_BIT(A_TN))
 // 16-byte units of history a block of max_names names and max_tokens positions takes at most
 static u64 tn_units(u32 max_names, u32 max_tokens) { return (u64)max_names + ((u64)max_names * max_tokens * 8u + 15u) / 16u; }
 
@@ -481,7 +464,7 @@ static u64 tn_units(u32 max_names, u32 max_tokens) { return (u64)max_names + ((u
 static int tn_stage(rans4x16_hip_ctx *c, int nblk, const TnIn &in, TnOut o, u64 *d_out_off, u64 hist_bytes, size_t front, hipStream_t s)
 {
     TnWs w;
-    tn_carve(&w, c->tn, front, (size_t)nblk, (size_t)hist_bytes);
+    tn_carve(&w, c->at(A_TN), front, (size_t)nblk, (size_t)hist_bytes);
     o.off = d_out_off;
     hipLaunchKernelGGL(k_tn_claim, dim3((u32)nblk), dim3(64), 0, s, in, w);
     r4x16_launch_packed_scan(w.hclaim, w.hoff, 0, nblk, s);
@@ -518,9 +501,10 @@ extern "C" int rans4x16_hip_tok3_names_dev(rans4x16_hip_ctx *c, int nblk,
     // the histories of the batch: what its limits allow, under half of what the context may hold; a block whose history
     // ends beyond that reports UNSUPPORTED
     const u64 full = (u64)nblk * tn_units(max_names, max_tokens) * 16ull;
-    const u64 hist_bytes = std::min<u64>(full, r4x16_ws_room(c, c->tn_bytes + c->t3_bytes) / 2);
+    // (the tok3 arena counts as room although this call does not use it: the set of the one-call form below, kept)
+    const u64 hist_bytes = std::min<u64>(full, r4x16_room(c, TN_REUSE) / 2);
     TnWs w;
-    if (ensure_tn(c, tn_carve(&w, nullptr, 0, (size_t)nblk, (size_t)hist_bytes)) != 0) return -1;
+    if (r4x16_ensure(c, A_TN, tn_carve(&w, nullptr, 0, (size_t)nblk, (size_t)hist_bytes), false) != 0) return -1;
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
     const TnIn in = {d_cols, col_capacity, d_col_id, d_col_off, d_col_size, d_ncol, d_last_start, d_nreads, d_blk_status,
                      max_columns, max_names, max_tokens};
@@ -534,12 +518,12 @@ struct TnDir { u64 *off; u32 *size; i32 *status; u32 *ncol, *last_start, *nreads
 
 static size_t tn_dir_carve(TnDir *d, u8 *base, size_t nblk, size_t nitems, u64 col_bytes)
 {
-    TnCarver cv = {base, 0};
+    Carver cv(base);
     d->off = cv.take<u64>(nblk + 1); d->size = cv.take<u32>(nblk); d->status = cv.take<i32>(nblk);
     d->ncol = cv.take<u32>(nblk); d->last_start = cv.take<u32>(nblk); d->nreads = cv.take<u32>(nblk);
     d->col_id = cv.take<i32>(nitems); d->col_off = cv.take<u64>(nitems); d->col_size = cv.take<u32>(nitems);
     d->cols = cv.take<u8>((size_t)col_bytes + 16);
-    return cv.off;
+    return cv.total();
 }
 
 extern "C" int rans4x16_hip_tok3_decode_names_dev(rans4x16_hip_ctx *c, int nblk,
@@ -568,13 +552,13 @@ extern "C" int rans4x16_hip_tok3_decode_names_dev(rans4x16_hip_ctx *c, int nblk,
     TnWs w;
     const size_t front = tn_dir_carve(&d, nullptr, (size_t)nblk, (size_t)nitems, col_bytes);
     const size_t need = tn_carve(&w, nullptr, front, (size_t)nblk, (size_t)hist_bytes);
-    if (need > r4x16_ws_room(c, c->tn_bytes + c->t3_bytes) / 2) {
+    if (need > r4x16_room(c, TN_REUSE) / 2) {
         c->err = "tok3_decode_names_dev: the columns and histories of this batch (" + std::to_string(need >> 20) +
                  " MiB) do not fit half of max_workspace_mb: split the batch";
         return -1;
     }
-    if (ensure_tn(c, need) != 0) return -1;
-    tn_dir_carve(&d, c->tn, (size_t)nblk, (size_t)nitems, col_bytes);
+    if (r4x16_ensure(c, A_TN, need, false) != 0) return -1;
+    tn_dir_carve(&d, c->at(A_TN), (size_t)nblk, (size_t)nitems, col_bytes);
     // (the unpack orders itself on the context's arenas, and so does the stage behind it)
     if (rans4x16_hip_tok3_unpack_dev(c, nblk, d_in, d_in_off, d_in_size, d.cols, col_bytes, d.off, d.size, d.status, d.ncol, d.last_start,
                                      d.nreads, d.col_id, d.col_off, d.col_size, max_columns, max_in_size, max_col_size, s) != 0) return -1;

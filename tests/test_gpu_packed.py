@@ -349,6 +349,21 @@ def test_the_gathered_route_walks_its_own_chunks(H, routes, oracle, what):
 
 
 @pytest.mark.gpu
+def test_the_slot_arena_grows_and_is_reused(H, oracle):
+    """A fresh context, the dense route (its slots lie in the packed arena) over 3 blocks of 4 KiB, then 13, then 3 again:
+    the first call allocates the arena, the second finds it too small and grows it - synchronize, free, allocate - and
+    the third lays its slots out in an arena larger than it asked for."""
+    import datagen
+    dc = H.DeviceCodec(0)
+    blocks = [datagen.tile(datagen.BASE_NAMES[j % len(datagen.BASE_NAMES)], 4096, j + 1).tobytes() for j in range(13)]
+    want = [oracle.compress(b, 1) for b in blocks]
+    for n in (3, 13, 3):
+        p = _Packed(dc, blocks[:n], _alloc_for(want[:n]))
+        p.compress(order=1)
+        _check_dense(p, want[:n], ("regrow", n))
+
+
+@pytest.mark.gpu
 def test_two_streams_of_one_context_share_the_slot_arena_in_order(H, dc, oracle):
     import torch
     blocks = inputs()

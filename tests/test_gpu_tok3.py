@@ -317,6 +317,23 @@ def test_constructed_blocks_round_trip(dc, oracle, nblk):
     assert _check_unpack(u, want, expect, 16, ("constructed", nblk)) == sum(i != 4 for i in pick)
 
 
+def test_the_tok3_arena_grows_and_is_reused(dc, oracle):
+    """A fresh context, pack and unpack of 3 blocks of one 4 KiB column each, then of 13, then of 3 again: the first
+    calls allocate the tok3 arena, the pack of 13 finds it too small and grows it - synchronize, free, allocate - and
+    the last calls lay their arrays out in an arena larger than they asked for."""
+    import htscodecs_amd
+    fresh = htscodecs_amd.DeviceCodec(0)
+    blocks = [(4 + j, 6, [(0x07, _text(4096, 100 + j))]) for j in range(13)]
+    framed = [M.frame(oracle.compress, b[2], [0, 1], b[0], b[1])[0] for b in blocks]
+    expect = [(M.walk(c), _columns_of(b)) for c, b in zip(framed, blocks)]
+    assert all(w.status == 0 for w, _ in expect)
+    for n in (3, 13, 3):
+        p = _pack(fresh, blocks[:n], [0, 1], 5000, sum(len(c) for c in framed[:n]))
+        _check_pack(p, framed[:n], ("regrow", n))
+        u = _unpack(fresh, framed[:n], 16, 5000, sum(w.total for w, _ in expect[:n]))
+        assert _check_unpack(u, framed[:n], expect[:n], 16, ("regrow", n)) == n
+
+
 def test_a_column_equal_to_column_id_0_is_written_in_full(oracle):
     d = _constructed(oracle, 5000)[3]
     cont = M.frame(oracle.compress, d[2], [0, 1], d[0], d[1])[0]

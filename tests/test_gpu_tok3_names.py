@@ -220,6 +220,19 @@ def test_decode_names_of_all_fixtures_in_one_call(dc, ref):
     assert sizing.off == r.off and all(s == N.CAPACITY for s in sizing.st) and not any(sizing.osz) and not any(sizing.nn)
 
 
+def test_the_names_arena_grows_and_is_reused(dc, ref):
+    """A fresh context, the one-call form over 3 fixtures (containers of 2 to 11 KiB), then 13, then 3 again: the first
+    call allocates the names arena (the columns, then the histories), the second finds it too small and grows it -
+    synchronize, free, allocate - and the third lays both out in an arena larger than it asked for."""
+    import htscodecs_amd
+    fresh = htscodecs_amd.DeviceCodec(0)
+    assert fresh.L.rans4x16_hip_set_dev_stripe_planes(fresh.ctx.h, 4, 2 * max(w.largest_col for _, _, w, _, _, _ in ref)) == 0
+    for n in (3, 13, 3):
+        part = ref[:n]
+        r = _decode_names(fresh, part)
+        assert _check(r, _expect_fixtures(part, r.cap), ("regrow", n)) == n
+
+
 def test_decode_names_without_a_size_hint(dc, ref):
     part = ref[:3]
     r = _decode_names(dc, part, hint=False, max_col=max(w.largest_col for _, _, w, _, _, _ in part))
