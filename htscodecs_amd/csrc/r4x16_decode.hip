@@ -124,39 +124,99 @@ __device__ __forceinline__ u32 lookup_step(const IMG &img, u32 row, u32 look, u3
     return e + (up ? 1u : 0u);                  //  turn it into a select of 0/1 and an or, e being even)
 }
 
-// One lookup + state update on a packed row (r4x16_common.h, "level 1": 10-bit tables, <= 48 symbols).
-// `row` is the LDS address of the context's row, `root` its first dword (read a step ahead), `first` the index of
-// the row's first symbol of non-zero frequency.  Fields sit at bits 0, 11 and 22 of a dword with zero bits at 10 and
+// One lookup + state update on a packed row of up to 48 symbols (r4x16_common.h, "level 1", layout 2: 10-bit tables).
+// `row` is the LDS address of the context's row, `root` its first dword and `hdr` its alpha word (both read a step
+// ahead, from the head entry of the symbol that opened the context); bits PK_FIRST_SHIFT.. of hdr are `first`, the index
+// of the row's first symbol of non-zero frequency.  Fields sit at bits 0, 11 and 22 of a dword with zero bits at 10 and
 // 21: adding GM = guards - (m | m << 11 | m << 22) leaves guard bit i set exactly when field i >= m (a field plus
 // 1024 minus m stays inside its eleven bits), so two "field < m" tests cost one add, one and, one popcount.
 // Returns the compact symbol index; x becomes freq * (x >> 10) + m - start.
-// WIDE: 49..96 symbols, root = eight u16 separators L[12 k] + 1 (r4x16_common.h), counted like the u16 rows' roots.
-template <bool WIDE>
-__device__ __forceinline__ u32 lookup_step_pk(u32 row, u32x2 rootv, u32x2 rootw, u32 first, u32 &x)
+// The step is two dependent LDS round trips - head entry -> group -> (symbol) -> head entry - and a lone wave issues in
+// order, so the look-up is cut where its reads are issued (chain_decode_dir's rule: what does not depend on a read
+// stands IN ITS SHADOW).  With `pin` (steps 1.. of a trip):
+//     issue half : m, GM, the root count, ga, the two group reads
+//     shadow()   : the caller's work that needs neither read, fenced on both sides - then x >> 10 and g * 12 + first
+//     finish half: pivot compares, selects, guard count -> the symbol; symbol(s) lets the caller request the head entry
+//                  of s AT ONCE, fenced, so that the rest of the state update and the renormalisation stand in THAT
+//                  read's shadow (left to itself the compiler requests it behind the state update, where only the
+//                  work now moved into the group's shadow used to cover it)
+// Held with __builtin_amdgcn_sched_barrier(0) and volatile group reads; plain arithmetic is not held by a fence (the
+// instruction selector places it before the scheduler sees the fence) and gets an empty volatile asm where it matters.
+// ROCm 7.2's hipcc obeys: 11 - 12 instructions between the group read and its wait, 1 - 3 without (tools/isa_count.py).
+// Without `pin`: shadow() right behind the reads and symbol() at the end, unfenced - the compiler's own order.
+struct NoShadow { __device__ __forceinline__ void operator()() const {} };
+template <class SH, class SY>
+__device__ __forceinline__ u32 lookup_step_pk(u32 row, u32 root, u32 hdr, u32 &x, bool pin, SH shadow, SY symbol)
+{
+    const u32 GB = 0x00200400u;
+    // ---- issue half ----------------------------------------------------------------------------
+    const u32 m = x & 1023u;
+    const u32 GM = GB - __umul24(m, 0x400801u);
+    // group of twelve: #{L[12], L[24], L[36]} below m
+    const u32 gneg = __popc((root + GM) & GB);                // 2 - #{L[12], L[24] < m}
+    const bool r3 = root < (m << 22);                         // L[36] < m: the top field needs no guard
+    const u32 g = (r3 ? 3u : 2u) - gneg;
+    const u32 ga = row + 16u * g;
+    u32 D0, D1, D2, D3, D4;
+    if (pin) {
+        const u32x4 Dq = *(LAS const volatile u32x4 *)(unsigned long)ga;
+        D0 = Dq.x; D1 = Dq.y; D2 = Dq.z; D3 = Dq.w; D4 = *(LAS const volatile u32 *)(unsigned long)(ga + 16u);
+    } else {
+        const u32x4 Dq = *(LAS const u32x4 *)(unsigned long)ga;          // the group: one 16-byte read (rows are 16-byte aligned)
+        D0 = Dq.x; D1 = Dq.y; D2 = Dq.z; D3 = Dq.w; D4 = *(LAS const u32 *)(unsigned long)(ga + 16u);
+    }
+    // ---- the group read's shadow ---------------------------------------------------------------
+    if (pin) __builtin_amdgcn_sched_barrier(0);
+    shadow();
+    u32 xs = x >> 10;
+    if (pin) asm volatile("" : "+v"(xs));                     // (a plain shift is not held by the fences: it sinks to its use)
+    // `first` arrives with the + 2 already in it (the image stores first + 2): two multiply-adds and a subtraction
+    // instead of two multiplies, a three-way add, a subtraction and an add
+    const u32 first = hdr >> PK_FIRST_SHIFT;
+    u32 t;
+    asm("v_mad_u32_u24 %0, %1, 12, %2" : "=v"(t) : "v"(g), "v"(first));
+    if (pin) __builtin_amdgcn_sched_barrier(0);
+    // ---- finish half ---------------------------------------------------------------------------
+    // dword of three.  A leaf dword holds L[3i + 1], L[3i + 2] in its guarded low fields and L[3i] in its TOP field, so
+    // the pivots L[12g + 3], L[12g + 6], L[12g + 9] are tested without extraction: top field < m  <=>  dword < m << 22.
+    const u32 m22 = m << 22;
+    const bool s0 = D1 < m22, s1 = D2 < m22, s2 = D3 < m22;
+    u32 D = D0, Dn = D1;
+    if (s0) { D = D1; Dn = D2; }
+    if (s1) { D = D2; Dn = D3; }
+    if (s2) { D = D3; Dn = D4; }
+    const u32 q = (u32)s0 + (u32)s1 + (u32)s2;
+    // inside the dword: the two low fields against m by their guard bits
+    const u32 rneg = __popc((D + GM) & GB);                   // 2 - r,  r = #{L[3q + 1], L[3q + 2] below m}
+    asm("v_mad_u32_u24 %0, %1, 3, %2" : "=v"(t) : "v"(q), "v"(t));
+    const u32 s = t - rneg;
+    if (pin) { symbol(s); __builtin_amdgcn_sched_barrier(0); }
+    const u32 r11 = 22u - 11u * rneg;
+    // the candidates in stride-11 order: P = L[3q], L[3q + 1], L[3q + 2];  C = L[3q + 1], L[3q + 2], L[3q + 3]
+    const u32 P = (D << 11) | (D >> 22);                      // (not a rotation: bit 21 is a guard bit, the top field must land on bit 0)
+    const u32 Cc = (D & 0x003fffffu) | (Dn & 0xffc00000u);    // (one v_bfi_b32)
+    const u32 prev = __builtin_amdgcn_ubfe(P, r11, 10);       // L[c]: end of the symbol before (1023 stands for -1)
+    const u32 cur = __builtin_amdgcn_ubfe(Cc, r11, 10);       // L[c + 1]: end of this symbol
+    const u32 np = ~prev;
+    const u32 fm1 = (cur + np) & 1023u;                       // freq - 1
+    const u32 off = (m + np) & 1023u;                         // m - start
+    x = __umul24(fm1, xs) + xs + off;                         // freq <= 1024, x >> 10 < 2^22: exact mod 2^32
+    if (!pin) symbol(s);
+    return s;
+}
+
+// The same on a WIDE packed row (49..96 symbols): root = eight u16 separators L[12 k] + 1 (r4x16_common.h), counted like
+// the u16 rows' roots, `first` = hdr >> PK_FIRST_SHIFT.  In one piece, in the order it was measured in.
+__device__ __forceinline__ u32 lookup_step_pkw(u32 row, u32x2 rootv, u32x2 rootw, u32 first, u32 &x)
 {
     const LImg img0{0u};
     const u32 GB = 0x00200400u;
     const u32 m = x & 1023u;
     const u32 GM = GB - __umul24(m, 0x400801u);
-    u32 g, ga;
-    if (WIDE) {
-        const u32 mm = __umul24(m, 0x10001u) + 0x80008000u;
-        g = count_le(mm, rootv) + count_le(mm, rootw);        // #{k : L[12 k] < m}
-        ga = row + 16u + 16u * g;
-    } else {
-        // group of twelve: #{L[12], L[24], L[36]} below m
-        const u32 root = rootv.x;
-        const u32 gneg = __popc((root + GM) & GB);            // 2 - #{L[12], L[24] < m}
-        const bool r3 = root < (m << 22);                     // L[36] < m: the top field needs no guard
-        g = (r3 ? 3u : 2u) - gneg;
-        ga = row + 16u * g;
-    }
-    u32 D0, D1, D2, D3, D4;
-    if (WIDE) { D0 = img0.ld32(ga); D1 = img0.ld32(ga + 4); D2 = img0.ld32(ga + 8); D3 = img0.ld32(ga + 12); D4 = img0.ld32(ga + 16); }
-    else {
-        const u32x4 Dq = *(LAS const u32x4 *)(unsigned long)ga;          // the group: one 16-byte read (rows are 16-byte aligned)
-        D0 = Dq.x; D1 = Dq.y; D2 = Dq.z; D3 = Dq.w; D4 = img0.ld32(ga + 16);
-    }
+    const u32 mm = __umul24(m, 0x10001u) + 0x80008000u;
+    const u32 g = count_le(mm, rootv) + count_le(mm, rootw);   // #{k : L[12 k] < m}
+    const u32 ga = row + 16u + 16u * g;
+    const u32 D0 = img0.ld32(ga), D1 = img0.ld32(ga + 4), D2 = img0.ld32(ga + 8), D3 = img0.ld32(ga + 12), D4 = img0.ld32(ga + 16);
     // dword of three.  A leaf dword holds L[3i + 1], L[3i + 2] in its guarded low fields and L[3i] in its TOP field, so
     // the pivots L[12g + 3], L[12g + 6], L[12g + 9] are tested without extraction: top field < m  <=>  dword < m << 22.
     const u32 m22 = m << 22;
@@ -262,6 +322,12 @@ __device__ __forceinline__ u32 chain_decode(IMG img, u32 nsym, gcu8 *words, u32 
 //     with the table lookups, and the right one is picked once the quad ballot is known;
 //   * decoded bytes are gathered four at a time per chain and stored as dwords (order-1), so a
 //     wave issues one store per four symbols instead of four.
+// Packed rows of layout 2 (LV == 1, what the headline runs on) have a step of their own in the trip body, laid out
+// around its two dependent reads like chain_decode_dir's: in steps 1.. of a trip the ring reads, the cursor and the
+// output bookkeeping stand in the shadow of the look-up's group read (lookup_step_pk) instead of at the top of the
+// step.  92.3 -> 87.2 ms on the headline's decode chain; the ring reads in front of the group read and only their
+// consumers behind it: 4.8 ms slower per benchmark step (profiles/dec_shadow.md).  The other row kinds keep the
+// step below and compile to what they did before.
 // LDS per stream: image, then RING_BYTES.
 // ---------------------------------------------------------------------------------------------
 #ifndef PK_MIN_NSYM
@@ -352,10 +418,85 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
     // takes the FAST body: no per-lane liveness selects and no end-of-stream test.
     auto trip = [&](auto fastc) {
         constexpr bool FAST = decltype(fastc)::value;
+        u32 wmp = 0;                                      // layout 2: the quad's word requests of the step before (bits 0..3)
 #pragma unroll
         for (int u = 0; u < TRIP; u++) {
             const u32 T = t + (u32)u;                     // index of this step
             const bool live = FAST ? true : T < count;
+            if constexpr (PK2) {
+                // ---- packed rows, layout 2 (order 1 only): the step laid out around its two dependent LDS reads, the
+                // group and the head entry of the symbol found in it (lookup_step_pk).  In steps 1.. of a trip everything
+                // that depends on neither read stands in the group read's shadow: the cursor's advance over the words of
+                // the step before, the ring address and the ring reads, the byte and the flags of the step before.
+                // Step 0 keeps the order of the other row kinds (ring reads, look-up, bookkeeping), unfenced: its look-up
+                // is what the compiler hoists into the loop header, common to both bodies, and the 16-byte store and
+                // its branch stand behind it.
+                static_assert(ORDER == 1 && !BYTE, "layout 2 is an order-1 layout of rANS 4x16");
+                const bool pin = u > 0;
+                u32 cb = 0, d0 = 0, d1 = 0, d2 = 0, rootn = 0, hn = 0;
+                auto ring_read = [&]() __attribute__((always_inline)) {
+                    cb = off0 + 2 * cursor;
+                    const u32 ra = cb & (RB - 4u);
+                    const u32x2 d01 = *(LAS const volatile u32x2_a4 *)(ring + ra);     // (aligned dwords, volatile: see below)
+                    d0 = d01.x; d1 = d01.y; d2 = *(lvcu32 *)(ring + ra + 8);
+                };
+                auto book = [&]() __attribute__((always_inline)) {                      // (as below)
+                    if (u > 0 || t > 0) {
+                        if (!FAST) bad |= live ? hdr : 0u;
+                        else if (u & 1) bad |= hdr | hdr_even;
+                        else hdr_even = hdr;
+                        acc = (FAST || T <= count) ? __builtin_amdgcn_alignbit(hdr, acc, 8) : acc;
+                    }
+                    if ((u & 3) == 0 && T >= 4 && (FAST || T <= count)) {
+                        a0 = a1; a1 = a2; a2 = a3; a3 = acc;
+                        if (u == 0 && (t & 15u) == 0 && active) {
+                            const u32x4 v = {a0, a1, a2, a3};
+                            *(GAS u32x4_unaligned *)op = v;
+                            op += 16;
+                        }
+                    }
+                };
+                // the head entry of the symbol just decoded: the root of ITS row and its alpha word, one 8-byte read
+                auto head_read = [&](u32 sy) __attribute__((always_inline)) {
+                    const u32x2 h = *(LAS const volatile u32x2 *)(unsigned long)(lds_addr(img_lds) + 8u * sy);
+                    rootn = h.x; hn = h.y;
+                };
+                auto shadow = [&]() __attribute__((always_inline)) {
+                    asm volatile("" : "+v"(wmp));                 // (holds the mask and the count behind the fence)
+                    cursor += __popc(wmp & 0xfu);
+                    ring_read();
+                    book();
+                };
+                u32 xn = x, s;
+                if (pin) s = lookup_step_pk(row, root.x, hdr, xn, true, shadow, head_read);
+                else {
+                    ring_read();
+                    s = lookup_step_pk(row, root.x, hdr, xn, false, NoShadow(), head_read);
+                    book();
+                }
+                u32 rown1;
+                asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(rown1) : "v"(s), "v"(roww), "v"(rows));   // (the compiler's own choice is a 64-bit multiply-add)
+                hdr = live ? hn : hdr;
+                row = live ? rown1 : row;
+                root.x = live ? rootn : root.x;
+                x = live ? xn : x;
+                // renormalise (as below)
+                const bool want = live && x < RANS_LOW;
+                const u32 wq = (u32)(__ballot(want) >> (lane & ~3u));      // the quad's requests in bits 0..3 (quad_ballot, not yet masked)
+                const u32 pre = __popc(wq & below);
+                const bool take = FAST ? want : (want && cursor + pre < nwords);
+                const u32 wlo = __builtin_amdgcn_alignbyte(d1, d0, cb), whi = __builtin_amdgcn_alignbyte(d2, d1, cb);
+                const u32 w = __builtin_amdgcn_perm(whi, wlo, __umul24(pre, 0x0202u) + 0x0c0c0100u);
+                u32 xr = (x << 16) | w;
+                asm volatile("" : "+v"(xr));
+                x = take ? xr : x;
+                // the count of this step's words is added in the next step's shadow; the last step of a trip adds its
+                // own, so the cursor is whole wherever the loop looks at it
+                if (u + 1 < TRIP) wmp = wq;
+                else cursor += __popc(wq & 0xfu);
+                continue;
+            }
+            // ---- every other row kind ----
             // next four candidate words (8 bytes at any byte alignment) from the ring; issued
             // before the table lookups so that their latency hides under them
             const u32 cb = BYTE ? off0 + cursor : off0 + 2 * cursor;
@@ -372,25 +513,20 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
             spec.rows = rows; spec.roww = roww;
             const bool speculate = ORDER == 1 && LV == 2;
             u32 s, rown1 = 0;
-            u32 hn_first = 0;
             u32x2 rootn1 = {0u, 0u}, rootn2 = {0u, 0u};
             if (PKD) {
-                s = lookup_step_pk<WIDE>(row, root, root2, hdr >> PK_FIRST_SHIFT, xn);
+                s = lookup_step_pkw(row, root, root2, hdr >> PK_FIRST_SHIFT, xn);
                 // the next row's root: requested as soon as the symbol is known, used at the top of the next step
                 asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(rown1) : "v"(s), "v"(roww), "v"(rows));   // (the compiler's own choice is a 64-bit multiply-add)
                 if (WIDE) {
                     rootn1 = *(LAS const volatile u32x2_a4 *)(unsigned long)rown1;
                     rootn2 = *(LAS const volatile u32x2_a4 *)(unsigned long)(rown1 + 8u);
-                } else if (PK2) {
-                    // the head entry of the symbol just decoded: the root of ITS row and its alpha word, one 8-byte read
-                    const u32x2 h = *(LAS const volatile u32x2 *)(unsigned long)(lds_addr(img_lds) + 8u * s);
-                    rootn1.x = h.x; hn_first = h.y;
                 } else
                     rootn1.x = *(LAS const volatile u32 *)(unsigned long)rown1;
             } else {
                 s = lookup_step<(PKD ? 2 : LV)>(img0, row, look, mask, xn, LV == 2 ? &root : nullptr, speculate ? &spec : nullptr);
             }
-            const u32 hn = PK2 ? hn_first : img.ld16(2 * s);   // byte value | ROW_EMPTY of the new context
+            const u32 hn = img.ld16(2 * s);   // byte value | ROW_EMPTY of the new context
             if (BYTE) badb |= (FAST || live) ? hn : 0u;   // rANS 4x8: ROW_BAD on ANY decoded symbol, the last one included
             u32 byte0 = 0;
             if (ORDER == 0) {

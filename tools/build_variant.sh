@@ -7,11 +7,18 @@ name=$1; shift
 mkdir -p ../variants ../../build/var_$name
 rm -f ../../build/var_$name/*.o
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -fno-fast-math -Wno-unused-function -Wno-unused-variable"
+# the translation units are the Makefile's: SRC, and SRC_ILP with the Makefile's ILP flags
+SRC=$(sed -n 's/^SRC *:= *//p' Makefile); SRC_ILP=$(sed -n 's/^SRC_ILP *:= *//p' Makefile); ILP=$(sed -n 's/^ILP *:= *//p' Makefile)
+[ -n "$SRC" ] && [ -n "$SRC_ILP" ] || { echo "build_variant: no SRC / SRC_ILP in the Makefile" >&2; exit 1; }
 objs=""; pids=""
-for f in r4x16_api r4x16_host r4x16_multi r4x16_stripe r4x16_sched r4x16_decode r4x16_encode r4x16_enc_chain r4x16_enc_chain_rec; do
-  /opt/rocm/bin/hipcc $FLAGS "$@" -c $f.hip -o ../../build/var_$name/$f.o & pids="$pids $!"; objs="$objs ../../build/var_$name/$f.o"
+for f in $SRC; do
+  o=../../build/var_$name/${f%.hip}.o
+  /opt/rocm/bin/hipcc $FLAGS "$@" -c $f -o $o & pids="$pids $!"; objs="$objs $o"
 done
-/opt/rocm/bin/hipcc $FLAGS -mllvm -amdgpu-sched-strategy=max-ilp "$@" -c r4x16_enc_chain_pk.hip -o ../../build/var_$name/r4x16_enc_chain_pk.o & pids="$pids $!"
+for f in $SRC_ILP; do
+  o=../../build/var_$name/${f%.hip}.o
+  /opt/rocm/bin/hipcc $FLAGS $ILP "$@" -c $f -o $o & pids="$pids $!"; objs="$objs $o"
+done
 for p in $pids; do wait $p || { echo "build_variant: a compile failed" >&2; exit 1; }; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -Wl,--version-script=exports.map -o ../variants/lib$name.so $objs ../../build/var_$name/r4x16_enc_chain_pk.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -Wl,--version-script=exports.map -o ../variants/lib$name.so $objs
 echo built ../variants/lib$name.so

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Instruction mix of the hot-loop bodies in build/asm/*.s (made by `make -C htscodecs_amd/csrc asm`).
-usage: tools/isa_count.py <kernel-name-substring> [block-label-substring]"""
+usage: tools/isa_count.py <kernel-name-substring> [block-label-substring]
+       tools/isa_count.py --json <out>     the hot bodies' counts (and, for the decode chain on packed rows, the number of
+                                           instructions in the shadow of each step's group read and head read)"""
 import re
 import sys
 from collections import Counter
@@ -26,6 +28,42 @@ HOT = {   # kernel-name mangled prefix -> (label, instruction that occurs once p
     "_Z11k_enc_chainILb1ELb1ELb0EE": ("k_enc_chain<true,true,false>", "ds_write_b16"),
     "_Z15k_enc_chain_rec": ("k_enc_chain_rec", "ds_write_b16"),
 }
+
+
+def shadows(b, first, second=None):
+    """For each `first` in the block (a read on the step's dependent path; `second`: the read that completes it, taken
+    where it follows within four instructions), the number of instructions issued between the read and the s_waitcnt
+    that waits for it: what the step issues in the read's shadow.  LDS operations return in order, so a wait for
+    lgkmcnt(c) covers the read once no more than c LDS operations were issued behind it; earlier waits (for reads
+    issued before it) and s_nop are not counted as work.  A read whose wait lies in another block (the look-up that
+    the loop header holds) is left out."""
+    out = []
+    for i, x in enumerate(b):
+        if x.split()[0] != first:
+            continue
+        j = i
+        if second:
+            for k in range(i + 1, min(i + 5, len(b))):
+                if re.match(second, b[k]):
+                    j = k
+                    break
+        behind, work = j - i, 0                  # LDS operations issued behind `first`
+        for k in range(j + 1, len(b)):
+            op = b[k].split()[0]
+            if op == 's_waitcnt':
+                m = re.search(r'lgkmcnt\((\d+)\)', b[k])
+                if m and int(m.group(1)) <= behind:
+                    out.append(work)
+                    break
+            elif op.startswith('ds_'):
+                behind += 1; work += 1
+            elif op != 's_nop':
+                work += 1
+    return out
+
+
+GROUP_READ = ("ds_read_b128", r"ds_read_b32 .*offset:16\b")      # lookup_step_pk's group: 16 bytes + the dword after them
+HEAD_READ = ("ds_read_b64", None)                                 # the head entry of the symbol just decoded
 
 
 def to_json(out_path):
@@ -56,6 +94,11 @@ def to_json(out_path):
                         best = (per, {"steps_in_block": steps, "instructions_per_step": round(per, 1),
                                       "valu_per_step": round(cat('v_') / steps, 1), "lds_per_step": round(cat('ds_') / steps, 1),
                                       "salu_and_waits_per_step": round(cat('s_') / steps, 1)})
+                        if marker == "v_lshrrev_b64" and c["ds_read_b128"]:      # the decode chain on packed rows
+                            best[1].update({"instructions_in_block": len(b), "s_waitcnt_in_block": c["s_waitcnt"],
+                                            "s_nop_in_block": c["s_nop"],
+                                            "group_shadow_per_step": shadows(b, *GROUP_READ),
+                                            "head_shadow_per_step": shadows(b, *HEAD_READ)})
                 if best:
                     res["kernels"][label] = best[1]
     with open(out_path, 'w') as f:
@@ -81,6 +124,8 @@ def main():
                 cat = lambda p: sum(v for k, v in c.items() if k.startswith(p))
                 print(f"{name}\n  {lab[:100]}\n  total {len(b)}  valu {cat('v_')}  ds {cat('ds_')}  salu {cat('s_')}  vmem {cat('global_') + cat('buffer_') + cat('flat_')}")
                 print('  ', c.most_common(50))
+                if c["ds_read_b128"]:
+                    print('   group shadow per step', shadows(b, *GROUP_READ), ' head shadow per step', shadows(b, *HEAD_READ))
 
 if __name__ == '__main__':
     main()
