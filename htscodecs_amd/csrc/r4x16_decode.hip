@@ -322,8 +322,9 @@ __device__ __forceinline__ u32 chain_decode(IMG img, u32 nsym, gcu8 *words, u32 
 //     with the table lookups, and the right one is picked once the quad ballot is known;
 //   * decoded bytes are gathered four at a time per chain and stored as dwords (order-1), so a
 //     wave issues one store per four symbols instead of four.
-// Packed rows of layout 2 (LV == 1, what the headline runs on) have a step of their own in the trip body, laid out
-// around its two dependent reads like chain_decode_dir's: in steps 1.. of a trip the ring reads, the cursor and the
+// Packed rows of layout 2 (LV == 1) have a step of their own in the trip body - on the short ring only: with the
+// 256-byte ring, what the headline runs on, they have chain_decode_pk2 below, which carries this step's layout through
+// the whole loop.  The step is laid out around its two dependent reads like chain_decode_dir's: in steps 1.. of a trip the ring reads, the cursor and the
 // output bookkeeping stand in the shadow of the look-up's group read (lookup_step_pk) instead of at the top of the
 // step.  92.3 -> 87.2 ms on the headline's decode chain; the ring reads in front of the group read and only their
 // consumers behind it: 4.8 ms slower per benchmark step (profiles/dec_shadow.md).  The other row kinds keep the
@@ -678,6 +679,272 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
         for (u32 j = 0; j < rem; j++) op[j] = (u8)(acc >> (8 * (4 - rem + j)));
     }
     return active ? ((bad & ROW_EMPTY) | (BYTE ? badb & ROW_BAD : 0u)) : 0u;        // idle lanes ran on garbage in the fast trips
+}
+
+// ---------------------------------------------------------------------------------------------
+// The chain decoder for packed rows of layout 2 on the 256-byte ring (LV == 1, TRIP == 8: what the headline runs on).
+// The step is lookup_step_pk's, cut into the same three pieces, but the cut is carried through the whole loop: a step
+// ENDS by issuing the next step's issue half (m, GM, the root count, the two group reads, then the cursor's advance and
+// the ring reads), so the look-up of a trip's first step is in flight across the back edge and the loop test, the
+// fast / slow decision and the ring-refill check stand in its shadow - by construction, not because the compiler
+// happens to hoist it into the loop header (profiles/r04_dec_variants.md: the two variants that lost that hoist).
+// Every step of every trip, the first included, therefore has the one pinned order.
+// In front of the 8-step loop runs a loop of 16-step trips, all fast, while every stream of the wave has sixteen
+// steps and 64 words left: one 16-byte store per trip from four accumulators that are never rotated, no (t & 15) test,
+// no first-trip conditions (a step's bookkeeping belongs to the shadow of the NEXT step's group read, so the byte of a
+// trip's last step is booked, and the trip's store made, at the end of that same trip).  It hands the 8-step loop
+// t = tb, a multiple of 16, with everything up to step tb booked and stored: that loop's first trip skips step 0's
+// bookkeeping where it used to test t > 0, and the tail after the loop knows that nothing is queued if no trip followed.
+// Ring: FOUR live quarters (h .. h + 3 while the cursor is in h: a 16-step trip moves it by up to 128 bytes - one word
+// per chain and step, whatever the stream holds - and reads 12 further), the next two waiting in registers; a refill
+// parks one or two of them in the quarters the cursor has left.  The 8-step loop keeps one waiting.
+// The short ring (TRIP == 4, off by default) keeps chain_decode_lds' layout-2 step.
+// Headline step 146.5 -> 144.6 ms with the carried look-up alone, -> 139.4 with the 16-step trips
+// (profiles/dec_trip16.md, with the two placements that cost them 4.5 and 7 ms).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 *ring, gcu8 *words, u32 words_len,
+                                                gu8 *out, u32 out_sz, u32 x, bool active, u32 lane)
+{
+    const u32 imga = lds_addr(img_lds);
+    const u32 k = lane & 3;
+    const u32 rows = imga + pk_head_bytes(nsym), roww = pk_row_bytes(nsym);
+    const u32 nwords = words_len >> 1;
+    const u32 below = (1u << k) - 1u;
+    constexpr u32 RB = 256u, GB = 0x00200400u;
+    const u32 oq = out_sz >> 2;
+    u32 count = active ? oq + (k == 3 ? out_sz - 4 * oq : 0) : 0u;
+    gu8 *op = out + (u64)k * oq;
+
+    // ---- word ring: as in chain_decode_lds, with all four quarters live --------------------------
+    gcu8 *abase = (gcu8 *)((u64)words & ~15ull);
+    const u32 off0 = (u32)((u64)words & 15ull);
+    const u32 avail = off0 + words_len;
+    const u32 lastc = avail ? (avail - 1u) >> 4 : 0u;
+    const bool loadable = active && avail != 0;
+    auto load_chunk = [&](u32 c) -> u32x4 {
+        u32x4 v = {0, 0, 0, 0};
+        if (loadable) v = *(gcu32x4 *)(abase + 16ull * (c < lastc ? c : lastc));
+        return v;
+    };
+    // parks a quarter in the slot of stream quarter `qi`; the 8-byte wrap copy follows slot 0
+    auto park = [&](u32 qi, u32x4 v) __attribute__((always_inline)) {
+        const u32 slot = (qi & 3u) * 64u + 16u * k;
+        *(u32x4 *)(ring + slot) = v;
+        if (slot == 0) *(u32x2 *)(ring + RB) = v.xy;
+    };
+    if (active) {
+        park(0, load_chunk(k));
+        park(1, load_chunk(k + 4));
+        park(2, load_chunk(k + 8));
+        park(3, load_chunk(k + 12));
+    }
+    // quarters 4 and 5; in the 16-step trips penda holds the even quarter of the two waiting and pendb the odd one
+    u32x4 penda = load_chunk(16 + k), pendb = load_chunk(20 + k);
+    u32 half = 0;                                         // index of the 64-byte quarter holding the cursor
+    __syncthreads();
+
+    u32 row = rows, cursor = 0, bad = 0, t = 0, tb = 0;
+    u32 rootx = *(LAS const u32 *)(unsigned long)imga;
+    u32 hdr = *(LAS const u16 *)(unsigned long)(imga + 4u), hdr_even = 0;
+    if (count) bad = hdr;
+    u32 acc = 0, a0 = 0, a1 = 0, a2 = 0, a3 = 0;          // as in chain_decode_lds
+
+    // ---- the step, in its three pieces -----------------------------------------------------------
+    // carried from a step's issue half to its finish half (across the back edge for a trip's first step)
+    u32 m = 0, GM = 0, t12 = 0, xs = 0, D0 = 0, D1 = 0, D2 = 0, D3 = 0, D4 = 0, d0 = 0, d1 = 0, d2 = 0, cb = 0, g = 0;
+    // issue half of the step after one whose word requests were `wq`; the caller's bookkeeping follows, then issue_end
+    auto issue = [&](u32 wq, bool adv) __attribute__((always_inline)) {
+        m = x & 1023u;
+        GM = GB - __umul24(m, 0x400801u);
+        const u32 gneg = __popc((rootx + GM) & GB);
+        const bool r3 = rootx < (m << 22);
+        g = (r3 ? 3u : 2u) - gneg;
+        const u32 ga = row + 16u * g;
+        const u32x4 Dq = *(LAS const volatile u32x4 *)(unsigned long)ga;
+        D0 = Dq.x; D1 = Dq.y; D2 = Dq.z; D3 = Dq.w; D4 = *(LAS const volatile u32 *)(unsigned long)(ga + 16u);
+        __builtin_amdgcn_sched_barrier(0);
+        if (adv) {
+            asm volatile("" : "+v"(wq));                  // (holds the mask and the count behind the fence)
+            cursor += __popc(wq & 0xfu);
+        }
+        cb = off0 + 2 * cursor;
+        const u32 ra = cb & (RB - 4u);
+        const u32x2 d01 = *(LAS const volatile u32x2_a4 *)(ring + ra);
+        d0 = d01.x; d1 = d01.y; d2 = *(lvcu32 *)(ring + ra + 8);
+    };
+    auto issue_end = [&]() __attribute__((always_inline)) {
+        xs = x >> 10;
+        asm volatile("" : "+v"(xs));                      // (a plain shift is not held by the fences: it sinks to its use)
+        asm("v_mad_u32_u24 %0, %1, 12, %2" : "=v"(t12) : "v"(g), "v"(hdr >> PK_FIRST_SHIFT));
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // finish half, state update and renormalisation; returns the quad's word requests in bits 0..3
+    auto finish = [&](auto fastc, bool live) __attribute__((always_inline)) -> u32 {
+        constexpr bool FAST = decltype(fastc)::value;
+        const u32 m22 = m << 22;
+        const bool s0 = D1 < m22, s1 = D2 < m22, s2 = D3 < m22;
+        u32 D = D0, Dn = D1;
+        if (s0) { D = D1; Dn = D2; }
+        if (s1) { D = D2; Dn = D3; }
+        if (s2) { D = D3; Dn = D4; }
+        const u32 q = (u32)s0 + (u32)s1 + (u32)s2;
+        const u32 rneg = __popc((D + GM) & GB);
+        u32 tt;
+        asm("v_mad_u32_u24 %0, %1, 3, %2" : "=v"(tt) : "v"(q), "v"(t12));
+        const u32 s = tt - rneg;
+        // the head entry of the symbol just decoded: the root of ITS row and its alpha word, one 8-byte read, at once
+        const u32x2 h = *(LAS const volatile u32x2 *)(unsigned long)(imga + 8u * s);
+        __builtin_amdgcn_sched_barrier(0);
+        const u32 r11 = 22u - 11u * rneg;
+        const u32 P = (D << 11) | (D >> 22);
+        const u32 Cc = (D & 0x003fffffu) | (Dn & 0xffc00000u);
+        const u32 prev = __builtin_amdgcn_ubfe(P, r11, 10);
+        const u32 cur = __builtin_amdgcn_ubfe(Cc, r11, 10);
+        const u32 np = ~prev;
+        const u32 fm1 = (cur + np) & 1023u;
+        const u32 off = (m + np) & 1023u;
+        const u32 xn = __umul24(fm1, xs) + xs + off;
+        u32 rown1;
+        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(rown1) : "v"(s), "v"(roww), "v"(rows));
+        hdr = live ? h.y : hdr;
+        row = live ? rown1 : row;
+        rootx = live ? h.x : rootx;
+        x = live ? xn : x;
+        const bool want = live && x < RANS_LOW;
+        const u32 wq = (u32)(__ballot(want) >> (lane & ~3u));
+        const u32 pre = __popc(wq & below);
+        const bool take = FAST ? want : (want && cursor + pre < nwords);
+        const u32 wlo = __builtin_amdgcn_alignbyte(d1, d0, cb), whi = __builtin_amdgcn_alignbyte(d2, d1, cb);
+        const u32 w = __builtin_amdgcn_perm(whi, wlo, __umul24(pre, 0x0202u) + 0x0c0c0100u);
+        u32 xr = (x << 16) | w;
+        asm volatile("" : "+v"(xr));
+        x = take ? xr : x;
+        return wq;
+    };
+
+    issue(0u, false);
+    issue_end();
+
+    // ---- 16-step trips -----------------------------------------------------------------------------
+    {
+        u32 b0 = 0, b1 = 0, b2 = 0;                        // with acc: the four dwords of a trip
+        if (wave_any(active)) {
+            while (!wave_any(active && (t + 16u > count || cursor + 64u > nwords))) {
+#pragma unroll
+                for (int u = 1; u <= 16; u++) {           // step t + u - 1, then the issue half and the bookkeeping of step t + u
+                    const u32 wq = finish(std::true_type{}, true);
+                    issue(wq, true);
+                    // flags of the row now in use (ROW_EMPTY is tested after the loop), two steps per three-way or;
+                    // the row in use at t + 16 counts only if that step exists
+                    if (u == 16) bad |= hdr_even | (t + 16u < count ? hdr : 0u);
+                    else if (u & 1) hdr_even = hdr;
+                    else bad |= hdr | hdr_even;
+                    u32 &A = u <= 4 ? b0 : u <= 8 ? b1 : u <= 12 ? b2 : acc;
+                    A = __builtin_amdgcn_alignbit(hdr, A, 8);
+                    issue_end();
+                }
+                t += 16u;
+                // ring refill: the cursor is at most two quarters on
+                const u32 nh = (off0 + 2 * cursor) >> 6;
+                if (wave_any(active && nh != half)) {
+                    // (both waiting quarters are waited for HERE, where they arrived long ago: a wait inside one of the
+                    //  branches below would also wait for the request that the branch before it has just made)
+                    asm volatile("" : : "v"(penda), "v"(pendb));
+#pragma unroll
+                    for (int r = 0; r < 2; r++)
+                        if (active && nh != half) {       // idle lanes hold garbage cursors: they must not write LDS
+                            // (a request lands in the registers of the quarter just parked, as in the 8-step loop: with
+                            //  "the younger takes the older one's registers, the request the younger one's" the compiler
+                            //  had it arrive in temporaries and waited for it AT ONCE to copy it)
+                            if (half & 1u) { park(half, pendb); pendb = load_chunk(4 * (half + 6) + k); }
+                            else { park(half, penda); penda = load_chunk(4 * (half + 6) + k); }
+                            half++;
+                        }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+                // the trip's sixteen bytes, BEHIND the refill: vmcnt counts stores as well, and the refill's wait for
+                // its quarters would wait for a store issued in front of it (144.3 ms per benchmark step against 140.0)
+                if (active) {
+                    const u32x4 v = {b0, b1, b2, acc};
+                    *(GAS u32x4_unaligned *)op = v;
+                }
+                op += 16;
+            }
+        }
+        tb = t;
+    }
+    u32x4 pend0 = (half & 1u) ? pendb : penda;            // quarter half + 4
+
+    // ---- 8-step trips ------------------------------------------------------------------------------
+    auto trip = [&](auto fastc) {
+        constexpr bool FAST = decltype(fastc)::value;
+        // bookkeeping of step t + u (chain_decode_lds'): the byte of the step before and the flags of the row now in use
+        auto book = [&](int u) __attribute__((always_inline)) {
+            const u32 T = t + (u32)u;
+            if (u == 0 && t == tb) return;                // nothing decoded yet, or booked by the 16-step trips
+            if (!FAST) bad |= T < count ? hdr : 0u;
+            else if (u & 1) bad |= hdr | hdr_even;
+            else hdr_even = hdr;
+            acc = (FAST || T <= count) ? __builtin_amdgcn_alignbit(hdr, acc, 8) : acc;
+            if ((u & 3) == 0 && (FAST || T <= count)) {
+                a0 = a1; a1 = a2; a2 = a3; a3 = acc;
+                if (u == 0 && (t & 15u) == 0 && active) {
+                    const u32x4 v = {a0, a1, a2, a3};
+                    *(GAS u32x4_unaligned *)op = v;
+                    op += 16;
+                }
+            }
+        };
+        book(0);
+#pragma unroll
+        for (int u = 0; u < TRIP_STEPS; u++) {
+            const u32 wq = finish(fastc, FAST ? true : t + (u32)u < count);
+            if (u + 1 < TRIP_STEPS) {
+                issue(wq, true);
+                book(u + 1);
+                issue_end();
+            } else
+                cursor += __popc(wq & 0xfu);              // the cursor is whole wherever the loop looks at it
+        }
+        t += TRIP_STEPS;
+    };
+    while (wave_any(t < count)) {
+        const bool slow = active && (t + TRIP_STEPS > count || cursor + 4 * TRIP_STEPS > nwords);
+        if (!wave_any(slow)) trip(std::true_type{});
+        else trip(std::false_type{});
+        // the next trip's first look-up, common to both bodies; what follows stands in its shadow
+        issue(0u, false);
+        issue_end();
+
+        // ring refill when the cursor has entered a new 64-byte quarter (at most 64 bytes ago)
+        const u32 nh = (off0 + 2 * cursor) >> 6;
+        if (wave_any(active && nh != half)) {
+            if (active && nh != half) {                   // idle lanes hold garbage cursors: they must not write LDS
+                park(half, pend0);
+                pend0 = load_chunk(4 * (nh + 4) + k);
+                half = nh;
+            }
+            // (one wave per workgroup, LDS operations execute in issue order: see chain_decode_lds)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (count) {
+        // t steps ran.  A chain whose count equals t still has its last byte in hdr and its last four symbols
+        // unstored - unless no 8-step trip followed the 16-step ones, which book and store everything up to tb.
+        // Otherwise dwords were queued at steps 4, 8, .. <= min(count, t - 4) and stored 16 bytes at a time.
+        const bool all = t == tb;
+        const u32 lastq = all || count < t - 4 ? count : t - 4;
+        const u32 pushed = lastq >> 2, nd = all ? 0u : pushed & 3u;
+        if (count == t && !all) acc = __builtin_amdgcn_alignbit(hdr, acc, 8);
+        if (nd == 3) { *(gu32_unaligned *)op = a1; op += 4; }
+        if (nd >= 2) { *(gu32_unaligned *)op = a2; op += 4; }
+        if (nd >= 1) { *(gu32_unaligned *)op = a3; op += 4; }
+        const u32 rem = count - 4 * pushed;
+        for (u32 j = 0; j < rem; j++) op[j] = (u8)(acc >> (8 * (4 - rem + j)));
+    }
+    return active ? bad & ROW_EMPTY : 0u;                  // idle lanes ran on garbage in the fast trips
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1968,6 +2235,9 @@ __global__ __launch_bounds__(WAVE) void k_dec_chain(const DecItem *items, DecDes
                 bad |= chain_decode_dir<0, false>(im, nsym, ring, words, words_len, out, out_sz, x0, look, 0u, active && order == 0, lane);
             }
         } else {
+        if constexpr (LV == 1 && TRIP == TRIP_STEPS)
+            bad = chain_decode_pk2(im, nsym, ring, words, words_len, out, out_sz, x0, active && order == 1, lane);
+        else
         bad = chain_decode_lds<1, LV, TRIP>(im, nsym, ring, words, words_len, out, out_sz, x0, look, active && order == 1, lane);
         if (LV != 1 && LV != 5)                               // packed rows exist for order-1 streams only
             bad |= chain_decode_lds<0, ((LV == 1 || LV == 5) ? 2 : LV)>(im, nsym, ring, words, words_len, out, out_sz, x0, look, active && order == 0, lane);

@@ -19,8 +19,9 @@ def blocks_of(src, name):
     blocks.append((lab, cur))
     return blocks
 
-HOT = {   # kernel-name mangled prefix -> (label, instruction that occurs once per step in the hot body)
-    "_Z11k_dec_chainILb1ELi1ELi8EE": ("k_dec_chain<true,1>", "v_lshrrev_b64"),
+HOT = {   # kernel-name mangled prefix -> (label, instruction that occurs once per step in the hot body[, its least steps: 4])
+    # (the body of sixteen steps, which holds its own loop control and store: the bodies of eight behind it finish a stream)
+    "_Z11k_dec_chainILb1ELi1ELi8EE": ("k_dec_chain<true,1>", "v_lshrrev_b64", 16),
     "_Z11k_dec_chainILb1ELi6ELi8EE": ("k_dec_chain<true,6>", "v_lshrrev_b64"),
     # the packed rows: the short-index kind with the frequency table (what the headline's quality blocks run on; the
     # label bench.py looks up), and the kind with the full index
@@ -79,13 +80,13 @@ def to_json(out_path):
     for f in glob.glob(os.path.join(root, '*gfx950.s')):
         src = open(f).read()
         for name in sorted(set(re.findall(r'^(_Z\w+):', src, flags=re.M))):
-            for pre, (label, marker) in HOT.items():
+            for pre, (label, marker, *least) in HOT.items():
                 if not name.startswith(pre):
                     continue
                 best = None
                 for lab, b in blocks_of(src, name):
                     steps = sum(1 for x in b if x.split()[0] == marker)
-                    if steps < 4:
+                    if steps < (least[0] if least else 4):
                         continue
                     per = len(b) / steps
                     if best is None or per < best[0]:            # the leanest body with >= 4 steps: the full-trip one
