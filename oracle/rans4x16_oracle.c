@@ -388,10 +388,13 @@ static double approx_log(double a)            /* fast_log, :620-623 */
     return (u.x - 4606921278410026770LL) * 1.539095918623324e-16;
 }
 
-int orc_compute_shift(const uint32_t *F0, const uint32_t (*F)[256], const uint32_t *T, int *S)
+/* `st` (may be NULL) receives what the decision was made from - for tests that have to know which side of a rule an input
+ * is on, from this arithmetic and not from a second one. */
+static int compute_shift(const uint32_t *F0, const uint32_t (*F)[256], const uint32_t *T, int *S, orc_shift_stats *st)
 {
     double e10 = 0, e12 = 0;
     int max_tot = 0;
+    if (st) memset(st, 0, sizeof(*st));
     for (int i = 0; i < 256; i++) {
         if (!F0[i]) continue;
         int target = (int)pow2_ceil(T[i]);
@@ -407,19 +410,33 @@ int orc_compute_shift(const uint32_t *F0, const uint32_t (*F)[256], const uint32
             if (!F[i][j]) continue;
             present++;
             int x = (int)((double)(1 << O1_BITS_LO) * F[i][j] / T[i]);
+            if (st && x < 1) st->clamped10++;
             e10 -= F[i][j] * (approx_log(x > 1 ? x : 1) - l10);
             x = (int)((double)(1 << O1_BITS_HI) * F[i][j] / T[i]);
+            if (st && x < 1) st->clamped12++;
             e12 -= F[i][j] * (approx_log(x > 1 ? x : 1) - l12);
             e10 += 4;
             e12 += 6;
         }
+        if (st) { st->present[i] = present; st->tiny10[i] = tiny10; st->tiny12[i] = tiny12; st->target0[i] = target; }
         if (present < 64 && target > 128) target /= 2;    /* :678-681 */
         if (target > 1024) target /= 2;
         if (target > (1 << O1_BITS_HI)) target = 1 << O1_BITS_HI;
         S[i] = target;
         if (max_tot < target) max_tot = target;
     }
+    if (st) { st->e10 = e10; st->e12 = e12; st->ratio = e10 / e12; st->max_tot = max_tot; }
     return (e10 / e12 < 1.01 || max_tot <= (1 << O1_BITS_LO)) ? O1_BITS_LO : O1_BITS_HI;
+}
+
+int orc_compute_shift(const uint32_t *F0, const uint32_t (*F)[256], const uint32_t *T, int *S)
+{
+    return compute_shift(F0, F, T, S, NULL);
+}
+
+int orc_compute_shift_stats(const uint32_t *F0, const uint32_t (*F)[256], const uint32_t *T, int *S, orc_shift_stats *st)
+{
+    return compute_shift(F0, F, T, S, st);
 }
 
 /* ------------------------------------------------------------------------------------

@@ -40,6 +40,15 @@ int      orc_var_put_u32(uint8_t *cp, uint32_t v);
 int      orc_var_get_u32(const uint8_t *cp, const uint8_t *endp, uint32_t *v);
 int      orc_normalise_freq(uint32_t *F, int size, uint32_t tot);
 int      orc_compute_shift(const uint32_t *F0, const uint32_t (*F)[256], const uint32_t *T, int *S);
+/* The same decision with what it was made from: the two entropy estimates and their quotient (the value compared with
+ * 1.01), the largest per-row target, and per context byte the count of symbols, of "tiny" ones at either precision and
+ * the row's target before the halving rules; the numbers of terms whose scaled frequency truncated to 0. */
+typedef struct {
+    double e10, e12, ratio;
+    int max_tot, clamped10, clamped12;
+    int present[256], tiny10[256], tiny12[256], target0[256];
+} orc_shift_stats;
+int      orc_compute_shift_stats(const uint32_t *F0, const uint32_t (*F)[256], const uint32_t *T, int *S, orc_shift_stats *st);
 /* Bare streams (no container byte / size): the O0stream / O1stream of SURVEY Appendix A. */
 int      orc_o0_encode(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t cap, uint32_t *out_len);
 int      orc_o0_decode(const uint8_t *in, uint32_t in_size, uint8_t *out, uint32_t out_sz);
