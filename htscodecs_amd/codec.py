@@ -599,6 +599,63 @@ class DeviceCodec:
         if rc != 0:
             raise RuntimeError("tok3_decode_names_dev: " + self.ctx.error())
 
+    # ---- tok3 name encoding (include/rans4x16_hip.h part 2e) ---------------------------------------------------------
+    def tok3_tokenise(self, d_in, in_off, in_size, d_cols, cols_off, cols_size, status, blk_first, col_id, col_off, col_size,
+                      last_start, nreads, max_in_size, max_names, max_name_len, max_columns, max_tokens=128, total_in_size=0,
+                      search_slots=0, col_capacity=None):
+        """rans4x16_hip_tok3_tokenise_dev: the name blocks d_in[in_off[b]:in_off[b] + in_size[b]] (a name ends at any byte
+        <= '\\n') turned into their token columns at d_cols[cols_off[b]:cols_off[b + 1]]; blk_first (int32, nblk + 1) and
+        col_id / col_off / col_size (int32 / int64 / int32, nblk x max_columns) are the dense directory tok3_pack takes,
+        last_start / nreads its header values.  d_cols None: the sizing pass.  search_slots 1: the exact search alone."""
+        t = self.torch
+        nblk = in_size.numel()
+        assert d_in.dtype == t.uint8 and in_off.dtype == t.int64 and in_off.numel() >= nblk and in_size.dtype == t.int32
+        assert d_cols is None or d_cols.dtype == t.uint8
+        assert cols_off.dtype == t.int64 and cols_off.numel() == nblk + 1
+        assert blk_first.dtype == t.int32 and blk_first.numel() == nblk + 1
+        for x in (cols_size, status, last_start, nreads):
+            assert x.dtype == t.int32 and x.numel() == nblk
+        assert col_id.dtype == t.int32 and col_off.dtype == t.int64 and col_size.dtype == t.int32
+        for x in (col_id, col_off, col_size):
+            assert x.numel() == nblk * int(max_columns)
+        cap = (d_cols.numel() if d_cols is not None else 0) if col_capacity is None else int(col_capacity)
+        assert cap <= (d_cols.numel() if d_cols is not None else 0)
+        rc = self.L.rans4x16_hip_tok3_tokenise_dev(
+            self.ctx.h, nblk, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_cols.data_ptr() if d_cols is not None else None, cap, cols_off.data_ptr(), cols_size.data_ptr(), status.data_ptr(),
+            blk_first.data_ptr(), col_id.data_ptr(), col_off.data_ptr(), col_size.data_ptr(), last_start.data_ptr(),
+            nreads.data_ptr(), int(max_in_size), int(max_names), int(max_name_len), int(max_tokens), int(max_columns),
+            int(total_in_size), int(search_slots), self._stream())
+        if rc != 0:
+            raise RuntimeError("tok3_tokenise_dev: " + self.ctx.error())
+
+    def tok3_encode_names(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size, max_names,
+                          max_name_len, max_columns, max_tokens=128, max_col_size=0, total_in_size=0, search_slots=0,
+                          chosen=None, blk_first=None, out_capacity=None):
+        """rans4x16_hip_tok3_encode_names_dev: the name blocks d_in[in_off[b]:in_off[b] + in_size[b]] tokenised, their
+        columns compressed with the best of `methods` and framed into one container per block at
+        d_out[out_off[b]:out_off[b + 1]] - tok3_tokenise and tok3_pack in one call, the columns kept in an arena of the
+        context.  chosen (int32, nblk x max_columns) / blk_first (int32, nblk + 1): optional.  d_out None: the sizing pass."""
+        t = self.torch
+        nblk = in_size.numel()
+        assert d_in.dtype == t.uint8 and in_off.dtype == t.int64 and in_off.numel() >= nblk and in_size.dtype == t.int32
+        assert d_out is None or d_out.dtype == t.uint8
+        assert out_off.dtype == t.int64 and out_off.numel() == nblk + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32 and out_size.numel() == nblk and status.numel() == nblk
+        assert chosen is None or (chosen.dtype == t.int32 and chosen.numel() == nblk * int(max_columns))
+        assert blk_first is None or (blk_first.dtype == t.int32 and blk_first.numel() == nblk + 1)
+        cap = (d_out.numel() if d_out is not None else 0) if out_capacity is None else int(out_capacity)
+        assert cap <= (d_out.numel() if d_out is not None else 0)
+        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        rc = self.L.rans4x16_hip_tok3_encode_names_dev(
+            self.ctx.h, nblk, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            len(methods), meth, chosen.data_ptr() if chosen is not None else None,
+            blk_first.data_ptr() if blk_first is not None else None, int(max_in_size), int(max_names), int(max_name_len),
+            int(max_tokens), int(max_columns), int(max_col_size), int(total_in_size), int(search_slots), self._stream())
+        if rc != 0:
+            raise RuntimeError("tok3_encode_names_dev: " + self.ctx.error())
+
     # ---- rANS 4x8 (CRAM 3.0), include/rans4x8_hip.h part 2a: the same surface, every result assembled in place -------
     def compress_packed_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, order, max_in_size,
                             d_order=None, out_capacity=None):

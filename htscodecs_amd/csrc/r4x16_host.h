@@ -109,6 +109,16 @@ size_t r4x16_packed_carve(PackedSlots *p, u8 *base, size_t n, size_t chunk, u64 
 u64 r4x16_packed_stride(u32 max_in_size, int order, bool any_order);
 void r4x16_launch_packed_slots(const BatchArgs *a, const PackedSlots *p, int n, size_t chunk, u32 max_in_size, hipStream_t s);
 int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64_t total_in_size, hipStream_t s, const PackedOut *pk);
+// rans4x16_hip_tok3_pack_dev's body (r4x16_tok3.hip), with what rans4x16_hip_tok3_encode_names_dev adds: the blocks its
+// tokeniser refused (d_pre, [nblk] or nullptr), and a column count that lies on the device at d_blk_first[nblk]
+// (n_on_device: n is the room of the directory, the entries behind the count have size 0)
+int r4x16_tok3_pack_run(rans4x16_hip_ctx *c, int nblk, int n, const uint32_t *d_blk_first,
+                        const unsigned char *d_in, const uint64_t *d_col_off, const uint32_t *d_col_size,
+                        const int32_t *d_col_id, const uint32_t *d_last_start, const uint32_t *d_nreads,
+                        unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                        uint32_t *d_out_size, int32_t *d_status,
+                        int k, const int *methods, int32_t *d_chosen,
+                        uint32_t max_col_size, uint64_t total_col_size, const int32_t *d_pre, bool n_on_device, hipStream_t stream);
 // rANS 4x8: the encode pipeline of r4x16_api.hip over a batch in chunks.  pk == nullptr && sel == nullptr: the slot call.
 // pk: results back to back at pk->out + pk->off[i].  sel: best-of-k, k <= 2 candidates per block (sel->k == 0: one, the
 // call's order / d_order), the winner into the caller's slot (pk == nullptr) or the dense arena.

@@ -313,15 +313,19 @@ __global__ __launch_bounds__(1024) void k_t3_first_max(const u32 *blk_first, u32
     }
 }
 
-struct T3In { const u32 *blk_first; const u32 *size; const i32 *id; const u32 *last_start, *nreads; };
+// pre: [nblk] or nullptr - a block with a non-zero entry reports that status and is not framed; n_dev: nullptr, or where
+// the number of columns lies on the device (the directory of r4x16_tok3_enc.hip: the launch's n is then only its bound)
+struct T3In { const u32 *blk_first; const u32 *size; const i32 *id; const u32 *last_start, *nreads; const i32 *pre; const u32 *n_dev; };
 
 // one wave per block: the verdict, the duplicates, every column's place behind the header, the block's size
-__global__ __launch_bounds__(64) void k_t3_dup(T3In in, T3Cols w, const u32 *pmax, u32 *out_size, i32 *status, int nblk, u32 n, u32 max_col)
+__global__ __launch_bounds__(64) void k_t3_dup(T3In in, T3Cols w, const u32 *pmax, u32 *out_size, i32 *status, int nblk, u32 n_bound, u32 max_col)
 {
     const int b = (int)blockIdx.x;
     const u32 lane = threadIdx.x;
     const u32 first = in.blk_first[b], next = in.blk_first[b + 1];
-    i32 st = ST_OK;
+    const u32 n = in.n_dev ? (*in.n_dev < n_bound ? *in.n_dev : n_bound) : n_bound;
+    i32 st = in.pre ? in.pre[b] : ST_OK;
+    if (st != ST_OK) { if (lane == 0) { status[b] = st; out_size[b] = 0; } return; }
     if ((b == 0 && first != 0) || (b == nblk - 1 && next != n) || first > next || next > n || next - first > T3_MAX_IDS || first < pmax[b]) st = ST_SIZE;
     const u32 cnt = st == ST_OK ? next - first : 0u;
     for (u32 c0 = 0; c0 < cnt && st == ST_OK; c0 += 64) {                 // the first column that cannot be written
@@ -404,6 +408,22 @@ extern "C" int rans4x16_hip_tok3_pack_dev(rans4x16_hip_ctx *c, int nblk, int n, 
                                           uint32_t max_col_size, uint64_t total_col_size, void *stream)
 {
     if (!c) return -1;
+    return r4x16_tok3_pack_run(c, nblk, n, d_blk_first, d_in, d_col_off, d_col_size, d_col_id, d_last_start, d_nreads, d_out, out_capacity,
+                               d_out_off, d_out_size, d_status, k, methods, d_chosen, max_col_size, total_col_size, nullptr, false,
+                               (hipStream_t)stream);
+}
+
+// The call above, and the second half of rans4x16_hip_tok3_encode_names_dev (r4x16_tok3_enc.hip).  n_on_device: n is the
+// directory's room - the number of columns lies at d_blk_first[nblk], the entries behind it are idle (size 0) and belong
+// to no block; d_pre: the blocks an earlier stage refused.
+int r4x16_tok3_pack_run(rans4x16_hip_ctx *c, int nblk, int n, const uint32_t *d_blk_first,
+                        const unsigned char *d_in, const uint64_t *d_col_off, const uint32_t *d_col_size,
+                        const int32_t *d_col_id, const uint32_t *d_last_start, const uint32_t *d_nreads,
+                        unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                        uint32_t *d_out_size, int32_t *d_status,
+                        int k, const int *methods, int32_t *d_chosen,
+                        uint32_t max_col_size, uint64_t total_col_size, const int32_t *d_pre, bool n_on_device, hipStream_t stream)
+{
     if (nblk < 0 || n < 0 || (nblk == 0 && n) || k < 1 || k > 32 || !methods || !d_out_off ||
         (nblk && (!d_blk_first || !d_last_start || !d_nreads || (!d_out && out_capacity) || !d_out_size || !d_status)) ||
         (n && (!d_in || !d_col_off || !d_col_size || !d_col_id))) {
@@ -424,7 +444,7 @@ extern "C" int rans4x16_hip_tok3_pack_dev(rans4x16_hip_ctx *c, int nblk, int n, 
     u64 stream_bytes = (u64)n * r4x16_bound_hd(max_col_size, lean);
     if (total_col_size) stream_bytes = std::min<u64>(stream_bytes, (u64)(1.05 * (double)total_col_size) + 1 + (u64)n * (r4x16_bound_hd(0, lean) + 4ull));
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = stream;
     if (nblk == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
     T3Cols w;
     const size_t need = t3_cols_carve(&w, nullptr, (size_t)n, (size_t)nblk, stream_bytes);
@@ -446,7 +466,7 @@ extern "C" int rans4x16_hip_tok3_pack_dev(rans4x16_hip_ctx *c, int nblk, int n, 
         if (rc != 0) return -1;
         hipLaunchKernelGGL(k_t3_hash, dim3((u32)((n + 3) / 4)), dim3(256), 0, s, w, n);
     }
-    const T3In in = {d_blk_first, d_col_size, d_col_id, d_last_start, d_nreads};
+    const T3In in = {d_blk_first, d_col_size, d_col_id, d_last_start, d_nreads, d_pre, n_on_device ? d_blk_first + nblk : nullptr};
     const PackedOut pk = {d_out, d_out_off, out_capacity};
     hipLaunchKernelGGL(k_t3_first_max, dim3(1), dim3(1024), 0, s, d_blk_first, w.pmax, nblk);
     hipLaunchKernelGGL(k_t3_dup, dim3((u32)nblk), dim3(64), 0, s, in, w, (const u32 *)w.pmax, d_out_size, d_status, nblk, (u32)n, max_col_size);

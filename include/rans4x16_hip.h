@@ -279,8 +279,8 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
  * The CRAM 3.1 name tokeniser (htscodecs tokenise_name3.c) turns a block of read names into token columns, compresses
  * each with the best of a method list and frames them into one container (encode_names, :1431-1531); decode_names
  * (:1546-1669) walks the container and decodes the columns before it rebuilds the names.  These calls do the column
- * half of both on the device, rANS flavour (use_arith = 0); part 2d turns the decoded columns into names (decode_name).
- * The encoding tokeniser - trie, encode_name - is serial per name and stays with the caller.
+ * half of both on the device, rANS flavour (use_arith = 0); part 2d turns the decoded columns into names (decode_name),
+ * part 2e the names into the columns this part packs (the encoding tokeniser: trie, encode_name).
  *
  * A container: last_start (4 bytes, little endian), nreads (4), use_arith (1), then per column a type byte
  * (type | 128 on the first column of a token position, | 64 for a duplicate) followed by var_put_u32(clen) and the
@@ -374,7 +374,7 @@ int rans4x16_hip_tok3_unpack_dev(rans4x16_hip_ctx *ctx, int nblk,
 /* ---- 2d. tok3 name decoding ---------------------------------------------------------------------
  * The second half of decode_names (htscodecs tokenise_name3.c:1546-1694): the token columns of a name block become its
  * read names, NUL-separated, on the device - decode_name (:1018-1189) and the loop around it (:1671-1689).  rANS flavour
- * (use_arith = 0) only; the encoding direction is not built.
+ * (use_arith = 0) only; the encoding direction is part 2e.
  *
  * rans4x16_hip_tok3_names_dev: the stage.  Its inputs are what rans4x16_hip_tok3_unpack_dev wrote, DEVICE arrays all:
  *   d_cols, col_capacity         the column arena and its size in bytes; a column that does not lie inside it fails its
@@ -447,6 +447,86 @@ int rans4x16_hip_tok3_decode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
                                        uint32_t *d_out_size, uint32_t *d_nnames, int32_t *d_status, uint32_t *d_name_start,
                                        uint32_t max_columns, uint32_t max_in_size, uint32_t max_col_size,
                                        uint32_t max_names, uint32_t max_tokens, uint64_t total_col_size, void *stream);
+
+/* ---- 2e. tok3 name encoding ---------------------------------------------------------------------
+ * The first half of encode_names (htscodecs tokenise_name3.c:1334-1429): a block of read names becomes the token columns
+ * that rans4x16_hip_tok3_pack_dev compresses and frames - build_trie / search_trie (:507-712), encode_name (:729-1013,
+ * mode 1) and the drop rule (:1406-1429), on the device.  rANS flavour (use_arith = 0) only.
+ *
+ * rans4x16_hip_tok3_tokenise_dev: nblk name blocks at d_in + d_in_off[b], d_in_size[b] bytes.  Every array is a DEVICE
+ * array; the call only enqueues and reads nothing back.
+ *   d_cols, col_capacity, d_cols_off[nblk + 1], d_cols_size[nblk]  one dense arena as in the packed calls: block b's columns
+ *                                back to back, ids ascending, at d_cols + d_cols_off[b]; the offsets are sums before the
+ *                                capacity rule; d_cols == NULL with col_capacity 0 is a sizing pass; a block that ends beyond
+ *                                col_capacity reports R4X16_E_CAPACITY and size 0.  A block's columns take at most 6 x its
+ *                                bytes (a lone '0' costs six: type, width, value; a name's own six - its N_DUP / N_DIFF byte,
+ *                                the distance, its N_END - are paid for by its separator), so 6 x the bytes of the batch is
+ *                                a capacity that needs no sizing pass
+ *   d_blk_first[nblk + 1], d_col_id / d_col_off / d_col_size  what rans4x16_hip_tok3_pack_dev takes, d_col_off relative to
+ *                                d_cols: the directory is dense, n = d_blk_first[nblk] entries, and needs room for
+ *                                nblk x max_columns; ids ascend inside a block, no column is empty, a refused block has none
+ *   d_last_start, d_nreads, d_status  [nblk]
+ *   max_in_size (1 .. 16,776,960), max_names (1 .. 2^24 - 1), max_name_len (<= 16384), max_tokens (1..128), max_columns (1..2048): host limits
+ *   total_in_size                the bytes of all blocks (0 = unknown: nblk x max_in_size is reserved), host
+ *   search_slots                 slots of a block's table of name prefixes, rounded up to a power of two (host); 0 = sized by
+ *                                the library (16 x max_names, at most 2 x max_in_size).  A block whose table fills up, and
+ *                                every block with search_slots = 1, finds its earlier names by the exact search alone,
+ *                                which costs names x names; the columns are the same
+ * The rules, with the reference's lines:
+ *   Framing (:1334-1380).  A name ends at any byte <= '\n'; nreads is the number of such bytes, last_start the offset
+ *   behind the last of them; what follows it is ignored; names may be empty.
+ *   The earlier name (:507-554, :621-712).  For name n of len bytes: `from` is the most recent earlier name of at least len
+ *   bytes that starts with all of n, else n; p3 the same for n's first prefix_len bytes, none if n is shorter.
+ *   exact = from != n && len; pnum = exact ? from : p3, and without either n - 1 (0 for the first name).  pnum == n happens:
+ *   distance 0, nothing to match against.  The name is N_DUP only if exact and pnum has len bytes; an exact hit on a
+ *   longer name is N_DIFF against that name.  prefix_len, is_fixed and fixed_len are :632-670's four formats, quirks kept.
+ *   Tokens (:729-1013).  A fixed prefix is one N_ALPHA.  Behind it: in a maximal stretch of letters and punctuation the
+ *   bytes before the first letter are N_CHAR each and the rest is one token, N_CHAR if it is one byte, else N_ALPHA; a
+ *   stretch of digits is cut into pieces of nine from its start, N_DIGITS0 if the piece starts with '0' or the earlier
+ *   name has a N_DIGITS0 of the same width there (:916-919), else N_DIGITS; any other byte is a N_CHAR.  Against the
+ *   earlier name's token at the same position: N_MATCH, N_DDELTA / N_DDELTA0 for a difference of 1..255 (N_DDELTA only
+ *   while 5 + deltas so far > literals so far at that position, :934), else the literal.
+ *   Columns (:342-500).  As encode_token_* writes them; N_DZLEN has no type byte.  A type column that is N_MATCH behind
+ *   its first byte is dropped if its position has another column (:1406-1429).
+ * Statuses, for input the reference cannot encode: nreads == 0: SIZE (create_context fails); a byte >= 0x80 inside a name:
+ * UNSUPPORTED (the reference aborts); a name whose N_END would lie at position max_tokens or beyond: UNSUPPORTED (the
+ * reference runs over its arrays at 128); more names than max_names, a name above max_name_len, a block above max_in_size
+ * (not read), a block that ends beyond total_in_size, more columns than max_columns: UNSUPPORTED.  A block fails as a whole:
+ * its status, size 0, no columns; d_last_start / d_nreads are what the framing found (0 for a block that was not read); its
+ * neighbours are not affected.  Nothing outside the blocks' ranges is written.
+ * The names, token records (20 bytes per byte of input) and tables wait in an arena of the context; a batch whose arena
+ * does not fit half of max_workspace_mb is refused with -1: split it.  One wave tokenises one block.
+ *
+ * rans4x16_hip_tok3_encode_names_dev: encode_names as one call, names in and containers out - the tokeniser into a column
+ * arena of the context (6 x total_in_size bytes; total_in_size 0: 6 x nblk x max_in_size), then the stages of
+ * rans4x16_hip_tok3_pack_dev over its directory.  It takes the tokeniser's input and limits and the pack's k, methods
+ * and dense output arena (d_out, out_capacity, d_out_off, d_out_size, d_status: as there, the sizing pass included).
+ * The number of columns stays on the device: the pack's stages run over all nblk x max_columns entries of the directory,
+ * those behind the last column as empty items, so max_columns should not be far above what the blocks have.
+ *   d_chosen       [nblk x max_columns] or NULL: the method of column i of the dense directory
+ *   d_blk_first    [nblk + 1] or NULL: receives the directory's block starts, which say whose column i is
+ *   max_col_size   largest column (host), 0: 4 x max_in_size, which no column exceeds; it sizes the encoder's internal slots
+ * A block the tokeniser refuses reports that status and size 0; every other block what rans4x16_hip_tok3_pack_dev
+ * reports for its columns, byte for byte what encode_names returns for the block with the same method list.  A batch whose
+ * arenas do not fit half of max_workspace_mb is refused with -1: split it.
+ * Both calls only enqueue and read nothing back; -1 on bad arguments (a NULL context included). */
+int rans4x16_hip_tok3_tokenise_dev(rans4x16_hip_ctx *ctx, int nblk,
+                                   const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                   unsigned char *d_cols, uint64_t col_capacity, uint64_t *d_cols_off,
+                                   uint32_t *d_cols_size, int32_t *d_status,
+                                   uint32_t *d_blk_first, int32_t *d_col_id, uint64_t *d_col_off, uint32_t *d_col_size,
+                                   uint32_t *d_last_start, uint32_t *d_nreads,
+                                   uint32_t max_in_size, uint32_t max_names, uint32_t max_name_len,
+                                   uint32_t max_tokens, uint32_t max_columns, uint64_t total_in_size,
+                                   uint32_t search_slots, void *stream);
+int rans4x16_hip_tok3_encode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
+                                       const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                       unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                       uint32_t *d_out_size, int32_t *d_status,
+                                       int k, const int *methods, int32_t *d_chosen, uint32_t *d_blk_first,
+                                       uint32_t max_in_size, uint32_t max_names, uint32_t max_name_len,
+                                       uint32_t max_tokens, uint32_t max_columns, uint32_t max_col_size,
+                                       uint64_t total_in_size, uint32_t search_slots, void *stream);
 
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
