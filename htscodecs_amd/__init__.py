@@ -13,6 +13,7 @@ from .codec import (  # noqa: F401
     rans_compress_bound_4x16, rans_compress_4x16, rans_uncompress_4x16,
     compress_batch, compress_best_batch, uncompress_batch, DeviceCodec, MultiCodec,
     rans_compress, rans_uncompress, compress_batch_4x8, uncompress_batch_4x8,
+    tok3_level_methods, tok3_encode_names_batch, tok3_decode_names_batch, encode_names, decode_names,
 )
 
 __all__ = [
@@ -20,4 +21,5 @@ __all__ = [
     "rans_compress_bound_4x16", "rans_compress_4x16", "rans_uncompress_4x16",
     "compress_batch", "compress_best_batch", "uncompress_batch", "DeviceCodec", "MultiCodec",
     "rans_compress", "rans_uncompress", "compress_batch_4x8", "uncompress_batch_4x8",
+    "tok3_level_methods", "tok3_encode_names_batch", "tok3_decode_names_batch", "encode_names", "decode_names",
 ]

@@ -134,7 +134,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -145,13 +145,14 @@ class _Ctx:
 
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
-ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4}
+ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
     "expand": ("wave", "workgroup"),
     "launch": ("in_order", "side_by_side"),
     "result": ("in_slot", "dense", "gathered"),
+    "names": ("enc_chunks", "dec_chunks", "uploaded", "refused"),
 }
 
 _tls = threading.local()
@@ -321,6 +322,98 @@ def tok3_scan(container, max_columns=0, max_col_size=0):
         raise ValueError("tok3_scan: bad arguments")
     return rc, {"last_start": u32[0].value, "nreads": u32[1].value, "ndesc": u32[2].value, "ncol": u32[3].value,
                 "total_col_size": total.value, "largest_col": u32[4].value, "largest_stream": u32[5].value}
+
+
+def tok3_level_methods(level):
+    """rans4x16_hip_tok3_level_methods: the method list encode_names tries per column at `level`.  Needs no GPU."""
+    m = (C.c_int * 9)()
+    k = _lib.load().rans4x16_hip_tok3_level_methods(int(level), m)
+    return list(m[:k])
+
+
+def _free(addr):
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free.restype = None
+    libc.free(addr)
+
+
+def set_names_chunk_blocks(blocks, ctx=None):
+    """rans4x16_hip_set_names_chunk_blocks on the calling thread's context: at most `blocks` blocks per chunk of the
+    names batches below (0: by room alone)."""
+    ctx = ctx or _thread_ctx()
+    if ctx.L.rans4x16_hip_set_names_chunk_blocks(ctx.h, int(blocks)) != 0:
+        raise ValueError("names_chunk_blocks: %r" % (blocks,))
+
+
+def _names_batch(blocks, encode, methods=None, ctx=None):
+    """Either names batch with out[i] == NULL: the library allocates exactly the results."""
+    ctx = ctx or _thread_ctx()
+    L = ctx.L
+    n = len(blocks)
+    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+    dummy = np.zeros(1, dtype=np.uint8)
+    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
+    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
+    out_p = (C.c_void_p * n)()
+    out_sz = (C.c_uint * n)()
+    a, b = (C.c_uint * n)(), (C.c_uint * n)()
+    status = (C.c_int * n)()
+    if encode:
+        meth = (C.c_int * len(methods))(*methods)
+        rc = L.rans4x16_hip_tok3_encode_names_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, len(methods), meth, a, b, status)
+    else:
+        rc = L.rans4x16_hip_tok3_decode_names_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, a, status)
+    res = []
+    for i in range(n):
+        res.append(C.string_at(out_p[i], out_sz[i]) if out_p[i] and status[i] == 0 and rc >= 0 else None)
+        if out_p[i]:
+            _free(out_p[i])
+    if rc < 0:
+        raise RuntimeError("names batch failed: " + ctx.error())
+    return res, list(a), list(b), list(status)
+
+
+def tok3_encode_names_batch(blocks, level=None, methods=None, ctx=None):
+    """encode_names over a list of name blocks (bytes) in one call: (containers | None, last_starts, statuses).  The method
+    list is `methods`, or that of `level` (tok3_level_methods); nreads of block i is in container i's header."""
+    if methods is None:
+        methods = tok3_level_methods(9 if level is None else level)
+    res, last_start, _, status = _names_batch(blocks, True, methods=list(methods), ctx=ctx)
+    return res, last_start, status
+
+
+def tok3_decode_names_batch(containers, ctx=None):
+    """decode_names over a list of containers in one call: (names | None - NUL-separated, last_start bytes -, statuses)."""
+    res, _, _, status = _names_batch(containers, False, ctx=ctx)
+    return res, status
+
+
+def encode_names(block, level):
+    """The single-block drop-in symbol: bytes -> (container, last_start) or None.  The caller's buffer is a copy here, so
+    the NULs the call writes over the separators are not seen."""
+    L = _lib.load()
+    buf = C.create_string_buffer(bytes(block), max(len(block), 1))
+    out_len, last_start = C.c_int(0), C.c_int(0)
+    p = L.rans4x16_hip_tok3_encode_names(buf, len(block), int(level), 0, C.byref(out_len), C.byref(last_start))
+    if not p:
+        return None
+    res = C.string_at(p, out_len.value)
+    _free(p)
+    return res, last_start.value
+
+
+def decode_names(container):
+    """The single-block drop-in symbol: container bytes -> NUL-separated names or None."""
+    L = _lib.load()
+    buf = bytes(container)
+    out_len = C.c_uint32(0)
+    p = L.rans4x16_hip_tok3_decode_names(buf, len(buf), C.byref(out_len))
+    if not p:
+        return None
+    res = C.string_at(p, out_len.value)
+    _free(p)
+    return res
 
 
 class DeviceCodec:

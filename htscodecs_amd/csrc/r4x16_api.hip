@@ -260,6 +260,13 @@ extern "C" int rans4x16_hip_set_dev_stripe_encode(rans4x16_hip_ctx *c, int max_p
     return 0;
 }
 
+extern "C" int rans4x16_hip_set_names_chunk_blocks(rans4x16_hip_ctx *c, int blocks)
+{
+    if (!c || blocks < 0) return -1;
+    c->names_chunk_blocks = blocks;
+    return 0;
+}
+
 extern "C" const char *rans4x16_hip_last_error(const rans4x16_hip_ctx *c) { return c ? c->err.c_str() : "no context"; }
 extern "C" size_t rans4x16_hip_workspace_bytes(const rans4x16_hip_ctx *c) { return c ? c->arena[A_WS].bytes : 0; }
 
@@ -320,8 +327,9 @@ static int route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, hipStrea
     HIPCHK(c, hipEventRecord(r.ev, s));
     return 0;
 }
-static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS, R4X16_RESULT_KINDS};
-static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS, "route kinds");
+static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS, R4X16_RESULT_KINDS,
+                                               R4X16_NAMES_KINDS};
+static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS && R4X16_NAMES_KINDS <= ROUTE_KINDS, "route kinds");
 extern "C" int rans4x16_hip_route_read(rans4x16_hip_ctx *c, int which, long *counts, int n, int reset)
 {
     if (!c || which < 0 || which >= ROUTE_WHICH || n < 0 || (n && !counts)) return -1;
@@ -696,9 +704,6 @@ extern "C" int rans4x16_hip_uncompress_batch(rans4x16_hip_ctx *c, int n,
 // ---------------------------------------------------------------------------------------------
 // The five htscodecs entry points (htscodecs/rANS_static4x16.h:41-50).
 // ---------------------------------------------------------------------------------------------
-// device memory a thread's context keeps between single-block calls; a call that needed more gives it back
-#define SINGLE_CALL_KEEP ((size_t)1 << 30)
-
 static rans4x16_hip_ctx *thread_ctx()
 {
     // one context per host thread: the reference API is re-entrant from thread pools
@@ -708,6 +713,8 @@ static rans4x16_hip_ctx *thread_ctx()
     if (h.c) opts_snapshot(h.c);                   // no context argument: these calls follow the process-wide options
     return h.c;
 }
+
+rans4x16_hip_ctx *r4x16_thread_ctx() { return thread_ctx(); }
 
 // ---------------------------------------------------------------------------------------------
 // The combiner behind the single-block entry points.  A CRAM reader / writer calls rans_compress_to_4x16 or

@@ -66,7 +66,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 5
+#define ROUTE_WHICH 6
 #define ROUTE_KINDS 8
 struct HostPipe;
 void r4x16_pipe_destroy(HostPipe *);
@@ -119,6 +119,14 @@ int r4x16_tok3_pack_run(rans4x16_hip_ctx *c, int nblk, int n, const uint32_t *d_
                         uint32_t *d_out_size, int32_t *d_status,
                         int k, const int *methods, int32_t *d_chosen,
                         uint32_t max_col_size, uint64_t total_col_size, const int32_t *d_pre, bool n_on_device, hipStream_t stream);
+// the names arena of the two one-call tok3 forms under given limits (r4x16_tok3_enc.hip, r4x16_tok3_names.hip), and the
+// context behind the drop-in symbols of the calling thread (r4x16_api.hip): what the host-buffer names calls
+// (r4x16_tok3_host.hip) plan and run with
+size_t r4x16_tok3_tokenise_need(int nblk, u32 max_in_size, u32 max_names, u32 max_name_len, u64 total_in_size);
+size_t r4x16_tok3_decode_names_need(int nblk, u32 max_columns, u32 max_names, u32 max_tokens, u64 col_bytes);
+rans4x16_hip_ctx *r4x16_thread_ctx();
+// device memory a thread's context keeps between single-block calls; a call that needed more gives it back
+#define SINGLE_CALL_KEEP ((size_t)1 << 30)
 // rANS 4x8: the encode pipeline of r4x16_api.hip over a batch in chunks.  pk == nullptr && sel == nullptr: the slot call.
 // pk: results back to back at pk->out + pk->off[i].  sel: best-of-k, k <= 2 candidates per block (sel->k == 0: one, the
 // call's order / d_order), the winner into the caller's slot (pk == nullptr) or the dense arena.
@@ -147,6 +155,7 @@ struct rans4x16_hip_ctx {
     int dev_stripe_enc = 0;                 // encode with per-block orders: planes a block reserves (rans4x16_hip_set_dev_stripe_encode)
     bool in_stripe = false;                 // inside the recursive call over the internal items
     bool in_packed = false;                 // inside a packed call's slot call over its internal slots (r4x16_packed.hip)
+    int names_chunk_blocks = 0;             // host-buffer names batches: blocks per chunk at most (rans4x16_hip_set_names_chunk_blocks)
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;

@@ -1,5 +1,5 @@
 // r4x16_plan.h - the arithmetic every device call plans its arenas with: the carver that lays a layout out, the search
-// for the largest chunk of blocks that fits a budget, and the back-off when an allocation fails all the same.  Host
+// for the largest chunk of blocks that fits a budget, the cut of a batch of unequal blocks into ranges, and the back-off when an allocation fails all the same.  Host
 // only and pure: nothing here knows the context or the runtime, so a stand-alone program can check it
 // (tests/host/plan_check.cpp).  The context's side - which arenas there are, how they grow, what a call may take - is
 // r4x16_ensure / r4x16_room (r4x16_host.h).
@@ -43,6 +43,21 @@ static inline size_t r4x16_fit_chunk(size_t n, size_t limit, size_t cap, F bytes
     }
     const size_t rounds = (n + lo - 1) / lo;
     return (n + rounds - 1) / rounds;
+}
+
+// Blocks whose footprints differ (the host-buffer names batches): contiguous ranges of whole blocks, cut greedily from the
+// front.  A range takes blocks while the sum of their footprints stays within cap and their number within limit
+// (limit 0: no limit), and one block at least - a block that exceeds cap alone is a range of its own, the allocation
+// decides.  ends[r] = one past the last block of range r (ends has room for n); returns the number of ranges, 0 for n = 0.
+static inline size_t r4x16_cut_ranges(const size_t *foot, size_t n, size_t cap, size_t limit, size_t *ends)
+{
+    size_t r = 0;
+    for (size_t i = 0; i < n;) {
+        size_t sum = foot[i], j = i + 1;
+        while (j < n && (limit == 0 || j - i < limit) && sum <= cap && foot[j] <= cap - sum) sum += foot[j++];
+        ends[r++] = i = j;
+    }
+    return r;
 }
 
 // Out of memory although the plan fitted (other contexts and processes share the card): walk the batch in smaller

@@ -619,6 +619,14 @@ static size_t te_need(TeWs *w, u8 *base, size_t front, int nblk, const TeLimits 
     return te_carve(w, base, front, (size_t)nblk, l.max_names, slots, te_table_slots(l), l.max_name_len / 32u + 1u);
 }
 
+// what rans4x16_hip_tok3_tokenise_dev takes of the names arena with these limits: the host-buffer calls plan their chunks with it
+size_t r4x16_tok3_tokenise_need(int nblk, u32 max_in_size, u32 max_names, u32 max_name_len, u64 total_in_size)
+{
+    TeWs w;
+    const TeLimits l = {max_in_size, max_names, max_name_len, T3_MAX_TOKENS, T3_MAX_IDS, total_in_size, 0};
+    return te_need(&w, nullptr, 0, nblk, l);
+}
+
 // the stage; `front`: bytes at the start of the context's names arena that the caller holds
 static int te_stage(rans4x16_hip_ctx *c, int nblk, const TeIn &in, const TeOut &o, const TeLimits &l, size_t front, bool idle, hipStream_t s)
 {

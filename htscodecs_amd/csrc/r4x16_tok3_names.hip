@@ -526,6 +526,15 @@ static size_t tn_dir_carve(TnDir *d, u8 *base, size_t nblk, size_t nitems, u64 c
     return cv.total();
 }
 
+// what rans4x16_hip_tok3_decode_names_dev takes of the names arena with these limits: the host-buffer calls plan their chunks with it
+size_t r4x16_tok3_decode_names_need(int nblk, u32 max_columns, u32 max_names, u32 max_tokens, u64 col_bytes)
+{
+    TnDir d;
+    TnWs w;
+    const size_t front = tn_dir_carve(&d, nullptr, (size_t)nblk, (size_t)nblk * max_columns, col_bytes);
+    return tn_carve(&w, nullptr, front, (size_t)nblk, (size_t)((u64)nblk * tn_units(max_names, max_tokens) * 16ull));
+}
+
 extern "C" int rans4x16_hip_tok3_decode_names_dev(rans4x16_hip_ctx *c, int nblk,
                                                   const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
                                                   unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,

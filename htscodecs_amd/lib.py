@@ -122,6 +122,16 @@ SIGNATURES = {
                                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]),
+    # tok3 names with host buffers (include/rans4x16_hip.h part 2f)
+    "rans4x16_hip_tok3_level_methods": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    "rans4x16_hip_tok3_encode_names": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_int)]),
+    "rans4x16_hip_tok3_decode_names": (C.c_void_p, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rans4x16_hip_tok3_encode_names_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rans4x16_hip_tok3_decode_names_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]),
+    "rans4x16_hip_set_names_chunk_blocks": (C.c_int, [C.c_void_p, C.c_int]),
     # rANS 4x8's packed and best-of-two device-resident calls (include/rans4x8_hip.h part 2a)
     "rans4x8_hip_compress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -528,6 +528,57 @@ int rans4x16_hip_tok3_encode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
                                        uint32_t max_tokens, uint32_t max_columns, uint32_t max_col_size,
                                        uint64_t total_in_size, uint32_t search_slots, void *stream);
 
+/* ---- 2f. tok3 names with host buffers -------------------------------------------------------------
+ * encode_names / decode_names of htscodecs tokenise_name3.c (:1334-1531, :1546-1694) with HOST buffers in and out, rANS
+ * flavour (use_arith = 0): the boundary of parts 2c to 2e for a caller that holds a `char *blk` and knows none of their
+ * limits.  include/tok3_names_hip.h gives the two functions their reference names.
+ *
+ * rans4x16_hip_tok3_level_methods: the row of tokenise_name3.c:1254-1260 that `level` selects ((level - 1) / 2, clamped to
+ * 0..4), written to methods[0..k-1]; returns k (<= 9).  Pure host, usable without a GPU.
+ *
+ * rans4x16_hip_tok3_encode_names / rans4x16_hip_tok3_decode_names: the reference's two functions with the reference's
+ * ownership - a malloc'ed result the caller free()s, NULL on failure.  They are the batch calls below with nblk = 1, on the
+ * context the five rANS symbols of part 1 use for the calling thread.  encode: the method list is that of `level`;
+ * use_arith != 0 returns NULL (the reason on stderr, once per process); last_start_p may be NULL; after success every byte
+ * <= '\n' in front of last_start has been overwritten with NUL in the caller's buffer, as the reference does (:1374), and
+ * the bytes from last_start on are left alone.  decode: *out_len = last_start bytes of NUL-separated names.
+ *
+ * rans4x16_hip_tok3_encode_names_batch / rans4x16_hip_tok3_decode_names_batch: nblk independent blocks in host memory.
+ *   in[i], in_size[i]   block i: names (encode) / a container (decode); never written
+ *   out[i], out_size[i] out[i] == NULL on entry: the library malloc()s exactly the result and the caller free()s it;
+ *                       else out_size[i] is the capacity on entry.  out_size[i] is the size on return.  A result that does
+ *                       not fit reports R4X16_E_CAPACITY and nothing is written; a failed block has out_size[i] = 0 and an
+ *                       out[i] that was NULL stays NULL; its neighbours are not affected
+ *   k, methods          encode: the method list of every column, as in rans4x16_hip_tok3_pack_dev
+ *   last_start, nreads (encode), nnames (decode), status: [nblk] each, any of them may be NULL
+ * Returns the number of failed blocks, -1 if the batch could not be run (no GPU, bad arguments, no memory for a single
+ * block); nblk == 0 returns 0.
+ * Block i's bytes and status are those of rans4x16_hip_tok3_encode_names_dev / rans4x16_hip_tok3_decode_names_dev with
+ * the same method list and limits that admit the block: the library finds the limits itself.  Encode: a kernel measures
+ * the names and the longest name of every block and the host reads the maxima back (max_tokens is 128, max_columns 2048);
+ * what exceeds the device calls' hard limits (a block above 16,776,960 bytes - it is not uploaded -, a name above 16,384
+ * bytes, 2^24 names or more) is clamped, so that the device refuses that block alone with R4X16_E_UNSUPPORTED.  Decode:
+ * rans4x16_hip_tok3_scan gives each container's limits; one it refuses reports the scan's status and is not uploaded
+ * (use_arith != 0 is R4X16_E_UNSUPPORTED there); X_STRIPE columns (levels 3 and up) are decoded as after
+ * rans4x16_hip_set_dev_stripe_planes(ctx, 4, largest column), and the context's own setting is left as the caller had
+ * it.  A container whose columns and histories alone do not fit half of what the context may take (a hostile size
+ * field, as a rule) reports R4X16_E_UNSUPPORTED and is not uploaded.
+ * The batch is walked in chunks of whole blocks whose arenas fit half of max_workspace_mb and of the free memory;
+ * rans4x16_hip_set_names_chunk_blocks(ctx, n) bounds a chunk to n blocks (0, the default: by room alone) - a setter like
+ * rans4x16_hip_set_dev_stripe_planes rather than a named option.  The calls synchronise. */
+int rans4x16_hip_tok3_level_methods(int level, int *methods);
+unsigned char *rans4x16_hip_tok3_encode_names(char *blk, int len, int level, int use_arith,
+                                              int *out_len, int *last_start_p);
+unsigned char *rans4x16_hip_tok3_decode_names(unsigned char *in, uint32_t sz, uint32_t *out_len);
+int rans4x16_hip_tok3_encode_names_batch(rans4x16_hip_ctx *ctx, int nblk,
+                                         const unsigned char *const *in, const unsigned int *in_size,
+                                         unsigned char **out, unsigned int *out_size,
+                                         int k, const int *methods, unsigned int *last_start, unsigned int *nreads, int *status);
+int rans4x16_hip_tok3_decode_names_batch(rans4x16_hip_ctx *ctx, int nblk,
+                                         const unsigned char *const *in, const unsigned int *in_size,
+                                         unsigned char **out, unsigned int *out_size, unsigned int *nnames, int *status);
+int rans4x16_hip_set_names_chunk_blocks(rans4x16_hip_ctx *ctx, int blocks);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
@@ -609,7 +660,8 @@ enum {
     R4X16_ROUTE_DECODE = 1,   /* decode chain: streams per row kind (R4X16_DEC_*)                                    */
     R4X16_ROUTE_EXPAND = 2,   /* run-length expansion: blocks of the calls whose expansion kernel was that kind       */
     R4X16_ROUTE_LAUNCH = 3,   /* chain launches (encode and decode): in stream order, or classes side by side        */
-    R4X16_ROUTE_RESULT = 4    /* encode results: blocks per way they reached the caller's memory (R4X16_RESULT_*)     */
+    R4X16_ROUTE_RESULT = 4,   /* encode results: blocks per way they reached the caller's memory (R4X16_RESULT_*)     */
+    R4X16_ROUTE_NAMES = 5     /* host-buffer names batches (part 2f): chunks and blocks (R4X16_NAMES_*)                */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -635,6 +687,13 @@ enum {   /* R4X16_ROUTE_RESULT: device-resident encode calls, counted in blocks 
     R4X16_RESULT_DENSE = 1,   /* packed call, dense finish: assembled at its final offset, every byte moved once              */
     R4X16_RESULT_GATHERED = 2,/* packed call over the stripe / best-of-k routes: encoded into an internal slot, then copied    */
     R4X16_RESULT_KINDS = 3
+};
+enum {   /* R4X16_ROUTE_NAMES */
+    R4X16_NAMES_ENC_CHUNKS = 0, /* chunks run by rans4x16_hip_tok3_encode_names_batch                                   */
+    R4X16_NAMES_DEC_CHUNKS = 1, /* chunks run by rans4x16_hip_tok3_decode_names_batch                                   */
+    R4X16_NAMES_UPLOADED = 2,   /* blocks uploaded, either direction                                                   */
+    R4X16_NAMES_REFUSED = 3,    /* blocks refused before upload (above the size limit, refused by the scan)            */
+    R4X16_NAMES_KINDS = 4
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
