@@ -701,6 +701,9 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
 // The short ring (TRIP == 4, off by default) keeps chain_decode_lds' layout-2 step.
 // Headline step 146.5 -> 144.6 ms with the carried look-up alone, -> 139.4 with the 16-step trips
 // (profiles/dec_trip16.md, with the two placements that cost them 4.5 and 7 ms).
+// The step itself differs from lookup_step_pk's in two places, both written out in `issue` and `finish` below: the group
+// count takes the top field's compare as a borrow, and the pivot pick is a two-level search; with the three idle slots
+// (s_nop) of the step gone as well, a step is 67.8 instructions for 74.8 (profiles/dec_pivot.md).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 *ring, gcu8 *words, u32 words_len,
                                                 gu8 *out, u32 out_sz, u32 x, bool active, u32 lane)
@@ -751,15 +754,24 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
 
     // ---- the step, in its three pieces -----------------------------------------------------------
     // carried from a step's issue half to its finish half (across the back edge for a trip's first step)
-    u32 m = 0, GM = 0, t12 = 0, xs = 0, D0 = 0, D1 = 0, D2 = 0, D3 = 0, D4 = 0, d0 = 0, d1 = 0, d2 = 0, cb = 0, g = 0;
+    u32 m = 0, m22 = 0, GM = 0, t12 = 0, xs = 0, D0 = 0, D1 = 0, D2 = 0, D3 = 0, D4 = 0, d0 = 0, d1 = 0, d2 = 0, cb = 0, g = 0;
     // issue half of the step after one whose word requests were `wq`; the caller's bookkeeping follows, then issue_end
     auto issue = [&](u32 wq, bool adv) __attribute__((always_inline)) {
         m = x & 1023u;
         GM = GB - __umul24(m, 0x400801u);
-        const u32 gneg = __popc((rootx + GM) & GB);
-        const bool r3 = rootx < (m << 22);
-        g = (r3 ? 3u : 2u) - gneg;
-        const u32 ga = row + 16u * g;
+        m22 = m << 22;
+        // group of twelve: g = 3 - gneg - (L[36] >= m), gneg = 2 - #{L[12], L[24] < m} by the guard bits.  The top field's
+        // compare is the BORROW of the subtraction: one instruction where a select of 2 / 3 and a subtraction stood, and
+        // no idle slot - a select that names vcc as an operand has to stand two slots behind the compare, and stood one
+        // behind it.  Written out because the compiler makes a select of 0 / -1, a subtraction and an add of the C form.
+        u32 ga;
+        asm("v_cmp_ge_u32_e32 vcc, %[root], %[m22]\n\t"
+            "v_add_u32_e32 %[g], %[root], %[GM]\n\t"
+            "v_and_b32_e32 %[g], 0x200400, %[g]\n\t"
+            "v_bcnt_u32_b32 %[g], %[g], 0\n\t"
+            "v_subb_co_u32_e32 %[g], vcc, 3, %[g], vcc\n\t"
+            "v_lshl_add_u32 %[ga], %[g], 4, %[row]"
+            : [g] "=&v"(g), [ga] "=v"(ga) : [root] "v"(rootx), [m22] "v"(m22), [GM] "v"(GM), [row] "v"(row) : "vcc");
         const u32x4 Dq = *(LAS const volatile u32x4 *)(unsigned long)ga;
         D0 = Dq.x; D1 = Dq.y; D2 = Dq.z; D3 = Dq.w; D4 = *(LAS const volatile u32 *)(unsigned long)(ga + 16u);
         __builtin_amdgcn_sched_barrier(0);
@@ -781,21 +793,44 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
     // finish half, state update and renormalisation; returns the quad's word requests in bits 0..3
     auto finish = [&](auto fastc, bool live) __attribute__((always_inline)) -> u32 {
         constexpr bool FAST = decltype(fastc)::value;
-        const u32 m22 = m << 22;
-        const bool s0 = D1 < m22, s1 = D2 < m22, s2 = D3 < m22;
-        u32 D = D0, Dn = D1;
-        if (s0) { D = D1; Dn = D2; }
-        if (s1) { D = D2; Dn = D3; }
-        if (s2) { D = D3; Dn = D4; }
-        const u32 q = (u32)s0 + (u32)s1 + (u32)s2;
-        const u32 rneg = __popc((D + GM) & GB);
-        u32 tt;
-        asm("v_mad_u32_u24 %0, %1, 3, %2" : "=v"(tt) : "v"(q), "v"(t12));
-        const u32 s = tt - rneg;
+        // dword of three: the pivots L[12g + 3], L[12g + 6], L[12g + 9] are the top fields of D1, D2, D3 (top field < m <=>
+        // dword < m << 22: lookup_step_pk).  A TWO-LEVEL search - D2 first, then the middle dword of the half it chose -
+        // where lookup_step_pk compares all three and walks D, Dn through three pairs of selects: nine instructions for
+        // twelve.  The fields of a row ascend (k_dec_front builds every row from cumulative sums of the frequencies it
+        // parsed: write_row_pk, 1023 beyond the end), so the three flags are monotone and both forms choose the same dword
+        // (tests/test_dec_pivot_cpu.py).  Nothing depends on that for memory safety: q = 2 s1 + t is in 0 .. 3 for any
+        // input, as the sum of three flags is, so s, the head read and the row address keep their bounds on idle lanes
+        // that run on garbage.
+        // Written out, up to the address of the head entry, because the order matters: a compare's result can be read two
+        // slots behind it at the earliest, whether vcc is named or implied.  t has A, C in that gap; s1 has nothing that
+        // the step needs anyway (all that is independent of the group stands in ITS shadow, where it hides the read's
+        // latency), hence the one s_nop 1.  The compiler's own order of the C form has an s_nop 1 and a second wait.
+        unsigned long long tmask;
+        u32 D, Dn, B, rneg, s;
+        asm("v_cmp_lt_u32_e32 vcc, %[D2], %[m22]\n\t"                  // s1 = L[12g + 6] < m
+            "s_nop 1\n\t"
+            "v_cndmask_b32_e32 %[B], %[D1], %[D3], vcc\n\t"            // B = s1 ? D3 : D1
+            "v_cmp_lt_u32_e64 %[t], %[B], %[m22]\n\t"                  // t = the top field of B < m
+            "v_cndmask_b32_e32 %[D], %[D0], %[D2], vcc\n\t"            // A = s1 ? D2 : D0
+            "v_cndmask_b32_e32 %[Dn], %[D2], %[D4], vcc\n\t"           // C = s1 ? D4 : D2
+            "v_cndmask_b32_e64 %[D], %[D], %[B], %[t]\n\t"             // D = t ? B : A
+            "v_cndmask_b32_e64 %[s], 0, 2, vcc\n\t"
+            "v_add_u32_e32 %[rneg], %[D], %[GM]\n\t"
+            "v_cndmask_b32_e64 %[Dn], %[B], %[Dn], %[t]\n\t"           // Dn = t ? C : B
+            "v_and_b32_e32 %[rneg], 0x200400, %[rneg]\n\t"
+            "v_addc_co_u32_e64 %[s], vcc, %[s], 0, %[t]\n\t"           // q = 2 s1 + t
+            "v_bcnt_u32_b32 %[rneg], %[rneg], 0\n\t"                   // 2 - #{L[3q + 1], L[3q + 2] below m}
+            "v_mad_u32_u24 %[s], %[s], 3, %[t12]\n\t"
+            "v_sub_u32_e32 %[s], %[s], %[rneg]\n\t"
+            "v_lshl_add_u32 %[B], %[s], 3, %[imga]"                     // the head entry of s
+            : [D] "=&v"(D), [Dn] "=&v"(Dn), [B] "=&v"(B), [rneg] "=&v"(rneg), [s] "=&v"(s), [t] "=&s"(tmask)
+            : [D0] "v"(D0), [D1] "v"(D1), [D2] "v"(D2), [D3] "v"(D3), [D4] "v"(D4), [m22] "v"(m22), [GM] "v"(GM),
+              [t12] "v"(t12), [imga] "v"(imga) : "vcc");
         // the head entry of the symbol just decoded: the root of ITS row and its alpha word, one 8-byte read, at once
-        const u32x2 h = *(LAS const volatile u32x2 *)(unsigned long)(imga + 8u * s);
+        const u32x2 h = *(LAS const volatile u32x2 *)(unsigned long)B;
         __builtin_amdgcn_sched_barrier(0);
-        const u32 r11 = 22u - 11u * rneg;
+        u32 r11;                                          // 22 - 11 rneg (rneg comes out of an asm: the compiler no longer
+        asm("v_mad_i32_i24 %0, %1, -11, 22" : "=v"(r11) : "v"(rneg));     //  knows it small and would multiply in 64 bits)
         const u32 P = (D << 11) | (D >> 22);
         const u32 Cc = (D & 0x003fffffu) | (Dn & 0xffc00000u);
         const u32 prev = __builtin_amdgcn_ubfe(P, r11, 10);
@@ -816,8 +851,8 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
         const bool take = FAST ? want : (want && cursor + pre < nwords);
         const u32 wlo = __builtin_amdgcn_alignbyte(d1, d0, cb), whi = __builtin_amdgcn_alignbyte(d2, d1, cb);
         const u32 w = __builtin_amdgcn_perm(whi, wlo, __umul24(pre, 0x0202u) + 0x0c0c0100u);
-        u32 xr = (x << 16) | w;
-        asm volatile("" : "+v"(xr));
+        // (no empty asm on xr: it was followed by its reader, and the compiler pads every asm that far with an s_nop)
+        const u32 xr = (x << 16) | w;
         x = take ? xr : x;
         return wq;
     };
