@@ -14,6 +14,7 @@ from .codec import (  # noqa: F401
     compress_batch, compress_best_batch, uncompress_batch, DeviceCodec, MultiCodec,
     rans_compress, rans_uncompress, compress_batch_4x8, uncompress_batch_4x8,
     tok3_level_methods, tok3_encode_names_batch, tok3_decode_names_batch, encode_names, decode_names,
+    arith_uncompress, arith_uncompress_batch,
 )
 
 __all__ = [
@@ -22,4 +23,5 @@ __all__ = [
     "compress_batch", "compress_best_batch", "uncompress_batch", "DeviceCodec", "MultiCodec",
     "rans_compress", "rans_uncompress", "compress_batch_4x8", "uncompress_batch_4x8",
     "tok3_level_methods", "tok3_encode_names_batch", "tok3_decode_names_batch", "encode_names", "decode_names",
+    "arith_uncompress", "arith_uncompress_batch",
 ]

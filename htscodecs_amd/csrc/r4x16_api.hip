@@ -110,7 +110,7 @@ extern "C" const char *rans4x16_hip_option_name(int index) { return index >= 0 &
 
 // ---- the context's arenas (r4x16_host.h) -----------------------------------------------------------------------
 static const char *const ARENA_NAME[A_COUNT] = {"workspace", "staging arena", "stripe / candidate arena", "packed calls' slot arena",
-                                                "tok3 arena", "tok3 names arena"};
+                                                "tok3 arena", "tok3 names arena", "arith arena"};
 
 static void arena_release(rans4x16_hip_ctx *c, unsigned mask)
 {
@@ -302,6 +302,8 @@ static int route_fold(rans4x16_hip_ctx *c)
     int rc = 0;
     for (auto &r : c->route_pending) {
         if (hipEventSynchronize(r.ev) != hipSuccess) rc = -1;
+        else if (r.which == R4X16_ROUTE_ARITH)
+            for (int k = 0; k < R4X16_ARITH_KINDS; k++) c->route[r.which][k] += (long)r.cnt[k];   // counted per kind on the device
         else
             for (u32 ci = 0; ci < CLS_MAX; ci++) {
                 int freq_table = 0;
@@ -315,21 +317,23 @@ static int route_fold(rans4x16_hip_ctx *c)
     c->route_pending.clear();
     return rc;
 }
-static int route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, hipStream_t s)
+int r4x16_route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words, hipStream_t s)
 {
+    if (words > CLS_MAX) { c->err = "route read-out: too many counters"; return -1; }
     if (c->route_pending.size() >= 64 && route_fold(c) != 0) { c->err = "route read-out: a counted launch failed"; return -1; }
     RouteSnap r{which, nullptr, nullptr};
     HIPCHK(c, hipHostMalloc((void **)&r.cnt, CLS_MAX * sizeof(u32), hipHostMallocDefault));
     memset(r.cnt, 0, CLS_MAX * sizeof(u32));
     if (hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(r.cnt); c->err = "route read-out: no event"; return -1; }
     c->route_pending.push_back(r);
-    HIPCHK(c, hipMemcpyAsync(r.cnt, d_cnt + SCHED_COUNT, CLS_MAX * sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(r.cnt, d_cnt, words * sizeof(u32), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipEventRecord(r.ev, s));
     return 0;
 }
 static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS, R4X16_RESULT_KINDS,
-                                               R4X16_NAMES_KINDS};
-static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS && R4X16_NAMES_KINDS <= ROUTE_KINDS, "route kinds");
+                                               R4X16_NAMES_KINDS, R4X16_ARITH_KINDS};
+static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS && R4X16_NAMES_KINDS <= ROUTE_KINDS &&
+              R4X16_ARITH_KINDS <= ROUTE_KINDS && R4X16_ARITH_KINDS <= CLS_MAX, "route kinds");
 extern "C" int rans4x16_hip_route_read(rans4x16_hip_ctx *c, int which, long *counts, int n, int reset)
 {
     if (!c || which < 0 || which >= ROUTE_WHICH || n < 0 || (n && !counts)) return -1;
@@ -543,7 +547,7 @@ int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64
         r4x16_launch_enc_chain(&w, 3 * nb, s, fk, &c->opts, &c->hint[0]);
         if (c->timing) time_end(c, 0, s, t);
         if (c->opts.v[OPT_ROUTE_COUNT]) {
-            if (route_snap(c, 0, w.sched.cnt, s) != 0) return -1;
+            if (r4x16_route_snap(c, 0, w.sched.cnt + SCHED_COUNT, CLS_MAX, s) != 0) return -1;
             c->route[3][fk ? R4X16_LAUNCH_SIDE_BY_SIDE : R4X16_LAUNCH_IN_ORDER]++;
             if (pk) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_DENSE] += nb;
         }
@@ -640,7 +644,7 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
         r4x16_launch_dec_chain(&w, 2 * nb, s, fk, &c->opts, &c->hint[1]);
         if (c->timing) time_end(c, 1, s, t);
         if (c->opts.v[OPT_ROUTE_COUNT]) {
-            if (route_snap(c, 1, w.sched.cnt, s) != 0) return -1;
+            if (r4x16_route_snap(c, 1, w.sched.cnt + SCHED_COUNT, CLS_MAX, s) != 0) return -1;
             c->route[3][fk ? R4X16_LAUNCH_SIDE_BY_SIDE : R4X16_LAUNCH_IN_ORDER]++;
         }
         const int wg = r4x16_launch_dec_back(&a, &w, (int)base, nb, s, &c->opts);

@@ -66,7 +66,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 6
+#define ROUTE_WHICH 7
 #define ROUTE_KINDS 8
 struct HostPipe;
 void r4x16_pipe_destroy(HostPipe *);
@@ -81,6 +81,7 @@ enum R4Arena {
     A_PS,        // the packed calls' internal bound-sized slots and layout arrays (r4x16_packed.hip)
     A_T3,        // tok3 containers: the winners waiting to be framed / the directory of the columns to decode (r4x16_tok3.hip)
     A_TN,        // tok3 names: the names' histories; for the one-call form the columns in front of them (r4x16_tok3_names.hip)
+    A_AR,        // arith_dynamic decoding: items, stage arena, the order-1 rows that do not fit LDS (r4x16_arith.hip)
     A_COUNT
 };
 #define A_BIT(a) (1u << (a))
@@ -95,6 +96,8 @@ void r4x16_trim(rans4x16_hip_ctx *c, size_t keep);
 // stream ordering of a context's arenas (workspace, stripe arena) between calls on different streams: r4x16_api.hip
 int r4x16_ws_order_begin(rans4x16_hip_ctx *c, hipStream_t s);
 int r4x16_ws_order_end(rans4x16_hip_ctx *c, hipStream_t s);
+// route read-out: a copy of `words` device counters of list `which` behind what `s` holds, folded when the route is read
+int r4x16_route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words, hipStream_t s);
 int r4x16_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, int order, uint32_t max_in_size, hipStream_t s);
 // best-of-k and X_STRIPE under per-block orders (r4x16_best.hip); what they ask of r4x16_api.hip
 int r4x16_orders_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint64_t total_in_size,

@@ -132,6 +132,16 @@ SIGNATURES = {
     "rans4x16_hip_tok3_decode_names_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p]),
     "rans4x16_hip_set_names_chunk_blocks": (C.c_int, [C.c_void_p, C.c_int]),
+    # arith_dynamic decoding (include/rans4x16_hip.h part 2g)
+    "rans4x16_hip_arith_uncompress_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "rans4x16_hip_arith_peek_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rans4x16_hip_arith_uncompress_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
+    "rans4x16_hip_arith_uncompress_to": (C.c_void_p, [C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_uint)]),
+    "rans4x16_hip_arith_uncompress": (C.c_void_p, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint)]),
     # rANS 4x8's packed and best-of-two device-resident calls (include/rans4x8_hip.h part 2a)
     "rans4x8_hip_compress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

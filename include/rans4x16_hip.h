@@ -579,6 +579,62 @@ int rans4x16_hip_tok3_decode_names_batch(rans4x16_hip_ctx *ctx, int nblk,
                                          unsigned char **out, unsigned int *out_size, unsigned int *nnames, int *status);
 int rans4x16_hip_set_names_chunk_blocks(rans4x16_hip_ctx *ctx, int blocks);
 
+/* ---- 2g. arith_dynamic decoding (the CRAM 3.1 adaptive arithmetic coder) ---------------------------------------
+ * htscodecs/arith_dynamic.c's decoder on the device: one carry-less range coder and adaptive models per stream (order 0,
+ * order 1, with or without the coder's own run lengths), inside the containers of rANS 4x16 (X_PACK, X_CAT, X_NOSZ,
+ * X_STRIPE).  Decoding only: there is no arith encoder here yet, and tok3 containers with use_arith = 1 stay
+ * R4X16_E_UNSUPPORTED (parts 2c-2f).  A stream is one serial chain of dependent steps: one wave decodes it, so a
+ * batch wants many streams.
+ *
+ * rans4x16_hip_arith_uncompress_dev has the arguments and the contract of rans4x16_hip_uncompress_dev_sized: it only
+ * enqueues on `stream`, reads nothing back, writes d_out_size / d_status per block and nothing outside a block's slot
+ * [d_out_off[i], d_out_off[i] + d_out_cap[i]).  d_out_cap[i] is the capacity the reference's arith_uncompress_to is
+ * given (and the size of a bare X_NOSZ stream).  Statuses, as the reference returns NULL:
+ *   R4X16_E_EMPTY        a zero-length block
+ *   R4X16_E_TRUNCATED    the input ends inside the header, the X_PACK map or an X_CAT payload; stripe lengths beyond it
+ *   R4X16_E_SIZE         a size of INT_MAX or more; a plane length of 0; a plane that gives another size than its share;
+ *                        packed bytes that cannot fill the stored size
+ *   R4X16_E_CAPACITY     the stored size is above the capacity; for an X_STRIPE block, not equal to it (as for rANS);
+ *                        a packed size above the stored size
+ *   R4X16_E_UNSUPPORTED  X_EXT (bzip2), as a reference built without libbz2; a block above max_in_size (not read) or a
+ *                        size above max_out_size; in a batch that decodes to more than total_out_size (0: n x max_out_size)
+ *                        the blocks that no longer fit - several, and not necessarily the last ones
+ * Deviations from the reference, on malformed input only: a plane that is itself an X_STRIPE stream, and a stripe block
+ * with more planes or a larger size than rans4x16_hip_set_dev_stripe_planes reserved (0 planes, the default: every
+ * stripe block), report R4X16_E_UNSUPPORTED; N = 0 with a size above 0 reports R4X16_E_SIZE (the reference does not
+ * return from it).  An accepted damaged stream decodes to the reference's bytes: the core decoders never refuse.
+ * Returns 0 if enqueued, -1 on argument / allocation errors.
+ *
+ * rans4x16_hip_arith_peek_dev: flag byte and stored size per block; the two lie where rANS 4x16 has them, so this is
+ * rans4x16_hip_peek_dev's reader with its statuses.
+ *
+ * rans4x16_hip_arith_uncompress_batch: host buffers - out_size[i] holds the capacity of out[i] on entry and the size on
+ * return, status[i] the code.  One upload, the device call on the context's own stream, one download; it is not
+ * pipelined, and it synchronises.  Stripe blocks are decoded whatever the context's stripe setting, which is put back.
+ * Returns the number of blocks refused, -1 on errors.
+ *
+ * rans4x16_hip_arith_uncompress_to / rans4x16_hip_arith_uncompress: the arguments and the ownership of the reference's
+ * arith_uncompress_to / arith_uncompress (out == NULL: a malloc'd buffer of the stream's stored size, the caller's to
+ * free; NULL on failure), on the calling thread's context.  include/arith_dynamic_hip.h gives them the reference's names.
+ *
+ * Route read-out: R4X16_ROUTE_ARITH counts the entropy-coded streams (a stripe block's planes each) by where their models
+ * live: R4X16_ARITH_O0, R4X16_ARITH_O1_LDS, R4X16_ARITH_O1_GLOBAL; those with run lengths count under R4X16_ARITH_RLE too. */
+int rans4x16_hip_arith_uncompress_dev(rans4x16_hip_ctx *ctx, int n,
+                                      const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                      unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                      uint32_t *d_out_size, int32_t *d_status,
+                                      uint32_t max_in_size, uint32_t max_out_size, uint64_t total_out_size, void *stream);
+int rans4x16_hip_arith_peek_dev(rans4x16_hip_ctx *ctx, int n,
+                                const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                int32_t *d_format, uint32_t *d_raw_size, int32_t *d_status,
+                                uint32_t max_in_size, void *stream);
+int rans4x16_hip_arith_uncompress_batch(rans4x16_hip_ctx *ctx, int n,
+                                        const unsigned char *const *in, const unsigned int *in_size,
+                                        unsigned char *const *out, unsigned int *out_size, int *status);
+unsigned char *rans4x16_hip_arith_uncompress_to(unsigned char *in, unsigned int in_size,
+                                                unsigned char *out, unsigned int *out_size);
+unsigned char *rans4x16_hip_arith_uncompress(unsigned char *in, unsigned int in_size, unsigned int *out_size);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
@@ -661,7 +717,8 @@ enum {
     R4X16_ROUTE_EXPAND = 2,   /* run-length expansion: blocks of the calls whose expansion kernel was that kind       */
     R4X16_ROUTE_LAUNCH = 3,   /* chain launches (encode and decode): in stream order, or classes side by side        */
     R4X16_ROUTE_RESULT = 4,   /* encode results: blocks per way they reached the caller's memory (R4X16_RESULT_*)     */
-    R4X16_ROUTE_NAMES = 5     /* host-buffer names batches (part 2f): chunks and blocks (R4X16_NAMES_*)                */
+    R4X16_ROUTE_NAMES = 5,    /* host-buffer names batches (part 2f): chunks and blocks (R4X16_NAMES_*)                */
+    R4X16_ROUTE_ARITH = 6     /* arith_dynamic decoding (part 2g): streams per home of their models (R4X16_ARITH_*)    */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -694,6 +751,13 @@ enum {   /* R4X16_ROUTE_NAMES */
     R4X16_NAMES_UPLOADED = 2,   /* blocks uploaded, either direction                                                   */
     R4X16_NAMES_REFUSED = 3,    /* blocks refused before upload (above the size limit, refused by the scan)            */
     R4X16_NAMES_KINDS = 4
+};
+enum {   /* R4X16_ROUTE_ARITH: entropy-coded streams of rans4x16_hip_arith_uncompress_dev */
+    R4X16_ARITH_O0 = 0,         /* order 0: the model in registers                                                     */
+    R4X16_ARITH_O1_LDS = 1,     /* order 1, the rows in LDS                                                            */
+    R4X16_ARITH_O1_GLOBAL = 2,  /* order 1, the rows in the context's arena in global memory                           */
+    R4X16_ARITH_RLE = 3,        /* those of the three above that carry run lengths (counted there too)                 */
+    R4X16_ARITH_KINDS = 4
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
