@@ -1047,8 +1047,9 @@ extern "C" int rans4x8_hip_uncompress_dev(rans4x16_hip_ctx *c, int n,
     return r4x16_ws_order_end(c, s);
 }
 
-// host buffers: one staging pass (copy in, kernels, sizes back, copy out) on the context's stream
-static int run_host8(rans4x16_hip_ctx *c, int n, bool decode,
+// host buffers: the argument check of the 4x8 calls, then one staging pass on the context's stream (r4x16_run_slab) -
+// never the pipeline or the stripe routes
+static int host8_checked(rans4x16_hip_ctx *c, int n, bool decode,
                      const unsigned char *const *in, const unsigned int *in_size,
                      unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
 {
@@ -1056,61 +1057,18 @@ static int run_host8(rans4x16_hip_ctx *c, int n, bool decode,
     if (n <= 0) return n == 0 ? 0 : -1;
     if (!in || !in_size || !out || !out_size) { c->err = "rans4x8 batch: bad arguments"; return -1; }
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    std::vector<u64> in_off(n), out_off(n);
-    std::vector<u32> cap(n);
-    std::vector<i32> ord(n);
-    size_t in_tot = 0, out_tot = 0;
-    u32 max_in = 0;
-    for (int i = 0; i < n; i++) {
-        in_off[i] = in_tot; in_tot += align_up((size_t)in_size[i] + 16, 256);
-        cap[i] = out_size[i];
-        out_off[i] = out_tot; out_tot += align_up((size_t)cap[i] + 16, 256);
-        if (in_size[i] > max_in) max_in = in_size[i];
-        ord[i] = order ? order[i] : 0;
-    }
-    const size_t arr = align_up((size_t)n * 8, 256);
-    if (r4x16_ensure(c, A_STAGE, in_tot + out_tot + 6 * arr, true) != 0) return -1;
-    u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
-    u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
-    u32 *d_in_size = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
-    i32 *d_status = (i32 *)(meta + 5 * arr), *d_order = (i32 *)(meta + 5 * arr + arr / 2);
-    for (int i = 0; i < n; i++)
-        if (in_size[i]) HIPCHK(c, hipMemcpyAsync(d_in + in_off[i], in[i], in_size[i], hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_in_off, in_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_out_off, out_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_in_size, in_size, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_cap, cap.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_order, ord.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    const int rc = decode ? rans4x8_hip_uncompress_dev(c, n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_cap, d_osz, d_status, s)
-                          : rans4x8_hip_compress_dev(c, n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_cap, d_osz, d_status,
-                                                     0, d_order, max_in, s);
-    if (rc != 0) return -1;
-    std::vector<u32> osz(n);
-    std::vector<i32> st(n);
-    HIPCHK(c, hipMemcpyAsync(osz.data(), d_osz, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(st.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    int failed = 0;
-    for (int i = 0; i < n; i++) {
-        if (status) status[i] = st[i];
-        if (st[i] != 0) { out_size[i] = 0; failed++; continue; }
-        out_size[i] = osz[i];
-        if (osz[i]) HIPCHK(c, hipMemcpyAsync(out[i], d_out + out_off[i], osz[i], hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(c, hipStreamSynchronize(s));
-    return failed;
+    return r4x16_run_slab(c, n, decode, true, in, in_size, out, out_size, order, status);
 }
 
 extern "C" int rans4x8_hip_compress_batch(rans4x16_hip_ctx *c, int n, const unsigned char *const *in, const unsigned int *in_size,
                                           unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
 {
-    return run_host8(c, n, false, in, in_size, out, out_size, order, status);
+    return host8_checked(c, n, false, in, in_size, out, out_size, order, status);
 }
 extern "C" int rans4x8_hip_uncompress_batch(rans4x16_hip_ctx *c, int n, const unsigned char *const *in, const unsigned int *in_size,
                                             unsigned char *const *out, unsigned int *out_size, int *status)
 {
-    return run_host8(c, n, true, in, in_size, out, out_size, nullptr, status);
+    return host8_checked(c, n, true, in, in_size, out, out_size, nullptr, status);
 }
 
 // htscodecs/rANS_static.h:41-44: malloc'd results, NULL on failure
@@ -1125,7 +1083,7 @@ extern "C" unsigned char *rans_compress(unsigned char *in, unsigned int in_size,
     unsigned char *outs[1] = { out };
     unsigned int isz[1] = { in_size };
     int ord[1] = { order ? 1 : 0 };
-    const int rc = run_host8(c, 1, false, ins, isz, outs, &cap, ord, nullptr);
+    const int rc = host8_checked(c, 1, false, ins, isz, outs, &cap, ord, nullptr);
     r4x16_trim(c, SINGLE_CALL_KEEP);
     if (rc != 0) { free(out); return nullptr; }
     *out_size = cap;
@@ -1149,7 +1107,7 @@ extern "C" unsigned char *rans_uncompress(unsigned char *in, unsigned int in_siz
     const unsigned char *ins[1] = { in };
     unsigned char *outs[1] = { out };
     unsigned int isz[1] = { in_size };
-    const int rc = run_host8(c, 1, true, ins, isz, outs, &usz, nullptr, nullptr);
+    const int rc = host8_checked(c, 1, true, ins, isz, outs, &usz, nullptr, nullptr);
     r4x16_trim(c, SINGLE_CALL_KEEP);
     if (rc != 0) { free(out); return nullptr; }
     *out_size = usz;

@@ -460,53 +460,40 @@ extern "C" int rans4x16_hip_arith_uncompress_batch(rans4x16_hip_ctx *c, int n,
     // the host walk refuses what the device walk would refuse, before anything is uploaded, and gives the stripe limits
     std::vector<u64> in_off(n), out_off(n);
     std::vector<u32> isz(n, 0), cap(n, 0);
-    u64 in_total = 0, out_total = 0;
     u32 max_in = 0, max_out = 0, planes = 0, stripe_out = 0;
     for (int i = 0; i < n; i++) {
         ArHostSrc src{in[i]};
         ArTop top;
         ArNoSink sink;
         status[i] = in[i] && out[i] ? ar_parse(src, in_size[i], out_size[i], 255u, 0xffffffffu, &top, sink) : R4X16_E_UNSUPPORTED;
-        in_off[i] = in_total; out_off[i] = out_total;
         if (status[i] != AR_OK) { out_size[i] = 0; continue; }
         isz[i] = in_size[i]; cap[i] = out_size[i];
-        in_total += ((u64)isz[i] + 15u) & ~15ull; out_total += ((u64)cap[i] + 15u) & ~15ull;
         max_in = std::max(max_in, isz[i]); max_out = std::max(max_out, cap[i]);
         if (top.nplanes) { planes = std::max(planes, top.nplanes); stripe_out = std::max(stripe_out, top.out_size); }
     }
+    // slots of the size rounded up to 16; a refused block (size 0) takes none, its offsets are its successor's
+    const size_t in_total = r4x16_stage_slots(isz.data(), (size_t)n, 0, 16, in_off.data());
+    const size_t out_total = r4x16_stage_slots(cap.data(), (size_t)n, 0, 16, out_off.data());
     if (in_total == 0) return n;                                     // nothing was accepted
-    // staging: input bytes, output bytes, the six arrays
-    Carver cv(nullptr);
-    auto lay = [&](Carver &v, u8 **din, u8 **dout, u64 **dio, u64 **doo, u32 **dis, u32 **dcap, u32 **dos, i32 **dst) {
-        *din = v.take<u8>(in_total + 16); *dout = v.take<u8>(out_total + 16);
-        *dio = v.take<u64>(n); *doo = v.take<u64>(n); *dis = v.take<u32>(n); *dcap = v.take<u32>(n); *dos = v.take<u32>(n); *dst = v.take<i32>(n);
-    };
-    u8 *din, *dout; u64 *dio, *doo; u32 *dis, *dcap, *dos; i32 *dst;
-    lay(cv, &din, &dout, &dio, &doo, &dis, &dcap, &dos, &dst);
-    if (r4x16_ensure(c, A_STAGE, cv.total(), true) != 0) return -1;
-    Carver cv2(c->at(A_STAGE));
-    lay(cv2, &din, &dout, &dio, &doo, &dis, &dcap, &dos, &dst);
+    hipStream_t s = c->stream;
+    StageLayout L;
+    if (r4x16_stage_begin(c, &L, (size_t)n, in_total + 16, 0, out_total + 16, 0,
+                          {in_off.data(), out_off.data(), isz.data(), cap.data(), nullptr}, s) != 0)
+        return -1;
     std::vector<u8> up(in_total);
     for (int i = 0; i < n; i++) if (isz[i]) memcpy(up.data() + in_off[i], in[i], isz[i]);
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(din, up.data(), in_total, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dio, in_off.data(), 8ull * n, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(doo, out_off.data(), 8ull * n, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dis, isz.data(), 4ull * n, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dcap, cap.data(), 4ull * n, hipMemcpyHostToDevice, s));
-    const int keep_planes = c->dev_stripe_planes;
-    const unsigned int keep_out = c->dev_stripe_out;
-    c->dev_stripe_planes = (int)planes; c->dev_stripe_out = stripe_out;
-    const int rc = rans4x16_hip_arith_uncompress_dev(c, n, din, dio, dis, dout, doo, dcap, dos, dst, max_in, max_out, out_total, s);
-    c->dev_stripe_planes = keep_planes; c->dev_stripe_out = keep_out;
-    if (rc != 0) return -1;
+    HIPCHK(c, hipMemcpyAsync(L.in, up.data(), in_total, hipMemcpyHostToDevice, s));
+    {
+        StripeLimits limits(c, (int)planes, stripe_out);
+        if (rans4x16_hip_arith_uncompress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
+                                              max_in, max_out, out_total, s) != 0)
+            return -1;
+    }
     std::vector<u8> down(out_total);
     std::vector<u32> osz(n);
     std::vector<i32> dstat(n);
-    HIPCHK(c, hipMemcpyAsync(down.data(), dout, out_total, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(osz.data(), dos, 4ull * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(dstat.data(), dst, 4ull * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipMemcpyAsync(down.data(), L.out, out_total, hipMemcpyDeviceToHost, s));
+    if (r4x16_stage_verdicts(c, L, (size_t)n, osz.data(), dstat.data(), s) != 0) return -1;
     int bad = 0;
     for (int i = 0; i < n; i++) {
         if (isz[i]) {                                                // (a block the host walk refused was uploaded as an empty one)

@@ -22,6 +22,7 @@
 #include "r4x16_dev.h"
 #include "r4x16_sched.h"
 #include "r4x16_plan.h"
+#include "r4x16_stage.h"
 
 extern "C" {
 void r4x16_launch_dec_front(const BatchArgs *, const DecWs *, int, int, hipStream_t, const R4Opts *);
@@ -138,6 +139,17 @@ int r4x8_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, hipStre
 int r4x16_run_host_batch(rans4x16_hip_ctx *c, int n, bool decode,
                           const unsigned char *const *in, const unsigned int *in_size,
                           unsigned char *const *out, unsigned int *out_size, const int *order, int *status);
+// The host-buffer calls' staging arena (A_STAGE, laid out by r4x16_stage.h; r4x16_host.hip).  begin: the arena for a batch
+// of `items`, and the host arrays on their way up on `s` in this order (order == nullptr: the layout has no order array).
+// verdicts: the result sizes and statuses back in osz / status, and `s` waited for.  Payload moves at each site's own.
+struct StageArrays { const u64 *in_off, *out_off; const u32 *in_size, *cap; const i32 *order; };
+int r4x16_stage_begin(rans4x16_hip_ctx *c, StageLayout *L, size_t items, size_t in_bytes, size_t plane_bytes, size_t out_bytes,
+                      size_t pk_count, const StageArrays &h, hipStream_t s);
+int r4x16_stage_verdicts(rans4x16_hip_ctx *c, const StageLayout &L, size_t items, u32 *osz, i32 *status, hipStream_t s);
+// one staging pass (copy in, the device calls, sizes back, copy out) on the context's stream; x8: the rANS 4x8 calls
+int r4x16_run_slab(rans4x16_hip_ctx *c, int n, bool decode, bool x8,
+                   const unsigned char *const *in, const unsigned int *in_size,
+                   unsigned char *const *out, unsigned int *out_size, const int *order, int *status);
 
 struct rans4x16_hip_ctx {
     int device = 0;
@@ -174,6 +186,22 @@ struct rans4x16_hip_ctx {
     // route read-out (rans4x16_hip_route_read): counts folded so far, and the launches' copies not yet folded
     long route[ROUTE_WHICH][ROUTE_KINDS] = {};
     std::vector<RouteSnap> route_pending;
+};
+
+// The X_STRIPE limits of the device-resident decode calls (rans4x16_hip_set_dev_stripe_planes) for one call made on the
+// caller's behalf: set here, and the caller's own put back when the scope ends, whichever way it ends.
+struct StripeLimits {
+    rans4x16_hip_ctx *c;
+    int planes;
+    unsigned int out;
+    StripeLimits(rans4x16_hip_ctx *c_, int planes_, unsigned int out_) : c(c_), planes(c_->dev_stripe_planes), out(c_->dev_stripe_out)
+    {
+        c->dev_stripe_planes = planes_;
+        c->dev_stripe_out = out_;
+    }
+    ~StripeLimits() { c->dev_stripe_planes = planes; c->dev_stripe_out = out; }
+    StripeLimits(const StripeLimits &) = delete;
+    StripeLimits &operator=(const StripeLimits &) = delete;
 };
 
 #define HIPCHK(ctx, call)                                                                   \

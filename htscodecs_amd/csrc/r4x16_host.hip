@@ -9,91 +9,50 @@
 // ---------------------------------------------------------------------------------------------
 // (staging sizes come from the caller's arrays, and through the out == NULL decode entry from a size field of the stream
 //  itself: r4x16_ensure refuses more than half of the free memory - hostile input must not exhaust the device)
-static int stripe_compress_many(rans4x16_hip_ctx *, const std::vector<int> &, const unsigned char *const *, const unsigned int *,
-                                unsigned char *const *, unsigned int *, const int *, int *);
-static int stripe_uncompress_many(rans4x16_hip_ctx *, const std::vector<int> &, const unsigned char *const *, const unsigned int *,
-                                  unsigned char *const *, unsigned int *, int *);
-
-static int stripe_many_dev(rans4x16_hip_ctx *, bool, const std::vector<int> &, const unsigned char *const *, const unsigned int *,
-                           unsigned char *const *, unsigned int *, const int *, int *);
-static int run_plain_batch(rans4x16_hip_ctx *c, int n, bool decode,
-                           const unsigned char *const *in, const unsigned int *in_size,
-                           unsigned char *const *out, unsigned int *out_size, const int *order, int *status);
-
 static bool is_stripe(bool decode, const unsigned char *in, unsigned int in_size, int order)
 {
     if (decode) return in_size > 0 && (in[0] & X_STRIPE);
     return (order & X_STRIPE) && in_size > 20;                         // :1151
 }
 
-int r4x16_run_host_batch(rans4x16_hip_ctx *c, int n, bool decode,
-                          const unsigned char *const *in, const unsigned int *in_size,
-                          unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
+// The staging arena of one batch, and what comes back from it (r4x16_host.h)
+int r4x16_stage_begin(rans4x16_hip_ctx *c, StageLayout *L, size_t items, size_t in_bytes, size_t plane_bytes, size_t out_bytes,
+                      size_t pk_count, const StageArrays &h, hipStream_t s)
 {
-    if (!c) return -1;
-    if (n <= 0) return n == 0 ? 0 : -1;
-    HIPCHK(c, hipSetDevice(c->device));
-    // stripe blocks are expanded into one device batch of all their planes (and candidate methods)
-    std::vector<int> plain, striped;
-    int failed = 0;
-    for (int i = 0; i < n; i++) {
-        const int o = order ? order[i] : 0;
-        if (is_stripe(decode, in[i], in_size[i], o)) striped.push_back(i); else plain.push_back(i);
-    }
-    if (!striped.empty()) {
-        std::vector<int> sst(striped.size(), 0);
-        const bool dev_route = c->opts.v[OPT_HOST_STRIPE_DEV] != 0;
-        const int rc = dev_route ? stripe_many_dev(c, decode, striped, in, in_size, out, out_size, order, sst.data())
-                     : decode ? stripe_uncompress_many(c, striped, in, in_size, out, out_size, sst.data())
-                              : stripe_compress_many(c, striped, in, in_size, out, out_size, order, sst.data());
-        if (rc < 0) return -1;
-        for (size_t k = 0; k < striped.size(); k++) {
-            const int i = striped[k];
-            // decode: the status a device-resident call reports (a plane's own verdict included); encode: SIZE as before
-            if (status) status[i] = !sst[k] ? 0 : decode ? sst[k] : R4X16_E_SIZE;
-            if (sst[k]) { out_size[i] = 0; failed++; }
-        }
-    }
-    if (plain.empty()) return failed;
-    if ((int)plain.size() == n) {
-        const int f = run_plain_batch(c, n, decode, in, in_size, out, out_size, order, status);
-        return f < 0 ? -1 : failed + f;
-    }
-    const int m = (int)plain.size();
-    std::vector<const unsigned char *> pin(m);
-    std::vector<unsigned char *> pout(m);
-    std::vector<unsigned int> pis(m), pos(m);
-    std::vector<int> pord(m), pst(m);
-    for (int k = 0; k < m; k++) {
-        const int i = plain[k];
-        pin[k] = in[i]; pout[k] = out[i]; pis[k] = in_size[i]; pos[k] = out_size[i]; pord[k] = order ? order[i] : 0;
-    }
-    const int f = run_plain_batch(c, m, decode, pin.data(), pis.data(), pout.data(), pos.data(), pord.data(), pst.data());
-    if (f < 0) return -1;
-    for (int k = 0; k < m; k++) {
-        out_size[plain[k]] = pos[k];
-        if (status) status[plain[k]] = pst[k];
-    }
-    return failed + f;
+    const size_t total = r4x16_stage_layout(L, nullptr, items, in_bytes, plane_bytes, out_bytes, h.order != nullptr, pk_count);
+    if (r4x16_ensure(c, A_STAGE, total, true) != 0) return -1;
+    r4x16_stage_layout(L, c->at(A_STAGE), items, in_bytes, plane_bytes, out_bytes, h.order != nullptr, pk_count);
+    HIPCHK(c, hipMemcpyAsync(L->in_off, h.in_off, items * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(L->out_off, h.out_off, items * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(L->in_size, h.in_size, items * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(L->cap, h.cap, items * 4, hipMemcpyHostToDevice, s));
+    if (h.order) HIPCHK(c, hipMemcpyAsync(L->order, h.order, items * 4, hipMemcpyHostToDevice, s));
+    return 0;
 }
 
-// One slab of blocks: copy in, run the device path, copy out, all on the context's own stream.
-static int run_slab(rans4x16_hip_ctx *c, int n, bool decode,
-                    const unsigned char *const *in, const unsigned int *in_size,
-                    unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
+int r4x16_stage_verdicts(rans4x16_hip_ctx *c, const StageLayout &L, size_t items, u32 *osz, i32 *status, hipStream_t s)
+{
+    HIPCHK(c, hipMemcpyAsync(osz, L.osz, items * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status, L.status, items * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return 0;
+}
+
+// One slab of blocks: copy in, run the device path, copy out, all on the context's own stream.  x8: the rANS 4x8 pair of
+// device calls (they take no max_cap / sum_cap) instead of the 4x16 pair.
+int r4x16_run_slab(rans4x16_hip_ctx *c, int n, bool decode, bool x8,
+                   const unsigned char *const *in, const unsigned int *in_size,
+                   unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
 {
     hipStream_t s = c->stream;
-    // arena: [in blocks][out slots][offset/size/status arrays]
     std::vector<u64> in_off(n), out_off(n);
-    std::vector<u32> cap(n);
+    std::vector<u32> cap(out_size, out_size + n);
     std::vector<i32> ord(n);
-    size_t in_tot = 0, out_tot = 0;
+    const size_t in_tot = r4x16_stage_slots(in_size, (size_t)n, 16, 256, in_off.data());
+    const size_t out_tot = r4x16_stage_slots(cap.data(), (size_t)n, 16, 256, out_off.data());
     u32 max_in = 0, max_cap = 0;
     u64 sum_in = 0, sum_cap = 0;
     for (int i = 0; i < n; i++) {
-        in_off[i] = in_tot; in_tot += align_up((size_t)in_size[i] + 16, 256);
-        cap[i] = out_size[i];
-        out_off[i] = out_tot; out_tot += align_up((size_t)cap[i] + 16, 256);
         if (in_size[i] > max_in) max_in = in_size[i];
         // decode: only blocks with PACK / RLE need the stage buffers that max_out_cap sizes (r4x16_api.hip)
         const bool xfb = !decode || (in_size[i] && (in[i][0] & (X_PACK | X_RLE)));
@@ -102,43 +61,34 @@ static int run_slab(rans4x16_hip_ctx *c, int n, bool decode,
         if (xfb) sum_cap += cap[i];
         ord[i] = order ? order[i] : 0;
     }
-    const size_t arr = align_up((size_t)n * 8, 256);
-    const size_t total = in_tot + out_tot + 6 * arr;
-    if (r4x16_ensure(c, A_STAGE, total, true) != 0) return -1;
-    u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
-    u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
-    u32 *d_in_size = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
-    i32 *d_status = (i32 *)(meta + 5 * arr);
-    i32 *d_order = (i32 *)(meta + 5 * arr + arr / 2);
-
+    StageLayout L;
+    if (r4x16_stage_begin(c, &L, (size_t)n, in_tot, 0, out_tot, 0, {in_off.data(), out_off.data(), in_size, cap.data(), ord.data()}, s) != 0)
+        return -1;
     for (int i = 0; i < n; i++)
-        if (in_size[i]) HIPCHK(c, hipMemcpyAsync(d_in + in_off[i], in[i], in_size[i], hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_in_off, in_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_out_off, out_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_in_size, in_size, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_cap, cap.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_order, ord.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        if (in_size[i]) HIPCHK(c, hipMemcpyAsync(L.in + in_off[i], in[i], in_size[i], hipMemcpyHostToDevice, s));
 
     int rc;
-    if (decode)
-        rc = rans4x16_hip_uncompress_dev_sized(c, n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_cap, d_osz,
-                                               d_status, max_in, max_cap, sum_cap, s);
+    if (x8)
+        rc = decode ? rans4x8_hip_uncompress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status, s)
+                    : rans4x8_hip_compress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
+                                               0, L.order, max_in, s);
+    else if (decode)
+        rc = rans4x16_hip_uncompress_dev_sized(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz,
+                                               L.status, max_in, max_cap, sum_cap, s);
     else
-        rc = rans4x16_hip_compress_dev_sized(c, n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_cap, d_osz,
-                                             d_status, 0, d_order, max_in, sum_in, s);
+        rc = rans4x16_hip_compress_dev_sized(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz,
+                                             L.status, 0, L.order, max_in, sum_in, s);
     if (rc != 0) return -1;
 
     std::vector<u32> osz(n);
     std::vector<i32> st(n);
-    HIPCHK(c, hipMemcpyAsync(osz.data(), d_osz, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(st.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (r4x16_stage_verdicts(c, L, (size_t)n, osz.data(), st.data(), s) != 0) return -1;
     int failed = 0;
     for (int i = 0; i < n; i++) {
         if (status) status[i] = st[i];
         if (st[i] != 0) { out_size[i] = 0; failed++; continue; }
         out_size[i] = osz[i];
-        if (osz[i]) HIPCHK(c, hipMemcpyAsync(out[i], d_out + out_off[i], osz[i], hipMemcpyDeviceToHost, s));
+        if (osz[i]) HIPCHK(c, hipMemcpyAsync(out[i], L.out + out_off[i], osz[i], hipMemcpyDeviceToHost, s));
     }
     HIPCHK(c, hipStreamSynchronize(s));
     return failed;
@@ -299,33 +249,22 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
                          unsigned char *const *out, unsigned int *out_size, const int *order, int *status,
                          int threads, int nlanes, int K = 1, const int *methods = nullptr, int *win_k = nullptr)
 {
-    // ---- layout: the same arena as run_slab; K output slots per block --------------------------------
+    // ---- slots: one per block for the input, K per block for the output ----------------------------------
     const size_t ni = (size_t)n * (size_t)K;
     if (ni > (size_t)INT_MAX) { c->err = "host batch: too many candidates"; return -1; }
     std::vector<u64> in_off(n), in_off_it(ni), out_off(ni);
     std::vector<u32> cap(ni), in_size_it(ni);
     std::vector<i32> ord(ni);
-    size_t in_tot = 0, out_tot = 0;
-    for (int i = 0; i < n; i++) {
-        in_off[i] = in_tot; in_tot += align_up((size_t)in_size[i] + 16, 256);
+    const size_t in_tot = r4x16_stage_slots(in_size, (size_t)n, 16, 256, in_off.data());
+    const size_t out_tot = r4x16_stage_slots(out_size, (size_t)n, 16, 256, out_off.data(), (size_t)K);
+    for (int i = 0; i < n; i++)
         for (int k = 0; k < K; k++) {
             const size_t it = (size_t)i * K + k;
             in_off_it[it] = in_off[i];
             in_size_it[it] = in_size[i];
             cap[it] = out_size[i];
-            out_off[it] = out_tot; out_tot += align_up((size_t)cap[it] + 16, 256);
             ord[it] = methods ? methods[k] : (order ? order[i] : 0);
         }
-    }
-    const size_t arr = align_up(ni * 8, 256);
-    const size_t pk_bytes = align_up((size_t)n * sizeof(PackDesc), 256);
-    if (r4x16_ensure(c, A_STAGE, in_tot + out_tot + 6 * arr + pk_bytes, true) != 0) return -1;
-    u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
-    u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
-    u32 *d_in_size = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
-    i32 *d_status = (i32 *)(meta + 5 * arr);
-    i32 *d_order = (i32 *)(meta + 5 * arr + arr / 2);
-    PackDesc *d_pk = (PackDesc *)(meta + 6 * arr);
     std::vector<int> win(n, -1);                              // winning candidate of each block (K > 1)
 
     // ---- slabs: a multiple of the lane count, as few as the lane workspaces allow (8 GiB of input + capacity per
@@ -390,14 +329,13 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
     if (pipe_prepare(c, threads, nlanes, 3 * nslab, ni, (size_t)n) != 0) return -2;      // nothing started: the caller may take the single-pass route
     HostPipe *hp = c->pipe;
 
-    hipStream_t s0 = c->stream;
+    // the same arena as r4x16_run_slab's, with a gather descriptor per block behind the arrays
     const hipStream_t s_in = c->stream, s_out = hp->s_out;
-    HIPCHK(c, hipMemcpyAsync(d_in_off, in_off_it.data(), ni * 8, hipMemcpyHostToDevice, s0));
-    HIPCHK(c, hipMemcpyAsync(d_out_off, out_off.data(), ni * 8, hipMemcpyHostToDevice, s0));
-    HIPCHK(c, hipMemcpyAsync(d_in_size, in_size_it.data(), ni * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(c, hipMemcpyAsync(d_cap, cap.data(), ni * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(c, hipMemcpyAsync(d_order, ord.data(), ni * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(c, hipStreamSynchronize(s0));
+    StageLayout L;
+    if (r4x16_stage_begin(c, &L, ni, in_tot, 0, out_tot, (size_t)n,
+                          {in_off_it.data(), out_off.data(), in_size_it.data(), cap.data(), ord.data()}, s_in) != 0)
+        return -1;
+    HIPCHK(c, hipStreamSynchronize(s_in));
 
     std::atomic<int> broken{0};
     std::mutex err_mu;
@@ -443,18 +381,18 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
         const int lo = S.lo * K, m = (S.hi - S.lo) * K;          // items
         int rc;
         if (decode)
-            rc = rans4x16_hip_uncompress_dev_sized(l, m, d_in, d_in_off + lo, d_in_size + lo, d_out, d_out_off + lo, d_cap + lo,
-                                                   d_osz + lo, d_status + lo, S.max_in, S.max_cap, S.sum_cap * (u64)K, l->stream);
+            rc = rans4x16_hip_uncompress_dev_sized(l, m, L.in, L.in_off + lo, L.in_size + lo, L.out, L.out_off + lo, L.cap + lo,
+                                                   L.osz + lo, L.status + lo, S.max_in, S.max_cap, S.sum_cap * (u64)K, l->stream);
         else
-            rc = rans4x16_hip_compress_dev_sized(l, m, d_in, d_in_off + lo, d_in_size + lo, d_out, d_out_off + lo, d_cap + lo,
-                                                 d_osz + lo, d_status + lo, 0, d_order + lo, S.max_in, S.sum_in * (u64)K, l->stream);
+            rc = rans4x16_hip_compress_dev_sized(l, m, L.in, L.in_off + lo, L.in_size + lo, L.out, L.out_off + lo, L.cap + lo,
+                                                 L.osz + lo, L.status + lo, 0, L.order + lo, S.max_in, S.sum_in * (u64)K, l->stream);
         if (rc != 0) {
             std::lock_guard<std::mutex> g2(err_mu);
             if (!broken.exchange(1)) c->err = l->err;
             return false;
         }
-        PIPECHK(hipMemcpyAsync(hp->h_osz + lo, d_osz + lo, (size_t)m * 4, hipMemcpyDeviceToHost, l->stream));
-        PIPECHK(hipMemcpyAsync(hp->h_st + lo, d_status + lo, (size_t)m * 4, hipMemcpyDeviceToHost, l->stream));
+        PIPECHK(hipMemcpyAsync(hp->h_osz + lo, L.osz + lo, (size_t)m * 4, hipMemcpyDeviceToHost, l->stream));
+        PIPECHK(hipMemcpyAsync(hp->h_st + lo, L.status + lo, (size_t)m * 4, hipMemcpyDeviceToHost, l->stream));
         PIPECHK(hipEventRecord(hp->events[3 * j + 1], l->stream));
         S.launched.store(1, std::memory_order_release);
         if (trace) fprintf(stderr, "[pipe] slab %zu (%d blocks) launched on lane %zu at %.1f ms\n", j, S.hi - S.lo, li, now_ms());
@@ -470,7 +408,7 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
             for (int i = b0; i < b1; i++)
                 if (in_size[i]) memcpy(sl.pin + (in_off[i] - base), in[i], in_size[i]);
             if (extent) {
-                PIPECHK(hipMemcpyAsync(d_in + base, sl.pin, extent, hipMemcpyHostToDevice, s_in));
+                PIPECHK(hipMemcpyAsync(L.in + base, sl.pin, extent, hipMemcpyHostToDevice, s_in));
                 sl.fill = extent;
             }
             return flip(pc, s_in);
@@ -480,7 +418,7 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
             const size_t len = (size_t)(extent - p < PIPE_CHUNK ? extent - p : PIPE_CHUNK);
             PipeSlot &sl = pc.slot[pc.k];
             memcpy(sl.pin, in[b0] + p, len);
-            PIPECHK(hipMemcpyAsync(d_in + base + p, sl.pin, len, hipMemcpyHostToDevice, s_in));
+            PIPECHK(hipMemcpyAsync(L.in + base + p, sl.pin, len, hipMemcpyHostToDevice, s_in));
             sl.fill = len;
             if (!flip(pc, s_in)) return false;
         }
@@ -498,7 +436,7 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
             const u64 base = out_off[b0], extent = end - base;
             if (sum && extent <= PIPE_CHUNK && sum * 4 >= extent * 3) {
                 PipeSlot &sl = pc.slot[pc.k];                  // free: the previous unit ended with flip()
-                PIPECHK(hipMemcpyAsync(sl.pin, d_out + base, extent, hipMemcpyDeviceToHost, s_out));
+                PIPECHK(hipMemcpyAsync(sl.pin, L.out + base, extent, hipMemcpyDeviceToHost, s_out));
                 for (int i = b0; i < b1; i++)
                     if (hp->h_st[i] == 0 && hp->h_osz[i]) sl.outs.push_back({out[i], (size_t)(out_off[i] - base), hp->h_osz[i]});
                 sl.fill = extent;
@@ -522,7 +460,7 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
                     at = 0;
                 }
                 const size_t len = sz - p < PIPE_CHUNK - at ? sz - p : PIPE_CHUNK - at;
-                PIPECHK(hipMemcpyAsync(sl->pin + at, d_out + out_off[it] + p, len, hipMemcpyDeviceToHost, s_out));
+                PIPECHK(hipMemcpyAsync(sl->pin + at, L.out + out_off[it] + p, len, hipMemcpyDeviceToHost, s_out));
                 sl->outs.push_back({out[i] + p, at, len});
                 sl->fill = at + len;
                 p += len;
@@ -572,8 +510,8 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
         const size_t li = j % (size_t)nlanes;
         rans4x16_hip_ctx *l = hp->lanes[li];
         std::lock_guard<std::mutex> g(hp->lane_mu[li]);
-        PIPECHK(hipMemcpyAsync(d_pk + S.lo, hp->h_pk + S.lo, (size_t)m * sizeof(PackDesc), hipMemcpyHostToDevice, l->stream));
-        hipLaunchKernelGGL(k_pack_results, dim3((unsigned)m), dim3(256), 0, l->stream, (const u8 *)d_out, d_in, (const PackDesc *)(d_pk + S.lo));
+        PIPECHK(hipMemcpyAsync(L.pk + S.lo, hp->h_pk + S.lo, (size_t)m * sizeof(PackDesc), hipMemcpyHostToDevice, l->stream));
+        hipLaunchKernelGGL(k_pack_results, dim3((unsigned)m), dim3(256), 0, l->stream, (const u8 *)L.out, L.in, (const PackDesc *)(L.pk + S.lo));
         PIPECHK(hipGetLastError());
         PIPECHK(hipEventRecord(hp->events[3 * j + 2], l->stream));
         S.plan.store(4, std::memory_order_release);
@@ -583,7 +521,7 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
     auto copy_out_packed = [&](PipeCopier &pc, PipeSlab &S, int u) -> bool {
         const u64 a = (u64)u * PIPE_CHUNK, b = a + PIPE_CHUNK < S.pk_total ? a + PIPE_CHUNK : S.pk_total;
         PipeSlot &sl = pc.slot[pc.k];                              // free: the previous unit ended with flip()
-        PIPECHK(hipMemcpyAsync(sl.pin, d_in + in_off[S.lo] + a, (size_t)(b - a), hipMemcpyDeviceToHost, s_out));
+        PIPECHK(hipMemcpyAsync(sl.pin, L.in + in_off[S.lo] + a, (size_t)(b - a), hipMemcpyDeviceToHost, s_out));
         // first block whose result ends after a
         size_t i = (size_t)(std::upper_bound(S.poff.begin(), S.poff.end(), a) - S.poff.begin());
         i = i ? i - 1 : 0;
@@ -701,26 +639,32 @@ static int run_pipelined(rans4x16_hip_ctx *c, int n, bool decode,
     return failed;
 }
 
+// the pipeline's copier threads and lanes as the options ask, within what it has room for (16 lane mutexes)
+static void pipe_workers(const rans4x16_hip_ctx *c, long *threads, long *nlanes)
+{
+    *threads = std::min(std::max(c->opts.v[OPT_HOST_THREADS], 1L), 32L);
+    *nlanes = std::min(std::max(c->opts.v[OPT_HOST_LANES], 1L), 16L);
+}
+
 static int run_plain_batch(rans4x16_hip_ctx *c, int n, bool decode,
                            const unsigned char *const *in, const unsigned int *in_size,
                            unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
 {
     const long pipe_mb = c->opts.v[OPT_HOST_PIPE_MB];
-    long threads = c->opts.v[OPT_HOST_THREADS], nlanes = c->opts.v[OPT_HOST_LANES];
-    threads = threads < 1 ? 1 : threads > 32 ? 32 : threads;
-    nlanes = nlanes < 1 ? 1 : nlanes > 16 ? 16 : nlanes;
+    long threads, nlanes;
+    pipe_workers(c, &threads, &nlanes);
     size_t tot = 0;
     for (int i = 0; i < n; i++) tot += (size_t)in_size[i] + out_size[i];
     // small batches of few blocks keep the single pass (no threads to start); many small blocks take the pipeline
     // whatever their total, because the single pass issues one driver copy per block and direction
     // (5,000 x 4 KiB: 197 ms single pass, 35 ms pipelined; tools/small_batch_routes.py)
     if (pipe_mb <= 0 || (tot < ((size_t)pipe_mb << 20) && n < 32))
-        return run_slab(c, n, decode, in, in_size, out, out_size, order, status);
+        return r4x16_run_slab(c, n, decode, false, in, in_size, out, out_size, order, status);
     const long by_work = (long)(tot >> 21) + n / 64 + 1;           // a copier thread per 2 MiB / 64 blocks is plenty
     if (threads > by_work) threads = by_work;
     const int rc = run_pipelined(c, n, decode, in, in_size, out, out_size, order, status, (int)threads, (int)nlanes);
     // -2: the pipeline's resources (pinned buffers, lane contexts) could not be set up, e.g. a locked-memory limit
-    return rc == -2 ? run_slab(c, n, decode, in, in_size, out, out_size, order, status) : rc;
+    return rc == -2 ? r4x16_run_slab(c, n, decode, false, in, in_size, out, out_size, order, status) : rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -747,8 +691,32 @@ static int var_get_host(const unsigned char *cp, const unsigned char *endp, u32 
     return (int)(cp - op);
 }
 
+// What an X_STRIPE stream says of itself before any plane is touched (:1360-1400): the plane count, the uncompressed
+// size, where the header ends and the planes' compressed sizes.
+struct StripeHead { u32 N, ulen, hdr; u64 ctot; u32 clen[255]; };
+// The reference's checks on that header, against the caller's capacity `cap`.  Returns R4X16_E_SIZE, R4X16_E_CAPACITY, or
+// 0: N planes to decode - or none at all, N == 0 with ulen == 0, an empty block that is accepted as it is.
+static int stripe_head(const unsigned char *p, u32 in_size, u32 cap, StripeHead *h)
+{
+    const unsigned char *end = p + in_size;
+    h->hdr = 1; h->ctot = 0;
+    h->hdr += var_get_host(p + h->hdr, end, &h->ulen);
+    if (h->hdr >= in_size) return R4X16_E_SIZE;                        // :1367
+    h->N = p[h->hdr++];
+    if (h->ulen != cap) return R4X16_E_CAPACITY;                       // :1379 (caller sized the buffer)
+    if (h->N == 0) return h->ulen == 0 ? 0 : R4X16_E_SIZE;             // the reference spins forever here
+    for (u32 j = 0; j < h->N; j++) {
+        u32 cl;
+        h->hdr += var_get_host(p + h->hdr, end, &cl);
+        h->clen[j] = cl;
+        h->ctot += cl;
+        if (h->hdr > in_size || cl > in_size || cl < 1) return R4X16_E_SIZE;   // :1389
+    }
+    return h->hdr + h->ctot > in_size ? R4X16_E_SIZE : 0;              // :1398
+}
+
 // ---------------------------------------------------------------------------------------------
-// X_STRIPE blocks of a host batch through the DEVICE-RESIDENT stripe route (r4x16_stripe.hip, round 3): the blocks are
+// X_STRIPE blocks of a host batch through the DEVICE-RESIDENT stripe route (r4x16_stripe.hip): the blocks are
 // staged like any others and the prepare / pick / join kernels do on the device what stripe_compress_many /
 // stripe_uncompress_many below do with a read-back of the plane sizes in the middle of the call (those stay as the
 // route of R4X16_HOST_STRIPE_DEV=0).  Encode: the device route takes one `order` per call (N and the candidate methods
@@ -772,26 +740,14 @@ static int stripe_many_dev(rans4x16_hip_ctx *c, bool decode, const std::vector<i
             if (N > 255 || out_size[i] < r4x16_compress_bound(in_size[i], o)) continue;          // :1158
             ok[k] = 1; key[k] = o;
         } else {
-            // the checks the reference makes before it touches a plane (:1360-1400), on the host as before
-            const unsigned char *p = in[i], *end = p + in_size[i];
-            u32 ulen, hdr = 1;
-            hdr += var_get_host(p + hdr, end, &ulen);
-            if (hdr >= in_size[i]) continue;                               // :1367
-            const u32 N = p[hdr++];
-            if (ulen != out_size[i]) { fail[k] = R4X16_E_CAPACITY; continue; }   // :1379 (caller sized the buffer)
-            if (N == 0) { if (ulen == 0) { fail[k] = 0; out_size[i] = 0; } continue; }   // the reference spins forever here
-            u64 ctot = 0;
-            bool good = true;
-            for (u32 j = 0; j < N; j++) {
-                u32 cl;
-                hdr += var_get_host(p + hdr, end, &cl);
-                ctot += cl;
-                if (hdr > in_size[i] || cl > in_size[i] || cl < 1) { good = false; break; }   // :1389
-            }
-            if (!good || hdr + ctot > in_size[i]) continue;                // :1398
+            StripeHead h;
+            fail[k] = stripe_head(in[i], in_size[i], out_size[i], &h);
+            if (fail[k] != 0) continue;
+            if (h.N == 0) { out_size[i] = 0; continue; }
+            fail[k] = R4X16_E_SIZE;                          // until the device has decoded it
             ok[k] = 1;
-            if (N > max_planes) max_planes = N;
-            if (ulen > max_ulen) max_ulen = ulen;
+            if (h.N > max_planes) max_planes = h.N;
+            if (h.ulen > max_ulen) max_ulen = h.ulen;
         }
     }
     // groups of equal key, in order of first appearance
@@ -805,50 +761,36 @@ static int stripe_many_dev(rans4x16_hip_ctx *c, bool decode, const std::vector<i
         const int m = (int)g.size();
         std::vector<u64> in_off(m), out_off(m);
         std::vector<u32> isz(m), cap(m);
-        size_t in_tot = 0, out_tot = 0;
         u32 max_in = 0, max_cap = 0;
         for (int e = 0; e < m; e++) {
             const int i = which[g[e]];
-            in_off[e] = in_tot; in_tot += align_up((size_t)in_size[i] + 16, 256);
             isz[e] = in_size[i]; cap[e] = out_size[i];
-            out_off[e] = out_tot; out_tot += align_up((size_t)cap[e] + 16, 256);
             if (isz[e] > max_in) max_in = isz[e];
             if (cap[e] > max_cap) max_cap = cap[e];
         }
-        const size_t arr = align_up((size_t)m * 8, 256);
-        if (r4x16_ensure(c, A_STAGE, in_tot + out_tot + 6 * arr, true) != 0) return -1;
-        u8 *d_in = c->at(A_STAGE), *d_out = d_in + in_tot, *meta = d_out + out_tot;
-        u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
-        u32 *d_isz = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
-        i32 *d_st = (i32 *)(meta + 5 * arr);
+        const size_t in_tot = r4x16_stage_slots(isz.data(), (size_t)m, 16, 256, in_off.data());
+        const size_t out_tot = r4x16_stage_slots(cap.data(), (size_t)m, 16, 256, out_off.data());
+        StageLayout L;                                       // (encode: with a descriptor per block for the gather below)
+        if (r4x16_stage_begin(c, &L, (size_t)m, in_tot, 0, out_tot, decode ? 0 : (size_t)m,
+                              {in_off.data(), out_off.data(), isz.data(), cap.data(), nullptr}, s) != 0)
+            return -1;
         for (int e = 0; e < m; e++)
-            HIPCHK(c, hipMemcpyAsync(d_in + in_off[e], in[which[g[e]]], isz[e], hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(d_in_off, in_off.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(d_out_off, out_off.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(d_isz, isz.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(d_cap, cap.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(L.in + in_off[e], in[which[g[e]]], isz[e], hipMemcpyHostToDevice, s));
         int rc;
         if (decode) {
-            const int keep_planes = c->dev_stripe_planes;
-            const unsigned int keep_out = c->dev_stripe_out;
-            c->dev_stripe_planes = (int)max_planes;
-            c->dev_stripe_out = max_ulen;
-            rc = rans4x16_hip_uncompress_dev(c, m, d_in, d_in_off, d_isz, d_out, d_out_off, d_cap, d_osz, d_st, max_in, max_cap, s);
-            c->dev_stripe_planes = keep_planes;
-            c->dev_stripe_out = keep_out;
+            StripeLimits limits(c, (int)max_planes, max_ulen);
+            rc = rans4x16_hip_uncompress_dev(c, m, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status, max_in, max_cap, s);
         } else
-            rc = rans4x16_hip_compress_dev(c, m, d_in, d_in_off, d_isz, d_out, d_out_off, d_cap, d_osz, d_st, kv, nullptr, max_in, s);
+            rc = rans4x16_hip_compress_dev(c, m, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status, kv, nullptr, max_in, s);
         if (rc != 0) return -1;
-        std::vector<u32> osz(m);
-        std::vector<i32> st(m);
-        HIPCHK(c, hipMemcpyAsync(osz.data(), d_osz, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(st.data(), d_st, (size_t)m * 4, hipMemcpyDeviceToHost, s));
         // results: decode slots are full, so the slot region comes back as it is; encode results fill a fraction of
         // their bound-sized slots and are first gathered into the (by now dead) input region by k_pack_results - one
         // dense transfer instead of a DMA per block (1,000 blocks: 85 ms of driver calls)
         std::vector<u8> host;
-        if (decode) { host.resize(out_tot); HIPCHK(c, hipMemcpyAsync(host.data(), d_out, out_tot, hipMemcpyDeviceToHost, s)); }
-        HIPCHK(c, hipStreamSynchronize(s));
+        if (decode) { host.resize(out_tot); HIPCHK(c, hipMemcpyAsync(host.data(), L.out, out_tot, hipMemcpyDeviceToHost, s)); }
+        std::vector<u32> osz(m);
+        std::vector<i32> st(m);
+        if (r4x16_stage_verdicts(c, L, (size_t)m, osz.data(), st.data(), s) != 0) return -1;
         std::vector<PackDesc> pk;
         u64 T = 0;
         if (!decode) {
@@ -858,18 +800,15 @@ static int stripe_many_dev(rans4x16_hip_ctx *c, bool decode, const std::vector<i
                 pk.push_back(d);
                 T += ((u64)osz[e] + 63u) & ~(u64)63u;
             }
-            const size_t pk_bytes = pk.size() * sizeof(PackDesc);
-            if (!pk.empty() && T <= in_tot && pk_bytes <= 6 * arr) {
-                // (the descriptors go where the offset / size arrays were: nothing reads those any more)
-                PackDesc *d_pk = (PackDesc *)meta;
-                HIPCHK(c, hipMemcpyAsync(d_pk, pk.data(), pk_bytes, hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL(k_pack_results, dim3((unsigned)pk.size()), dim3(256), 0, s, (const u8 *)d_out, d_in, (const PackDesc *)d_pk);
+            if (!pk.empty() && T <= in_tot) {
+                HIPCHK(c, hipMemcpyAsync(L.pk, pk.data(), pk.size() * sizeof(PackDesc), hipMemcpyHostToDevice, s));
+                hipLaunchKernelGGL(k_pack_results, dim3((unsigned)pk.size()), dim3(256), 0, s, (const u8 *)L.out, L.in, (const PackDesc *)L.pk);
                 HIPCHK(c, hipGetLastError());
                 host.resize(T);
-                HIPCHK(c, hipMemcpyAsync(host.data(), d_in, T, hipMemcpyDeviceToHost, s));
+                HIPCHK(c, hipMemcpyAsync(host.data(), L.in, T, hipMemcpyDeviceToHost, s));
                 HIPCHK(c, hipStreamSynchronize(s));
             } else {
-                for (const PackDesc &d : pk) HIPCHK(c, hipMemcpyAsync(out[which[g[d.pad]]], d_out + d.src, d.len, hipMemcpyDeviceToHost, s));
+                for (const PackDesc &d : pk) HIPCHK(c, hipMemcpyAsync(out[which[g[d.pad]]], L.out + d.src, d.len, hipMemcpyDeviceToHost, s));
                 HIPCHK(c, hipStreamSynchronize(s));
                 pk.clear();
             }
@@ -923,7 +862,6 @@ static int stripe_compress_many(rans4x16_hip_ctx *c, const std::vector<int> &whi
     std::vector<u64> in_off(items), out_off(items);
     std::vector<u32> isz(items), cap(items);
     std::vector<i32> ord(items);
-    size_t out_tot = 0;
     u32 max_in = 0;
     for (size_t k = 0; k < nb; k++) {
         const Blk &b = B[k];
@@ -936,38 +874,28 @@ static int stripe_compress_many(rans4x16_hip_ctx *c, const std::vector<int> &whi
                 const size_t it = (size_t)b.item0 + (size_t)j * b.K + q;
                 in_off[it] = b.boff + first; isz[it] = part; ord[it] = b.cand[q] | X_NOSZ;
                 cap[it] = r4x16_compress_bound(part, ord[it]);
-                out_off[it] = out_tot; out_tot += align_up((size_t)cap[it] + 16, 256);
             }
             if (part > max_in) max_in = part;
             first += part;
         }
     }
-    const size_t arr = align_up(items * 8, 256), pk_bytes = align_up(items * sizeof(PackDesc), 256);
-    if (r4x16_ensure(c, A_STAGE, 2 * in_tot + out_tot + 6 * arr + pk_bytes, true) != 0) return -1;
-    u8 *d_in = c->at(A_STAGE), *d_pl = d_in + in_tot, *d_out = d_pl + in_tot, *meta = d_out + out_tot;
-    u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
-    u32 *d_isz = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
-    i32 *d_st = (i32 *)(meta + 5 * arr), *d_ord = (i32 *)(meta + 5 * arr + arr / 2);
-    PackDesc *d_pk = (PackDesc *)(meta + 6 * arr);
+    const size_t out_tot = r4x16_stage_slots(cap.data(), items, 16, 256, out_off.data());
     hipStream_t s = c->stream;
+    StageLayout L;                                                     // the planes mirror the input region
+    if (r4x16_stage_begin(c, &L, items, in_tot, in_tot, out_tot, items,
+                          {in_off.data(), out_off.data(), isz.data(), cap.data(), ord.data()}, s) != 0)
+        return -1;
     for (size_t k = 0; k < nb; k++) {
         if (!B[k].ok) continue;
         const int i = which[k];
-        HIPCHK(c, hipMemcpyAsync(d_in + B[k].boff, in[i], in_size[i], hipMemcpyHostToDevice, s));
-        r4x16_launch_stripe(d_in + B[k].boff, d_pl + B[k].boff, in_size[i], (u32)B[k].N, 0, s);
+        HIPCHK(c, hipMemcpyAsync(L.in + B[k].boff, in[i], in_size[i], hipMemcpyHostToDevice, s));
+        r4x16_launch_stripe(L.in + B[k].boff, L.planes + B[k].boff, in_size[i], (u32)B[k].N, 0, s);
     }
-    HIPCHK(c, hipMemcpyAsync(d_in_off, in_off.data(), items * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_out_off, out_off.data(), items * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_isz, isz.data(), items * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_cap, cap.data(), items * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_ord, ord.data(), items * 4, hipMemcpyHostToDevice, s));
-    if (rans4x16_hip_compress_dev(c, (int)items, d_pl, d_in_off, d_isz, d_out, d_out_off, d_cap, d_osz, d_st,
-                                  0, d_ord, max_in, s) != 0) return -1;
+    if (rans4x16_hip_compress_dev(c, (int)items, L.planes, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
+                                  0, L.order, max_in, s) != 0) return -1;
     std::vector<u32> osz(items);
     std::vector<i32> st(items);
-    HIPCHK(c, hipMemcpyAsync(osz.data(), d_osz, items * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(st.data(), d_st, items * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (r4x16_stage_verdicts(c, L, items, osz.data(), st.data(), s) != 0) return -1;
 
     // headers on the host, winners packed on the device (into the input + plane regions, dead by now)
     std::vector<PackDesc> pk;
@@ -1006,12 +934,12 @@ static int stripe_compress_many(rans4x16_hip_ctx *c, const std::vector<int> &whi
     if (pk.empty()) return 0;
     std::vector<u8> host(T);
     if (T <= 2 * (u64)in_tot) {
-        HIPCHK(c, hipMemcpyAsync(d_pk, pk.data(), pk.size() * sizeof(PackDesc), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_pack_results, dim3((unsigned)pk.size()), dim3(256), 0, s, (const u8 *)d_out, d_in, (const PackDesc *)d_pk);
+        HIPCHK(c, hipMemcpyAsync(L.pk, pk.data(), pk.size() * sizeof(PackDesc), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_pack_results, dim3((unsigned)pk.size()), dim3(256), 0, s, (const u8 *)L.out, L.in, (const PackDesc *)L.pk);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(host.data(), d_in, T, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(host.data(), L.in, T, hipMemcpyDeviceToHost, s));
     } else {
-        for (const PackDesc &d : pk) HIPCHK(c, hipMemcpyAsync(host.data() + d.dst, d_out + d.src, d.len, hipMemcpyDeviceToHost, s));
+        for (const PackDesc &d : pk) HIPCHK(c, hipMemcpyAsync(host.data() + d.dst, L.out + d.src, d.len, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(c, hipStreamSynchronize(s));
     // planes of a block are adjacent in the packed region, in order
@@ -1042,29 +970,17 @@ static int stripe_uncompress_many(rans4x16_hip_ctx *c, const std::vector<int> &w
     for (size_t k = 0; k < nb; k++) {
         const int i = which[k];
         Blk &b = B[k];
-        b.ok = false; fail[k] = R4X16_E_SIZE; b.item0 = (int)items; b.boff = in_tot; b.poff = pl_tot; b.N = 0;
-        const unsigned char *p = in[i], *end = p + in_size[i];
-        u32 ulen, hdr = 1;
-        hdr += var_get_host(p + hdr, end, &ulen);
-        if (hdr >= in_size[i]) continue;                               // :1367
-        const u32 N = p[hdr++];
-        if (ulen != out_size[i]) { fail[k] = R4X16_E_CAPACITY; continue; }   // :1379 (caller sized the buffer)
-        if (N == 0) { if (ulen == 0) { fail[k] = 0; out_size[i] = 0; } continue; }   // the reference spins forever here
-        u64 ctot = 0;
-        bool good = true;
-        const size_t c0 = clen_all.size();
-        for (u32 j = 0; j < N; j++) {
-            u32 cl;
-            hdr += var_get_host(p + hdr, end, &cl);
-            clen_all.push_back(cl);
-            ctot += cl;
-            if (hdr > in_size[i] || cl > in_size[i] || cl < 1) { good = false; break; }   // :1389
-        }
-        if (!good || hdr + ctot > in_size[i]) { clen_all.resize(c0); continue; }          // :1398
-        b.N = N; b.ulen = ulen; b.hdr = hdr; b.used = (u32)(hdr + ctot); b.ok = true;
-        items += N;
+        b.ok = false; b.item0 = (int)items; b.boff = in_tot; b.poff = pl_tot; b.N = 0;
+        StripeHead h;
+        fail[k] = stripe_head(in[i], in_size[i], out_size[i], &h);
+        if (fail[k] != 0) continue;
+        if (h.N == 0) { out_size[i] = 0; continue; }
+        fail[k] = R4X16_E_SIZE;                                        // until its planes have decoded
+        clen_all.insert(clen_all.end(), h.clen, h.clen + h.N);
+        b.N = h.N; b.ulen = h.ulen; b.hdr = h.hdr; b.used = (u32)(h.hdr + h.ctot); b.ok = true;
+        items += h.N;
         in_tot += align_up((size_t)b.used + 16, 256);
-        pl_tot += align_up((size_t)ulen + 16, 256);
+        pl_tot += align_up((size_t)h.ulen + 16, 256);
     }
     if (items == 0) return 0;
     if (items > (size_t)INT_MAX) { c->err = "stripe batch: too many planes"; return -1; }
@@ -1089,26 +1005,17 @@ static int stripe_uncompress_many(rans4x16_hip_ctx *c, const std::vector<int> &w
             }
         }
     }
-    const size_t arr = align_up(items * 8, 256);
-    if (r4x16_ensure(c, A_STAGE, in_tot + 2 * pl_tot + 6 * arr, true) != 0) return -1;
-    u8 *d_in = c->at(A_STAGE), *d_pl = d_in + in_tot, *d_out = d_pl + pl_tot, *meta = d_out + pl_tot;
-    u64 *d_in_off = (u64 *)meta, *d_out_off = (u64 *)(meta + arr);
-    u32 *d_isz = (u32 *)(meta + 2 * arr), *d_cap = (u32 *)(meta + 3 * arr), *d_osz = (u32 *)(meta + 4 * arr);
-    i32 *d_st = (i32 *)(meta + 5 * arr);
     hipStream_t s = c->stream;
+    StageLayout L;                                                     // the planes decode into L.planes, the joined blocks are L.out
+    if (r4x16_stage_begin(c, &L, items, in_tot, pl_tot, pl_tot, 0, {in_off.data(), out_off.data(), isz.data(), cap.data(), nullptr}, s) != 0)
+        return -1;
     for (size_t k = 0; k < nb; k++)
-        if (B[k].ok) HIPCHK(c, hipMemcpyAsync(d_in + B[k].boff, in[which[k]], B[k].used, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_in_off, in_off.data(), items * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_out_off, out_off.data(), items * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_isz, isz.data(), items * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_cap, cap.data(), items * 4, hipMemcpyHostToDevice, s));
-    if (rans4x16_hip_uncompress_dev(c, (int)items, d_in, d_in_off, d_isz, d_pl, d_out_off, d_cap, d_osz, d_st,
+        if (B[k].ok) HIPCHK(c, hipMemcpyAsync(L.in + B[k].boff, in[which[k]], B[k].used, hipMemcpyHostToDevice, s));
+    if (rans4x16_hip_uncompress_dev(c, (int)items, L.in, L.in_off, L.in_size, L.planes, L.out_off, L.cap, L.osz, L.status,
                                     max_in, max_cap, s) != 0) return -1;
     std::vector<u32> osz(items);
     std::vector<i32> st(items);
-    HIPCHK(c, hipMemcpyAsync(osz.data(), d_osz, items * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(st.data(), d_st, items * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (r4x16_stage_verdicts(c, L, items, osz.data(), st.data(), s) != 0) return -1;
     bool any = false;
     for (size_t k = 0; k < nb; k++) {
         Blk &b = B[k];
@@ -1118,12 +1025,12 @@ static int stripe_uncompress_many(rans4x16_hip_ctx *c, const std::vector<int> &w
             else if (osz[(size_t)b.item0 + j] != cap[(size_t)b.item0 + j]) b.ok = false;
         }
         if (!b.ok) continue;
-        r4x16_launch_stripe(d_pl + b.poff, d_out + b.poff, b.ulen, b.N, 1, s);
+        r4x16_launch_stripe(L.planes + b.poff, L.out + b.poff, b.ulen, b.N, 1, s);
         any = true;
     }
     if (any) {
         std::vector<u8> host(pl_tot);
-        HIPCHK(c, hipMemcpyAsync(host.data(), d_out, pl_tot, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(host.data(), L.out, pl_tot, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         for (size_t k = 0; k < nb; k++) {
             const Blk &b = B[k];
@@ -1135,6 +1042,57 @@ static int stripe_uncompress_many(rans4x16_hip_ctx *c, const std::vector<int> &w
         }
     }
     return 0;
+}
+
+int r4x16_run_host_batch(rans4x16_hip_ctx *c, int n, bool decode,
+                          const unsigned char *const *in, const unsigned int *in_size,
+                          unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
+{
+    if (!c) return -1;
+    if (n <= 0) return n == 0 ? 0 : -1;
+    HIPCHK(c, hipSetDevice(c->device));
+    // stripe blocks are expanded into one device batch of all their planes (and candidate methods)
+    std::vector<int> plain, striped;
+    int failed = 0;
+    for (int i = 0; i < n; i++) {
+        const int o = order ? order[i] : 0;
+        if (is_stripe(decode, in[i], in_size[i], o)) striped.push_back(i); else plain.push_back(i);
+    }
+    if (!striped.empty()) {
+        std::vector<int> sst(striped.size(), 0);
+        const bool dev_route = c->opts.v[OPT_HOST_STRIPE_DEV] != 0;
+        const int rc = dev_route ? stripe_many_dev(c, decode, striped, in, in_size, out, out_size, order, sst.data())
+                     : decode ? stripe_uncompress_many(c, striped, in, in_size, out, out_size, sst.data())
+                              : stripe_compress_many(c, striped, in, in_size, out, out_size, order, sst.data());
+        if (rc < 0) return -1;
+        for (size_t k = 0; k < striped.size(); k++) {
+            const int i = striped[k];
+            // decode: the status a device-resident call reports (a plane's own verdict included); encode: SIZE as before
+            if (status) status[i] = !sst[k] ? 0 : decode ? sst[k] : R4X16_E_SIZE;
+            if (sst[k]) { out_size[i] = 0; failed++; }
+        }
+    }
+    if (plain.empty()) return failed;
+    if ((int)plain.size() == n) {
+        const int f = run_plain_batch(c, n, decode, in, in_size, out, out_size, order, status);
+        return f < 0 ? -1 : failed + f;
+    }
+    const int m = (int)plain.size();
+    std::vector<const unsigned char *> pin(m);
+    std::vector<unsigned char *> pout(m);
+    std::vector<unsigned int> pis(m), pos(m);
+    std::vector<int> pord(m), pst(m);
+    for (int k = 0; k < m; k++) {
+        const int i = plain[k];
+        pin[k] = in[i]; pout[k] = out[i]; pis[k] = in_size[i]; pos[k] = out_size[i]; pord[k] = order ? order[i] : 0;
+    }
+    const int f = run_plain_batch(c, m, decode, pin.data(), pis.data(), pout.data(), pos.data(), pord.data(), pst.data());
+    if (f < 0) return -1;
+    for (int k = 0; k < m; k++) {
+        out_size[plain[k]] = pos[k];
+        if (status) status[plain[k]] = pst[k];
+    }
+    return failed + f;
 }
 
 // "Try K methods, keep the smallest" (tokenise_name3.c:1246-1300 compress()): every block is
@@ -1162,9 +1120,8 @@ extern "C" int rans4x16_hip_compress_best_batch(rans4x16_hip_ctx *c, int n,
     std::vector<int> best(n, -1), st(n, R4X16_E_UNSUPPORTED);
     std::vector<unsigned int> capv(out_size, out_size + n);
     if (!plain_m.empty()) {
-        long threads = c->opts.v[OPT_HOST_THREADS], nlanes = c->opts.v[OPT_HOST_LANES];
-        threads = threads < 1 ? 1 : threads > 32 ? 32 : threads;
-        nlanes = nlanes < 1 ? 1 : nlanes > 16 ? 16 : nlanes;
+        long threads, nlanes;
+        pipe_workers(c, &threads, &nlanes);
         size_t tot = 0;
         for (int i = 0; i < n; i++) tot += in_size[i];
         const long by_size = (long)(tot >> 22) + 1;                  // a copier thread per 4 MiB of input is plenty

@@ -1,8 +1,7 @@
 // r4x16_pack.h - the gather of sparse encode results (r4x16_host.hip's pipeline; tools/pack_gather.hip times it on its own)
 #pragma once
 #include "r4x16_dev.h"
-
-struct PackDesc { u64 src, dst; u32 len, pad; };      // one result to gather: slot offset, packed offset, bytes
+#include "r4x16_stage.h"                                // PackDesc
 
 // Sparse results (encode: every block owns a bound-sized slot and fills a fraction of it) are gathered by the device
 // into the slab's input region, which is dead once the slab's kernels have run, and cross PCIe as a few dense DMAs

@@ -289,15 +289,13 @@ static int nh_dec_chunk(rans4x16_hip_ctx *c, const std::vector<int> &which, cons
     HIPCHK(c, hipMemcpyAsync(d.in_off, in_off.data(), nb * 8, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d.in_size, isz.data(), nb * 4, hipMemcpyHostToDevice, s));
     // X_STRIPE columns (levels 3 and up): what rans4x16_hip_set_dev_stripe_planes arranges, for this call alone
-    const int keep_planes = c->dev_stripe_planes;
-    const unsigned int keep_out = c->dev_stripe_out;
-    c->dev_stripe_planes = 4;
-    c->dev_stripe_out = max_col;
-    const int rc = rans4x16_hip_tok3_decode_names_dev(c, (int)nb, d.in, d.in_off, d.in_size, d.o.out, out_bytes, d.o.off, d.o.size, d.o.nnames,
-                                                      d.o.status, nullptr, max_columns, max_in, max_col, max_names, T3_MAX_TOKENS,
-                                                      std::max<u64>(total_col, 1), s);
-    c->dev_stripe_planes = keep_planes;
-    c->dev_stripe_out = keep_out;
+    int rc;
+    {
+        StripeLimits limits(c, 4, max_col);
+        rc = rans4x16_hip_tok3_decode_names_dev(c, (int)nb, d.in, d.in_off, d.in_size, d.o.out, out_bytes, d.o.off, d.o.size, d.o.nnames,
+                                                d.o.status, nullptr, max_columns, max_in, max_col, max_names, T3_MAX_TOKENS,
+                                                std::max<u64>(total_col, 1), s);
+    }
     if (rc != 0) return -1;
     std::vector<u64> off(nb + 1);
     std::vector<u32> size(nb), nn(nb);
