@@ -41,10 +41,11 @@ struct ArBlk { i32 status; u32 out_size, nplanes, pad; };
 struct ArWs {
     ArItem *items;          // [nb * per]: block b's items from b * per
     ArBlk *blk;             // [nb]
-    u64 *cursor;            // bytes of the stage arena handed out
+    u64 *cursor;            // [0] bytes of the stage arena handed out (a chunk's); [1] bytes decoded into the caller's slots (the call's)
     u32 *route;             // [R4X16_ARITH_KINDS]; nullptr in the kernels' copy: option route_count is off
     u8 *stage;
     u64 stage_bytes;
+    u64 out_total;          // total_out_size: what the call's blocks may decode to together
     u8 *rows;               // [AR_GLOBAL_SLOTS] x AR_GLOBAL_ROW_BYTES
     u32 per;                // items a block reserves: max(1, planes)
     u32 planes, stripe_out; // rans4x16_hip_set_dev_stripe_planes
@@ -97,10 +98,14 @@ __global__ __launch_bounds__(256) void k_ar_front(BatchArgs a, ArWs w, int base,
     wsync();                                                        // lane 0's items are written before any lane marks the rest
     u32 live = st == AR_OK ? ((top.flags & AR_X_STRIPE) ? top.nplanes : 1u) : 0u;
     if (lane == 0 && live) {
-        // the block's place in the stage arena.  A batch that decodes to more than it announced does not fit: the blocks
-        // that find the arena full are refused, whichever they are (a refused block's claim stays taken)
-        const u64 at = need ? atomicAdd((unsigned long long *)w.cursor, (unsigned long long)need) : 0ull;
-        if (at + need > w.stage_bytes) { st = AR_E_UNSUPPORTED; live = 0; }
+        // the block's share of the announced total and its place in the stage arena.  A batch that decodes to more than it
+        // announced does not fit: the blocks that find the total spent are refused, whichever they are (a refused block's
+        // claim on the total stays taken).  Only a block within the total takes a place in the arena, which holds the
+        // total and 16 bytes an item: it finds one, and the test of the place is the bound of the decoders' stores
+        const u64 sum = top.out_size ? atomicAdd((unsigned long long *)w.cursor + 1, (unsigned long long)top.out_size) : 0ull;
+        const bool fits = sum + top.out_size <= w.out_total;
+        const u64 at = fits && need ? atomicAdd((unsigned long long *)w.cursor, (unsigned long long)need) : 0ull;
+        if (!fits || at + need > w.stage_bytes) { st = AR_E_UNSUPPORTED; live = 0; }
         else
             for (u32 j = 0; j < live; j++) {
                 items[j].stage += at;
@@ -371,9 +376,9 @@ __global__ __launch_bounds__(256) void k_ar_back(BatchArgs a, ArWs w, int base)
 static size_t ar_layout(u8 *base, size_t nb, size_t per, u64 stage_bytes, ArWs *w)
 {
     Carver cv(base);
+    w->cursor = cv.take<u64>(2);                                    // first: the call's count keeps its place from chunk to chunk
     w->items = cv.take<ArItem>(nb * per);
     w->blk = cv.take<ArBlk>(nb);
-    w->cursor = cv.take<u64>(1);
     w->route = cv.take<u32>(R4X16_ARITH_KINDS);
     w->stage = cv.take<u8>(stage_bytes);
     w->stage_bytes = stage_bytes;
@@ -411,10 +416,12 @@ extern "C" int rans4x16_hip_arith_uncompress_dev(rans4x16_hip_ctx *c, int n,
     a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
     a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
     a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
+    HIPCHK(c, hipMemsetAsync(c->at(A_AR), 0, 2 * sizeof(u64), s));
     for (size_t base = 0; base < (size_t)n; base += chunk) {
         const int nb = (int)std::min(chunk, (size_t)n - base);
         const u64 tot = std::min<u64>(total, (u64)nb * max_out_size);
         ar_layout(c->at(A_AR), (size_t)nb, per, tot + 16ull * nb * per, &w);
+        w.out_total = total;
         w.planes = (u32)c->dev_stripe_planes; w.stripe_out = c->dev_stripe_out;
         const int nitems = nb * (int)per;
         const bool count = c->opts.v[OPT_ROUTE_COUNT] != 0;
@@ -427,7 +434,10 @@ extern "C" int rans4x16_hip_arith_uncompress_dev(rans4x16_hip_ctx *c, int n,
         hipLaunchKernelGGL(k_ar_decode<AR_HOME_O1_LDS>, dim3(nitems), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_ar_decode<AR_HOME_O1_GLOBAL>, dim3(std::min(nitems, AR_GLOBAL_SLOTS)), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_ar_back, dim3(nb), dim3(256), 0, s, a, w, (int)base);
-        if (count && r4x16_route_snap(c, R4X16_ROUTE_ARITH, d_route, R4X16_ARITH_KINDS, s) != 0) return -1;
+        if (count) {
+            if (r4x16_route_snap(c, R4X16_ROUTE_ARITH, d_route, R4X16_ARITH_KINDS, s) != 0) return -1;
+            c->route[R4X16_ROUTE_LAUNCH][R4X16_LAUNCH_IN_ORDER]++;
+        }
     }
     HIPCHK(c, hipGetLastError());
     return r4x16_ws_order_end(c, s);

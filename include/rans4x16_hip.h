@@ -618,7 +618,9 @@ int rans4x16_hip_set_names_chunk_blocks(rans4x16_hip_ctx *ctx, int blocks);
  * free; NULL on failure), on the calling thread's context.  include/arith_dynamic_hip.h gives them the reference's names.
  *
  * Route read-out: R4X16_ROUTE_ARITH counts the entropy-coded streams (a stripe block's planes each) by where their models
- * live: R4X16_ARITH_O0, R4X16_ARITH_O1_LDS, R4X16_ARITH_O1_GLOBAL; those with run lengths count under R4X16_ARITH_RLE too. */
+ * live: R4X16_ARITH_O0, R4X16_ARITH_O1_LDS, R4X16_ARITH_O1_GLOBAL; those with run lengths count under R4X16_ARITH_RLE too.
+ * A batch above the workspace ceiling (option max_workspace_mb) is walked in chunks, and every chunk counts one
+ * R4X16_LAUNCH_IN_ORDER under R4X16_ROUTE_LAUNCH. */
 int rans4x16_hip_arith_uncompress_dev(rans4x16_hip_ctx *ctx, int n,
                                       const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
                                       unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
@@ -715,7 +717,8 @@ enum {
     R4X16_ROUTE_ENCODE = 0,   /* encode chain: streams per row kind (R4X16_ENC_*)                                    */
     R4X16_ROUTE_DECODE = 1,   /* decode chain: streams per row kind (R4X16_DEC_*)                                    */
     R4X16_ROUTE_EXPAND = 2,   /* run-length expansion: blocks of the calls whose expansion kernel was that kind       */
-    R4X16_ROUTE_LAUNCH = 3,   /* chain launches (encode and decode): in stream order, or classes side by side        */
+    R4X16_ROUTE_LAUNCH = 3,   /* chain launches (encode and decode): in stream order, or classes side by side; the    */
+                              /* arith call's chunks, in stream order                                                */
     R4X16_ROUTE_RESULT = 4,   /* encode results: blocks per way they reached the caller's memory (R4X16_RESULT_*)     */
     R4X16_ROUTE_NAMES = 5,    /* host-buffer names batches (part 2f): chunks and blocks (R4X16_NAMES_*)                */
     R4X16_ROUTE_ARITH = 6     /* arith_dynamic decoding (part 2g): streams per home of their models (R4X16_ARITH_*)    */

@@ -1,4 +1,5 @@
-"""What the GPU tests of arith_dynamic decoding share (test_gpu_arith.py, test_gpu_arith_hostile.py): one run of
+"""What the GPU tests of arith_dynamic decoding share (test_gpu_arith.py, test_gpu_arith_hostile.py,
+test_gpu_arith_trips.py): one run of
 rans4x16_hip_arith_uncompress_dev over a list of streams with the confinement pattern of test_gpu_confinement.py - the
 output slots a few bytes apart at every alignment in an arena filled with a pattern, every byte outside them compared
 afterwards - and the route the model expects."""
@@ -22,23 +23,31 @@ def expect(streams, caps, planes=0, stripe_out=0):
     return res, dict(route)
 
 
-def run_dev(dc, streams, caps, planes=0, stripe_out=0, stream=None, total=0, max_in=None, max_out=None):
+def run_dev(dc, streams, caps, planes=0, stripe_out=0, stream=None, total=0, max_in=None, max_out=None, in_off=None):
     """-> ([bytes or None], statuses, route).  Asserts that nothing outside the slots was written.  max_in / max_out /
-    total: what the call announces (default: the largest stream, the largest capacity, n x the largest capacity)."""
+    total: what the call announces (default: the largest stream, the largest capacity, n x the largest capacity).
+    in_off: where each stream lies in the input arena, whose start is 256-byte aligned (default: a few bytes apart,
+    from byte 3)."""
     import torch
     t = dc.torch if hasattr(dc, "torch") else torch
     n = len(streams)
     lay = Layout(caps, what=[s[:8].hex() for s in streams])
-    in_off, pos = [], 3
-    for i, s in enumerate(streams):
-        in_off.append(pos)
-        pos += len(s) + 1 + i % 7
+    if in_off is None:
+        in_off, pos = [], 3
+        for i, s in enumerate(streams):
+            in_off.append(pos)
+            pos += len(s) + 1 + i % 7
+    else:
+        spans = sorted((o, o + len(s)) for o, s in zip(in_off, streams))
+        assert len(in_off) == n and spans[0][0] >= 0 and all(a[1] <= b[0] for a, b in zip(spans, spans[1:]))
+        pos = spans[-1][1]
     arena_in = np.zeros(pos + 64, dtype=np.uint8)
     for o, s in zip(in_off, streams):
         arena_in[o:o + len(s)] = np.frombuffer(s, dtype=np.uint8)
     dev = dc.dev
     up = lambda a: t.from_numpy(a).to(dev)
     d_in, d_out = up(arena_in), up(lay.pattern.copy())
+    assert d_in.data_ptr() % 256 == 0
     d_ioff, d_ooff = up(np.array(in_off, dtype=np.int64)), up(lay.offs.copy())
     d_isz = up(np.array([len(s) for s in streams], dtype=np.int32))
     d_cap = up(np.array(caps, dtype=np.int64).astype(np.uint32).view(np.int32))

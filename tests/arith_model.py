@@ -182,8 +182,112 @@ def encode_core(data, order, rle):
     return bytes([m & 0xff]) + rc.finish()
 
 
-def decode_core(buf, pos, end, out_sz, order, rle):
-    """arith_uncompress_O0 / O1 / O0_RLE / O1_RLE over buf[pos:end], out_sz bytes; end > pos"""
+def _census_symbol(rc, m, ev, where):
+    """Decoder.symbol and Model._update once more, counting what the step did under (where, event): the census of
+    decode_core.  `where` is the home of a symbol model ("o0", "o1_lds", "o1_global") or "run" for a run-length model;
+    the boundary events - a swap at a list position that is a multiple of 4 above 0 - are a symbol model's alone."""
+    tot = m.tot
+    if tot and rc.range >= tot:
+        rc.range //= tot
+        freq = rc.code // rc.range
+    else:
+        freq = 0
+        ev[where, "range_lt_tot"] += 1
+    if freq > MAX_FREQ:
+        ev[where, "freq_gt_max"] += 1
+        return 0
+    F, S = m.F, m.S
+    acc, i, n = 0, 0, len(F)
+    while i < n:
+        acc += F[i]
+        if acc > freq:
+            break
+        i += 1
+    else:
+        ev[where, "ran_off"] += 1
+        return 0
+    acc -= F[i]
+    rc.code = (rc.code - acc * rc.range) & M32
+    rc.range = (rc.range * F[i]) & M32
+    while rc.range < TOP:
+        if rc.pos >= rc.end:
+            ev[where, "starved"] += 1
+            break
+        rc.code = ((rc.code << 8) + rc.buf[rc.pos]) & M32
+        rc.pos += 1
+        rc.range = (rc.range << 8) & M32
+    sym = S[i]
+    F[i] += STEP
+    m.tot += STEP
+    before = i > 0 and F[i] > F[i - 1]
+    halved = m.tot > MAX_FREQ
+    if halved:
+        t = 0
+        for k in range(n):
+            F[k] -= F[k] >> 1
+            t += F[k]
+        m.tot = t
+    swap = i > 0 and F[i] > F[i - 1]
+    if swap:
+        F[i], F[i - 1] = F[i - 1], F[i]
+        S[i], S[i - 1] = S[i - 1], S[i]
+    edge = where != "run" and i > 0 and i % 4 == 0
+    for name, on in (("halve", halved), ("swap", swap), ("halve_swap", halved and swap),
+                     ("halve_tie", halved and before and not swap)):
+        if on:
+            ev[where, name] += 1
+            if edge and name != "halve":
+                ev[where, name + "_boundary"] += 1
+    return sym
+
+
+def _census_core(buf, pos, end, out_sz, order, rle, ev, where):
+    """decode_core's loop over _census_symbol, with the events of the run loop (under "run") and the payload's size:
+    ev[where, "payload", end - pos] counts the pieces of that size"""
+    m = buf[pos] or 256
+    models = [Model(m) for _ in range(256 if order else 1)]
+    runs = [Model(4) for _ in range(258)] if rle else None
+    rc = Decoder(buf, pos + 1, end)
+    ev[where, "payload", end - pos] += 1
+    if pos + 6 >= end:
+        ev[where, "short_start"] += 1
+    out = bytearray(out_sz)
+    last, i = 0, 0
+    while i < out_sz:
+        c = _census_symbol(rc, models[last if order else 0], ev, where)
+        out[i] = c
+        last = c
+        if rle:
+            run, rctx, trips = 0, last, 0
+            while True:
+                if rctx == 257:
+                    ev["run", "ctx257"] += 1
+                r = _census_symbol(rc, runs[rctx], ev, "run")
+                rctx = _run_ctx(rctx, last)
+                run += r
+                trips += 1
+                if not (r == 3 and run < out_sz):
+                    break
+            if trips >= 3:
+                ev["run", "chain3"] += 1
+            if r == 3:
+                ev["run", "chain_cut"] += 1
+            if run > out_sz - 1 - i:
+                ev["run", "run_clipped"] += 1
+            while run and i + 1 < out_sz:
+                run -= 1
+                i += 1
+                out[i] = last
+        i += 1
+    return bytes(out)
+
+
+def decode_core(buf, pos, end, out_sz, order, rle, events=None, where=None):
+    """arith_uncompress_O0 / O1 / O0_RLE / O1_RLE over buf[pos:end], out_sz bytes; end > pos.  events: a
+    collections.Counter that takes the census of this piece (_census_core: the same bytes by a loop that counts), under
+    the home `where`; None: nothing is counted."""
+    if events is not None:
+        return _census_core(buf, pos, end, out_sz, order, rle, events, where)
     m = buf[pos] or 256
     models = [Model(m) for _ in range(256 if order else 1)]
     runs = [Model(4) for _ in range(258)] if rle else None
@@ -319,9 +423,10 @@ def lds_home(m):
     return m * ((m + 3) // 4 * 4) * 4 + m * 4 <= 32768 - 258 * 16
 
 
-def _piece(buf, pos, end, cap, trace=None):
+def _piece(buf, pos, end, cap, trace=None, events=None):
     """One stream without X_STRIPE at buf[pos:end]; cap None: the size comes from the stream.  (status, bytes).
-    trace: a list that takes the route kind of the entropy-coded piece, and "rle" if it carries run lengths."""
+    trace: a list that takes the route kind of the entropy-coded piece, and "rle" if it carries run lengths.
+    events: decode_core's census counter."""
     flags = buf[pos]
     p = pos + 1
     if flags & X_NOSZ:
@@ -354,9 +459,10 @@ def _piece(buf, pos, end, cap, trace=None):
         elif flags & X_EXT:
             return E_UNSUPPORTED, b""
         else:
-            tmp = decode_core(buf, p, end, dec, (flags & 3) == 1, bool(flags & X_RLE))
+            home = "o0" if (flags & 3) != 1 else "o1_lds" if lds_home(buf[p] or 256) else "o1_global"
+            tmp = decode_core(buf, p, end, dec, (flags & 3) == 1, bool(flags & X_RLE), events, home)
             if trace is not None:
-                trace.append("o0" if (flags & 3) != 1 else "o1_lds" if lds_home(buf[p] or 256) else "o1_global")
+                trace.append(home)
                 if flags & X_RLE:
                     trace.append("rle")
     else:
@@ -369,16 +475,28 @@ def _piece(buf, pos, end, cap, trace=None):
     return OK, tmp
 
 
-def uncompress_to(buf, cap=None, max_planes=255, max_stripe_out=None, trace=None):
+def uncompress_to(buf, cap=None, max_planes=255, max_stripe_out=None, trace=None, events=None):
     """arith_uncompress_to(buf, len(buf), out, &cap); cap None: out == NULL.  max_planes / max_stripe_out: what
-    rans4x16_hip_set_dev_stripe_planes reserved (the device call's limits; None: no limit)."""
+    rans4x16_hip_set_dev_stripe_planes reserved (the device call's limits; None: no limit).  events: a
+    collections.Counter for the census of the pieces of an accepted block (decode_core); a block that is refused counts
+    nothing, as in `trace`: the device decodes none of its pieces."""
+    if events is None:
+        return _uncompress_to(buf, cap, max_planes, max_stripe_out, trace, None)
+    mine = type(events)()
+    res = _uncompress_to(buf, cap, max_planes, max_stripe_out, trace, mine)
+    if res[0] == OK:
+        events.update(mine)
+    return res
+
+
+def _uncompress_to(buf, cap, max_planes, max_stripe_out, trace, events):
     buf = bytes(buf)
     size = len(buf)
     if size == 0:
         return E_EMPTY, b""
     if not buf[0] & X_STRIPE:
         t = []
-        st, out = _piece(buf, 0, size, cap, t)
+        st, out = _piece(buf, 0, size, cap, t, events)
         if trace is not None and st == OK:
             trace.extend(t)
         return st, out
@@ -415,7 +533,7 @@ def uncompress_to(buf, cap=None, max_planes=255, max_stripe_out=None, trace=None
         want = ulen // N + (ulen % N > i)
         if buf[meta] & X_STRIPE:
             return E_UNSUPPORTED, b""                        # a plane that is itself a stripe stream: not supported
-        st, p = _piece(buf, meta, size, want, t)
+        st, p = _piece(buf, meta, size, want, t, events)
         if st:
             return st, b""
         if len(p) != want:

@@ -155,8 +155,8 @@ def test_what_the_call_announces_is_enforced_beside_good_neighbours(dc):
     # a block above max_in_size is not read; a stored size above max_out_size is refused (its slot would hold it)
     outs, st, _ = run_dev(dc, [good, long_in, good, long_out, good], [1000, 3000, 1000, 4000, 1037], max_in=len(good), max_out=1037)
     assert st == [0, U, 0, U, 0] and outs[0] == outs[2] == outs[4] == raw
-    # a batch that decodes to more than total_out_size: the stage arena holds two of these four blocks (1,008 bytes each
-    # of 2,000 + 16 a block); which two is not determined
+    # a batch that decodes to more than total_out_size: the total holds two of these four blocks (1,000 bytes each of
+    # 2,000); which two is not determined
     outs, st, _ = run_dev(dc, [good] * 4, [1000] * 4, total=2000)
     assert sorted(st) == [0, 0, U, U] and all(o == raw for o, x in zip(outs, st) if x == 0)
 

@@ -1,5 +1,6 @@
 """Damaged arith_dynamic streams through the device call and the host batch (include/rans4x16_hip.h part 2g): the
-reference-answered ones of tests/golden/arith/edge.bin and a few hundred made from model-coded streams of at most 8 KB.
+reference-answered ones of tests/golden/arith/edge.bin, a few hundred made from model-coded streams of at most 8 KB, and
+some sixty of streams whose rows live in global memory and whose payload is longer than the coder's input window.
 Every case is compared and none is left out: a refused one must be refused with the walk's status, an accepted one must
 match the expected bytes, the neighbours' slots and the guard bytes must be untouched (arith_gpu.run_dev).  The inputs
 are bytes the decoder must survive; each is run once."""
@@ -50,6 +51,15 @@ def test_model_made_damaged_streams_through_the_device_call(dc):
     assert len(cases) >= 290
     _, st, _ = check(dc, [s for s, _ in cases], [c for _, c in cases], planes=PLANES, stripe_out=STRIPE_OUT)
     assert 40 < sum(1 for x in st if x) < len(st) - 40                # both verdicts are well represented
+
+
+def test_damaged_streams_of_the_global_home_through_the_device_call(dc):
+    """bases with an alphabet above 84 and more than 1 KiB of payload: the guards of the step with the rows in global
+    memory and the input window past its first refill (test_arith_inputs_cpu.py holds the list to that)"""
+    cases = K.global_damaged()
+    assert len(cases) >= 60
+    _, st, route = check(dc, [s for s, _ in cases], [c for _, c in cases], planes=PLANES, stripe_out=STRIPE_OUT)
+    assert route["o1_global"] >= 30 and any(st) and not all(st)
 
 
 def test_damaged_streams_through_the_host_batch_and_the_single_call(dc):
