@@ -15,6 +15,7 @@ from .codec import (  # noqa: F401
     rans_compress, rans_uncompress, compress_batch_4x8, uncompress_batch_4x8,
     tok3_level_methods, tok3_encode_names_batch, tok3_decode_names_batch, encode_names, decode_names,
     arith_uncompress, arith_uncompress_batch,
+    arith_compress, arith_compress_batch, arith_compress_bound, arith_compress_cap,
 )
 
 __all__ = [
@@ -24,4 +25,5 @@ __all__ = [
     "rans_compress", "rans_uncompress", "compress_batch_4x8", "uncompress_batch_4x8",
     "tok3_level_methods", "tok3_encode_names_batch", "tok3_decode_names_batch", "encode_names", "decode_names",
     "arith_uncompress", "arith_uncompress_batch",
+    "arith_compress", "arith_compress_batch", "arith_compress_bound", "arith_compress_cap",
 ]

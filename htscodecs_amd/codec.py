@@ -134,7 +134,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -145,7 +145,8 @@ class _Ctx:
 
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
-ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6}
+ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
+               "arith_enc": 7}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -154,6 +155,7 @@ ROUTE_KINDS = {
     "result": ("in_slot", "dense", "gathered"),
     "names": ("enc_chunks", "dec_chunks", "uploaded", "refused"),
     "arith": ("o0", "o1_lds", "o1_global", "rle"),
+    "arith_enc": ("o0", "o1_lds", "o1_global", "rle", "stored"),
 }
 
 _tls = threading.local()
@@ -455,6 +457,57 @@ def arith_uncompress(comp, out_size=None):
     return out.raw[:n.value] if p else None
 
 
+def arith_compress_bound(size, order):
+    """The reference's arith_compress_bound (host arithmetic)."""
+    return _lib.load().rans4x16_hip_arith_compress_bound(int(size), int(order))
+
+
+def arith_compress_cap(size, order):
+    """rans4x16_hip_arith_compress_cap: the smallest capacity a block of `size` bytes is accepted with under `order`."""
+    return _lib.load().rans4x16_hip_arith_compress_cap(int(size), int(order))
+
+
+def arith_compress_batch(blocks, orders, caps=None, ctx=None):
+    """rans4x16_hip_arith_compress_batch: blocks (bytes) and the order word of each -> (list of bytes | None, statuses).
+    caps: the capacity of each output (default: arith_compress_cap).  One upload, one device call, one download."""
+    ctx = ctx or _thread_ctx()
+    L = ctx.L
+    n = len(blocks)
+    if caps is None:
+        caps = [L.rans4x16_hip_arith_compress_cap(len(b), int(o)) for b, o in zip(blocks, orders)]
+    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+    outs = [np.empty(max(int(c), 1), dtype=np.uint8) for c in caps]
+    dummy = np.zeros(1, dtype=np.uint8)
+    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
+    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
+    out_sz = (C.c_uint * n)(*[int(c) for c in caps])
+    ords = (C.c_int * n)(*[int(o) for o in orders])
+    status = (C.c_int * n)()
+    rc = L.rans4x16_hip_arith_compress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, ords, status)
+    if rc < 0:
+        raise RuntimeError("arith batch failed: " + ctx.error())
+    return [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)], list(status)
+
+
+def arith_compress(data, order, out_size=None):
+    """The reference's arith_compress (out_size None) / arith_compress_to with a buffer of out_size bytes: the stream, or
+    None where the call returns NULL."""
+    L = _lib.load()
+    buf = bytes(data)
+    n = C.c_uint(0 if out_size is None else int(out_size))
+    if out_size is None:
+        p = L.rans4x16_hip_arith_compress(buf, len(buf), C.byref(n), int(order))
+        if not p:
+            return None
+        res = C.string_at(p, n.value)
+        _free(p)
+        return res
+    out = C.create_string_buffer(max(int(out_size), 1))
+    p = L.rans4x16_hip_arith_compress_to(buf, len(buf), out, C.byref(n), int(order))
+    return out.raw[:n.value] if p else None
+
+
 class DeviceCodec:
     """Device-resident batches on torch tensors (torch is used for device memory and streams
     only).  All tensors must live on the context's device."""
@@ -556,7 +609,7 @@ class DeviceCodec:
         if rc != 0:
             raise RuntimeError("uncompress_dev: " + self.ctx.error())
 
-    # ---- arith_dynamic decoding (include/rans4x16_hip.h part 2g) --------------------------------------------------
+    # ---- arith_dynamic, both directions (include/rans4x16_hip.h parts 2g, 2h) --------------------------------------------------
     def arith_uncompress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status,
                          max_in_size, max_out_size, total_out_size=0):
         """rans4x16_hip_arith_uncompress_dev: uncompress()'s arguments over arith_dynamic streams.  Enqueues only."""
@@ -571,6 +624,24 @@ class DeviceCodec:
             status.data_ptr(), int(max_in_size), int(max_out_size), int(total_out_size), self._stream())
         if rc != 0:
             raise RuntimeError("arith_uncompress_dev: " + self.ctx.error())
+
+    def arith_compress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status, order,
+                       max_in_size, d_order=None, total_in_size=0):
+        """rans4x16_hip_arith_compress_dev: compress()'s arguments, arith_dynamic streams out.  Enqueues only.  X_STRIPE
+        under d_order needs set_stripe_encode."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
+        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert d_order is None or d_order.dtype == t.int32
+        rc = self.L.rans4x16_hip_arith_compress_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(),
+            status.data_ptr(), int(order), d_order.data_ptr() if d_order is not None else None,
+            int(max_in_size), int(total_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("arith_compress_dev: " + self.ctx.error())
 
     def arith_peek(self, d_in, in_off, in_size, fmt, raw_size, status, max_in_size):
         """rans4x16_hip_arith_peek_dev: peek()'s arguments and results over arith_dynamic streams."""

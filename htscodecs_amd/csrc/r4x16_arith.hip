@@ -17,16 +17,7 @@
 // max_out_size by k_ar_front; an item that has no work enters none.  All stores are plain vector stores.
 #include "r4x16_host.h"
 #include "r4x16_arith_parse.h"
-
-#define AR_MAX_FREQ 65519u                       // c_simple_model.h MAX_FREQ
-#define AR_STEP 16u
-#define AR_TOP (1u << 24)
-#define AR_NRUN 258
-#define AR_LDS_BUDGET 32768u                     // order-1 wave: run models + rows + totals
-#define AR_RUN_BYTES (AR_NRUN * 16u)
-#define AR_ROWS_BYTES (AR_LDS_BUDGET - AR_RUN_BYTES)
-#define AR_GLOBAL_ROW_BYTES (256u * 256u * 4u + 256u * 4u)
-#define AR_GLOBAL_SLOTS 1024                     // waves of the global home in flight at most: four a compute unit
+#include "r4x16_arith_model.h"
 
 enum { AR_HOME_O0 = 0, AR_HOME_O1_LDS = 1, AR_HOME_O1_GLOBAL = 2, AR_HOME_NONE = 3 };
 
@@ -51,7 +42,6 @@ struct ArWs {
     u32 planes, stripe_out; // rans4x16_hip_set_dev_stripe_planes
 };
 
-__host__ __device__ static inline u32 ar_row_stride(u32 m) { return (m + 3u) & ~3u; }
 __host__ __device__ static inline u32 ar_rows_bytes(u32 m) { return m * ar_row_stride(m) * 4u + m * 4u; }
 
 // ---- front ------------------------------------------------------------------------------------------------------
@@ -182,13 +172,6 @@ struct ArCoder {
         }
     }
 };
-
-__device__ __forceinline__ u32 ar_get(const u32x4 &e, u32 k) { return k == 0 ? e.x : k == 1 ? e.y : k == 2 ? e.z : e.w; }
-__device__ __forceinline__ void ar_set(u32x4 &e, u32 k, u32 v, bool on)
-{
-    e.x = on && k == 0 ? v : e.x; e.y = on && k == 1 ? v : e.y; e.z = on && k == 2 ? v : e.z; e.w = on && k == 3 ? v : e.w;
-}
-__device__ __forceinline__ u32 ar_half(u32 e) { const u32 f = e & 0xffffu; return (e & 0xffff0000u) | (f - (f >> 1)); }
 
 // One symbol of a model that lies across the wave (SIMPLE_MODEL(256,_decodeSymbol), c_simple_model.h:148-179).  e: this
 // lane's four entries, zero beyond the live ones; tot: their sum over the wave.  *dirty: this lane's entries changed.

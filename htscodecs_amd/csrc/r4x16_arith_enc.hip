@@ -1,0 +1,739 @@
+// r4x16_arith_enc.hip - encoding with htscodecs' adaptive arithmetic codec (arith_dynamic.c:621-863 arith_compress_to, the
+// four core coders, c_simple_model.h, c_range_coder.h) on the device: include/rans4x16_hip.h part 2h.
+//
+// The mirror of r4x16_arith.hip, on its model layout (r4x16_arith_model.h) and with its three homes of the models:
+//   k_are_front   one wave per block: what arith_compress_to decides before it codes - the flag rules, the items (one for
+//                 a plain block; for an X_STRIPE block every candidate method of every plane), the transposition, hts_pack,
+//                 the alphabet byte - and the items' places in the stage arena
+//   k_are_encode  one wave per item: the models and the range coder (the hot loop); an item ends early once it cannot
+//                 come out smaller than its input, which the reference stores (X_CAT)
+//   k_are_back    a workgroup per block: the reference's bytes in the caller's slot - flag byte, sizes, pack map, body;
+//                 for a stripe block the first smallest candidate of every plane
+// The step, the early end and the capacity rule: DESIGN 4.7.
+//
+// Loops: the encode loop consumes an input byte a trip, the run loop three bytes of a run a trip; the flush of pending 0xFF
+// bytes runs over bytes counted before; the front's loops run over the block's bytes (size <= max_in_size) or its planes
+// (<= 255).  Stores: an item's stage slots hold its length rounded up to 16, plus 16 for the coded body, and are claimed
+// as a whole before anything is written; the coded body is cut off at the input's length (the early end), five closing
+// bytes at most behind it.  All stores are plain vector stores.
+#include "r4x16_host.h"
+#include "r4x16_arith_parse.h"
+#include "r4x16_arith_model.h"
+
+enum { ARE_NONE = 0, ARE_CODE = 1, ARE_STORED = 2 };
+#define ARE_CANDS 3u                             // candidate methods a plane has at most (arith_dynamic.c:690-693)
+#define ARE_META 28u                             // size varint 5, pack map 17, packed length 5
+
+struct AreItem {
+    u64 src;                // the bytes to code: in d_in, or in the stage arena (src_stage)
+    u64 out;                // the coded body in the stage arena: 16-byte aligned, n rounded up to 16, plus 16
+    u32 n;                  // bytes to code (after packing)
+    u32 body;               // bytes of the coded body, the alphabet byte included (k_are_encode)
+    u8 flags;               // the flag byte as the front resolved it; the fall-back to X_CAT is the back's
+    u8 state;               // ARE_*
+    u8 home;                // R4X16_ARITH_ENC_O0 / _O1_LDS / _O1_GLOBAL
+    u8 m;                   // the alphabet byte: the largest byte + 1 (0 means 256)
+    u8 src_stage, nmeta, rle, pad;
+    u8 meta[ARE_META];      // behind the flag byte: the size unless X_NOSZ, the pack map, the packed length
+};
+struct AreBlk { i32 status; u32 nplanes, flags, size; };          // nplanes 0: a plain block (item 0)
+struct AreWs {
+    AreItem *items;         // [nb * per]: block b's items from b * per, candidate c of plane j at j * ARE_CANDS + c
+    AreBlk *blk;            // [nb]
+    u64 *cursor;            // bytes of the stage arena handed out (a chunk's)
+    u32 *route;             // [R4X16_ARITH_ENC_KINDS]; nullptr in the kernels' copy: option route_count is off
+    u8 *stage;
+    u64 stage_bytes;
+    u8 *rows;               // [AR_GLOBAL_SLOTS] x AR_GLOBAL_ROW_BYTES
+    u32 per;                // items a block reserves: 1, or ARE_CANDS x planes
+    u32 planes;             // planes a stripe block may have (0: stripe blocks report UNSUPPORTED)
+};
+
+__host__ __device__ static inline u32 are_r16(u32 v) { return (v + 15u) & ~15u; }
+__host__ __device__ static inline bool are_lds_home(u32 m) { return m * ar_row_stride(m) * 4u + m * 4u <= AR_ROWS_BYTES; }
+// candidate c of plane j (:690-693), -1 past the last
+__host__ __device__ static inline int are_method(u32 j, u32 c)
+{
+    if (c == 0) return 1;
+    if (j == 0) return c == 1 ? 64 : c == 2 ? 0 : -1;
+    if (c > 1) return -1;
+    return j == 1 ? 0 : 128;
+}
+// what of the order word decides before any byte is read: 0, or the status of a block that is refused
+__host__ __device__ static inline int are_order_check(u32 size, int order, u32 *nplanes)
+{
+    *nplanes = 0;
+    if ((order & AR_X_STRIPE) && size > 20) {
+        const u32 N = (u32)order >> 8 ? (u32)order >> 8 : 4u;
+        if (N > 255) return AR_E_UNSUPPORTED;                        // :648: the reference's NULL
+        *nplanes = N;
+        return AR_OK;
+    }
+    return (order & AR_X_EXT) ? AR_E_UNSUPPORTED : AR_OK;            // bzip2: a reference built without it
+}
+__host__ __device__ static inline u32 are_cap(u32 size, int order)
+{
+    u32 N;
+    // a plain block: flag 1, size 5, pack map 17, packed length 5.  A stripe block: flag, size, N; a plane its length (5) and,
+    // where method 1 is among its candidates (an odd order), at most the flag and the bytes themselves; under an even
+    // order a plane from the third on has X_PACK alone and may carry the map and the packed length as well
+    if (are_order_check(size, order, &N) == AR_OK && N) return size + 7u + ((order & 1) ? 6u : 28u) * N;
+    return size + 28u;
+}
+// stage bytes of one plane of len bytes coded as candidates [0, nc): its copy (a stripe block's), its packed form, the bodies
+__host__ __device__ static inline u64 are_plane_need(u32 len, bool copy, bool pack, u32 nc)
+{
+    return (copy ? (u64)are_r16(len) : 0ull) + (pack ? (u64)are_r16((len + 1u) / 2u) : 0ull) + (u64)nc * ((u64)are_r16(len) + 16u);
+}
+
+// ---- front ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 wave_max(u32 v)
+{
+    for (int o = 32; o; o >>= 1) { const u32 x = (u32)__shfl_xor((int)v, o); v = x > v ? x : v; }
+    return v;
+}
+
+struct ArePlane {           // wave-uniform
+    const u8 *raw; u32 len, max_raw;
+    u64 raw_at; bool raw_stage;
+    u32 nsym;               // hts_pack's count (0: not looked at)
+    u64 pk_at; u32 pk_len, max_pk;
+    u8 map[16];
+};
+
+// The plane's bytes: read at in[x * stride], copied to `copy` (or nullptr), their maximum, and under `seen` the symbols
+// that occur.  All lanes.
+__device__ static u32 are_scan(const u8 *in, u32 stride, u32 len, u8 *copy, u32 *seen, u32 lane)
+{
+    u32 mx = 0;
+    for (u32 x = lane; x < len; x += WAVE) {
+        const u32 c = in[(size_t)x * stride];
+        mx = c > mx ? c : mx;
+        if (copy) copy[x] = (u8)c;
+        if (seen) seen[c] = 1u;
+    }
+    return wave_max(mx);
+}
+
+// hts_pack (pack.c:56-151) of P.raw into dst: seen[] holds the symbols that occur and becomes symbol -> code
+__device__ static void are_pack(ArePlane &P, u8 *dst, u32 *seen, u32 lane)
+{
+    u32 n = 0;
+    for (u32 q = 0; q < 4; q++) {
+        const u32 s = q * WAVE + lane;
+        const bool p = seen[s] != 0;
+        const u64 mask = __ballot(p);
+        const u32 rank = n + (u32)__popcll(mask & ((1ull << lane) - 1ull));
+        n += (u32)__popcll(mask);
+        wsync();
+        seen[s] = rank;
+        // (the map's entries: lane-uniform registers, so each is read from the lane that found it)
+        for (u32 k = 0; k < 16; k++) {
+            const u64 at = __ballot(p && rank == k);
+            if (at) P.map[k] = (u8)(q * WAVE + (u32)__builtin_ctzll(at));
+        }
+    }
+    wsync();
+    P.nsym = n;
+    P.pk_len = 0; P.max_pk = 0;
+    if (n > 16 || n <= 1) return;
+    const u32 per = n > 4 ? 2u : n > 2 ? 4u : 8u, bits = 8u / per;
+    P.pk_len = (P.len + per - 1) / per;
+    u32 mx = 0;
+    for (u32 k = lane; k < P.pk_len; k += WAVE) {
+        u32 b = 0;
+        for (u32 t = 0; t < per; t++) { const u32 x = k * per + t; if (x < P.len) b |= seen[P.raw[x]] << (bits * t); }
+        dst[k] = (u8)b;
+        mx = b > mx ? b : mx;
+    }
+    P.max_pk = wave_max(mx);
+}
+
+__device__ __forceinline__ u32 are_var_len(u32 v)
+{
+    u32 groups = 1;
+    for (u32 t = v >> 7; t; t >>= 7) groups++;
+    return groups;
+}
+__device__ __forceinline__ u32 are_var_put(u8 *cp, u32 v)
+{
+    u32 groups = 1;
+    for (u32 t = v >> 7; t; t >>= 7) groups++;
+    for (u32 g = groups; g-- > 0;) *cp++ = (u8)(((v >> (7u * g)) & 0x7fu) | (g ? 0x80u : 0u));
+    return groups;
+}
+
+// One candidate: plane P under `order` (a plain block's order word, a plane's method | X_NOSZ), as :760-811 resolve it.
+// Lane 0 writes the item; every lane gets its state.
+__device__ static u32 are_item(AreItem *dst, const ArePlane &P, u32 order, u64 in_base, u64 out_at, u32 lane, u32 *route)
+{
+    AreItem it;
+    u32 flags = order & 0xffu, ord = order & 3u, n = P.len, nm = 0;
+    it.src = P.raw_stage ? P.raw_at : in_base; it.src_stage = P.raw_stage;
+    u32 mx = P.max_raw;
+    if (!(flags & AR_X_NOSZ)) nm += are_var_put(it.meta + nm, P.len);
+    if ((flags & AR_X_PACK) && P.len) {
+        if (P.nsym > 16 && P.nsym != 256) flags &= ~(u32)AR_X_PACK;
+        else if (P.nsym == 256) { it.meta[nm++] = 0; nm += are_var_put(it.meta + nm, P.len); }   // the count byte wraps: the flag stays
+        else {
+            it.meta[nm++] = (u8)P.nsym;
+            for (u32 k = 0; k < P.nsym; k++) it.meta[nm++] = P.map[k];
+            n = P.pk_len; mx = P.max_pk;
+            nm += are_var_put(it.meta + nm, n);
+            it.src = P.pk_at; it.src_stage = 1;
+        }
+    } else flags &= ~(u32)AR_X_PACK;
+    if ((flags & AR_X_RLE) && !n) flags &= ~(u32)AR_X_RLE;
+    if (ord && n < 8) { flags &= ~3u; ord = 0; }
+    it.n = n; it.body = 0; it.out = out_at;
+    it.flags = (u8)flags; it.nmeta = (u8)nm; it.pad = 0;
+    it.m = (u8)(n ? mx + 1u : 1u);
+    it.rle = (flags & AR_X_RLE) != 0;
+    const u32 m = it.m ? it.m : 256u;
+    it.home = ord == 1 ? (are_lds_home(m) ? R4X16_ARITH_ENC_O1_LDS : R4X16_ARITH_ENC_O1_GLOBAL) : R4X16_ARITH_ENC_O0;
+    it.state = (flags & AR_X_CAT) ? ARE_STORED : ARE_CODE;          // an explicit X_CAT stores the bytes
+    for (u32 k = nm; k < ARE_META; k++) it.meta[k] = 0;
+    if (lane == 0) {
+        *dst = it;
+        if (route) {
+            if (it.state == ARE_STORED) atomicAdd(&route[R4X16_ARITH_ENC_STORED], 1u);
+            else {
+                atomicAdd(&route[it.home], 1u);
+                if (it.rle) atomicAdd(&route[R4X16_ARITH_ENC_RLE], 1u);
+            }
+        }
+    }
+    return it.state;
+}
+
+__global__ __launch_bounds__(256) void k_are_front(BatchArgs a, AreWs w, int base, int nb, u32 max_in)
+{
+    __shared__ u32 seen_all[4][256];
+    const u32 lane = threadIdx.x & 63u;
+    u32 *seen = seen_all[threadIdx.x >> 6];
+    const int b = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (b >= nb) return;
+    const int g = base + b;
+    const u32 size = a.in_size[g], cap = a.out_cap[g];
+    const int order = a.d_order ? a.d_order[g] : a.order;
+    AreItem *items = w.items + (size_t)b * w.per;
+    u32 N = 0;
+    int st = size > max_in ? AR_E_UNSUPPORTED : are_order_check(size, order, &N);
+    if (st == AR_OK && N > w.planes) st = AR_E_UNSUPPORTED;                          // more planes than the call reserved
+    if (st == AR_OK && cap < are_cap(size, order)) st = AR_E_CAPACITY;
+    // the block's stage bytes, from its size and its order word alone, claimed before anything is written
+    const u32 even = (order & 3) == 0;
+    u64 need = 0;
+    if (st == AR_OK) {
+        if (!N) need = are_plane_need(size, false, (order & AR_X_PACK) != 0, 1);
+        else for (u32 j = 0; j < N; j++) {
+            const u32 len = size / N + ((size % N) > j);
+            u32 nc = 0;
+            for (u32 c = 0; c < ARE_CANDS; c++) { const int mt = are_method(j, c); nc += mt >= 0 && !(even && (mt & 1)); }
+            need += are_plane_need(len, true, j >= 2, nc);
+        }
+    }
+    u64 at = 0;
+    if (st == AR_OK && lane == 0) at = atomicAdd((unsigned long long *)w.cursor, (unsigned long long)need);
+    at = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)at);
+    if (st == AR_OK && at + need > w.stage_bytes) st = AR_E_UNSUPPORTED;             // (the arena holds what the host sized it for)
+    u32 live = 0;
+    if (st == AR_OK) {
+        const u8 *in = a.in + a.in_off[g];
+        const u32 P_n = N ? N : 1u;
+        live = N ? N * ARE_CANDS : 1u;
+        for (u32 j = 0; j < P_n; j++) {
+            ArePlane P;
+            P.len = N ? size / N + ((size % N) > j) : size;
+            P.nsym = 0; P.pk_at = 0; P.pk_len = 0; P.max_pk = 0;
+            for (u32 k = 0; k < 16; k++) P.map[k] = 0;
+            bool pack = false;
+            if (!N) pack = (order & AR_X_PACK) != 0 && size != 0;
+            else pack = j >= 2 && P.len != 0;
+            if (pack) { for (u32 k = lane; k < 256; k += WAVE) seen[k] = 0; wsync(); }
+            P.raw_stage = N != 0;
+            P.raw_at = at;
+            u8 *copy = N ? w.stage + at : nullptr;
+            P.max_raw = are_scan(in + (N ? j : 0u), N ? N : 1u, P.len, copy, pack ? seen : nullptr, lane);
+            if (N) at += are_r16(P.len);
+            wsync();                                                                 // the copy and the symbols seen, before they are read
+            P.raw = N ? copy : in;
+            if (!N ? (order & AR_X_PACK) != 0 : j >= 2) {
+                P.pk_at = at;
+                if (pack) are_pack(P, w.stage + at, seen, lane);
+                at += are_r16((P.len + 1u) / 2u);
+                wsync();
+            }
+            if (!N) { are_item(items, P, (u32)order & ~(u32)AR_X_STRIPE, a.in_off[g], at, lane, w.route); break; }   // (:634: 20 bytes and fewer are not striped)
+            for (u32 c = 0; c < ARE_CANDS; c++) {
+                const int mt = are_method(j, c);
+                AreItem *dst = items + (size_t)j * ARE_CANDS + c;
+                if (mt < 0 || (even && (mt & 1))) { if (lane == 0) dst->state = ARE_NONE; continue; }
+                are_item(dst, P, (u32)mt | AR_X_NOSZ, 0, at, lane, w.route);
+                at += are_r16(P.len) + 16u;
+            }
+        }
+    }
+    for (u32 j = live + lane; j < w.per; j += WAVE) items[j].state = ARE_NONE;
+    if (lane == 0) {
+        AreBlk bk;
+        bk.status = st; bk.nplanes = st == AR_OK ? N : 0u; bk.flags = (u32)order & 0xffu & ~(u32)AR_X_NOSZ; bk.size = size;
+        w.blk[b] = bk;
+    }
+}
+
+// ---- the step ---------------------------------------------------------------------------------------------------
+// The bytes to code: ArCoder's window (r4x16_arith.hip) - 1 KB in registers, 16 bytes a lane, read by a scalar lane read;
+// the last bytes, which fill no whole 16-byte piece, come from memory
+struct AreIn {
+    const u8 *base;
+    u32x4 held;
+    u32 wbase, wlen, end;
+    __device__ AreIn(const u8 *in, u32 n) : base(in), held{0, 0, 0, 0}, wbase(0), wlen(0), end(n) {}
+    __device__ __forceinline__ void fill(u32 p, u32 lane)
+    {
+        wbase = p & ~15u;
+        const u32 mine = wbase + 16u * lane;
+        held = u32x4{0, 0, 0, 0};
+        if (mine + 16u <= end) held = *(const u32x4_unaligned *)(base + mine);
+        const u32 room = (end - wbase) & ~15u;
+        wlen = room < 1024u ? room : 1024u;
+    }
+    __device__ __forceinline__ u32 byte(u32 p, u32 lane)           // p < end
+    {
+        if (p - wbase >= wlen) {
+            if (p + 16u > end) return base[p];
+            fill(p, lane);
+        }
+        const u32 so = (u32)__builtin_amdgcn_readfirstlane((int)(p - wbase));
+        const int ln = (int)(so >> 4);
+        const u32 d0 = (u32)__builtin_amdgcn_readlane((int)held.x, ln), d1 = (u32)__builtin_amdgcn_readlane((int)held.y, ln),
+                  d2 = (u32)__builtin_amdgcn_readlane((int)held.z, ln), d3 = (u32)__builtin_amdgcn_readlane((int)held.w, ln);
+        const u32 lo = (so & 4u) ? d1 : d0, hi = (so & 4u) ? d3 : d2;
+        return (((so & 8u) ? hi : lo) >> (8u * (so & 3u))) & 0xffu;
+    }
+};
+
+// The range coder (c_range_coder.h:42-110) and its bytes, four at a time as ArOut stores them.  All of it wave-uniform.
+struct AreCoder {
+    u32 low, range, ffnum, carry, cache;
+    u32 *dst; u32 acc, n;
+    __device__ AreCoder(u32 *d, u32 first) : low(0), range(0xffffffffu), ffnum(0), carry(0), cache(0), dst(d), acc(first), n(1) {}
+    __device__ __forceinline__ void put(u32 b, u32 lane)
+    {
+        acc |= b << (8u * (n & 3u));
+        if ((++n & 3u) == 0) { if (lane == 0) dst[(n >> 2) - 1] = acc; acc = 0; }
+    }
+    __device__ __forceinline__ void flush(u32 lane) { if ((n & 3u) && lane == 0) dst[n >> 2] = acc; }
+    // bytes the body has for certain: written, or pending behind the cache byte
+    __device__ __forceinline__ u32 sure() const { return n + ffnum; }
+    __device__ __forceinline__ void shift_low(u32 lane)             // RC_ShiftLow, :71-89
+    {
+        if (low < 0xff000000u || carry) {
+            put((cache + carry) & 0xffu, lane);
+            for (; ffnum; ffnum--) put((carry - 1u) & 0xffu, lane);
+            cache = low >> 24;
+            carry = 0;
+        } else ffnum++;
+        low <<= 8;
+    }
+    __device__ __forceinline__ void encode(u32 cum, u32 f, u32 tot, u32 lane)      // RC_Encode, :97-104
+    {
+        const u32 old = low;
+        range /= tot;
+        low += cum * range;
+        range *= f;
+        carry += low < old;
+        while (range < AR_TOP) { range <<= 8; shift_low(lane); }
+    }
+    __device__ __forceinline__ void finish(u32 lane) { for (int k = 0; k < 5; k++) shift_low(lane); flush(lane); }
+};
+
+// One symbol of a model that lies across the wave (SIMPLE_MODEL(256,_encodeSymbol), c_simple_model.h:100-135): ar_symbol's
+// step with the search turned round - the entry is found by its symbol, its cumulative frequency by the scan.
+__device__ __forceinline__ void are_symbol(u32x4 &e, u32 &tot, u32 c, AreCoder &rc, u32 lane, bool *dirty)
+{
+    *dirty = false;
+    // live means frequency != 0: the positions behind the list read as symbol 0
+    const bool k0 = (e.x & 0xffffu) && (e.x >> 16) == c, k1 = (e.y & 0xffffu) && (e.y >> 16) == c,
+               k2 = (e.z & 0xffffu) && (e.z >> 16) == c, k3 = (e.w & 0xffffu) && (e.w >> 16) == c;
+    const u64 hit = __ballot(k0 || k1 || k2 || k3);
+    if (hit == 0) return;                                           // (cannot be: c is below the alphabet byte)
+    const int L = (int)__builtin_ctzll(hit);
+    const u32 j_l = k0 ? 0u : k1 ? 1u : k2 ? 2u : 3u;
+    const u32 c0 = e.x & 0xffffu, c1 = c0 + (e.y & 0xffffu), c2 = c1 + (e.z & 0xffffu), c3 = c2 + (e.w & 0xffffu);
+    const u32 incl = wave_incl_scan(c3, lane);
+    const u32 cum_l = incl - c3 + (j_l == 0 ? 0u : j_l == 1 ? c0 : j_l == 2 ? c1 : c2);
+    const u32 j = (u32)__builtin_amdgcn_readlane((int)j_l, L);
+    const u32 cum = (u32)__builtin_amdgcn_readlane((int)cum_l, L);
+    const u32 ent = (u32)__builtin_amdgcn_readlane((int)ar_get(e, j_l), L);
+    rc.encode(cum, ent & 0xffffu, tot, lane);
+    const bool own = lane == (u32)L;
+    u32 cur = ent + AR_STEP;                                         // (a frequency is at most the total: no carry into the symbol)
+    ar_set(e, j, cur, own);
+    tot += AR_STEP;
+    bool all = false;
+    if (tot > AR_MAX_FREQ) {                                        // normalise: every live entry, the total summed again
+        e.x = ar_half(e.x); e.y = ar_half(e.y); e.z = ar_half(e.z); e.w = ar_half(e.w);
+        cur = ar_half(cur);
+        tot = wave_sum((e.x & 0xffffu) + (e.y & 0xffffu) + (e.z & 0xffffu) + (e.w & 0xffffu));
+        all = true;
+    }
+    // one step of bubble sort: strictly greater than the position before (position 0 has the sentinel before it)
+    bool prev_lane = false;
+    if (j || L) {
+        const u32 prev = j ? (u32)__builtin_amdgcn_readlane((int)ar_get(e, j - 1), L) : (u32)__builtin_amdgcn_readlane((int)e.w, L - 1);
+        if ((cur & 0xffffu) > (prev & 0xffffu)) {
+            ar_set(e, j, prev, own);
+            if (j) ar_set(e, j - 1, cur, own);
+            else { ar_set(e, 3, cur, lane + 1 == (u32)L); prev_lane = lane + 1 == (u32)L; }
+        }
+    }
+    *dirty = own || all || prev_lane;
+}
+
+// One symbol of a run-length model (SIMPLE_MODEL(258,_encodeSymbol) after _init(.., 4)): four live entries, held by every
+// lane alike
+__device__ __forceinline__ void are_run_symbol(u32x4 &e, u32 part, AreCoder &rc, u32 lane)
+{
+    const u32 c0 = e.x & 0xffffu, c1 = c0 + (e.y & 0xffffu), c2 = c1 + (e.z & 0xffffu), c3 = c2 + (e.w & 0xffffu);
+    const u32 j = (e.x >> 16) == part ? 0u : (e.y >> 16) == part ? 1u : (e.z >> 16) == part ? 2u : 3u;
+    const u32 ent = ar_get(e, j);
+    rc.encode(j == 0 ? 0u : j == 1 ? c0 : j == 2 ? c1 : c2, ent & 0xffffu, c3, lane);
+    u32 cur = ent + AR_STEP;
+    ar_set(e, j, cur, true);
+    if (c3 + AR_STEP > AR_MAX_FREQ) {
+        e.x = ar_half(e.x); e.y = ar_half(e.y); e.z = ar_half(e.z); e.w = ar_half(e.w);
+        cur = ar_half(cur);
+    }
+    if (j) {
+        const u32 prev = ar_get(e, j - 1);
+        if ((cur & 0xffffu) > (prev & 0xffffu)) { ar_set(e, j, prev, true); ar_set(e, j - 1, cur, true); }
+    }
+}
+
+// HOME: R4X16_ARITH_ENC_O0 / _O1_LDS / _O1_GLOBAL.  One wave per item, the items of other homes passed over; the global
+// home's waves stride over the items, each with the row slot of its workgroup.
+template <int HOME>
+__global__ __launch_bounds__(64) void k_are_encode(const u8 *in, AreWs w, int nitems)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds[(HOME == R4X16_ARITH_ENC_O1_LDS ? AR_LDS_BUDGET : AR_RUN_BYTES) / 4];
+    const u32 lane = threadIdx.x;
+    u32x4 *runs = (u32x4 *)lds;
+    for (int it = (int)blockIdx.x; it < nitems; it += (int)gridDim.x) {
+        AreItem *item = w.items + it;
+        if (item->state != ARE_CODE || item->home != HOME) continue;
+        const bool rle = item->rle != 0;
+        const u32 n = item->n;
+        const u32 m = item->m ? item->m : 256u;
+        const u32 stride = ar_row_stride(m);
+        u32 *rows = HOME == R4X16_ARITH_ENC_O1_LDS ? lds + AR_RUN_BYTES / 4 : (u32 *)(w.rows + (size_t)blockIdx.x * AR_GLOBAL_ROW_BYTES);
+        u32 *tots = rows + (HOME == R4X16_ARITH_ENC_O1_LDS ? m * stride : 256u * 256u);
+        if (rle) for (u32 k = lane; k < AR_NRUN * 4u; k += WAVE) lds[k] = 1u | ((k & 3u) << 16);
+        u32x4 e = {0, 0, 0, 0};
+        u32 tot = m;
+        if (HOME == R4X16_ARITH_ENC_O0) {
+            const u32 p = 4u * lane;
+            e.x = p < m ? 1u | (p << 16) : 0u; e.y = p + 1 < m ? 1u | ((p + 1) << 16) : 0u;
+            e.z = p + 2 < m ? 1u | ((p + 2) << 16) : 0u; e.w = p + 3 < m ? 1u | ((p + 3) << 16) : 0u;
+        } else {
+            for (u32 k = lane; k < m * stride; k += WAVE) { const u32 s = k % stride; rows[k] = s < m ? 1u | (s << 16) : 0u; }
+            for (u32 k = lane; k < m; k += WAVE) tots[k] = m;
+        }
+        wsync();
+        AreIn src(item->src_stage ? w.stage + item->src : in + item->src, n);
+        AreCoder rc((u32 *)(w.stage + item->out), m & 0xffu);
+        u32 last = 0, i = 0;
+        const bool mine = 4u * lane < stride;
+        // the early end: the body only grows, and the reference stores the bytes once it is no smaller than they are (:850)
+        bool stored = rc.sure() >= n;
+        while (!stored && i < n) {
+            bool dirty;
+            const u32 c = src.byte(i++, lane);
+            if (HOME == R4X16_ARITH_ENC_O0) are_symbol(e, tot, c, rc, lane, &dirty);
+            else {
+                u32x4 *row = (u32x4 *)(rows + last * stride);
+                e = mine ? row[lane] : u32x4{0, 0, 0, 0};
+                tot = tots[last];
+                are_symbol(e, tot, c, rc, lane, &dirty);
+                if (dirty && mine) row[lane] = e;
+                if (lane == 0) tots[last] = tot;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the next step's row may be this one
+            }
+            last = c;
+            stored = rc.sure() >= n;
+            if (rle && !stored) {
+                u32 run = 0, rctx = last;
+                while (i < n && src.byte(i, lane) == last) { run++; i++; }
+                do {                                                               // arith_dynamic.c:432-443, :548-559
+                    const u32 part = run < 4u ? run : 3u;
+                    u32x4 re = runs[rctx];
+                    are_run_symbol(re, part, rc, lane);
+                    if (lane == 0) runs[rctx] = re;
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    run -= part;
+                    rctx = rctx == last ? 256u : rctx + (rctx < AR_NRUN - 1u);
+                    if (part == 3u && run == 0) {                                  // the closing zero
+                        re = runs[rctx];
+                        are_run_symbol(re, 0u, rc, lane);
+                        if (lane == 0) runs[rctx] = re;
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    }
+                    stored = rc.sure() >= n;
+                } while (run && !stored);
+            }
+        }
+        if (!stored) { rc.finish(lane); stored = rc.n >= n; }
+        if (lane == 0) {
+            item->body = rc.n;
+            if (stored) item->state = ARE_STORED;
+            if (stored && w.route) atomicAdd(&w.route[R4X16_ARITH_ENC_STORED], 1u);
+        }
+        wsync();                                                                   // the next item's models overwrite these
+    }
+}
+
+// ---- back -------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 are_len(const AreItem &it) { return 1u + it.nmeta + (it.state == ARE_STORED ? it.n : it.body); }
+
+// One stream at dst: the flag byte with the bits of :851-852, what the front put behind it, the body or the bytes themselves
+__device__ __forceinline__ void are_put(u8 *dst, const AreItem &it, const u8 *in, const u8 *stage, u32 t)
+{
+    const bool cat = it.state == ARE_STORED;
+    if (t == 0) dst[0] = cat ? (u8)((it.flags & ~7u) | AR_X_CAT) : it.flags;
+    if (t < it.nmeta) dst[1 + t] = it.meta[t];
+    const u8 *src = cat ? (it.src_stage ? stage + it.src : in + it.src) : stage + it.out;
+    group_copy<256>(dst + 1 + it.nmeta, src, cat ? it.n : it.body, t);
+}
+
+__global__ __launch_bounds__(256) void k_are_back(BatchArgs a, AreWs w, int base)
+{
+    __shared__ u32 win[255], at[256];
+    const int b = (int)blockIdx.x, g = base + b;
+    const u32 t = threadIdx.x;
+    const AreBlk bk = w.blk[b];
+    if (bk.status != AR_OK) {
+        if (t == 0) { a.status[g] = bk.status; a.out_size[g] = 0; }
+        return;
+    }
+    const AreItem *items = w.items + (size_t)b * w.per;
+    u8 *dst = a.out + a.out_off[g];
+    const u32 cap = a.out_cap[g];                                    // (at least are_cap, the front's test: every result fits; tested all the same)
+    if (!bk.nplanes) {
+        const AreItem &it = items[0];
+        const bool fits = are_len(it) <= cap;
+        if (fits) are_put(dst, it, a.in, w.stage, t);
+        if (t == 0) { a.status[g] = fits ? AR_OK : AR_E_CAPACITY; a.out_size[g] = fits ? are_len(it) : 0u; }
+        return;
+    }
+    const u32 N = bk.nplanes;
+    if (t < N) {                                                     // the smallest candidate, the first of them in table order
+        u32 best = 0xffffffffu, bc = 0;
+        for (u32 c = 0; c < ARE_CANDS; c++) {
+            const AreItem &it = items[t * ARE_CANDS + c];
+            if (it.state == ARE_NONE) continue;
+            const u32 len = are_len(it);
+            if (len < best) { best = len; bc = c; }
+        }
+        win[t] = bc; at[t] = best;
+    }
+    __syncthreads();
+    if (t == 0) {                                                    // :672-677, :752: flags, size, N, the planes' lengths
+        u64 all = 2u + are_var_len(bk.size);
+        for (u32 j = 0; j < N; j++) all += (u64)are_var_len(at[j]) + at[j];
+        const bool fits = all <= cap;
+        if (fits) {
+            u32 p = 0;
+            dst[p++] = (u8)bk.flags;
+            p += are_var_put(dst + p, bk.size);
+            dst[p++] = (u8)N;
+            for (u32 j = 0; j < N; j++) p += are_var_put(dst + p, at[j]);
+            for (u32 j = 0; j < N; j++) { const u32 len = at[j]; at[j] = p; p += len; }
+        }
+        at[255] = fits;
+        a.status[g] = fits ? AR_OK : AR_E_CAPACITY; a.out_size[g] = fits ? (u32)all : 0u;
+    }
+    __syncthreads();
+    if (!at[255]) return;
+    for (u32 j = 0; j < N; j++) are_put(dst + at[j], items[j * ARE_CANDS + win[j]], a.in, w.stage, t);
+}
+
+// ---- the device call ----------------------------------------------------------------------------------------------
+static size_t are_layout(u8 *base, size_t nb, size_t per, u64 stage_bytes, AreWs *w)
+{
+    Carver cv(base);
+    w->cursor = cv.take<u64>(1);
+    w->items = cv.take<AreItem>(nb * per);
+    w->blk = cv.take<AreBlk>(nb);
+    w->route = cv.take<u32>(R4X16_ARITH_ENC_KINDS);
+    w->stage = cv.take<u8>(stage_bytes);
+    w->stage_bytes = stage_bytes;
+    w->rows = cv.take<u8>((size_t)std::min<size_t>(nb * per, AR_GLOBAL_SLOTS) * AR_GLOBAL_ROW_BYTES);
+    w->per = (u32)per;
+    return cv.total();
+}
+
+extern "C" unsigned int rans4x16_hip_arith_compress_bound(unsigned int size, int order)
+{
+    // arith_dynamic.c:80-86, its expression in its order of evaluation (the sum is a double, converted at the end)
+    return (unsigned int)((order == 0
+        ? 1.05 * size + 257 * 3 + 4
+        : 1.05 * size + 257 * 257 * 3 + 4 + 257 * 3 + 4) +
+        ((order & AR_X_PACK) ? 1 : 0) +
+        ((order & AR_X_RLE) ? 1 + 257 * 3 + 4 : 0) + 5);
+}
+
+extern "C" unsigned int rans4x16_hip_arith_compress_cap(unsigned int size, int order) { return are_cap(size, order); }
+
+extern "C" int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *c, int n,
+                                               const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                               unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                               uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
+                                               uint32_t max_in_size, uint64_t total_in_size, void *stream)
+{
+    if (!c) return -1;
+    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
+        c->err = "arith_compress_dev: bad arguments";
+        return -1;
+    }
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // the planes a stripe block may have: the one order's own, or what rans4x16_hip_set_dev_stripe_encode reserved
+    u32 planes = 0;
+    if (d_order) planes = (u32)c->dev_stripe_enc;
+    else if (are_order_check(21u, order, &planes) != AR_OK) planes = 0;
+    const size_t per = planes ? (size_t)planes * ARE_CANDS : 1;
+    // the stage arena: a plain block's packed form and its body; a stripe block's planes, their packed forms and a body
+    // a candidate (are_plane_need: 4.5 bytes a byte at most, and the roundings of every item)
+    const u64 total = total_in_size ? total_in_size : (u64)n * max_in_size;
+    AreWs w;
+    auto stage_for = [&](size_t nb) {
+        const u64 tot = std::min<u64>(total, (u64)nb * max_in_size);
+        return tot * (planes ? 5u : 2u) + 64ull * nb * per + 64ull * nb;
+    };
+    auto bytes_for = [&](size_t nb) { return are_layout(nullptr, nb, per, stage_for(nb), &w); };
+    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / per, r4x16_room(c, A_BIT(A_AR)), bytes_for);
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_AR, bytes_for(nb), false); }) != 0) return -1;
+    BatchArgs a;
+    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
+    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
+    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
+    for (size_t base = 0; base < (size_t)n; base += chunk) {
+        const int nb = (int)std::min(chunk, (size_t)n - base);
+        are_layout(c->at(A_AR), (size_t)nb, per, stage_for((size_t)nb), &w);
+        w.planes = planes;
+        const int nitems = nb * (int)per;
+        const bool count = c->opts.v[OPT_ROUTE_COUNT] != 0;
+        u32 *const d_route = w.route;
+        HIPCHK(c, hipMemsetAsync(w.cursor, 0, sizeof(u64), s));
+        if (count) HIPCHK(c, hipMemsetAsync(d_route, 0, R4X16_ARITH_ENC_KINDS * sizeof(u32), s));
+        else w.route = nullptr;
+        hipLaunchKernelGGL(k_are_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, w, (int)base, nb, max_in_size);
+        hipLaunchKernelGGL(k_are_encode<R4X16_ARITH_ENC_O0>, dim3(nitems), dim3(64), 0, s, d_in, w, nitems);
+        hipLaunchKernelGGL(k_are_encode<R4X16_ARITH_ENC_O1_LDS>, dim3(nitems), dim3(64), 0, s, d_in, w, nitems);
+        hipLaunchKernelGGL(k_are_encode<R4X16_ARITH_ENC_O1_GLOBAL>, dim3(std::min(nitems, AR_GLOBAL_SLOTS)), dim3(64), 0, s, d_in, w, nitems);
+        hipLaunchKernelGGL(k_are_back, dim3(nb), dim3(256), 0, s, a, w, (int)base);
+        if (count) {
+            if (r4x16_route_snap(c, R4X16_ROUTE_ARITH_ENC, d_route, R4X16_ARITH_ENC_KINDS, s) != 0) return -1;
+            c->route[R4X16_ROUTE_LAUNCH][R4X16_LAUNCH_IN_ORDER]++;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    return r4x16_ws_order_end(c, s);
+}
+
+// ---- host buffers -------------------------------------------------------------------------------------------------
+// One upload, the device call with per-block orders, one download; not pipelined.  Stripe encoding is switched on for the
+// call (rans4x16_hip_set_dev_stripe_encode with the most planes of the batch) and the caller's setting put back.
+extern "C" int rans4x16_hip_arith_compress_batch(rans4x16_hip_ctx *c, int n,
+                                                 const unsigned char *const *in, const unsigned int *in_size,
+                                                 unsigned char *const *out, unsigned int *out_size, const int *order, int *status)
+{
+    if (!c) return -1;
+    if (n < 0 || (n && (!in || !in_size || !out || !out_size || !order || !status))) { c->err = "arith_compress_batch: bad arguments"; return -1; }
+    if (n == 0) return 0;
+    // what the order word and the capacity refuse is refused here, before anything is uploaded
+    std::vector<u64> in_off(n), out_off(n);
+    std::vector<u32> isz(n, 0), cap(n, 0);
+    std::vector<i32> ord(n, 0);
+    std::vector<u8> take(n, 0);
+    u32 max_in = 0, planes = 0;
+    int taken = 0, bad = 0;
+    for (int i = 0; i < n; i++) {
+        u32 N = 0;
+        status[i] = (in[i] || !in_size[i]) && out[i] ? are_order_check(in_size[i], order[i], &N) : R4X16_E_UNSUPPORTED;
+        if (status[i] == AR_OK && out_size[i] < are_cap(in_size[i], order[i])) status[i] = AR_E_CAPACITY;
+        if (status[i] != AR_OK) { out_size[i] = 0; bad++; continue; }
+        take[i] = 1; taken++;
+        isz[i] = in_size[i]; cap[i] = are_cap(in_size[i], order[i]); ord[i] = order[i];
+        max_in = std::max(max_in, isz[i]); planes = std::max(planes, N);
+    }
+    if (!taken) return bad;
+    HIPCHK(c, hipSetDevice(c->device));
+    // slots of the size rounded up to 16; a refused block takes none (its capacity 0 refuses it on the device as well)
+    const size_t in_total = r4x16_stage_slots(isz.data(), (size_t)n, 0, 16, in_off.data());
+    const size_t out_total = r4x16_stage_slots(cap.data(), (size_t)n, 0, 16, out_off.data());
+    hipStream_t s = c->stream;
+    StageLayout L;
+    if (r4x16_stage_begin(c, &L, (size_t)n, in_total + 16, 0, out_total + 16, 0,
+                          {in_off.data(), out_off.data(), isz.data(), cap.data(), ord.data()}, s) != 0)
+        return -1;
+    std::vector<u8> up(in_total + 1);
+    for (int i = 0; i < n; i++) if (isz[i]) memcpy(up.data() + in_off[i], in[i], isz[i]);
+    if (in_total) HIPCHK(c, hipMemcpyAsync(L.in, up.data(), in_total, hipMemcpyHostToDevice, s));
+    {
+        const int keep = c->dev_stripe_enc;
+        c->dev_stripe_enc = (int)planes;
+        const int rc = rans4x16_hip_arith_compress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
+                                                       0, L.order, max_in, in_total, s);
+        c->dev_stripe_enc = keep;
+        if (rc != 0) return -1;
+    }
+    std::vector<u8> down(out_total);
+    std::vector<u32> osz(n);
+    std::vector<i32> dstat(n);
+    HIPCHK(c, hipMemcpyAsync(down.data(), L.out, out_total, hipMemcpyDeviceToHost, s));
+    if (r4x16_stage_verdicts(c, L, (size_t)n, osz.data(), dstat.data(), s) != 0) return -1;
+    bad = 0;
+    for (int i = 0; i < n; i++) {
+        if (take[i]) {
+            status[i] = dstat[i];
+            out_size[i] = dstat[i] == 0 ? osz[i] : 0;
+            if (dstat[i] == 0 && osz[i]) memcpy(out[i], down.data() + out_off[i], osz[i]);
+        }
+        bad += status[i] != 0;
+    }
+    return bad;
+}
+
+// ---- the reference's calls (arith_dynamic.h), on the calling thread's context -------------------------------------
+extern "C" unsigned char *rans4x16_hip_arith_compress_to(unsigned char *in, unsigned int in_size,
+                                                        unsigned char *out, unsigned int *out_size, int order)
+{
+    if (!out_size || (!in && in_size)) return nullptr;
+    u32 N;
+    if (are_order_check(in_size, order, &N) != AR_OK) return nullptr;            // before any device is asked for
+    if (out && *out_size < are_cap(in_size, order)) return nullptr;
+    rans4x16_hip_ctx *c = r4x16_thread_ctx();
+    if (!c) return nullptr;
+    unsigned int cap = out ? *out_size : rans4x16_hip_arith_compress_bound(in_size, order);
+    unsigned char *buf = out ? out : (unsigned char *)malloc(cap);
+    if (!buf) return nullptr;
+    unsigned char none = 0;
+    const unsigned char *ins[1] = {in ? in : &none};
+    unsigned char *outs[1] = {buf};
+    unsigned int osz[1] = {cap};
+    int st[1] = {0};
+    const int rc = rans4x16_hip_arith_compress_batch(c, 1, ins, &in_size, outs, osz, &order, st);
+    r4x16_trim(c, SINGLE_CALL_KEEP);
+    if (rc != 0 || st[0] != 0) { if (!out) free(buf); return nullptr; }
+    *out_size = osz[0];
+    return buf;
+}
+
+extern "C" unsigned char *rans4x16_hip_arith_compress(unsigned char *in, unsigned int in_size, unsigned int *out_size, int order)
+{
+    return rans4x16_hip_arith_compress_to(in, in_size, nullptr, out_size, order);
+}

@@ -67,7 +67,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 7
+#define ROUTE_WHICH 8
 #define ROUTE_KINDS 8
 struct HostPipe;
 void r4x16_pipe_destroy(HostPipe *);
@@ -82,7 +82,7 @@ enum R4Arena {
     A_PS,        // the packed calls' internal bound-sized slots and layout arrays (r4x16_packed.hip)
     A_T3,        // tok3 containers: the winners waiting to be framed / the directory of the columns to decode (r4x16_tok3.hip)
     A_TN,        // tok3 names: the names' histories; for the one-call form the columns in front of them (r4x16_tok3_names.hip)
-    A_AR,        // arith_dynamic decoding: items, stage arena, the order-1 rows that do not fit LDS (r4x16_arith.hip)
+    A_AR,        // arith_dynamic, either direction: items, stage arena, the order-1 rows that do not fit LDS (r4x16_arith.hip, r4x16_arith_enc.hip)
     A_COUNT
 };
 #define A_BIT(a) (1u << (a))

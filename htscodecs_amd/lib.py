@@ -142,6 +142,16 @@ SIGNATURES = {
                                                      C.c_void_p, C.c_void_p]),
     "rans4x16_hip_arith_uncompress_to": (C.c_void_p, [C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_uint)]),
     "rans4x16_hip_arith_uncompress": (C.c_void_p, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint)]),
+    # arith_dynamic encoding (include/rans4x16_hip.h part 2h)
+    "rans4x16_hip_arith_compress_bound": (C.c_uint, [C.c_uint, C.c_int]),
+    "rans4x16_hip_arith_compress_cap": (C.c_uint, [C.c_uint, C.c_int]),
+    "rans4x16_hip_arith_compress_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "rans4x16_hip_arith_compress_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rans4x16_hip_arith_compress_to": (C.c_void_p, [C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_uint), C.c_int]),
+    "rans4x16_hip_arith_compress": (C.c_void_p, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint), C.c_int]),
     # rANS 4x8's packed and best-of-two device-resident calls (include/rans4x8_hip.h part 2a)
     "rans4x8_hip_compress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

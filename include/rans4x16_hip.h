@@ -582,8 +582,8 @@ int rans4x16_hip_set_names_chunk_blocks(rans4x16_hip_ctx *ctx, int blocks);
 /* ---- 2g. arith_dynamic decoding (the CRAM 3.1 adaptive arithmetic coder) ---------------------------------------
  * htscodecs/arith_dynamic.c's decoder on the device: one carry-less range coder and adaptive models per stream (order 0,
  * order 1, with or without the coder's own run lengths), inside the containers of rANS 4x16 (X_PACK, X_CAT, X_NOSZ,
- * X_STRIPE).  Decoding only: there is no arith encoder here yet, and tok3 containers with use_arith = 1 stay
- * R4X16_E_UNSUPPORTED (parts 2c-2f).  A stream is one serial chain of dependent steps: one wave decodes it, so a
+ * X_STRIPE).  The encoder is part 2h.  tok3 containers with use_arith = 1 stay R4X16_E_UNSUPPORTED (parts 2c-2f).
+ * A stream is one serial chain of dependent steps: one wave decodes it, so a
  * batch wants many streams.
  *
  * rans4x16_hip_arith_uncompress_dev has the arguments and the contract of rans4x16_hip_uncompress_dev_sized: it only
@@ -636,6 +636,60 @@ int rans4x16_hip_arith_uncompress_batch(rans4x16_hip_ctx *ctx, int n,
 unsigned char *rans4x16_hip_arith_uncompress_to(unsigned char *in, unsigned int in_size,
                                                 unsigned char *out, unsigned int *out_size);
 unsigned char *rans4x16_hip_arith_uncompress(unsigned char *in, unsigned int in_size, unsigned int *out_size);
+
+/* ---- 2h. arith_dynamic encoding -------------------------------------------------------------------------------
+ * htscodecs/arith_dynamic.c's arith_compress_to on the device: the bytes the reference writes, for every order word it
+ * takes - order 0 / 1, X_RLE, X_PACK, X_CAT, X_NOSZ and X_STRIPE with its candidate methods per plane, the smallest
+ * kept, the first smallest where several tie.  One wave encodes a stream, so a batch wants many.
+ *
+ * rans4x16_hip_arith_compress_bound: the reference's arith_compress_bound, host arithmetic.
+ *
+ * rans4x16_hip_arith_compress_dev has the arguments and the contract of rans4x16_hip_compress_dev_sized: it only enqueues
+ * on `stream`, reads nothing back, writes d_out_size / d_status per block and nothing outside a block's slot
+ * [d_out_off[i], d_out_off[i] + d_out_cap[i]).  `order` applies to all blocks unless d_order is given; total_in_size 0
+ * means n x max_in_size.  X_STRIPE blocks are encoded when one `order` serves all blocks; under d_order only after
+ * rans4x16_hip_set_dev_stripe_encode(ctx, max_planes), which reserves max_planes x 3 items a block.  Statuses:
+ *   R4X16_E_UNSUPPORTED  X_EXT (bzip2), as a reference built without libbz2; X_STRIPE with more than 255 planes (the
+ *                        reference's NULL), with more planes than reserved, or under d_order without the setting; a block
+ *                        above max_in_size (not read); in a batch larger than total_in_size the blocks that no longer fit
+ *   R4X16_E_CAPACITY     d_out_cap[i] below rans4x16_hip_arith_compress_cap(size, order): nothing is written
+ * Capacity.  The reference's behaviour with a buffer below arith_compress_bound is undefined (its core coders return NULL
+ * unnoticed, and the fall-back compares against a size nobody wrote).  The result here is defined as what
+ * arith_compress(in, size, &n, order) returns, and any capacity is accepted that holds the worst case of that result:
+ * size + 28 for a plain block (flag 1, size 5, pack map 17, packed length 5); size + 7 + 6 x N for a stripe block of N
+ * planes under an odd order (every plane has method 1 among its candidates: its length, a flag and at most its bytes),
+ * size + 7 + 28 x N under an even one (a plane from the third on is tried with X_PACK alone and may carry the map and
+ * the packed length besides).  rans4x16_hip_arith_compress_cap returns that value; it is never above the bound.  This
+ * deviation is confined to buffers the reference would have mishandled.
+ * Returns 0 if enqueued, -1 on argument / allocation errors.
+ *
+ * rans4x16_hip_arith_compress_batch: host buffers - out_size[i] holds the capacity of out[i] on entry and the size on
+ * return, status[i] the code, order[i] the block's order word.  One upload, the device call on the context's own stream,
+ * one download; it is not pipelined, and it synchronises.  Stripe blocks are encoded whatever the context's stripe
+ * setting, which is put back.  Returns the number of blocks refused, -1 on errors.
+ *
+ * rans4x16_hip_arith_compress_to / rans4x16_hip_arith_compress: the arguments and the ownership of the reference's
+ * arith_compress_to / arith_compress (out == NULL: a malloc'd buffer of the bound, the caller's to free; *out_size the
+ * capacity on entry and the size on return; NULL on failure), on the calling thread's context.
+ * include/arith_dynamic_hip.h gives them the reference's names.
+ *
+ * Route read-out: R4X16_ROUTE_ARITH_ENC counts the candidate streams (a stripe block's planes under each method) that
+ * reached the coder by the home of their models, those with run lengths under R4X16_ARITH_ENC_RLE too, and under
+ * R4X16_ARITH_ENC_STORED every candidate that came out as X_CAT: an explicit X_CAT, and a coded one that ended no smaller
+ * than its input (it is counted under its home as well).  Chunks count as in part 2g. */
+unsigned int rans4x16_hip_arith_compress_bound(unsigned int size, int order);
+unsigned int rans4x16_hip_arith_compress_cap(unsigned int size, int order);
+int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *ctx, int n,
+                                    const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                    unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                    uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
+                                    uint32_t max_in_size, uint64_t total_in_size, void *stream);
+int rans4x16_hip_arith_compress_batch(rans4x16_hip_ctx *ctx, int n,
+                                      const unsigned char *const *in, const unsigned int *in_size,
+                                      unsigned char *const *out, unsigned int *out_size, const int *order, int *status);
+unsigned char *rans4x16_hip_arith_compress_to(unsigned char *in, unsigned int in_size,
+                                              unsigned char *out, unsigned int *out_size, int order);
+unsigned char *rans4x16_hip_arith_compress(unsigned char *in, unsigned int in_size, unsigned int *out_size, int order);
 
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
@@ -721,7 +775,8 @@ enum {
                               /* arith call's chunks, in stream order                                                */
     R4X16_ROUTE_RESULT = 4,   /* encode results: blocks per way they reached the caller's memory (R4X16_RESULT_*)     */
     R4X16_ROUTE_NAMES = 5,    /* host-buffer names batches (part 2f): chunks and blocks (R4X16_NAMES_*)                */
-    R4X16_ROUTE_ARITH = 6     /* arith_dynamic decoding (part 2g): streams per home of their models (R4X16_ARITH_*)    */
+    R4X16_ROUTE_ARITH = 6,    /* arith_dynamic decoding (part 2g): streams per home of their models (R4X16_ARITH_*)    */
+    R4X16_ROUTE_ARITH_ENC = 7 /* arith_dynamic encoding (part 2h): candidate streams (R4X16_ARITH_ENC_*)               */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -761,6 +816,14 @@ enum {   /* R4X16_ROUTE_ARITH: entropy-coded streams of rans4x16_hip_arith_uncom
     R4X16_ARITH_O1_GLOBAL = 2,  /* order 1, the rows in the context's arena in global memory                           */
     R4X16_ARITH_RLE = 3,        /* those of the three above that carry run lengths (counted there too)                 */
     R4X16_ARITH_KINDS = 4
+};
+enum {   /* R4X16_ROUTE_ARITH_ENC: candidate streams of rans4x16_hip_arith_compress_dev */
+    R4X16_ARITH_ENC_O0 = 0,        /* coded with order 0: the model in registers                                        */
+    R4X16_ARITH_ENC_O1_LDS = 1,    /* coded with order 1, the rows in LDS                                               */
+    R4X16_ARITH_ENC_O1_GLOBAL = 2, /* coded with order 1, the rows in the context's arena in global memory              */
+    R4X16_ARITH_ENC_RLE = 3,       /* those of the three above that carry run lengths (counted there too)               */
+    R4X16_ARITH_ENC_STORED = 4,    /* candidates that came out as X_CAT: asked for, or ended no smaller than their input */
+    R4X16_ARITH_ENC_KINDS = 5
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
