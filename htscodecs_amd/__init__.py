@@ -14,6 +14,7 @@ from .codec import (  # noqa: F401
     compress_batch, compress_best_batch, uncompress_batch, DeviceCodec, MultiCodec,
     rans_compress, rans_uncompress, compress_batch_4x8, uncompress_batch_4x8,
     tok3_level_methods, tok3_encode_names_batch, tok3_decode_names_batch, encode_names, decode_names,
+    tok3_scan_any, set_tok3_arith, TOK3_ARITH_DECODE, TOK3_ARITH_ENCODE,
     arith_uncompress, arith_uncompress_batch,
     arith_compress, arith_compress_batch, arith_compress_bound, arith_compress_cap,
 )
@@ -24,6 +25,7 @@ __all__ = [
     "compress_batch", "compress_best_batch", "uncompress_batch", "DeviceCodec", "MultiCodec",
     "rans_compress", "rans_uncompress", "compress_batch_4x8", "uncompress_batch_4x8",
     "tok3_level_methods", "tok3_encode_names_batch", "tok3_decode_names_batch", "encode_names", "decode_names",
+    "tok3_scan_any", "set_tok3_arith", "TOK3_ARITH_DECODE", "TOK3_ARITH_ENCODE",
     "arith_uncompress", "arith_uncompress_batch",
     "arith_compress", "arith_compress_batch", "arith_compress_bound", "arith_compress_cap",
 ]

@@ -327,6 +327,48 @@ def tok3_scan(container, max_columns=0, max_col_size=0):
                 "total_col_size": total.value, "largest_col": u32[4].value, "largest_stream": u32[5].value}
 
 
+def tok3_scan_any(container, max_columns=0, max_col_size=0):
+    """rans4x16_hip_tok3_scan_any: tok3_scan for either flavour.  Returns (status, info, use_arith): a container whose byte
+    8 is set is walked by the same rules, not refused, and use_arith is 1 for it.  Needs no GPU."""
+    L = _lib.load()
+    buf = bytes(container)
+    u32 = [C.c_uint32(0) for _ in range(6)]
+    total = C.c_uint64(0)
+    arith = C.c_int(0)
+    rc = L.rans4x16_hip_tok3_scan_any(buf, len(buf), int(max_columns), int(max_col_size), C.byref(u32[0]), C.byref(u32[1]),
+                                      C.byref(u32[2]), C.byref(u32[3]), C.byref(total), C.byref(u32[4]), C.byref(u32[5]),
+                                      C.byref(arith))
+    if rc < 0:
+        raise ValueError("tok3_scan_any: bad arguments")
+    return rc, {"last_start": u32[0].value, "nreads": u32[1].value, "ndesc": u32[2].value, "ncol": u32[3].value,
+                "total_col_size": total.value, "largest_col": u32[4].value, "largest_stream": u32[5].value}, arith.value
+
+
+TOK3_ARITH_DECODE, TOK3_ARITH_ENCODE = 1, 2
+
+
+def set_tok3_arith(mode, ctx=None):
+    """rans4x16_hip_set_tok3_arith on the calling thread's context (or `ctx`): returns the previous mode."""
+    ctx = ctx or _thread_ctx()
+    was = ctx.L.rans4x16_hip_set_tok3_arith(ctx.h, int(mode))
+    if was < 0:
+        raise ValueError("set_tok3_arith: %r is outside 0..3" % (mode,))
+    return was
+
+
+def thread_tok3_arith(mode):
+    """rans4x16_hip_set_tok3_arith on rans4x16_hip_thread_ctx(), the library's own context of the calling thread - the one
+    the single-block symbols (encode_names, decode_names, ..) run on: returns the previous mode.  Needs a GPU."""
+    L = _lib.load()
+    h = L.rans4x16_hip_thread_ctx()
+    if not h:
+        raise RuntimeError("rans4x16_hip_thread_ctx: no usable HIP device")
+    was = L.rans4x16_hip_set_tok3_arith(h, int(mode))
+    if was < 0:
+        raise ValueError("set_tok3_arith: %r is outside 0..3" % (mode,))
+    return was
+
+
 def tok3_level_methods(level):
     """rans4x16_hip_tok3_level_methods: the method list encode_names tries per column at `level`.  Needs no GPU."""
     m = (C.c_int * 9)()
@@ -349,9 +391,16 @@ def set_names_chunk_blocks(blocks, ctx=None):
         raise ValueError("names_chunk_blocks: %r" % (blocks,))
 
 
-def _names_batch(blocks, encode, methods=None, ctx=None):
-    """Either names batch with out[i] == NULL: the library allocates exactly the results."""
+def _names_batch(blocks, encode, methods=None, ctx=None, tok3_arith=None):
+    """Either names batch with out[i] == NULL: the library allocates exactly the results.  tok3_arith: None leaves the
+    context's mode alone; 0 / 1 runs the call without / with the arith flavour and puts the context's mode back."""
     ctx = ctx or _thread_ctx()
+    if tok3_arith is not None:
+        was = set_tok3_arith((TOK3_ARITH_ENCODE if encode else TOK3_ARITH_DECODE) if tok3_arith else 0, ctx)
+        try:
+            return _names_batch(blocks, encode, methods, ctx)
+        finally:
+            set_tok3_arith(was, ctx)
     L = ctx.L
     n = len(blocks)
     srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
@@ -377,28 +426,34 @@ def _names_batch(blocks, encode, methods=None, ctx=None):
     return res, list(a), list(b), list(status)
 
 
-def tok3_encode_names_batch(blocks, level=None, methods=None, ctx=None):
+def tok3_encode_names_batch(blocks, level=None, methods=None, ctx=None, tok3_arith=None):
     """encode_names over a list of name blocks (bytes) in one call: (containers | None, last_starts, statuses).  The method
-    list is `methods`, or that of `level` (tok3_level_methods); nreads of block i is in container i's header."""
+    list is `methods`, or that of `level` (tok3_level_methods); nreads of block i is in container i's header.  tok3_arith:
+    1 writes the arith flavour (use_arith = 1), 0 the rANS one, None what the context's mode says (set_tok3_arith)."""
     if methods is None:
         methods = tok3_level_methods(9 if level is None else level)
-    res, last_start, _, status = _names_batch(blocks, True, methods=list(methods), ctx=ctx)
+    res, last_start, _, status = _names_batch(blocks, True, methods=list(methods), ctx=ctx, tok3_arith=tok3_arith)
     return res, last_start, status
 
 
-def tok3_decode_names_batch(containers, ctx=None):
-    """decode_names over a list of containers in one call: (names | None - NUL-separated, last_start bytes -, statuses)."""
-    res, _, _, status = _names_batch(containers, False, ctx=ctx)
+def tok3_decode_names_batch(containers, ctx=None, tok3_arith=None):
+    """decode_names over a list of containers in one call: (names | None - NUL-separated, last_start bytes -, statuses).
+    tok3_arith: 1 reads either flavour, block by block; 0 the rANS one alone; None what the context's mode says."""
+    res, _, _, status = _names_batch(containers, False, ctx=ctx, tok3_arith=tok3_arith)
     return res, status
 
 
-def encode_names(block, level):
+def encode_names(block, level, use_arith=0):
     """The single-block drop-in symbol: bytes -> (container, last_start) or None.  The caller's buffer is a copy here, so
-    the NULs the call writes over the separators are not seen."""
+    the NULs the call writes over the separators are not seen.  use_arith != 0 goes to the arith flavour's symbol, as
+    include/tok3_names_hip.h forwards it."""
     L = _lib.load()
     buf = C.create_string_buffer(bytes(block), max(len(block), 1))
     out_len, last_start = C.c_int(0), C.c_int(0)
-    p = L.rans4x16_hip_tok3_encode_names(buf, len(block), int(level), 0, C.byref(out_len), C.byref(last_start))
+    if use_arith:
+        p = L.rans4x16_hip_tok3_arith_encode_names(buf, len(block), int(level), C.byref(out_len), C.byref(last_start))
+    else:
+        p = L.rans4x16_hip_tok3_encode_names(buf, len(block), int(level), 0, C.byref(out_len), C.byref(last_start))
     if not p:
         return None
     res = C.string_at(p, out_len.value)
@@ -407,11 +462,13 @@ def encode_names(block, level):
 
 
 def decode_names(container):
-    """The single-block drop-in symbol: container bytes -> NUL-separated names or None."""
+    """The single-block drop-in symbol: container bytes -> NUL-separated names or None.  A container whose byte 8
+    (use_arith) is set goes to the arith flavour's symbol, as include/tok3_names_hip.h forwards it."""
     L = _lib.load()
     buf = bytes(container)
     out_len = C.c_uint32(0)
-    p = L.rans4x16_hip_tok3_decode_names(buf, len(buf), C.byref(out_len))
+    fn = L.rans4x16_hip_tok3_arith_decode_names if len(buf) > 8 and buf[8] else L.rans4x16_hip_tok3_decode_names
+    p = fn(buf, len(buf), C.byref(out_len))
     if not p:
         return None
     res = C.string_at(p, out_len.value)
@@ -689,6 +746,40 @@ class DeviceCodec:
             chosen.data_ptr() if chosen is not None else None, int(max_in_size), int(total_in_size), self._stream())
         if rc != 0:
             raise RuntimeError("compress_best_packed_dev: " + self.ctx.error())
+
+    def arith_compress_best_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size,
+                                   chosen=None, total_in_size=0, out_capacity=None):
+        """rans4x16_hip_arith_compress_best_packed_dev: compress_best_packed for the adaptive arithmetic coder.  d_out None
+        (with out_capacity 0 or None) is the sizing pass."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
+        assert in_off.dtype == t.int64 and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == in_off.numel() + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert chosen is None or chosen.dtype == t.int32
+        room = d_out.numel() if d_out is not None else 0
+        cap = room if out_capacity is None else int(out_capacity)
+        assert cap <= room
+        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        rc = self.L.rans4x16_hip_arith_compress_best_packed_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            len(methods), meth, chosen.data_ptr() if chosen is not None else None, int(max_in_size), int(total_in_size),
+            self._stream())
+        if rc != 0:
+            raise RuntimeError("arith_compress_best_packed_dev: " + self.ctx.error())
+
+    def arith_best_chunk_blocks(self, n, methods, max_in_size, total_in_size=0):
+        """rans4x16_hip_arith_best_chunk_blocks: the blocks per chunk arith_compress_best_packed plans for these arguments."""
+        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        rc = self.L.rans4x16_hip_arith_best_chunk_blocks(self.ctx.h, int(n), len(methods), meth, int(max_in_size), int(total_in_size))
+        if rc < 0:
+            raise RuntimeError("arith_best_chunk_blocks: " + self.ctx.error())
+        return rc
+
+    def set_tok3_arith(self, mode):
+        """rans4x16_hip_set_tok3_arith: 0, TOK3_ARITH_DECODE (1), TOK3_ARITH_ENCODE (2) or both; returns the previous mode."""
+        return set_tok3_arith(mode, self.ctx)
 
     def peek(self, d_in, in_off, in_size, fmt, raw_size, status, max_in_size):
         """rans4x16_hip_peek_dev: first byte (fmt, int32) and stored uncompressed size (raw_size, int32 holding the

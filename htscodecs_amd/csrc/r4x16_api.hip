@@ -267,6 +267,14 @@ extern "C" int rans4x16_hip_set_names_chunk_blocks(rans4x16_hip_ctx *c, int bloc
     return 0;
 }
 
+extern "C" int rans4x16_hip_set_tok3_arith(rans4x16_hip_ctx *c, int mode)
+{
+    if (!c || mode < 0 || mode > (R4X16_TOK3_ARITH_DECODE | R4X16_TOK3_ARITH_ENCODE)) return -1;
+    const int was = c->tok3_arith;
+    c->tok3_arith = mode;
+    return was;
+}
+
 extern "C" const char *rans4x16_hip_last_error(const rans4x16_hip_ctx *c) { return c ? c->err.c_str() : "no context"; }
 extern "C" size_t rans4x16_hip_workspace_bytes(const rans4x16_hip_ctx *c) { return c ? c->arena[A_WS].bytes : 0; }
 
@@ -720,6 +728,7 @@ static rans4x16_hip_ctx *thread_ctx()
 }
 
 rans4x16_hip_ctx *r4x16_thread_ctx() { return thread_ctx(); }
+extern "C" rans4x16_hip_ctx *rans4x16_hip_thread_ctx(void) { return thread_ctx(); }
 
 // ---------------------------------------------------------------------------------------------
 // The combiner behind the single-block entry points.  A CRAM reader / writer calls rans_compress_to_4x16 or

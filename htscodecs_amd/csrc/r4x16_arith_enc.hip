@@ -9,6 +9,9 @@
 //                 come out smaller than its input, which the reference stores (X_CAT)
 //   k_are_back    a workgroup per block: the reference's bytes in the caller's slot - flag byte, sizes, pack map, body;
 //                 for a stripe block the first smallest candidate of every plane
+// Best of k (rans4x16_hip_arith_compress_best_packed_dev, the end of this file): a chunk's blocks go through these three
+// kernels once, as k items each with the method as the item's order word, into slots of this unit's own; k_ab_pick takes
+// the smallest, k_pk_scan lays the winners out and k_ab_gather copies each to its place.
 // The step, the early end and the capacity rule: DESIGN 4.7.
 //
 // Loops: the encode loop consumes an input byte a trip, the run loop three bytes of a run a trip; the flush of pending 0xFF
@@ -573,6 +576,13 @@ static size_t are_layout(u8 *base, size_t nb, size_t per, u64 stage_bytes, AreWs
     return cv.total();
 }
 
+// the stage arena of nb blocks of a call that holds `total` bytes in blocks of at most max_in
+static u64 are_stage_bytes(size_t nb, size_t per, u32 planes, u64 total, u32 max_in)
+{
+    const u64 tot = std::min<u64>(total, (u64)nb * max_in);
+    return tot * (planes ? 5u : 2u) + 64ull * nb * per + 64ull * nb;
+}
+
 extern "C" unsigned int rans4x16_hip_arith_compress_bound(unsigned int size, int order)
 {
     // arith_dynamic.c:80-86, its expression in its order of evaluation (the sum is a double, converted at the end)
@@ -608,10 +618,7 @@ extern "C" int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *c, int n,
     // a candidate (are_plane_need: 4.5 bytes a byte at most, and the roundings of every item)
     const u64 total = total_in_size ? total_in_size : (u64)n * max_in_size;
     AreWs w;
-    auto stage_for = [&](size_t nb) {
-        const u64 tot = std::min<u64>(total, (u64)nb * max_in_size);
-        return tot * (planes ? 5u : 2u) + 64ull * nb * per + 64ull * nb;
-    };
+    auto stage_for = [&](size_t nb) { return are_stage_bytes(nb, per, planes, total, max_in_size); };
     auto bytes_for = [&](size_t nb) { return are_layout(nullptr, nb, per, stage_for(nb), &w); };
     size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / per, r4x16_room(c, A_BIT(A_AR)), bytes_for);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
@@ -640,6 +647,196 @@ extern "C" int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *c, int n,
             c->route[R4X16_ROUTE_LAUNCH][R4X16_LAUNCH_IN_ORDER]++;
         }
     }
+    HIPCHK(c, hipGetLastError());
+    return r4x16_ws_order_end(c, s);
+}
+
+// ---- best of k, results back to back --------------------------------------------------------------------------------
+// Candidate j of block lb of a chunk is item lb * k + j of one rans4x16_hip_arith_compress_dev call with per-item orders.
+// Its slot holds rans4x16_hip_arith_compress_cap of its size and method, rounded up to 16; the slots lie back to back
+// (k_pk_scan over their sizes), so a chunk's arena is k times its input plus a constant an item.  A candidate that is
+// not tried - a stripe method on a size that is no multiple of 4 (tokenise_name3.c:1270), a block above max_in_size, a
+// slot beyond the arena (a batch that holds more than it announced) - has capacity 0: the front refuses it before it
+// makes an item, so it is neither coded nor counted.
+#define AB_MAX_K 32
+struct AbMethods { int k; int m[AB_MAX_K]; };
+struct AbWs {
+    u64 *in_off, *slot_off /*[items + 1]*/; u32 *in_size, *need, *cap, *out_size; i32 *status, *order; u32 *win /*[nb]*/; u8 *slots; u64 slot_bytes;
+};
+
+static size_t ab_carve(AbWs *w, u8 *base, size_t nb, size_t k, u64 slot_bytes)
+{
+    const size_t items = nb * k;
+    Carver cv(base);
+    w->in_off = cv.take<u64>(items); w->slot_off = cv.take<u64>(items + 1);
+    w->in_size = cv.take<u32>(items); w->need = cv.take<u32>(items); w->cap = cv.take<u32>(items); w->out_size = cv.take<u32>(items);
+    w->status = cv.take<i32>(items); w->order = cv.take<i32>(items); w->win = cv.take<u32>(nb);
+    w->slots = cv.take<u8>((size_t)slot_bytes + 256);
+    w->slot_bytes = slot_bytes;
+    return cv.total();
+}
+
+__device__ __forceinline__ bool ab_skipped(u32 size, int method) { return (method & AR_X_STRIPE) && (size & 3u); }
+
+__global__ __launch_bounds__(256) void k_ab_expand(const u64 *in_off, const u32 *in_size, AbWs w, AbMethods pm, int base, u32 items, u32 max_in)
+{
+    const u32 q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= items) return;
+    const int g = base + (int)(q / (u32)pm.k), m = pm.m[q % (u32)pm.k];
+    const u32 sz = in_size[g];
+    w.in_off[q] = in_off[g];
+    w.in_size[q] = sz;
+    w.order[q] = m;
+    w.need[q] = (sz > max_in || ab_skipped(sz, m)) ? 0u : are_r16(are_cap(sz, m));
+}
+
+__global__ __launch_bounds__(256) void k_ab_admit(AbWs w, u32 items)
+{
+    const u32 q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= items) return;
+    w.cap[q] = w.slot_off[q + 1] <= w.slot_bytes ? w.need[q] : 0u;
+}
+
+// the smallest result, the first of them in list order; the status of a block without one is that of the first candidate
+// that was tried, UNSUPPORTED if none was.  A tried candidate that failed although its size and its order word are
+// acceptable found no room - no slot, or no stage bytes: the batch holds more than it announced - and fails the block as a
+// whole (UNSUPPORTED): the smallest of the rest would not be the smallest of the list.
+__global__ __launch_bounds__(256) void k_ab_pick(const u32 *in_size, AbWs w, AbMethods pm, u32 *out_size, i32 *status, i32 *chosen, int base, int nb,
+                                                 u32 max_in)
+{
+    const int lb = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (lb >= nb) return;
+    const int g = base + lb;
+    const u32 sz = in_size[g];
+    int win = -1, first = -1;
+    u32 best = 0;
+    bool no_room = false;
+    for (int j = 0; j < pm.k; j++) {
+        if (ab_skipped(sz, pm.m[j])) continue;
+        const size_t q = (size_t)lb * pm.k + j;
+        if (first < 0) first = j;
+        u32 N;
+        if (w.status[q] != AR_OK && sz <= max_in && are_order_check(sz, pm.m[j], &N) == AR_OK) no_room = true;
+        if (w.status[q] == AR_OK && (win < 0 || w.out_size[q] < best)) { best = w.out_size[q]; win = j; }
+    }
+    i32 st = AR_OK;
+    if (no_room) { win = -1; st = AR_E_UNSUPPORTED; }
+    else if (win < 0) st = first >= 0 ? w.status[(size_t)lb * pm.k + first] : AR_E_UNSUPPORTED;
+    w.win[lb] = win >= 0 ? (u32)win : 0u;
+    status[g] = st;
+    out_size[g] = win >= 0 ? best : 0u;
+    if (chosen) chosen[g] = win >= 0 ? pm.m[win] : -1;
+}
+
+__global__ __launch_bounds__(256) void k_ab_gather(PackedOut pk, AbWs w, int k, u32 *out_size, i32 *status, int base)
+{
+    const u32 tid = threadIdx.x;
+    const int lb = (int)blockIdx.x, i = base + lb;
+    const u32 sz = out_size[i];
+    if (sz == 0) return;
+    if (pk.off[i + 1] > pk.capacity) {
+        if (tid == 0) { status[i] = AR_E_CAPACITY; out_size[i] = 0; }
+        return;
+    }
+    group_copy<256>(pk.out + pk.off[i], w.slots + w.slot_off[(size_t)lb * k + w.win[lb]], sz, tid);
+}
+
+// What the call plans before it enqueues: the methods, the planes a stripe candidate may have, the items an inner item
+// reserves, the batch's bytes and the blocks per chunk - this call's candidate slots (the packed arena) and the inner
+// call's arena for k items a block fit the room together, so that the inner call takes the chunk in one pass.
+struct AbPlan { AbMethods pm; u32 planes; size_t per; u64 total; size_t chunk; };
+static u64 ab_slot_bytes(const AbPlan &p, size_t nb, u32 max_in)
+{
+    return (u64)p.pm.k * (std::min<u64>(p.total, (u64)nb * max_in) + (u64)nb * (64u + 28u * p.planes));
+}
+static u64 ab_inner_total(const AbPlan &p, size_t nb, u32 max_in) { return (u64)p.pm.k * std::min<u64>(p.total, (u64)nb * max_in); }
+
+static int ab_plan(rans4x16_hip_ctx *c, int n, int k, const int *methods, uint32_t max_in_size, uint64_t total_in_size, AbPlan *p)
+{
+    p->pm = AbMethods{};
+    p->pm.k = k;
+    p->planes = 0;
+    for (int j = 0; j < k; j++) {
+        u32 N = 0;
+        if ((methods[j] & AR_X_STRIPE) && are_order_check(21u, methods[j], &N) != AR_OK) { c->err = "arith_compress_best_packed_dev: more than 255 stripes"; return -1; }
+        p->planes = std::max(p->planes, N);
+        p->pm.m[j] = methods[j];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    p->per = p->planes ? (size_t)p->planes * ARE_CANDS : 1;
+    p->total = total_in_size ? total_in_size : (u64)n * max_in_size;
+    p->chunk = 0;
+    if (n == 0) return 0;
+    AbWs w;
+    AreWs iw;
+    auto bytes = [&](size_t nb) {
+        return ab_carve(&w, nullptr, nb, (size_t)k, ab_slot_bytes(*p, nb, max_in_size)) +
+               are_layout(nullptr, nb * k, p->per, are_stage_bytes(nb * k, p->per, p->planes, ab_inner_total(*p, nb, max_in_size), max_in_size), &iw);
+    };
+    p->chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / (p->per * k), r4x16_room(c, A_BIT(A_PS) | A_BIT(A_AR)), bytes);
+    return 0;
+}
+
+extern "C" int rans4x16_hip_arith_best_chunk_blocks(rans4x16_hip_ctx *c, int n, int k, const int *methods, uint32_t max_in_size,
+                                                    uint64_t total_in_size)
+{
+    if (!c) return -1;
+    if (n < 0 || k < 1 || k > AB_MAX_K || !methods) { c->err = "arith_best_chunk_blocks: bad arguments"; return -1; }
+    AbPlan p;
+    if (ab_plan(c, n, k, methods, max_in_size, total_in_size, &p) != 0) return -1;
+    return (int)p.chunk;
+}
+
+extern "C" int rans4x16_hip_arith_compress_best_packed_dev(rans4x16_hip_ctx *c, int n,
+                                                           const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                                           unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                                           uint32_t *d_out_size, int32_t *d_status,
+                                                           int k, const int *methods, int32_t *d_chosen,
+                                                           uint32_t max_in_size, uint64_t total_in_size, void *stream)
+{
+    if (!c) return -1;
+    if (n < 0 || k < 1 || k > AB_MAX_K || !methods || !d_out_off ||
+        (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
+        c->err = "arith_compress_best_packed_dev: bad arguments";
+        return -1;
+    }
+    AbPlan p;
+    if (ab_plan(c, n, k, methods, max_in_size, total_in_size, &p) != 0) return -1;
+    const AbMethods &pm = p.pm;
+    const u32 planes = p.planes;
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
+    AbWs w;
+    auto slot_bytes = [&](size_t nb) { return ab_slot_bytes(p, nb, max_in_size); };
+    auto mine = [&](size_t nb) { return ab_carve(&w, nullptr, nb, (size_t)k, slot_bytes(nb)); };
+    auto inner_total = [&](size_t nb) { return ab_inner_total(p, nb, max_in_size); };
+    size_t chunk = p.chunk;
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_PS, mine(nb), false); }) != 0) return -1;
+    const PackedOut pk = {d_out, d_out_off, out_capacity};
+    const size_t keep_ws = c->max_ws;
+    const int keep_planes = c->dev_stripe_enc;
+    int rc = 0;
+    for (size_t base = 0; base < (size_t)n && rc == 0; base += chunk) {
+        const int nb = (int)std::min(chunk, (size_t)n - base);
+        const u32 items = (u32)nb * (u32)k;
+        const size_t arena = ab_carve(&w, c->at(A_PS), (size_t)nb, (size_t)k, slot_bytes((size_t)nb));
+        const dim3 per_item((items + 255) / 256);
+        hipLaunchKernelGGL(k_ab_expand, per_item, dim3(256), 0, s, d_in_off, d_in_size, w, pm, (int)base, items, max_in_size);
+        r4x16_launch_packed_scan(w.need, w.slot_off, 0, (int)items, s);
+        hipLaunchKernelGGL(k_ab_admit, per_item, dim3(256), 0, s, w, items);
+        c->max_ws = keep_ws > arena + ((size_t)1 << 20) ? keep_ws - arena : (size_t)1 << 20;
+        c->dev_stripe_enc = (int)planes;
+        rc = rans4x16_hip_arith_compress_dev(c, (int)items, d_in, w.in_off, w.in_size, w.slots, w.slot_off, w.cap, w.out_size, w.status, 0,
+                                             w.order, max_in_size, inner_total((size_t)nb), s);
+        c->dev_stripe_enc = keep_planes;
+        c->max_ws = keep_ws;
+        if (rc != 0) break;
+        hipLaunchKernelGGL(k_ab_pick, dim3((u32)(nb + 255) / 256), dim3(256), 0, s, d_in_size, w, pm, d_out_size, d_status, d_chosen, (int)base, nb, max_in_size);
+        r4x16_launch_packed_scan(d_out_size, d_out_off, (int)base, nb, s);
+        hipLaunchKernelGGL(k_ab_gather, dim3((u32)nb), dim3(256), 0, s, pk, w, k, d_out_size, d_status, (int)base);
+    }
+    if (rc != 0) return -1;
     HIPCHK(c, hipGetLastError());
     return r4x16_ws_order_end(c, s);
 }

@@ -170,6 +170,7 @@ struct rans4x16_hip_ctx {
     int dev_stripe_enc = 0;                 // encode with per-block orders: planes a block reserves (rans4x16_hip_set_dev_stripe_encode)
     bool in_stripe = false;                 // inside the recursive call over the internal items
     bool in_packed = false;                 // inside a packed call's slot call over its internal slots (r4x16_packed.hip)
+    int tok3_arith = 0;                     // tok3 calls: R4X16_TOK3_ARITH_* (rans4x16_hip_set_tok3_arith); 0: the rANS flavour alone
     int names_chunk_blocks = 0;             // host-buffer names batches: blocks per chunk at most (rans4x16_hip_set_names_chunk_blocks)
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;

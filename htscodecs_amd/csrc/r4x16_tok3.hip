@@ -18,6 +18,13 @@
 //                        the others become the items of one rans4x16_hip_uncompress_dev_sized call, capacity = claim
 //           k_t3_fill  : duplicate columns copied from the decoded original, type columns synthesised, 16 bytes a piece
 //           k_t3_verdict: per block the first failing column's status, sizes, the caller's directory.
+//         After rans4x16_hip_set_tok3_arith(ctx, R4X16_TOK3_ARITH_DECODE) the walk admits containers with use_arith set
+//         and notes each block's flavour; k_t3_admit then fills two masked item lists over the same entries - an entry
+//         has its length and capacity in its own flavour's list and 0 in the other (the arith list's length reaches to the
+//         container's end, see k_t3_admit) - and rans4x16_hip_arith_uncompress_dev
+//         runs over the second with statuses and sizes of its own, so that neither decoder touches what the other reports.
+//         Pack writes use_arith = 1 and takes its winners from rans4x16_hip_arith_compress_best_packed_dev after
+//         R4X16_TOK3_ARITH_ENCODE; hash, duplicates, scan and frame do not look at the streams' flavour.
 //
 // Loops: trip counts are launch arguments (nblk, n, max_columns) or sizes checked first - a column's stream is at most
 // the bound of max_col_size (the inner call's guarantee), a block has at most T3_MAX_IDS columns (more cannot have
@@ -33,9 +40,11 @@ typedef u64 u64_unaligned __attribute__((aligned(1)));
 // An entry claims lead + size bytes at off: the type column synthesised in front of it, then its own column at col_off.
 struct T3Items {
     u64 *in_off; u32 *clen, *in_size, *claim, *size, *lead, *cap, *kind_a; u64 *off, *col_off; u32 *out_size; i32 *status; i32 *pre;
+    // the arith flavour's masked list and results ([nitems]) and the blocks' flavours ([nblk]); nullptr: arith is not admitted
+    u32 *in_size_a, *cap_a, *out_size_a; i32 *status_a; u8 *arith;
 };
 
-static size_t t3_items_carve(T3Items *w, u8 *base, size_t nitems, size_t nblk)
+static size_t t3_items_carve(T3Items *w, u8 *base, size_t nitems, size_t nblk, bool arith)
 {
     Carver cv(base);
     w->in_off = cv.take<u64>(nitems); w->clen = cv.take<u32>(nitems); w->in_size = cv.take<u32>(nitems);
@@ -43,6 +52,11 @@ static size_t t3_items_carve(T3Items *w, u8 *base, size_t nitems, size_t nblk)
     w->cap = cv.take<u32>(nitems); w->kind_a = cv.take<u32>(nitems);
     w->off = cv.take<u64>(nitems + 1); w->col_off = cv.take<u64>(nitems); w->out_size = cv.take<u32>(nitems); w->status = cv.take<i32>(nitems);
     w->pre = cv.take<i32>(nblk);
+    w->in_size_a = w->cap_a = w->out_size_a = nullptr; w->status_a = nullptr; w->arith = nullptr;
+    if (arith) {
+        w->in_size_a = cv.take<u32>(nitems); w->cap_a = cv.take<u32>(nitems); w->out_size_a = cv.take<u32>(nitems);
+        w->status_a = cv.take<i32>(nitems); w->arith = cv.take<u8>(nblk);
+    }
     return cv.total();
 }
 
@@ -81,8 +95,9 @@ __global__ __launch_bounds__(64) void k_t3_walk(const u8 *in, const u64 *in_off,
         if (size <= max_in) {
             ByteSrc src(in + in_off[b]);
             DevDir dir = {w, dir_id, in_off[b], base};
-            st = t3_walk(src, size, maxc, max_col, map, dir, &sum);
+            st = t3_walk(src, size, maxc, max_col, w.arith != nullptr, map, dir, &sum);
         }
+        if (w.arith) w.arith[b] = (u8)sum.arith;
         w.pre[b] = st;
         ncol[b] = st == T3_OK ? sum.ndesc : 0u;
         last_start[b] = sum.last_start;
@@ -103,14 +118,25 @@ __device__ __forceinline__ bool t3_admitted(const T3Items &w, size_t b, u32 maxc
     return w.pre[b] == ST_OK && w.off[(b + 1) * maxc] <= capacity;
 }
 
-__global__ __launch_bounds__(256) void k_t3_admit(T3Items w, u64 *out_off, u64 capacity, u32 nblk, u32 maxc, u64 nitems)
+// blk_off / blk_size: the containers, for the arith flavour's input length (below)
+__global__ __launch_bounds__(256) void k_t3_admit(T3Items w, const u64 *blk_off, const u32 *blk_size, u64 *out_off, u64 capacity, u32 nblk,
+                                                  u32 maxc, u64 nitems)
 {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
     if (i >= nitems) return;
     const size_t b = (size_t)(i / maxc);
     const bool run = t3_admitted(w, b, maxc, capacity) && (w.kind_a[i] >> 16) == T3_PLAIN;
-    w.in_size[i] = run ? w.clen[i] : 0u;
-    w.cap[i] = run ? w.size[i] : 0u;
+    const bool ar = w.arith && w.arith[b];
+    w.in_size[i] = run && !ar ? w.clen[i] : 0u;
+    w.cap[i] = run && !ar ? w.size[i] : 0u;
+    if (w.arith) {
+        // The arith decoder is handed the rest of the container, as the reference hands it (tokenise_name3.c:1214), not
+        // the clen bytes of the stream: c_range_coder.h:64 starts to decode only if more than five bytes lie in front of
+        // in_end, and the reference's own writer gives a near-constant column a body of exactly five.  Such a column
+        // decodes because another descriptor follows it (and to zeros where none does, here as there).
+        w.in_size_a[i] = run && ar ? (u32)(blk_off[b] + blk_size[b] - w.in_off[i]) : 0u;
+        w.cap_a[i] = run && ar ? w.size[i] : 0u;
+    }
     w.col_off[i] = w.off[i] + w.lead[i];
     if (i == (u64)b * maxc) {
         out_off[b] = w.off[i];
@@ -160,17 +186,20 @@ __global__ __launch_bounds__(64) void k_t3_verdict(T3Items w, T3Out o, u64 capac
     i32 st = w.pre[b];
     const u64 start = w.off[base], end = w.off[base + maxc];
     if (st == ST_OK && end > capacity) st = ST_CAPACITY;
+    const bool ar = w.arith && w.arith[b];                                // the block's columns were the arith decoder's
+    const i32 *cst = ar ? w.status_a : w.status;
+    const u32 *csz = ar ? w.out_size_a : w.out_size;
     if (st == ST_OK)
         for (u32 c0 = 0; c0 < maxc; c0 += 64) {                           // the first column that failed to decode
             const u32 c = c0 + lane;
             // (a stream may decode to fewer bytes than its size field says - X_PACK over an empty payload - where the
             //  reference trips its assert, :1655: the column would not be what the directory says)
             const bool bad = c < maxc && (w.kind_a[base + c] >> 16) == T3_PLAIN &&
-                             (w.status[base + c] != ST_OK || w.out_size[base + c] != w.size[base + c]);
+                             (cst[base + c] != ST_OK || csz[base + c] != w.size[base + c]);
             const u64 m = __ballot(bad);
             if (m) {
                 const size_t f = base + c0 + (u32)__builtin_ctzll(m);
-                st = w.status[f] != ST_OK ? w.status[f] : ST_SIZE;
+                st = cst[f] != ST_OK ? cst[f] : ST_SIZE;
                 break;
             }
         }
@@ -206,22 +235,26 @@ extern "C" int rans4x16_hip_tok3_unpack_dev(rans4x16_hip_ctx *c, int nblk,
     hipStream_t s = (hipStream_t)stream;
     if (nblk == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
     T3Items w;
-    if (r4x16_ensure(c, A_T3, t3_items_carve(&w, nullptr, (size_t)nitems, (size_t)nblk), false) != 0) return -1;
-    const size_t arena = t3_items_carve(&w, c->at(A_T3), (size_t)nitems, (size_t)nblk);
+    const bool arith = (c->tok3_arith & R4X16_TOK3_ARITH_DECODE) != 0;
+    if (r4x16_ensure(c, A_T3, t3_items_carve(&w, nullptr, (size_t)nitems, (size_t)nblk, arith), false) != 0) return -1;
+    const size_t arena = t3_items_carve(&w, c->at(A_T3), (size_t)nitems, (size_t)nblk, arith);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
     const dim3 per_item((u32)((nitems + 255) / 256));
     hipLaunchKernelGGL(k_t3_walk, dim3((u32)nblk), dim3(64), 0, s, d_in, d_in_off, d_in_size, w, d_col_id, d_ncol, d_last_start, d_nreads,
                        max_columns, max_in_size, max_col_size);
     r4x16_launch_packed_scan(w.claim, w.off, 0, (int)nitems, s);
-    hipLaunchKernelGGL(k_t3_admit, per_item, dim3(256), 0, s, w, d_out_off, out_capacity, (u32)nblk, max_columns, nitems);
+    hipLaunchKernelGGL(k_t3_admit, per_item, dim3(256), 0, s, w, d_in_off, d_in_size, d_out_off, out_capacity, (u32)nblk, max_columns, nitems);
     const u64 total = std::max<u64>(std::min<u64>(out_capacity, nitems * (u64)max_col_size), 1);
     const size_t keep_ws = c->max_ws;
     c->max_ws = keep_ws > arena + ((size_t)1 << 20) ? keep_ws - arena : (size_t)1 << 20;
     // the sizing pass (no arena, capacity 0): only blocks that claim 0 bytes are admitted and nothing is written, but the
     // slot call wants a pointer - the tok3 arena's own
     unsigned char *out = d_out ? d_out : c->at(A_T3);
-    const int rc = rans4x16_hip_uncompress_dev_sized(c, (int)nitems, d_in, w.in_off, w.in_size, out, w.col_off, w.cap, w.out_size, w.status,
-                                                     max_in_size, max_col_size, total, s);
+    int rc = rans4x16_hip_uncompress_dev_sized(c, (int)nitems, d_in, w.in_off, w.in_size, out, w.col_off, w.cap, w.out_size, w.status,
+                                               max_in_size, max_col_size, total, s);
+    if (rc == 0 && arith)
+        rc = rans4x16_hip_arith_uncompress_dev(c, (int)nitems, d_in, w.in_off, w.in_size_a, out, w.col_off, w.cap_a, w.out_size_a, w.status_a,
+                                               max_in_size, max_col_size, total, s);
     c->max_ws = keep_ws;
     if (rc != 0) return -1;
     hipLaunchKernelGGL(k_t3_fill, dim3((u32)((nitems + 3) / 4)), dim3(256), 0, s, w, (const i32 *)d_col_id, d_out, out_capacity, max_columns, nitems);
@@ -368,7 +401,7 @@ __global__ __launch_bounds__(64) void k_t3_dup(T3In in, T3Cols w, const u32 *pma
     if (lane == 0) { status[b] = st; out_size[b] = st == ST_OK ? (u32)run : 0u; }
 }
 
-__global__ __launch_bounds__(256) void k_t3_frame(T3In in, T3Cols w, PackedOut pk, u32 *out_size, i32 *status)
+__global__ __launch_bounds__(256) void k_t3_frame(T3In in, T3Cols w, PackedOut pk, u32 *out_size, i32 *status, u32 use_arith)
 {
     const int b = (int)blockIdx.x;
     const u32 tid = threadIdx.x, lane = tid & 63u;
@@ -382,7 +415,7 @@ __global__ __launch_bounds__(256) void k_t3_frame(T3In in, T3Cols w, PackedOut p
     if (tid == 0) {
         const u32 ls = in.last_start[b], nr = in.nreads[b];
         for (int k = 0; k < 4; k++) { dst[k] = (u8)(ls >> (8 * k)); dst[4 + k] = (u8)(nr >> (8 * k)); }
-        dst[8] = 0;                                                       // use_arith
+        dst[8] = (u8)use_arith;
     }
     const u32 first = in.blk_first[b], next = in.blk_first[b + 1];
     for (u32 c = first + (tid >> 6); c < next; c += 4) {
@@ -433,16 +466,21 @@ int r4x16_tok3_pack_run(rans4x16_hip_ctx *c, int nblk, int n, const uint32_t *d_
     // What the winners of n columns take together at most: the candidate that is always tried (a method without X_STRIPE
     // where the list has one: the others are skipped for sizes that are no multiple of 4) and has the smallest bound
     // succeeds within its bound, and the winner is no larger.  The bounds are 1.05 x size + a constant, rounded.
+    const bool arith = (c->tok3_arith & R4X16_TOK3_ARITH_ENCODE) != 0;
+    auto bound = [&](u32 size, int m) { return arith ? rans4x16_hip_arith_compress_cap(size, m) : r4x16_bound_hd(size, m); };
     int lean = -1;
     bool plain = false;
     for (int j = 0; j < k; j++) plain |= !(methods[j] & X_STRIPE);
     for (int j = 0; j < k; j++) {
         if ((methods[j] & X_STRIPE) && ((unsigned)methods[j] >> 8) > 255) { c->err = "tok3_pack_dev: more than 255 stripes"; return -1; }
         if (plain && (methods[j] & X_STRIPE)) continue;
-        if (lean < 0 || r4x16_bound_hd(max_col_size, methods[j]) < r4x16_bound_hd(max_col_size, lean)) lean = methods[j];
+        if (lean < 0 || bound(max_col_size, methods[j]) < bound(max_col_size, lean)) lean = methods[j];
     }
-    u64 stream_bytes = (u64)n * r4x16_bound_hd(max_col_size, lean);
-    if (total_col_size) stream_bytes = std::min<u64>(stream_bytes, (u64)(1.05 * (double)total_col_size) + 1 + (u64)n * (r4x16_bound_hd(0, lean) + 4ull));
+    // (arith: rans4x16_hip_arith_compress_cap is the size plus a constant of the method's - one for blocks of up to 20
+    //  bytes, which are never striped, and one for larger blocks)
+    const u64 per_col = arith ? std::max<u64>(bound(0, lean), bound(21, lean) - 21u) : bound(0, lean);
+    u64 stream_bytes = (u64)n * bound(max_col_size, lean);
+    if (total_col_size) stream_bytes = std::min<u64>(stream_bytes, (u64)(1.05 * (double)total_col_size) + 1 + (u64)n * (per_col + 4ull));
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream;
     if (nblk == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
@@ -460,8 +498,11 @@ int r4x16_tok3_pack_run(rans4x16_hip_ctx *c, int nblk, int n, const uint32_t *d_
     if (n) {
         const size_t keep_ws = c->max_ws;
         c->max_ws = keep_ws > arena + ((size_t)1 << 20) ? keep_ws - arena : (size_t)1 << 20;
-        const int rc = rans4x16_hip_compress_best_packed_dev(c, n, d_in, d_col_off, d_col_size, w.streams, stream_bytes, w.s_off, w.s_size,
-                                                             w.s_status, k, methods, d_chosen, max_col_size, total_col_size, s);
+        const int rc = arith
+            ? rans4x16_hip_arith_compress_best_packed_dev(c, n, d_in, d_col_off, d_col_size, w.streams, stream_bytes, w.s_off, w.s_size,
+                                                          w.s_status, k, methods, d_chosen, max_col_size, total_col_size, s)
+            : rans4x16_hip_compress_best_packed_dev(c, n, d_in, d_col_off, d_col_size, w.streams, stream_bytes, w.s_off, w.s_size,
+                                                    w.s_status, k, methods, d_chosen, max_col_size, total_col_size, s);
         c->max_ws = keep_ws;
         if (rc != 0) return -1;
         hipLaunchKernelGGL(k_t3_hash, dim3((u32)((n + 3) / 4)), dim3(256), 0, s, w, n);
@@ -471,7 +512,7 @@ int r4x16_tok3_pack_run(rans4x16_hip_ctx *c, int nblk, int n, const uint32_t *d_
     hipLaunchKernelGGL(k_t3_first_max, dim3(1), dim3(1024), 0, s, d_blk_first, w.pmax, nblk);
     hipLaunchKernelGGL(k_t3_dup, dim3((u32)nblk), dim3(64), 0, s, in, w, (const u32 *)w.pmax, d_out_size, d_status, nblk, (u32)n, max_col_size);
     r4x16_launch_packed_scan(d_out_size, d_out_off, 0, nblk, s);
-    hipLaunchKernelGGL(k_t3_frame, dim3((u32)nblk), dim3(256), 0, s, in, w, pk, d_out_size, d_status);
+    hipLaunchKernelGGL(k_t3_frame, dim3((u32)nblk), dim3(256), 0, s, in, w, pk, d_out_size, d_status, arith ? 1u : 0u);
     HIPCHK(c, hipGetLastError());
     return r4x16_ws_order_end(c, s);
 }

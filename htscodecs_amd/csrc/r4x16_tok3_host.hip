@@ -14,6 +14,10 @@
 // Decode, per chunk: rans4x16_hip_tok3_scan per container on the host (descriptors only) gives the limits; the accepted
 // containers gathered -> rans4x16_hip_tok3_decode_names_dev -> sizes read, the dense arena copied down and scattered.
 //
+// The arith flavour (rans4x16_hip_set_tok3_arith): with ENCODE the pack stages write use_arith = 1 and the bounds below
+// are the arith coder's; with DECODE the scan admits either flavour and the device calls decode each block by its own.
+// rans4x16_hip_tok3_arith_encode_names / _decode_names set the mode for their one call and put the caller's back.
+//
 // Arenas: A_STAGE is this unit's (layouts below, dry for the plan and over the arena for the run); A_TN, A_T3, A_WS and
 // A_XS are those of the device calls.  Everything runs on the context's own stream.
 #include "r4x16_host.h"
@@ -85,10 +89,10 @@ static size_t nh_dec_carve(NhDec *d, u8 *base, size_t nblk, size_t in_bytes, siz
 static size_t nh_slot(size_t bytes) { return align_up(bytes + NH_PAD, 64); }
 
 // the largest bound of the list for a column of `size` bytes: the winner is no larger than its own
-static u64 nh_col_bound(u32 size, int k, const int *methods)
+static u64 nh_col_bound(u32 size, int k, const int *methods, bool arith)
 {
     u32 best = 0;
-    for (int j = 0; j < k; j++) best = std::max(best, r4x16_compress_bound(size, methods[j]));
+    for (int j = 0; j < k; j++) best = std::max(best, arith ? rans4x16_hip_arith_compress_cap(size, methods[j]) : r4x16_compress_bound(size, methods[j]));
     return (u64)best + 6;                                                 // the type byte and var_put_u32(clen)
 }
 
@@ -176,7 +180,8 @@ static int nh_enc_chunk(rans4x16_hip_ctx *c, size_t lo, size_t nb, const unsigne
     HIPCHK(c, hipStreamSynchronize(s));
     u64 out_bound = (u64)nb * T3_HEADER, total_col = 0;
     u32 max_col = 1;
-    for (size_t i = 0; i < n; i++) { out_bound += nh_col_bound(csz[i], k, methods); total_col += csz[i]; max_col = std::max(max_col, csz[i]); }
+    const bool arith = (c->tok3_arith & R4X16_TOK3_ARITH_ENCODE) != 0;
+    for (size_t i = 0; i < n; i++) { out_bound += nh_col_bound(csz[i], k, methods, arith); total_col += csz[i]; max_col = std::max(max_col, csz[i]); }
     NhOut o;
     if (r4x16_ensure(c, A_TN, nh_out_carve(&o, nullptr, 0, nb, (size_t)out_bound), false) != 0) return -1;
     nh_out_carve(&o, c->at(A_TN), 0, nb, (size_t)out_bound);
@@ -346,7 +351,9 @@ extern "C" int rans4x16_hip_tok3_decode_names_batch(rans4x16_hip_ctx *c, int nbl
     const size_t cap = r4x16_room(c, NH_REUSE) / 2;
     for (int i = 0; i < nblk; i++) {
         NhScan &sc = scan[i];
-        sc.rc = rans4x16_hip_tok3_scan(in[i], in_size[i], 0, 0, &sc.last_start, &sc.nreads, &sc.ndesc, nullptr, &sc.total, &sc.largest_col, nullptr);
+        sc.rc = (c->tok3_arith & R4X16_TOK3_ARITH_DECODE)
+            ? rans4x16_hip_tok3_scan_any(in[i], in_size[i], 0, 0, &sc.last_start, &sc.nreads, &sc.ndesc, nullptr, &sc.total, &sc.largest_col, nullptr, nullptr)
+            : rans4x16_hip_tok3_scan(in[i], in_size[i], 0, 0, &sc.last_start, &sc.nreads, &sc.ndesc, nullptr, &sc.total, &sc.largest_col, nullptr);
         if (sc.rc < 0) { c->err = "tok3_decode_names_batch: bad arguments"; return -1; }
         if (sc.rc == R4X16_OK) {
             // a container that claims more than the context may take, alone: hostile or too large for this card
@@ -401,16 +408,22 @@ extern "C" int rans4x16_hip_tok3_level_methods(int level, int *methods)
     return rows[level][0];
 }
 
-extern "C" unsigned char *rans4x16_hip_tok3_encode_names(char *blk, int len, int level, int use_arith, int *out_len, int *last_start_p)
+// the mode a caller set on the thread's context (rans4x16_hip_thread_ctx), put back when the single-block call ends
+struct Tok3ArithMode {
+    rans4x16_hip_ctx *c;
+    int was;
+    Tok3ArithMode(rans4x16_hip_ctx *c_, int mode) : c(c_), was(c_->tok3_arith) { c->tok3_arith = mode; }
+    ~Tok3ArithMode() { c->tok3_arith = was; }
+    Tok3ArithMode(const Tok3ArithMode &) = delete;
+    Tok3ArithMode &operator=(const Tok3ArithMode &) = delete;
+};
+
+static unsigned char *nh_encode_one(char *blk, int len, int level, int mode, int *out_len, int *last_start_p)
 {
-    if (use_arith) {
-        static std::once_flag once;
-        std::call_once(once, [] { fprintf(stderr, "rans4x16_hip: encode_names with use_arith != 0 needs the adaptive arithmetic coder, which this library does not have\n"); });
-        return nullptr;
-    }
     if (!blk || len < 0 || !out_len) return nullptr;
     rans4x16_hip_ctx *c = r4x16_thread_ctx();
     if (!c) return nullptr;
+    Tok3ArithMode flavour(c, mode);
     int methods[9];
     const int k = rans4x16_hip_tok3_level_methods(level, methods);
     const unsigned char *ins[1] = {(const unsigned char *)blk};
@@ -427,11 +440,27 @@ extern "C" unsigned char *rans4x16_hip_tok3_encode_names(char *blk, int len, int
     return outs[0];
 }
 
-extern "C" unsigned char *rans4x16_hip_tok3_decode_names(unsigned char *in, uint32_t sz, uint32_t *out_len)
+extern "C" unsigned char *rans4x16_hip_tok3_encode_names(char *blk, int len, int level, int use_arith, int *out_len, int *last_start_p)
+{
+    if (use_arith) {
+        static std::once_flag once;
+        std::call_once(once, [] { fprintf(stderr, "rans4x16_hip: encode_names with use_arith != 0 is the arithmetic flavour: call rans4x16_hip_tok3_arith_encode_names (include/tok3_names_hip.h forwards there)\n"); });
+        return nullptr;
+    }
+    return nh_encode_one(blk, len, level, 0, out_len, last_start_p);
+}
+
+extern "C" unsigned char *rans4x16_hip_tok3_arith_encode_names(char *blk, int len, int level, int *out_len, int *last_start_p)
+{
+    return nh_encode_one(blk, len, level, R4X16_TOK3_ARITH_ENCODE, out_len, last_start_p);
+}
+
+static unsigned char *nh_decode_one(unsigned char *in, uint32_t sz, int mode, uint32_t *out_len)
 {
     if (!in || !out_len) return nullptr;
     rans4x16_hip_ctx *c = r4x16_thread_ctx();
     if (!c) return nullptr;
+    Tok3ArithMode flavour(c, mode);
     const unsigned char *ins[1] = {in};
     unsigned char *outs[1] = {nullptr};
     unsigned int isz[1] = {sz}, osz[1] = {0};
@@ -440,4 +469,14 @@ extern "C" unsigned char *rans4x16_hip_tok3_decode_names(unsigned char *in, uint
     if (rc != 0 || !outs[0]) return nullptr;
     *out_len = osz[0];
     return outs[0];
+}
+
+extern "C" unsigned char *rans4x16_hip_tok3_decode_names(unsigned char *in, uint32_t sz, uint32_t *out_len)
+{
+    return nh_decode_one(in, sz, 0, out_len);
+}
+
+extern "C" unsigned char *rans4x16_hip_tok3_arith_decode_names(unsigned char *in, uint32_t sz, uint32_t *out_len)
+{
+    return nh_decode_one(in, sz, R4X16_TOK3_ARITH_DECODE, out_len);
 }

@@ -1,6 +1,7 @@
-// r4x16_tok3_scan.hip - rans4x16_hip_tok3_scan (include/rans4x16_hip.h part 2c): the walk of r4x16_tok3_walk.h over a
-// container in host memory.  Pure host arithmetic, no GPU, no HIP header: this unit also compiles as plain C++
-// (g++ -x c++), which is how its sanitizer run is built (profiles/tok3.md).
+// r4x16_tok3_scan.hip - rans4x16_hip_tok3_scan and rans4x16_hip_tok3_scan_any (include/rans4x16_hip.h part 2c): the walk
+// of r4x16_tok3_walk.h over a container in host memory; _any admits the arith flavour (use_arith != 0) as well.  Pure host
+// arithmetic, no GPU, no HIP header: this unit also compiles as plain C++ (g++ -x c++), which is how its sanitizer run is
+// built (profiles/tok3.md, profiles/tok3_arith.md).
 #include "../../include/rans4x16_hip.h"
 #include "r4x16_tok3_walk.h"
 
@@ -22,9 +23,9 @@ struct HostDir {
 };
 }
 
-extern "C" int rans4x16_hip_tok3_scan(const unsigned char *in, size_t size, uint32_t max_columns, uint32_t max_col_size,
-                                      uint32_t *last_start, uint32_t *nreads, uint32_t *ndesc, uint32_t *ncol,
-                                      uint64_t *total_col_size, uint32_t *largest_col, uint32_t *largest_stream)
+static int scan(const unsigned char *in, size_t size, uint32_t max_columns, uint32_t max_col_size,
+                uint32_t *last_start, uint32_t *nreads, uint32_t *ndesc, uint32_t *ncol,
+                uint64_t *total_col_size, uint32_t *largest_col, uint32_t *largest_stream, bool admit_arith, int *use_arith)
 {
     T3Sum sum = {};
     int rc;
@@ -35,7 +36,7 @@ extern "C" int rans4x16_hip_tok3_scan(const unsigned char *in, size_t size, uint
         uint16_t map[T3_MAX_IDS];
         for (int i = 0; i < T3_MAX_IDS; i++) map[i] = T3_NONE;
         HostSrc src = {in};
-        rc = t3_walk(src, (uint32_t)size, max_columns ? max_columns : T3_MAX_IDS, max_col_size ? max_col_size : 0xffffffffu, map, dir, &sum);
+        rc = t3_walk(src, (uint32_t)size, max_columns ? max_columns : T3_MAX_IDS, max_col_size ? max_col_size : 0xffffffffu, admit_arith, map, dir, &sum);
     }
     if (last_start) *last_start = sum.last_start;
     if (nreads) *nreads = sum.nreads;
@@ -44,5 +45,20 @@ extern "C" int rans4x16_hip_tok3_scan(const unsigned char *in, size_t size, uint
     if (total_col_size) *total_col_size = sum.total;
     if (largest_col) *largest_col = sum.max_col;
     if (largest_stream) *largest_stream = sum.max_stream;
+    if (use_arith) *use_arith = (int)sum.arith;
     return rc;
+}
+
+extern "C" int rans4x16_hip_tok3_scan(const unsigned char *in, size_t size, uint32_t max_columns, uint32_t max_col_size,
+                                      uint32_t *last_start, uint32_t *nreads, uint32_t *ndesc, uint32_t *ncol,
+                                      uint64_t *total_col_size, uint32_t *largest_col, uint32_t *largest_stream)
+{
+    return scan(in, size, max_columns, max_col_size, last_start, nreads, ndesc, ncol, total_col_size, largest_col, largest_stream, false, nullptr);
+}
+
+extern "C" int rans4x16_hip_tok3_scan_any(const unsigned char *in, size_t size, uint32_t max_columns, uint32_t max_col_size,
+                                          uint32_t *last_start, uint32_t *nreads, uint32_t *ndesc, uint32_t *ncol,
+                                          uint64_t *total_col_size, uint32_t *largest_col, uint32_t *largest_stream, int *use_arith)
+{
+    return scan(in, size, max_columns, max_col_size, last_start, nreads, ndesc, ncol, total_col_size, largest_col, largest_stream, true, use_arith);
 }

@@ -6,7 +6,8 @@
 // A container: last_start (4 bytes, little endian), nreads (4), use_arith (1), then descriptors until the end:
 //   type byte t : t & 15 the token type, t & 128 "first column of the next token position", t & 64 duplicate
 //   duplicate   : two bytes j >> 4, j & 15 - the id of an earlier column whose bytes this one repeats
-//   plain       : var_put_u32(clen), then a rANS 4x16 stream of clen bytes
+//   plain       : var_put_u32(clen), then a stream of clen bytes - rANS 4x16, or arith_dynamic where use_arith is set;
+//                 flag byte and stored size lie at the same places in both, so the walk is one
 // A column's id is tnum << 4 | type.  A position opened by a column whose type is not 0 gets its type column (id
 // tnum << 4) synthesised first: nreads bytes, the type and then N_MATCH repeated (:1581-1591, :1619-1629).
 //
@@ -35,7 +36,8 @@ struct T3Sum {
     uint32_t last_start, nreads;   // header
     uint32_t ndesc, ncol;          // descriptors accepted; columns they give (descriptors + synthesised type columns)
     uint64_t total;                // bytes of all columns
-    uint32_t max_col, max_stream;  // largest column, largest rANS stream (clen)
+    uint32_t max_col, max_stream;  // largest column, largest stream (clen)
+    uint32_t arith;                // the block's flavour: byte 8 (use_arith) is set - its streams are arith_dynamic's
 };
 
 // varint.h:131-160 over [pos, end); returns the bytes consumed, 0 if there is none; *cont: the last byte read still had
@@ -63,18 +65,23 @@ T3_HD inline uint32_t t3_var_get(SRC &s, uint32_t pos, uint32_t end, uint32_t *v
 // container, b = clen; DUP: a = the descriptor whose PLAIN column it copies, T3_NONE for none; SYNTH: a copy of a type
 // column, a = the type) and `lead`, the bytes of the type column synthesised in front of it (0: none; its type is
 // id & 15) - and kind_at / a_at / size_at / id_at read back what was put.  map: T3_MAX_IDS entries, all T3_NONE on entry;
-// id -> descriptor.  max_columns bounds the descriptors.  Returns 0 or the status of the first descriptor that is
-// refused; *sum is what was accepted up to there.
+// id -> descriptor.  max_columns bounds the descriptors.  admit_arith: a container with use_arith set is walked (by the
+// same rules) and sum->arith says so; without it such a container is refused.  Returns 0 or the status of the first
+// descriptor that is refused; *sum is what was accepted up to there.
 template <class SRC, class DIR>
-T3_HD inline int t3_walk(SRC &in, uint32_t size, uint32_t max_columns, uint32_t max_col_size, uint16_t *map, DIR &dir, T3Sum *sum)
+T3_HD inline int t3_walk(SRC &in, uint32_t size, uint32_t max_columns, uint32_t max_col_size, bool admit_arith, uint16_t *map, DIR &dir,
+                         T3Sum *sum)
 {
-    sum->last_start = sum->nreads = sum->ndesc = sum->ncol = sum->max_col = sum->max_stream = 0;
+    sum->last_start = sum->nreads = sum->ndesc = sum->ncol = sum->max_col = sum->max_stream = sum->arith = 0;
     sum->total = 0;
     if (size < T3_HEADER) return T3_E_TRUNCATED;                                         // :1547
     const uint32_t last_start = (uint32_t)in.at(0) | ((uint32_t)in.at(1) << 8) | ((uint32_t)in.at(2) << 16) | ((uint32_t)in.at(3) << 24);
     const uint32_t nreads = (uint32_t)in.at(4) | ((uint32_t)in.at(5) << 8) | ((uint32_t)in.at(6) << 16) | ((uint32_t)in.at(7) << 24);
     sum->last_start = last_start; sum->nreads = nreads;
-    if (in.at(8) != 0) return T3_E_UNSUPPORTED;                                          // use_arith
+    if (in.at(8) != 0) {                                                                 // use_arith
+        if (!admit_arith) return T3_E_UNSUPPORTED;
+        sum->arith = 1;
+    }
     if (last_start >= 0x7fffffffu - 1024u) return T3_E_SIZE;                             // :1555 (negative as an int, or too large)
     uint32_t o = T3_HEADER;
     int tnum = -1, last_id = -1;

@@ -69,6 +69,11 @@ SIGNATURES = {
     "rans4x16_hip_tok3_scan": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rans4x16_hip_tok3_scan_any": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_int)]),
+    "rans4x16_hip_set_tok3_arith": (C.c_int, [C.c_void_p, C.c_int]),
     "rans4x16_hip_tok3_pack_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -127,6 +132,10 @@ SIGNATURES = {
     "rans4x16_hip_tok3_encode_names": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                                    C.POINTER(C.c_int)]),
     "rans4x16_hip_tok3_decode_names": (C.c_void_p, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rans4x16_hip_tok3_arith_encode_names": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                         C.POINTER(C.c_int)]),
+    "rans4x16_hip_tok3_arith_decode_names": (C.c_void_p, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rans4x16_hip_thread_ctx": (C.c_void_p, []),
     "rans4x16_hip_tok3_encode_names_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rans4x16_hip_tok3_decode_names_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -148,6 +157,11 @@ SIGNATURES = {
     "rans4x16_hip_arith_compress_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "rans4x16_hip_arith_compress_best_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                                             C.c_void_p]),
+    "rans4x16_hip_arith_best_chunk_blocks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64]),
     "rans4x16_hip_arith_compress_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "rans4x16_hip_arith_compress_to": (C.c_void_p, [C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_uint), C.c_int]),

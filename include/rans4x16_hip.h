@@ -279,8 +279,9 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
  * The CRAM 3.1 name tokeniser (htscodecs tokenise_name3.c) turns a block of read names into token columns, compresses
  * each with the best of a method list and frames them into one container (encode_names, :1431-1531); decode_names
  * (:1546-1669) walks the container and decodes the columns before it rebuilds the names.  These calls do the column
- * half of both on the device, rANS flavour (use_arith = 0); part 2d turns the decoded columns into names (decode_name),
- * part 2e the names into the columns this part packs (the encoding tokeniser: trie, encode_name).
+ * half of both on the device - the rANS flavour (use_arith = 0), and the arith flavour (use_arith = 1, the streams are
+ * arith_dynamic's, parts 2g and 2h) after rans4x16_hip_set_tok3_arith, below; part 2d turns the decoded columns into names
+ * (decode_name), part 2e the names into the columns this part packs (the encoding tokeniser: trie, encode_name).
  *
  * A container: last_start (4 bytes, little endian), nreads (4), use_arith (1), then per column a type byte
  * (type | 128 on the first column of a token position, | 64 for a duplicate) followed by var_put_u32(clen) and the
@@ -293,6 +294,29 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
  * stream (any of the pointers may be NULL), and returns 0 or the R4X16_E_* status the walk of
  * rans4x16_hip_tok3_unpack_dev gives with the same max_columns / max_col_size (0 = no limit: 2048 / 2^32 - 1); -1 on bad
  * arguments.  After a failure the counts and sizes are those of the columns accepted before it.
+ * rans4x16_hip_tok3_scan_any: the same walk, which accepts either flavour - use_arith != 0 is not refused - and reports
+ * byte 8 != 0 in *use_arith (may be NULL; 0 where the container has no byte 8).  Pure host arithmetic too.
+ *
+ * rans4x16_hip_set_tok3_arith(ctx, mode): the arith flavour (tokenise_name3.c with use_arith = 1: :1246-1300 swaps
+ * rans_compress_to_4x16 for arith_compress_to, :1314-1321 the decoder, :1511 writes the flag) for the tok3 calls of parts
+ * 2c to 2f on this context.  mode is 0 (the default) or a sum of
+ *   R4X16_TOK3_ARITH_DECODE  unpack_dev, decode_names_dev, decode_names_batch: a container with use_arith != 0 is walked
+ *                            by the same rules and its plain columns are decoded by rans4x16_hip_arith_uncompress_dev
+ *                            with the claim as capacity.  The flavour is per block: one batch may mix both, and each
+ *                            block's result is what it would be alone.  Nested X_STRIPE columns need
+ *                            rans4x16_hip_set_dev_stripe_planes as the rANS ones do (decode_names_batch arranges it).
+ *                            The decoder's in_size is the rest of the container from the stream's first byte, as the
+ *                            reference hands it (:1214), not clen: the range coder starts only if more than five bytes
+ *                            lie in front of its input's end (c_range_coder.h:64), and the reference's writer gives a
+ *                            near-constant column a body of exactly five - such a column decodes because a descriptor
+ *                            follows it (to zeros where none does, here as there).  The walk's own rule stays stricter:
+ *                            a clen that reaches beyond the container is TRUNCATED.
+ *   R4X16_TOK3_ARITH_ENCODE  pack_dev, encode_names_dev, encode_names_batch: byte 8 is 1 and every column's winner comes
+ *                            from rans4x16_hip_arith_compress_best_packed_dev (part 2h) with the given method list; the
+ *                            duplicate rule and the framing are unchanged.
+ * Returns the previous mode, -1 for a NULL context or a mode outside 0..3.  A setter like
+ * rans4x16_hip_set_dev_stripe_planes, not a named option.  In mode 0 the calls take the rANS path alone: no arith kernel
+ * runs and R4X16_ROUTE_ARITH* stay untouched; what the text below says about use_arith != 0 being refused holds there.
  *
  * rans4x16_hip_tok3_pack_dev: nblk name blocks with n columns in all.  Every array is a DEVICE array.
  *   d_blk_first[nblk + 1]       first column of each block; d_blk_first[0] = 0, d_blk_first[nblk] = n
@@ -305,7 +329,7 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
  *   d_out, out_capacity, d_out_off[nblk + 1], d_out_size, d_status: one dense arena as in
  *   rans4x16_hip_compress_packed_dev - offsets written by the call, sums before the capacity rule, d_out == NULL with
  *   out_capacity 0 as a sizing pass; a block that ends beyond out_capacity reports R4X16_E_CAPACITY and size 0.
- * Block b's bytes are what :1498-1531 writes: the header with use_arith = 0, then per column the type byte and either
+ * Block b's bytes are what :1498-1531 writes: the header with use_arith = 0 (1 under R4X16_TOK3_ARITH_ENCODE), then per column the type byte and either
  * var_put_u32(clen) and the winner's stream - the winner of rans4x16_hip_compress_best_dev's rules, X_STRIPE skip and
  * first-listed-wins included - or the three bytes of a duplicate.  A column is a duplicate of the first earlier column
  * of its block whose varint + stream has the same length, more than 4 bytes, and the same bytes (:1461-1477); columns
@@ -333,7 +357,7 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
  *   d_col_off - nreads.
  *   d_ncol (descriptors), d_last_start, d_nreads, d_out_size (bytes of all columns), d_status [nblk].
  * The walk (the statuses are those of rans4x16_hip_tok3_scan):
- *   - fewer than 9 bytes: TRUNCATED; use_arith != 0: UNSUPPORTED; last_start negative as an int or above
+ *   - fewer than 9 bytes: TRUNCATED; use_arith != 0: UNSUPPORTED unless rans4x16_hip_set_tok3_arith; last_start negative as an int or above
  *     INT_MAX - 1024: SIZE (:1555); a container above max_in_size: UNSUPPORTED, not read.
  *   - a | 128 descriptor opens the next tnum; the 128th: SIZE.  If its type is not 0 the position's type column (id
  *     tnum << 4) is synthesised first: nreads bytes, the type and then N_MATCH (10) repeated (:1581-1591, :1619-1629);
@@ -353,6 +377,12 @@ int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *ctx, int n,
  * d_ncol = 0, d_out_size = 0, its directory sizes are 0, the bytes inside its own range are unspecified (a block the walk
  * refuses has no range).  Nothing outside the ranges is written.  The call only enqueues and reads nothing back. */
 #define R4X16_TOK3_TYPE_COLUMN 0x10000   /* d_col_id flag of rans4x16_hip_tok3_unpack_dev, above */
+#define R4X16_TOK3_ARITH_DECODE 1
+#define R4X16_TOK3_ARITH_ENCODE 2
+int rans4x16_hip_set_tok3_arith(rans4x16_hip_ctx *ctx, int mode);
+int rans4x16_hip_tok3_scan_any(const unsigned char *in, size_t size, uint32_t max_columns, uint32_t max_col_size,
+                               uint32_t *last_start, uint32_t *nreads, uint32_t *ndesc, uint32_t *ncol,
+                               uint64_t *total_col_size, uint32_t *largest_col, uint32_t *largest_stream, int *use_arith);
 int rans4x16_hip_tok3_scan(const unsigned char *in, size_t size, uint32_t max_columns, uint32_t max_col_size,
                            uint32_t *last_start, uint32_t *nreads, uint32_t *ndesc, uint32_t *ncol,
                            uint64_t *total_col_size, uint32_t *largest_col, uint32_t *largest_stream);
@@ -374,7 +404,7 @@ int rans4x16_hip_tok3_unpack_dev(rans4x16_hip_ctx *ctx, int nblk,
 /* ---- 2d. tok3 name decoding ---------------------------------------------------------------------
  * The second half of decode_names (htscodecs tokenise_name3.c:1546-1694): the token columns of a name block become its
  * read names, NUL-separated, on the device - decode_name (:1018-1189) and the loop around it (:1671-1689).  rANS flavour
- * (use_arith = 0) only; the encoding direction is part 2e.
+ * (use_arith = 0) unless rans4x16_hip_set_tok3_arith (part 2c); the encoding direction is part 2e.
  *
  * rans4x16_hip_tok3_names_dev: the stage.  Its inputs are what rans4x16_hip_tok3_unpack_dev wrote, DEVICE arrays all:
  *   d_cols, col_capacity         the column arena and its size in bytes; a column that does not lie inside it fails its
@@ -451,7 +481,8 @@ int rans4x16_hip_tok3_decode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
 /* ---- 2e. tok3 name encoding ---------------------------------------------------------------------
  * The first half of encode_names (htscodecs tokenise_name3.c:1334-1429): a block of read names becomes the token columns
  * that rans4x16_hip_tok3_pack_dev compresses and frames - build_trie / search_trie (:507-712), encode_name (:729-1013,
- * mode 1) and the drop rule (:1406-1429), on the device.  rANS flavour (use_arith = 0) only.
+ * mode 1) and the drop rule (:1406-1429), on the device.  rANS flavour (use_arith = 0) unless
+ * rans4x16_hip_set_tok3_arith (part 2c).
  *
  * rans4x16_hip_tok3_tokenise_dev: nblk name blocks at d_in + d_in_off[b], d_in_size[b] bytes.  Every array is a DEVICE
  * array; the call only enqueues and reads nothing back.
@@ -530,7 +561,7 @@ int rans4x16_hip_tok3_encode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
 
 /* ---- 2f. tok3 names with host buffers -------------------------------------------------------------
  * encode_names / decode_names of htscodecs tokenise_name3.c (:1334-1531, :1546-1694) with HOST buffers in and out, rANS
- * flavour (use_arith = 0): the boundary of parts 2c to 2e for a caller that holds a `char *blk` and knows none of their
+ * flavour (use_arith = 0) unless rans4x16_hip_set_tok3_arith or the two _arith_ functions below: the boundary of parts 2c to 2e for a caller that holds a `char *blk` and knows none of their
  * limits.  include/tok3_names_hip.h gives the two functions their reference names.
  *
  * rans4x16_hip_tok3_level_methods: the row of tokenise_name3.c:1254-1260 that `level` selects ((level - 1) / 2, clamped to
@@ -542,6 +573,19 @@ int rans4x16_hip_tok3_encode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
  * use_arith != 0 returns NULL (the reason on stderr, once per process); last_start_p may be NULL; after success every byte
  * <= '\n' in front of last_start has been overwritten with NUL in the caller's buffer, as the reference does (:1374), and
  * the bytes from last_start on are left alone.  decode: *out_len = last_start bytes of NUL-separated names.
+ * These two keep to the rANS flavour whatever mode a context has: decode_names returns NULL for use_arith != 0.
+ *
+ * rans4x16_hip_tok3_arith_encode_names(blk, len, level, out_len, last_start_p) / rans4x16_hip_tok3_arith_decode_names: the
+ * same two functions for the arith flavour - the thread's context with rans4x16_hip_set_tok3_arith's mode set for the
+ * call and put back; ownership and NUL-writing as above.  The container's byte 8 is 1; `level` is the reference's inner
+ * level 1..9 (the reference's command line writes -17 for level 7 with use_arith = 1).  arith_decode_names takes the flavour
+ * from the container and reads rANS ones too.  include/tok3_names_hip.h forwards encode_names(.., use_arith != 0, ..) and
+ * decode_names of a container with byte 8 set to them.
+ *
+ * rans4x16_hip_thread_ctx: the context of the CALLING thread on which the single-block functions of this part and of parts
+ * 2g and 2h run (made at first use, NULL without a usable GPU).  It is the library's: it ends with its thread and must
+ * not be destroyed.  A caller may read its routes and its last error and set its options and setters; the four functions
+ * above set the tok3 mode they need for their one call and leave rans4x16_hip_set_tok3_arith's value as the caller had it.
  *
  * rans4x16_hip_tok3_encode_names_batch / rans4x16_hip_tok3_decode_names_batch: nblk independent blocks in host memory.
  *   in[i], in_size[i]   block i: names (encode) / a container (decode); never written
@@ -559,7 +603,7 @@ int rans4x16_hip_tok3_encode_names_dev(rans4x16_hip_ctx *ctx, int nblk,
  * what exceeds the device calls' hard limits (a block above 16,776,960 bytes - it is not uploaded -, a name above 16,384
  * bytes, 2^24 names or more) is clamped, so that the device refuses that block alone with R4X16_E_UNSUPPORTED.  Decode:
  * rans4x16_hip_tok3_scan gives each container's limits; one it refuses reports the scan's status and is not uploaded
- * (use_arith != 0 is R4X16_E_UNSUPPORTED there); X_STRIPE columns (levels 3 and up) are decoded as after
+ * (use_arith != 0 is R4X16_E_UNSUPPORTED there; under R4X16_TOK3_ARITH_DECODE rans4x16_hip_tok3_scan_any is the scan); X_STRIPE columns (levels 3 and up) are decoded as after
  * rans4x16_hip_set_dev_stripe_planes(ctx, 4, largest column), and the context's own setting is left as the caller had
  * it.  A container whose columns and histories alone do not fit half of what the context may take (a hostile size
  * field, as a rule) reports R4X16_E_UNSUPPORTED and is not uploaded.
@@ -570,6 +614,9 @@ int rans4x16_hip_tok3_level_methods(int level, int *methods);
 unsigned char *rans4x16_hip_tok3_encode_names(char *blk, int len, int level, int use_arith,
                                               int *out_len, int *last_start_p);
 unsigned char *rans4x16_hip_tok3_decode_names(unsigned char *in, uint32_t sz, uint32_t *out_len);
+unsigned char *rans4x16_hip_tok3_arith_encode_names(char *blk, int len, int level, int *out_len, int *last_start_p);
+unsigned char *rans4x16_hip_tok3_arith_decode_names(unsigned char *in, uint32_t sz, uint32_t *out_len);
+rans4x16_hip_ctx *rans4x16_hip_thread_ctx(void);
 int rans4x16_hip_tok3_encode_names_batch(rans4x16_hip_ctx *ctx, int nblk,
                                          const unsigned char *const *in, const unsigned int *in_size,
                                          unsigned char **out, unsigned int *out_size,
@@ -582,7 +629,8 @@ int rans4x16_hip_set_names_chunk_blocks(rans4x16_hip_ctx *ctx, int blocks);
 /* ---- 2g. arith_dynamic decoding (the CRAM 3.1 adaptive arithmetic coder) ---------------------------------------
  * htscodecs/arith_dynamic.c's decoder on the device: one carry-less range coder and adaptive models per stream (order 0,
  * order 1, with or without the coder's own run lengths), inside the containers of rANS 4x16 (X_PACK, X_CAT, X_NOSZ,
- * X_STRIPE).  The encoder is part 2h.  tok3 containers with use_arith = 1 stay R4X16_E_UNSUPPORTED (parts 2c-2f).
+ * X_STRIPE).  The encoder is part 2h.  tok3 containers with use_arith = 1 are R4X16_E_UNSUPPORTED (parts 2c-2f) unless
+ * rans4x16_hip_set_tok3_arith.
  * A stream is one serial chain of dependent steps: one wave decodes it, so a
  * batch wants many streams.
  *
@@ -673,6 +721,24 @@ unsigned char *rans4x16_hip_arith_uncompress(unsigned char *in, unsigned int in_
  * capacity on entry and the size on return; NULL on failure), on the calling thread's context.
  * include/arith_dynamic_hip.h gives them the reference's names.
  *
+ * rans4x16_hip_arith_compress_best_packed_dev: rans4x16_hip_compress_best_packed_dev for this coder - its arguments, its
+ * dense arena (offsets written by the call and summed before the capacity rule, d_out == NULL with out_capacity 0 as a
+ * sizing pass, R4X16_E_CAPACITY and size 0 for a block that ends beyond out_capacity), and the rules of
+ * rans4x16_hip_compress_best_dev: block i gets exactly the bytes of arith_compress_to(in, size, .., methods[j]) for the
+ * smallest result, the earlier method on ties; d_chosen[i] (may be NULL) is that methods[j] as given, -1 if no candidate
+ * succeeded; an X_STRIPE method is skipped when size % 4 != 0 (tokenise_name3.c:1270); a block whose every method was
+ * skipped, or that lies above max_in_size, reports R4X16_E_UNSUPPORTED; more than 255 planes in a method make the call
+ * return -1.  A batch that holds more than total_in_size announced runs out of room for some candidates: a block of which
+ * any tried candidate found no room reports R4X16_E_UNSUPPORTED as a whole, whatever its other candidates gave - a
+ * winner is always the smallest of ALL the methods that apply.  rans4x16_hip_arith_best_chunk_blocks(ctx, n, k, methods,
+ * max_in_size, total_in_size) returns the blocks per chunk the call plans for these arguments under the context's
+ * max_workspace_mb and the free memory of the moment (n where the batch is one chunk; -1 on bad arguments): host
+ * arithmetic, nothing is enqueued.  The k candidates of a chunk of blocks go through the coder's kernels in one pass, as
+ * k times as many items with per-item order words (no rans4x16_hip_set_dev_stripe_encode is needed, the context's setting
+ * is left alone), into slots of rans4x16_hip_arith_compress_cap bytes each in an arena of the context; the batch is walked
+ * in chunks under max_workspace_mb.  The call only enqueues, reads nothing back and writes nothing outside the blocks'
+ * ranges.  R4X16_ROUTE_ARITH_ENC counts every candidate stream that was tried.
+ *
  * Route read-out: R4X16_ROUTE_ARITH_ENC counts the candidate streams (a stripe block's planes under each method) that
  * reached the coder by the home of their models, those with run lengths under R4X16_ARITH_ENC_RLE too, and under
  * R4X16_ARITH_ENC_STORED every candidate that came out as X_CAT: an explicit X_CAT, and a coded one that ended no smaller
@@ -684,6 +750,14 @@ int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *ctx, int n,
                                     unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                     uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
                                     uint32_t max_in_size, uint64_t total_in_size, void *stream);
+int rans4x16_hip_arith_compress_best_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                                const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                                unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                                uint32_t *d_out_size, int32_t *d_status,
+                                                int k, const int *methods, int32_t *d_chosen,
+                                                uint32_t max_in_size, uint64_t total_in_size, void *stream);
+int rans4x16_hip_arith_best_chunk_blocks(rans4x16_hip_ctx *ctx, int n, int k, const int *methods,
+                                         uint32_t max_in_size, uint64_t total_in_size);
 int rans4x16_hip_arith_compress_batch(rans4x16_hip_ctx *ctx, int n,
                                       const unsigned char *const *in, const unsigned int *in_size,
                                       unsigned char *const *out, unsigned int *out_size, const int *order, int *status);

@@ -1,15 +1,18 @@
 /*
  * tok3_hip - read names through the name tokeniser of librans4x16_hip.so (include/rans4x16_hip.h part 2f).
  *
- *   tok3_hip [-<level>] [-r] [in [out]]     names, one per line -> containers
- *   tok3_hip -d [-r] [in [out]]             containers -> names, one per line
+ *   tok3_hip [-a] [-<level>] [-r] [in [out]]   names, one per line -> containers
+ *   tok3_hip -d [-r] [in [out]]                containers -> names, one per line
  *
  * Without -r the input is cut into blocks of 1 MiB that end behind a line end (a partial last line is carried into the
  * next block, as a caller does with encode_names' last_start) and every container is written behind its 4-byte size,
  * little endian.  All blocks of a file go to the GPU in ONE batch call: a block alone is one wave on the chip.
  * -r: the whole input is one naked block (encode) or one naked container (decode), through the two single-block
- * functions.  Levels 1..9 select the method list as in the reference; levels from 11 ask for the arithmetic coder,
- * which this library does not have.
+ * functions.  Levels 1..9 select the method list as in the reference.  -a writes the arith flavour (use_arith = 1: the
+ * columns go through the adaptive arithmetic coder), what the reference's command line spells as level + 10; levels from
+ * 11 are refused here with a pointer to -a.  -d takes the flavour from the data, container by container: it always
+ * asks for R4X16_TOK3_ARITH_DECODE, so a file of rANS containers alone also pays for the arith decoder's launches over
+ * fully masked lists (under a millisecond a call, profiles/tok3_arith.md).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,17 +46,18 @@ static int fail(const char *what) { fprintf(stderr, "tok3_hip: %s\n", what); ret
 
 int main(int argc, char **argv)
 {
-    int decode = 0, raw = 0, level = 9, a = 1;
+    int decode = 0, raw = 0, arith = 0, level = 9, a = 1;
     for (; a < argc && argv[a][0] == '-' && argv[a][1]; a++) {
         if (!strcmp(argv[a], "-d")) decode = 1;
         else if (!strcmp(argv[a], "-r")) raw = 1;
+        else if (!strcmp(argv[a], "-a")) arith = 1;
         else if (argv[a][1] >= '0' && argv[a][1] <= '9') level = atoi(argv[a] + 1);
         else {
-            fprintf(stderr, "usage: tok3_hip [-d] [-r] [-<level 1..9>] [in [out]]\n");
+            fprintf(stderr, "usage: tok3_hip [-d] [-r] [-a] [-<level 1..9>] [in [out]]\n");
             return 1;
         }
     }
-    if (level >= 11) return fail("levels from 11 select the arithmetic coder (use_arith), which this library does not have");
+    if (level >= 11) return fail("levels from 11 are not taken: for the arithmetic coder (use_arith) give -a and the level 1..9, -a -7 for -17");
     FILE *in = a < argc && strcmp(argv[a], "-") ? fopen(argv[a], "rb") : stdin;
     if (!in) { perror(argv[a]); return 1; }
     FILE *out = a + 1 < argc ? fopen(argv[a + 1], "wb") : stdout;
@@ -73,7 +77,7 @@ int main(int argc, char **argv)
             free(names);
         } else {
             int n = 0, last_start = 0;
-            unsigned char *c = encode_names((char *)data, (int)size, level, 0, &n, &last_start);
+            unsigned char *c = encode_names((char *)data, (int)size, level, arith, &n, &last_start);
             if (!c) return fail("encode_names failed");
             if ((size_t)last_start < size) fprintf(stderr, "tok3_hip: %zu bytes behind the last line end were not encoded\n", size - (size_t)last_start);
             if (put(out, c, (size_t)n) != 0) return fail("write error");
@@ -120,6 +124,7 @@ int main(int argc, char **argv)
     int *status = (int *)calloc(nblk ? nblk : 1, sizeof(*status));
     if (!res || !res_size || !status) return fail("out of memory");
     int methods[9], rc;
+    if (rans4x16_hip_set_tok3_arith(ctx, decode ? R4X16_TOK3_ARITH_DECODE : arith ? R4X16_TOK3_ARITH_ENCODE : 0) < 0) return fail("set_tok3_arith");
     if (decode) rc = rans4x16_hip_tok3_decode_names_batch(ctx, (int)nblk, ptr, len, res, res_size, NULL, status);
     else rc = rans4x16_hip_tok3_encode_names_batch(ctx, (int)nblk, ptr, len, res, res_size, rans4x16_hip_tok3_level_methods(level, methods),
                                                    methods, NULL, NULL, status);

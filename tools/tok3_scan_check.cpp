@@ -1,5 +1,5 @@
-// tok3_scan_check - rans4x16_hip_tok3_scan (htscodecs_amd/csrc/r4x16_tok3_scan.hip) over the containers given on the
-// command line and over damaged variants of them, as a stand-alone host program: built with a sanitizer it checks that
+// tok3_scan_check - rans4x16_hip_tok3_scan and rans4x16_hip_tok3_scan_any (htscodecs_amd/csrc/r4x16_tok3_scan.hip) over the
+// containers given on the command line (either flavour) and over damaged variants of them, as a stand-alone host program: built with a sanitizer it checks that
 // the walk reads nothing outside the buffer it was given, whatever the container says.  Every variant sits in a heap
 // allocation of exactly its own size.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include \
@@ -26,7 +26,21 @@ static int scan_exact(const std::vector<unsigned char> &v, uint32_t max_columns,
     uint32_t ls, nr, nd, nc, lc, lst;
     uint64_t tot;
     const int rc = rans4x16_hip_tok3_scan(p, v.size(), max_columns, max_col_size, &ls, &nr, &nd, &nc, &tot, &lc, &lst);
+    // the same bytes through the scan of either flavour: the same verdict where byte 8 is clear, else scan refuses at the
+    // header and scan_any walks on
+    uint32_t als, anr, and_, anc, alc, alst;
+    uint64_t atot;
+    int arith = -1;
+    const int arc = rans4x16_hip_tok3_scan_any(p, v.size(), max_columns, max_col_size, &als, &anr, &and_, &anc, &atot, &alc, &alst, &arith);
+    const bool flagged = v.size() > 8 && p[8] != 0;
     free(p);
+    if (arith != (flagged ? 1 : 0)) { fprintf(stderr, "scan_any reports flavour %d\n", arith); exit(2); }
+    if (!flagged && (arc != rc || als != ls || anr != nr || and_ != nd || anc != nc || atot != tot || alc != lc || alst != lst)) {
+        fprintf(stderr, "scan_any differs from scan on a container without the flag\n"); exit(2);
+    }
+    if (flagged && (rc != R4X16_E_UNSUPPORTED || nd != 0)) { fprintf(stderr, "scan walks a container with use_arith set\n"); exit(2); }
+    if (arc < 0 || arc > 9 || and_ > (max_columns ? max_columns : 2048u) || anc > 2u * and_ || alst > v.size()) { fprintf(stderr, "scan_any out of range\n"); exit(2); }
+    if (flagged) { by_status[arc]++; return arc; }
     if (rc < 0 || rc > 9) { fprintf(stderr, "scan returned %d\n", rc); exit(2); }
     if (nd > (max_columns ? max_columns : 2048u) || nc > 2u * nd || lst > v.size()) { fprintf(stderr, "scan counts out of range\n"); exit(2); }
     by_status[rc]++;
