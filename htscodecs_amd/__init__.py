@@ -17,6 +17,7 @@ from .codec import (  # noqa: F401
     tok3_scan_any, set_tok3_arith, TOK3_ARITH_DECODE, TOK3_ARITH_ENCODE,
     arith_uncompress, arith_uncompress_batch,
     arith_compress, arith_compress_batch, arith_compress_bound, arith_compress_cap,
+    fqz_scan, fqz_decompress, fqz_uncompress_batch,
 )
 
 __all__ = [
@@ -28,4 +29,5 @@ __all__ = [
     "tok3_scan_any", "set_tok3_arith", "TOK3_ARITH_DECODE", "TOK3_ARITH_ENCODE",
     "arith_uncompress", "arith_uncompress_batch",
     "arith_compress", "arith_compress_batch", "arith_compress_bound", "arith_compress_cap",
+    "fqz_scan", "fqz_decompress", "fqz_uncompress_batch",
 ]

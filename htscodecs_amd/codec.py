@@ -134,7 +134,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith", "arith_enc") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc", "fqz") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -146,7 +146,7 @@ class _Ctx:
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
-               "arith_enc": 7}
+               "arith_enc": 7, "fqz": 8}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -156,6 +156,7 @@ ROUTE_KINDS = {
     "names": ("enc_chunks", "dec_chunks", "uploaded", "refused"),
     "arith": ("o0", "o1_lds", "o1_global", "rle"),
     "arith_enc": ("o0", "o1_lds", "o1_global", "rle", "stored"),
+    "fqz": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
 }
 
 _tls = threading.local()
@@ -514,6 +515,61 @@ def arith_uncompress(comp, out_size=None):
     return out.raw[:n.value] if p else None
 
 
+def fqz_scan(stream):
+    """rans4x16_hip_fqz_scan: the header walk of one fqzcomp_qual stream.  Returns (status, info) with info the stored size,
+    the header's bytes, gflags, nparam, max_sel and max_sym.  Needs no GPU."""
+    L = _lib.load()
+    buf = bytes(stream)
+    v = [C.c_uint32(0) for _ in range(6)]
+    st = L.rans4x16_hip_fqz_scan(buf, len(buf), *[C.byref(x) for x in v])
+    keys = ("stored_size", "header_bytes", "gflags", "nparam", "max_sel", "max_sym")
+    return st, dict(zip(keys, (x.value for x in v)))
+
+
+def fqz_uncompress_batch(blocks, caps=None, nlengths=None, ctx=None):
+    """rans4x16_hip_fqz_uncompress_batch: fqzcomp_qual streams (bytes) -> (list of bytes | None, statuses, lengths, nrec).
+    caps: the capacity of each output (default: the stored size); nlengths: how many record lengths to take per block
+    (default: none) - lengths[i] holds min(nlengths[i], nrec[i]) entries.  One upload, one device call, one download."""
+    ctx = ctx or _thread_ctx()
+    L = ctx.L
+    n = len(blocks)
+    if caps is None:
+        caps = [fqz_scan(b)[1]["stored_size"] for b in blocks]
+    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+    outs = [np.empty(max(int(c), 1), dtype=np.uint8) for c in caps]
+    nl = [0] * n if nlengths is None else [int(v) for v in nlengths]
+    lens = [np.full(max(v, 1), -1, dtype=np.int32) for v in nl]
+    dummy = np.zeros(1, dtype=np.uint8)
+    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
+    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    len_p = (C.c_void_p * n)(*[a.ctypes.data for a in lens])
+    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
+    out_sz = (C.c_uint * n)(*[int(c) for c in caps])
+    nl_a = (C.c_int * n)(*nl)
+    nrec = (C.c_uint * n)()
+    status = (C.c_int * n)()
+    rc = L.rans4x16_hip_fqz_uncompress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, status, len_p, nl_a, nrec)
+    if rc < 0:
+        raise RuntimeError("fqz batch failed: " + ctx.error())
+    res = [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)]
+    return res, list(status), [lens[i][:min(nl[i], nrec[i])].tolist() for i in range(n)], list(nrec)
+
+
+def fqz_decompress(comp, nlengths=0):
+    """The reference's fqz_decompress: (the decoded qualities, the first nlengths record lengths - the entries behind the
+    last record are -1), or None where the reference returns NULL."""
+    L = _lib.load()
+    buf = bytes(comp)
+    n = C.c_size_t(0)
+    lens = (C.c_int * max(int(nlengths), 1))(*([-1] * max(int(nlengths), 1)))
+    p = L.rans4x16_hip_fqz_decompress(buf, len(buf), C.byref(n), lens if nlengths else None, int(nlengths))
+    if not p:
+        return None
+    res = C.string_at(p, n.value)
+    _free(p)
+    return res, list(lens)[:int(nlengths)]
+
+
 def arith_compress_bound(size, order):
     """The reference's arith_compress_bound (host arithmetic)."""
     return _lib.load().rans4x16_hip_arith_compress_bound(int(size), int(order))
@@ -709,6 +765,44 @@ class DeviceCodec:
                                                 fmt.data_ptr(), raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
         if rc != 0:
             raise RuntimeError("arith_peek_dev: " + self.ctx.error())
+
+    # ---- fqzcomp_qual decoding (include/rans4x16_hip.h part 2i) -------------------------------------------------------
+    def fqz_uncompress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status,
+                       max_in_size, max_out_size, total_out_size=0, d_len=None, len_off=None, len_cap=None, nrec=None):
+        """rans4x16_hip_fqz_uncompress_dev: arith_uncompress()'s arguments over fqzcomp_qual streams, and the four optional
+        ones: record lengths into d_len (int32) at len_off (int64, entries) up to len_cap (int32, entries), record counts
+        into nrec (int32).  Enqueues only."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
+        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert d_len is None or (d_len.dtype == t.int32 and len_off.dtype == t.int64 and len_cap.dtype == t.int32)
+        assert nrec is None or nrec.dtype == t.int32
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        rc = self.L.rans4x16_hip_fqz_uncompress_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            ptr(d_len), ptr(len_off), ptr(len_cap), ptr(nrec),
+            int(max_in_size), int(max_out_size), int(total_out_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("fqz_uncompress_dev: " + self.ctx.error())
+
+    def fqz_peek(self, d_in, in_off, in_size, raw_size, status, max_in_size):
+        """rans4x16_hip_fqz_peek_dev: the stored size of every fqzcomp_qual stream."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and in_off.dtype == t.int64 and in_size.dtype == t.int32
+        assert raw_size.dtype == t.int32 and status.dtype == t.int32
+        rc = self.L.rans4x16_hip_fqz_peek_dev(self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+                                              raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
+        if rc != 0:
+            raise RuntimeError("fqz_peek_dev: " + self.ctx.error())
+
+    def set_fqz_limits(self, max_slots=0, max_sym=0):
+        """rans4x16_hip_set_fqz_limits: the model slots in flight at most (0: 1024) and the largest max_sym a slot holds
+        (0: 255)."""
+        if self.L.rans4x16_hip_set_fqz_limits(self.ctx.h, int(max_slots), int(max_sym)) != 0:
+            raise ValueError("set_fqz_limits: " + self.ctx.error())
 
     # ---- packed calls (include/rans4x16_hip.h part 2a): one dense arena, offsets written by the device ----------
     def _packed_args(self, d_in, in_off, in_size, d_out, out_off, out_size, status):

@@ -17,7 +17,7 @@
 // max_out_size by k_ar_front; an item that has no work enters none.  All stores are plain vector stores.
 #include "r4x16_host.h"
 #include "r4x16_arith_parse.h"
-#include "r4x16_arith_model.h"
+#include "r4x16_arith_step.h"
 
 enum { AR_HOME_O0 = 0, AR_HOME_O1_LDS = 1, AR_HOME_O1_GLOBAL = 2, AR_HOME_NONE = 3 };
 
@@ -113,108 +113,6 @@ __global__ __launch_bounds__(256) void k_ar_front(BatchArgs a, ArWs w, int base,
         bk.status = st; bk.out_size = st == AR_OK ? top.out_size : 0u; bk.nplanes = st == AR_OK ? top.nplanes : 0u; bk.pad = 0;
         w.blk[b] = bk;
     }
-}
-
-// ---- the step ---------------------------------------------------------------------------------------------------
-struct ArCoder {
-    u32 code, range, pos, end;      // wave-uniform
-    // the input: a window of 1 KB held in registers, 16 bytes a lane, read by a scalar lane read (WinSrc's scheme,
-    // r4x16_dev.h), so that the byte-wise renormalisation never waits for memory; the last bytes, which fill no whole
-    // 16-byte piece, are read from memory.  (Not WinSrc itself: it points at a ByteSrc, and the two as members of one
-    // object - the pointer to a sibling member - put the whole coder into scratch memory, 112 bytes a lane.)
-    const u8 *base;
-    u32x4 held;
-    u32 wbase, wlen;
-    __device__ ArCoder(const u8 *in, u32 in_size, u32 lane) : code(0), range(0xffffffffu), pos(1), end(in_size), base(in),
-                                                             held{0, 0, 0, 0}, wbase(0), wlen(0)
-    {
-        if (pos + 5 >= end) pos = end;                              // c_range_coder.h:64-67: nothing is read, code stays 0
-        else for (int k = 0; k < 5; k++) code = (code << 8) | byte(pos++, lane);
-    }
-    __device__ __forceinline__ void fill(u32 p, u32 lane)
-    {
-        wbase = p & ~15u;
-        const u32 mine = wbase + 16u * lane;
-        held = u32x4{0, 0, 0, 0};
-        if (mine + 16u <= end) held = *(const u32x4_unaligned *)(base + mine);
-        const u32 room = (end - wbase) & ~15u;
-        wlen = room < 1024u ? room : 1024u;
-    }
-    __device__ __forceinline__ u32 byte(u32 p, u32 lane)           // p < end
-    {
-        if (p - wbase >= wlen) {
-            if (p + 16u > end) return base[p];
-            fill(p, lane);
-        }
-        const u32 so = (u32)__builtin_amdgcn_readfirstlane((int)(p - wbase));
-        const int ln = (int)(so >> 4);
-        const u32 d0 = (u32)__builtin_amdgcn_readlane((int)held.x, ln), d1 = (u32)__builtin_amdgcn_readlane((int)held.y, ln),
-                  d2 = (u32)__builtin_amdgcn_readlane((int)held.z, ln), d3 = (u32)__builtin_amdgcn_readlane((int)held.w, ln);
-        const u32 lo = (so & 4u) ? d1 : d0, hi = (so & 4u) ? d3 : d2;
-        return (((so & 8u) ? hi : lo) >> (8u * (so & 3u))) & 0xffu;
-    }
-    // RC_GetFreq: the guard included (c_range_coder.h:112-115)
-    __device__ __forceinline__ u32 get_freq(u32 tot)
-    {
-        if (tot == 0 || range < tot) return 0;
-        range /= tot;
-        return code / range;
-    }
-    // RC_Decode (:117-127): stops renormalising where the input ends
-    __device__ __forceinline__ void decode(u32 cum, u32 f, u32 lane)
-    {
-        code -= cum * range;
-        range *= f;
-        while (range < AR_TOP) {
-            if (pos >= end) return;
-            code = (code << 8) + byte(pos++, lane);
-            range <<= 8;
-        }
-    }
-};
-
-// One symbol of a model that lies across the wave (SIMPLE_MODEL(256,_decodeSymbol), c_simple_model.h:148-179).  e: this
-// lane's four entries, zero beyond the live ones; tot: their sum over the wave.  *dirty: this lane's entries changed.
-__device__ __forceinline__ u32 ar_symbol(u32x4 &e, u32 &tot, ArCoder &rc, u32 lane, bool *dirty)
-{
-    *dirty = false;
-    const u32 freq = rc.get_freq(tot);
-    if (freq > AR_MAX_FREQ) return 0;                               // :153: no update, no RC_Decode
-    const u32 c0 = e.x & 0xffffu, c1 = c0 + (e.y & 0xffffu), c2 = c1 + (e.z & 0xffffu), c3 = c2 + (e.w & 0xffffu);
-    const u32 incl = wave_incl_scan(c3, lane);
-    const u64 hit = __ballot(incl > freq);
-    if (hit == 0) return 0;                                         // :158: the scan ran off the list (freq >= tot)
-    const int L = (int)__builtin_ctzll(hit);
-    const u32 excl = incl - c3;
-    const u32 j_l = (u32)(excl + c0 <= freq) + (u32)(excl + c1 <= freq) + (u32)(excl + c2 <= freq);
-    const u32 cum_l = excl + (j_l == 0 ? 0u : j_l == 1 ? c0 : j_l == 2 ? c1 : c2);
-    const u32 j = (u32)__builtin_amdgcn_readlane((int)j_l, L);
-    const u32 cum = (u32)__builtin_amdgcn_readlane((int)cum_l, L);
-    const u32 ent = (u32)__builtin_amdgcn_readlane((int)ar_get(e, j_l), L);
-    rc.decode(cum, ent & 0xffffu, lane);
-    const bool own = lane == (u32)L;
-    u32 cur = ent + AR_STEP;                                         // (a frequency is at most the total: no carry into the symbol)
-    ar_set(e, j, cur, own);
-    tot += AR_STEP;
-    bool all = false;
-    if (tot > AR_MAX_FREQ) {                                        // normalise: every live entry, the total summed again
-        e.x = ar_half(e.x); e.y = ar_half(e.y); e.z = ar_half(e.z); e.w = ar_half(e.w);
-        cur = ar_half(cur);
-        tot = wave_sum((e.x & 0xffffu) + (e.y & 0xffffu) + (e.z & 0xffffu) + (e.w & 0xffffu));
-        all = true;
-    }
-    // one step of bubble sort: strictly greater than the position before (position 0 has the sentinel before it)
-    bool prev_lane = false;
-    if (j || L) {
-        const u32 prev = j ? (u32)__builtin_amdgcn_readlane((int)ar_get(e, j - 1), L) : (u32)__builtin_amdgcn_readlane((int)e.w, L - 1);
-        if ((cur & 0xffffu) > (prev & 0xffffu)) {
-            ar_set(e, j, prev, own);
-            if (j) ar_set(e, j - 1, cur, own);
-            else { ar_set(e, 3, cur, lane + 1 == (u32)L); prev_lane = lane + 1 == (u32)L; }
-        }
-    }
-    *dirty = own || all || prev_lane;
-    return ent >> 16;
 }
 
 // One symbol of a run-length model (SIMPLE_MODEL(258,_decodeSymbol) after _init(.., 4)): four live entries, held by every

@@ -67,7 +67,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 8
+#define ROUTE_WHICH 9
 #define ROUTE_KINDS 8
 struct HostPipe;
 void r4x16_pipe_destroy(HostPipe *);
@@ -82,7 +82,8 @@ enum R4Arena {
     A_PS,        // the packed calls' internal bound-sized slots and layout arrays (r4x16_packed.hip)
     A_T3,        // tok3 containers: the winners waiting to be framed / the directory of the columns to decode (r4x16_tok3.hip)
     A_TN,        // tok3 names: the names' histories; for the one-call form the columns in front of them (r4x16_tok3_names.hip)
-    A_AR,        // arith_dynamic, either direction: items, stage arena, the order-1 rows that do not fit LDS (r4x16_arith.hip, r4x16_arith_enc.hip)
+    A_AR,        // the adaptive coders: arith_dynamic, either direction - items, stage arena, the order-1 rows that do not fit LDS
+                 // (r4x16_arith.hip, r4x16_arith_enc.hip); fqzcomp_qual - blocks, tables, record tables, model slots (r4x16_fqz.hip)
     A_COUNT
 };
 #define A_BIT(a) (1u << (a))
@@ -171,6 +172,7 @@ struct rans4x16_hip_ctx {
     bool in_stripe = false;                 // inside the recursive call over the internal items
     bool in_packed = false;                 // inside a packed call's slot call over its internal slots (r4x16_packed.hip)
     int tok3_arith = 0;                     // tok3 calls: R4X16_TOK3_ARITH_* (rans4x16_hip_set_tok3_arith); 0: the rANS flavour alone
+    int fqz_slots = 0, fqz_max_sym = 255;   // fqzcomp_qual: model slots in flight at most (0: 1024), the largest max_sym a slot holds (rans4x16_hip_set_fqz_limits)
     int names_chunk_blocks = 0;             // host-buffer names batches: blocks per chunk at most (rans4x16_hip_set_names_chunk_blocks)
     // calls on different streams are ordered on the one workspace through this event
     hipEvent_t ws_done = nullptr;

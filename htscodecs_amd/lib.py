@@ -166,6 +166,19 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "rans4x16_hip_arith_compress_to": (C.c_void_p, [C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_uint), C.c_int]),
     "rans4x16_hip_arith_compress": (C.c_void_p, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint), C.c_int]),
+    # fqzcomp_qual decoding (include/rans4x16_hip.h part 2i)
+    "rans4x16_hip_fqz_scan": (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rans4x16_hip_set_fqz_limits": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "rans4x16_hip_fqz_uncompress_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "rans4x16_hip_fqz_peek_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rans4x16_hip_fqz_uncompress_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rans4x16_hip_fqz_decompress": (C.c_void_p, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int]),
     # rANS 4x8's packed and best-of-two device-resident calls (include/rans4x8_hip.h part 2a)
     "rans4x8_hip_compress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -765,6 +765,81 @@ unsigned char *rans4x16_hip_arith_compress_to(unsigned char *in, unsigned int in
                                               unsigned char *out, unsigned int *out_size, int order);
 unsigned char *rans4x16_hip_arith_compress(unsigned char *in, unsigned int in_size, unsigned int *out_size, int order);
 
+/* ---- 2i. fqzcomp_qual decoding (the CRAM 3.1 quality codec) ------------------------------------------------------
+ * htscodecs/fqzcomp_qual.c's decoder on the device: the range coder and the adaptive models of parts 2g and 2h, with a
+ * 16-bit context - up to 65,536 models a stream, in a slot of the context's arena - and the per-record machinery
+ * (selector, lengths, reverse flag, duplicates, parameter blocks and their tables).  Decoding only: fqz_compress,
+ * fqz_pick_parameters and fqz_qual_stats are not built.  DESIGN.md 4.8.
+ *
+ * rans4x16_hip_fqz_scan: walks the header of one stream in HOST memory.  Pure host arithmetic, usable without a GPU.
+ * Reports the stored size, the bytes in front of the range coder's input, gflags, nparam, max_sel and max_sym (the
+ * largest of the parameter blocks'; any of the pointers may be NULL) and returns 0 or the R4X16_E_* status the device
+ * gives the stream before it decodes a symbol:
+ *   R4X16_E_EMPTY        a zero-length block
+ *   R4X16_E_TRUNCATED    fewer than 10 bytes behind the size; a parameter block of fewer than 7 bytes; a qmap beyond the end
+ *   R4X16_E_UNSUPPORTED  a version other than 5
+ *   R4X16_E_SIZE         nparam = 0
+ *   R4X16_E_TABLE        where the reference is undefined: a table whose run lengths do not fill it
+ *                        (read_array returns -1, which the reference adds to its index unchecked - a table that starts
+ *                        at the end of the stream is one such), and PFLAG_DO_SEL in a parameter block with max_sel = 0
+ *
+ * rans4x16_hip_fqz_uncompress_dev has the arguments and the contract of rans4x16_hip_arith_uncompress_dev: it only
+ * enqueues on `stream`, reads no device list back, and writes nothing outside [d_out_off[i], d_out_off[i] + d_out_cap[i])
+ * and the lengths slots below.  Block i decodes to exactly the bytes of fqz_decompress, d_out_size[i] its stored size.
+ * Besides the scan's statuses, d_status[i] is
+ *   R4X16_E_CAPACITY     d_out_cap[i] below the stored size: nothing is written
+ *   R4X16_E_CONTEXT      a record's selector names a parameter block the stream does not have (the reference's NULL)
+ *   R4X16_E_SIZE         a record longer than the bytes that remain, or of length 0; a duplicate longer than the bytes
+ *                        decoded so far (the reference's NULL)
+ *   R4X16_E_UNSUPPORTED  a block above max_in_size (not read), a stored size above max_out_size or of 2^31 or more, a
+ *                        max_sym above rans4x16_hip_set_fqz_limits's, a block that finds total_out_size spent - the
+ *                        blocks are taken in their order - or no room for its parameter blocks (the arena holds four a
+ *                        block of the chunk and 256 at least: one stream always fits)
+ * On a refused block the bytes inside its slot may be anything.  Everything else is the reference's, bug for bug: a
+ * frequency above MAX_FREQ decodes symbol 0, a coder that runs dry goes on, a symbol beyond a stored qmap gives 255.
+ * The four arguments in front of max_in_size may be NULL (d_len_off and d_len_cap must be given with d_len):
+ *   d_len      record lengths: block i's record r at d_len[d_len_off[i] + r] for r < d_len_cap[i] - offsets and
+ *              capacities count ENTRIES; the reference's `lengths[rec] = len` for rec < nlengths
+ *   d_nrec     d_nrec[i] = the records of block i (0 for a refused one)
+ *
+ * rans4x16_hip_set_fqz_limits(ctx, max_slots, max_sym): max_slots caps the model slots - the streams decoded side by
+ * side; the others wait for a slot - at 1..1024 (0: 1024, four a compute unit).  max_sym (1..255; 0: 255) is the
+ * largest max_sym a slot holds: a slot is 65,536 x (4 x (max_sym + 1 rounded up to 4) + 4) bytes, 12.8 MB for the 45
+ * symbols of q40 data against 67.4 MB for 256, and the slots of a chunk count against max_workspace_mb.  Not named
+ * options: like rans4x16_hip_set_dev_stripe_planes they describe the batches to come, not the library.
+ *
+ * rans4x16_hip_fqz_peek_dev: the stored size per block - the varint at byte 0; this format has no flag byte.
+ * d_status[i]: R4X16_E_EMPTY, R4X16_E_UNSUPPORTED above max_in_size, R4X16_E_TRUNCATED where the varint runs past the block.
+ *
+ * rans4x16_hip_fqz_uncompress_batch: host buffers - out_size[i] holds the capacity of out[i] on entry and the size on
+ * return; lengths (NULL, or per block NULL or an array of nlengths[i] entries) and nrec (NULL or [n]) as above.  One
+ * upload, the device call with the slots sized for the batch's largest max_sym, one download.  Returns the number of
+ * failed blocks, -1 on a call error.
+ *
+ * rans4x16_hip_fqz_decompress: the arguments and the ownership of the reference's fqz_decompress (a malloc'd buffer of
+ * the stored size, the caller's to free; *uncomp_size is the stored size even on failure; NULL on failure), on the
+ * calling thread's context.  include/fqzcomp_qual_hip.h gives it the reference's name.
+ *
+ * Route read-out: R4X16_ROUTE_FQZ counts the streams that were decoded (R4X16_FQZ_*); each chunk of a call counts once
+ * as R4X16_LAUNCH_IN_ORDER under R4X16_ROUTE_LAUNCH. */
+int rans4x16_hip_fqz_scan(const unsigned char *in, unsigned int in_size, uint32_t *stored_size, uint32_t *header_bytes,
+                          uint32_t *gflags, uint32_t *nparam, uint32_t *max_sel, uint32_t *max_sym);
+int rans4x16_hip_set_fqz_limits(rans4x16_hip_ctx *ctx, int max_slots, int max_sym);
+int rans4x16_hip_fqz_uncompress_dev(rans4x16_hip_ctx *ctx, int n,
+                                    const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                    unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                    uint32_t *d_out_size, int32_t *d_status,
+                                    uint32_t *d_len, const uint64_t *d_len_off, const uint32_t *d_len_cap, uint32_t *d_nrec,
+                                    uint32_t max_in_size, uint32_t max_out_size, uint64_t total_out_size, void *stream);
+int rans4x16_hip_fqz_peek_dev(rans4x16_hip_ctx *ctx, int n,
+                              const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                              uint32_t *d_raw_size, int32_t *d_status, uint32_t max_in_size, void *stream);
+int rans4x16_hip_fqz_uncompress_batch(rans4x16_hip_ctx *ctx, int n,
+                                      const unsigned char *const *in, const unsigned int *in_size,
+                                      unsigned char *const *out, unsigned int *out_size, int *status,
+                                      int *const *lengths, const int *nlengths, unsigned int *nrec);
+char *rans4x16_hip_fqz_decompress(char *in, size_t comp_size, size_t *uncomp_size, int *lengths, int nlengths);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
@@ -850,7 +925,8 @@ enum {
     R4X16_ROUTE_RESULT = 4,   /* encode results: blocks per way they reached the caller's memory (R4X16_RESULT_*)     */
     R4X16_ROUTE_NAMES = 5,    /* host-buffer names batches (part 2f): chunks and blocks (R4X16_NAMES_*)                */
     R4X16_ROUTE_ARITH = 6,    /* arith_dynamic decoding (part 2g): streams per home of their models (R4X16_ARITH_*)    */
-    R4X16_ROUTE_ARITH_ENC = 7 /* arith_dynamic encoding (part 2h): candidate streams (R4X16_ARITH_ENC_*)               */
+    R4X16_ROUTE_ARITH_ENC = 7,/* arith_dynamic encoding (part 2h): candidate streams (R4X16_ARITH_ENC_*)               */
+    R4X16_ROUTE_FQZ = 8       /* fqzcomp_qual decoding (part 2i): decoded streams (R4X16_FQZ_*)                        */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -898,6 +974,15 @@ enum {   /* R4X16_ROUTE_ARITH_ENC: candidate streams of rans4x16_hip_arith_compr
     R4X16_ARITH_ENC_RLE = 3,       /* those of the three above that carry run lengths (counted there too)               */
     R4X16_ARITH_ENC_STORED = 4,    /* candidates that came out as X_CAT: asked for, or ended no smaller than their input */
     R4X16_ARITH_ENC_KINDS = 5
+};
+enum {   /* R4X16_ROUTE_FQZ: streams rans4x16_hip_fqz_uncompress_dev sent to a decode wave */
+    R4X16_FQZ_STREAMS = 0,      /* all of them                                                                         */
+    R4X16_FQZ_TAB_LDS = 1,      /* the parameter blocks' tables in LDS (up to eight parameter blocks)                  */
+    R4X16_FQZ_TAB_GLOBAL = 2,   /* the tables read from the context's arena                                            */
+    R4X16_FQZ_DO_REV = 3,       /* with GFLAG_DO_REV: a record table and the reversal pass                             */
+    R4X16_FQZ_MULTI_PARAM = 4,  /* with more than one parameter block                                                  */
+    R4X16_FQZ_DUP = 5,          /* accepted streams in which a duplicate record was copied                             */
+    R4X16_FQZ_KINDS = 6
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
