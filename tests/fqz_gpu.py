@@ -1,4 +1,4 @@
-"""What the GPU tests of fqzcomp_qual decoding share (test_gpu_fqz.py): one run of rans4x16_hip_fqz_uncompress_dev over a
+"""What the GPU tests of fqzcomp_qual decoding share (test_gpu_fqz.py, test_gpu_fqz_records.py): one run of rans4x16_hip_fqz_uncompress_dev over a
 list of streams with the confinement pattern of test_gpu_confinement.py - the output slots a few bytes apart at every
 alignment in an arena filled with a pattern, every byte outside them compared afterwards; the lengths slots a few
 entries apart in an arena of their own, every entry the call may not write compared - and the answers and the route of

@@ -208,22 +208,31 @@ def undefined(buf):
 
 # ---- the decoder (:1286-1490) ------------------------------------------------------------------------------------
 def _symbol(rc, m, ev, what):
-    """Decoder.symbol with the census: halvings, swaps, swaps across a lane boundary (a lane holds four list positions)"""
+    """Decoder.symbol with the census: halvings, swaps, swaps across a lane boundary (a lane holds four list positions),
+    an entry left level with the neighbour before it"""
     if ev is None:
         return rc.symbol(m)
     tot, pos_before = m.tot, rc.pos
     before, order = list(m.F), list(m.S)
     sym = rc.symbol(m)
+    halved = False
     if m.F == before:
         ev.append(what + ":no_update")                               # freq > MAX_FREQ, or the scan ran off the list
-    elif tot + STEP > MAX_FREQ:
-        ev.append(what + ":halve")
+    else:
+        halved = tot + STEP > MAX_FREQ
         i = m.S.index(sym)
-        if i > 0 and m.F[i] == m.F[i - 1]:                           # level with its neighbour after the halving: it stays
-            ev.append(what + ":halve_tie")
+        level = i > 0 and m.F[i] == m.F[i - 1]
+        if halved:
+            ev.append(what + ":halve")
+            if level:                                                # level with its neighbour after the halving: it stays
+                ev.append(what + ":halve_tie")
+        if level and m.S == order:                                   # after any update, and no swap: `>` not `>=`
+            ev.append(what + ":level")
     if m.S != order:
         i = order.index(sym)
         ev.append(what + ":swap")
+        if halved:
+            ev.append(what + ":halve_swap")                          # the step that halves the model also moves the entry up
         if i % 4 == 0:
             ev.append(what + ":swap_lane")
     if pos_before >= rc.end and m.F != before:
@@ -296,6 +305,8 @@ def decompress(buf, cap=None, nlengths=None, events=None, route=None):
                 out[i:i + ln] = out[i - ln:i]
                 if ev is not None:
                     ev.append("dup:taken")
+                    if ln > 64:
+                        ev.append("dup:wave")                        # the copy takes the wave a second trip
                     if len(lengths) > 1 and lengths[-2] != ln:
                         ev.append("dup:other_length")
                 i += ln
@@ -331,12 +342,19 @@ def decompress(buf, cap=None, nlengths=None, events=None, route=None):
         p -= 1
     if do_rev:
         at = 0
-        for ln, rev in zip(lengths, revs):
+        for k, (ln, rev) in enumerate(zip(lengths, revs)):
             if rev:
                 out[at:at + ln] = out[at:at + ln][::-1]
                 if ev is not None:
                     ev.append("rev:odd" if ln & 1 else "rev:even")
+                    ev.append("rev:wave" if ln > 32 else "rev:lane")    # the device's end pass: by the wave, by its lane
+                    if k >= 64:
+                        ev.append("rev:later_trip")                  # ... which takes 64 records a trip
             at += ln
+        if ev is not None:
+            for k in range(0, len(lengths) - 63, 64):
+                if all(r and ln > 32 for ln, r in zip(lengths[k:k + 64], revs[k:k + 64])):
+                    ev.append("rev:trip_all_wave")                   # a trip whose 64 records are all the wave's
     if route is not None and dups:
         route.update({"dup": 1})
     return OK, bytes(out), lengths if nlengths is None else lengths[:nlengths]
@@ -495,15 +513,15 @@ def fixtures():
     return res
 
 
-_edge = None
+_vectors = {}
 
 
-def edge():
-    """tests/golden/fqzcomp/edge.bin (its README): (inputs, damaged).  inputs: [(name, data, lens, flags, stream)];
-    damaged: [(stream, answer)] with answer None where the reference returns NULL, else (length, records, SHA-256)."""
-    global _edge
-    if _edge is None:
-        with open(os.path.join(GOLDEN, "edge.bin"), "rb") as f:
+def vectors(fn):
+    """a reference-made container of tests/golden/fqzcomp (its README): (inputs, damaged).  inputs: [(name, data or None,
+    lens, flags, stream, size, SHA-256 or None)]; damaged: [(stream, answer)] with answer None where the reference returns
+    NULL, else (length, records, SHA-256)."""
+    if fn not in _vectors:
+        with open(os.path.join(GOLDEN, fn), "rb") as f:
             b = f.read()
         assert b[:8] == b"FQEDGE1\n"
         pos = 8
@@ -537,8 +555,19 @@ def edge():
             else:
                 damaged.append((stream, None))
         assert pos == len(b)
-        _edge = (inputs, damaged)
-    return _edge
+        _vectors[fn] = (inputs, damaged)
+    return _vectors[fn]
+
+
+def edge():
+    """edge.bin: the header's and the loop's edges, streams of up to 1,000 records"""
+    return vectors("edge.bin")
+
+
+def records():
+    """records.bin: streams of thousands of records - the per-record models past their halvings, the end pass past its
+    first trip"""
+    return vectors("records.bin")
 
 
 def model_refused():

@@ -1,5 +1,5 @@
 """fqzcomp_qual decoding (include/rans4x16_hip.h part 2i), the half that needs no GPU: the Python model (fqz_model.py)
-against the reference's 16 streams and the reference-made vectors of tests/golden/fqzcomp/edge.bin, the header walk
+against the reference's 16 streams and the reference-made vectors of tests/golden/fqzcomp/edge.bin and records.bin, the header walk
 (htscodecs_amd/csrc/r4x16_fqz_parse.h) through the C ABI and as a stand-alone program under the sanitizers against the
 model, the census of what the GPU tests decode, the drop-in header from C and C++, and the symbols."""
 import collections
@@ -23,6 +23,10 @@ NO_CAP = 0xffffffff
 EVENTS = ("qual:halve", "qual:halve_tie", "qual:swap", "qual:swap_lane", "len:swap", "sel:swap", "row:first", "row:revisit",
           "clamp:p", "clamp:delta", "ctx:wrap", "len:carried", "param:switch", "dup:taken", "dup:other_length", "rev:odd", "rev:even",
           "coder:dry", "qmap:beyond",
+          # the per-record models past their first halving (a total of 65,519: record 4,080 to 4,095), the two-entry models'
+          # swaps and level entries, the end pass by lane, by wave and past its first trip of 64 records: records.bin
+          "len:halve", "sel:halve", "rev:halve", "dup:halve", "rev:swap", "dup:swap", "len:swap_lane", "sel:swap_lane",
+          "rev:level", "dup:level", "rev:lane", "rev:wave", "rev:later_trip", "dup:wave",
           "refuse:empty", "refuse:short", "refuse:version", "refuse:nparam", "refuse:param_short", "refuse:qmap",
           "refuse:param", "refuse:len_remainder", "refuse:len_zero", "refuse:dup_length",
           "undefined:read_array", "undefined:sel_model")
@@ -40,10 +44,12 @@ def decoded(stream):
 
 
 def all_streams():
-    """every stream the GPU tests decode: the fixtures, edge.bin's inputs and damaged streams, the model-made ones"""
+    """every stream the GPU tests decode: the fixtures, the inputs and damaged streams of edge.bin and records.bin, the
+    model-made ones"""
     inputs, damaged = M.edge()
+    rec_inputs, rec_damaged = M.records()
     return ([f[2] for f in M.fixtures()] + [i[4] for i in inputs] + [s for s, _ in damaged] +
-            [s for s, _ in M.model_refused()] + M.model_undefined())
+            [s for s, _ in M.model_refused()] + M.model_undefined() + [i[4] for i in rec_inputs] + [s for s, _ in rec_damaged])
 
 
 def test_the_model_decodes_the_16_reference_streams():
@@ -97,6 +103,99 @@ def test_the_model_gives_the_reference_answer_to_every_damaged_stream_of_edge_bi
     assert accepted >= 100 and len(damaged) - accepted >= 100
     # the deaths inside the loop: x >= nparam, len against the remainder, a duplicate longer than what is decoded
     assert sites["refuse:param"] >= 10 and sites["refuse:len_remainder"] >= 10 and sites["refuse:dup_length"] >= 10, sites
+
+
+def coder_order(data, lens, flags):
+    """the input as the coder sees it under GFLAG_DO_REV (the reversed records flipped), a record a list entry"""
+    recs, at = [], 0
+    for ln, f in zip(lens, flags):
+        recs.append(data[at:at + ln][::-1] if f & M.FREVERSE else data[at:at + ln])
+        at += ln
+    return recs
+
+
+def test_the_model_reproduces_every_entry_of_records_bin():
+    inputs, damaged = M.records()
+    by_name = {i[0]: i for i in inputs}
+    assert set(by_name) >= {"records", "rev_trips", "rev_edges", "bit_swap", "dup_long"}
+    for name, data, lens, flags, stream, size, digest in inputs:
+        st, out, got_lens, _ = decoded(stream)
+        assert st == 0 and got_lens == lens and len(out) == size == sum(lens), name
+        assert out == data if data is not None else hashlib.sha256(out).digest() == digest, name
+        assert data is not None or size > 4096, name
+    rev = lambda fl: [bool(f & M.FREVERSE) for f in fl]
+
+    # records: a slice's worth of short records under GFLAG_DO_REV, two parameter blocks that both select and dedup
+    name, data, lens, flags, stream, size, digest = by_name["records"]
+    h, ev = M.parse(stream)[1], decoded(stream)[3]
+    assert len(lens) >= 6600 and size <= 100000
+    assert h.gflags & M.GFLAG_DO_REV and h.nparam == 2
+    for pm in h.p:
+        assert pm.pflags & (M.PFLAG_DO_SEL | M.PFLAG_DO_DEDUP | M.PFLAG_DO_LEN) == M.PFLAG_DO_SEL | M.PFLAG_DO_DEDUP
+    sels = collections.Counter(f >> 16 for f in flags)
+    assert set(sels) == {0, 1} and min(sels.values()) >= 1000 and ev["param:switch"] >= 1000
+    assert set(lens) >= {1, 2, 3, 4, 5, 6, 31, 32, 33, 63, 64, 65} and sum(ln <= 6 for ln in lens) >= 0.9 * len(lens)
+    assert 0.35 <= sum(rev(flags)) / len(lens) <= 0.45
+    assert ev["dup:taken"] >= 50 and h.max_sym <= 4
+    for what in ("len", "sel", "rev", "dup"):
+        assert ev[what + ":halve"] >= (8 if what == "len" else 2), (what, ev[what + ":halve"])
+
+    # rev_trips: a trip that is all the wave's, one that is all the lanes', a mixed remainder with a partial last trip
+    name, data, lens, flags, stream, size, digest = by_name["rev_trips"]
+    ev = decoded(stream)[3]
+    assert M.parse(stream)[1].gflags & M.GFLAG_DO_REV and len(lens) > 192 and len(lens) % 64
+    assert all(rev(flags)[:128]) and min(lens[:64]) > 32 and max(lens[64:128]) <= 32 and set(lens[64:128]) >= {1, 2, 31, 32}
+    assert ev["rev:trip_all_wave"] == 1
+    tail = [(ln, r) for ln, r in zip(lens[128:], rev(flags)[128:])]
+    assert {ln for ln, r in tail if r} >= {33, 64, 65, 127, 128, 129} and {r for ln, r in tail} == {False, True}
+    assert rev(flags)[63] and lens[63] > 32 and rev(flags)[128] and lens[128] > 32 and lens[64] == lens[127] == 32
+    # rev_edges: both sides of the first two trip boundaries long and reversed
+    name, data, lens, flags, stream, size, digest = by_name["rev_edges"]
+    assert M.parse(stream)[1].gflags & M.GFLAG_DO_REV and len(lens) > 128 and len(lens) % 64
+    assert all(rev(flags)[k] and lens[k] > 32 for k in (63, 64, 127, 128))
+
+    # bit_swap: the step that first halves the revcomp model moves its entry up, and so with the dup model
+    name, data, lens, flags, stream, size, digest = by_name["bit_swap"]
+    h, ev = M.parse(stream)[1], decoded(stream)[3]
+    assert h.nparam == 1 and h.gflags & M.GFLAG_DO_REV and h.p[0].pflags & M.PFLAG_DO_DEDUP
+    assert len(lens) >= 4200 and set(lens) == {1, 2}
+    assert ev["rev:halve_swap"] >= 1
+    assert ev["dup:halve_swap"] >= 1
+    assert ev["rev:halve_tie"] == ev["dup:halve_tie"] == 0           # (no tie at a halving of a two-entry model: the README)
+
+    # dup_long: the copy by one lane, by a full wave, by a wave's second trip; behind a duplicate; behind a reversed record
+    name, data, lens, flags, stream, size, digest = by_name["dup_long"]
+    assert M.parse(stream)[1].gflags & M.GFLAG_DO_REV
+    recs = coder_order(data, lens, flags)
+    dup = [k > 0 and recs[k] == recs[k - 1] for k in range(len(recs))]
+    assert sum(dup) == decoded(stream)[3]["dup:taken"]
+    assert {lens[k] for k in range(len(recs)) if dup[k]} == {1, 63, 64, 65, 200, 1025}
+    assert any(dup[k] and dup[k - 1] for k in range(1, len(recs)))
+    after_rev = [k for k in range(1, len(recs)) if dup[k] and rev(flags)[k - 1] and not rev(flags)[k] and lens[k] > 1]
+    assert after_rev and all(recs[k] != recs[k][::-1] for k in after_rev)     # the copy is of the bytes before the end pass
+
+    # damaged variants of `records`, the reference's answer to each; the damage lies behind the first halvings
+    good = by_name["records"][4]
+    assert len(damaged) >= 12
+    accepted, first = 0, len(good)
+    for i, (stream, answer) in enumerate(damaged):
+        assert M.var_get(stream, 0, len(stream))[1] <= 1 << 20 and not M.undefined(stream), i
+        same = next((k for k in range(min(len(stream), len(good))) if stream[k] != good[k]), min(len(stream), len(good)))
+        assert stream != good and same >= M.parse(good)[1].hdr, i
+        first = min(first, same)
+        st, out, lens, ev = decoded(stream)
+        if answer is None:
+            assert st != 0, (i, "the reference refuses this stream")
+        else:
+            assert st == 0, (i, st, "the reference accepts this stream")
+            assert (len(out), len(lens), hashlib.sha256(out).hexdigest()) == answer, i
+            accepted += 1
+    assert accepted >= 4 and len(damaged) - accepted >= 4
+    ev = []
+    M.decompress(good[:first], events=ev)                            # what is decoded before the coder runs dry is the intact stream's
+    intact = ev[:ev.index("coder:dry")]
+    for what in ("len", "sel", "rev", "dup"):
+        assert what + ":halve" in intact, (what, first)
 
 
 def test_the_scan_through_the_c_abi_agrees_with_the_model_on_every_stream():
