@@ -9,8 +9,10 @@
 //   k_ar_decode  one wave per item: the range coder and the models (the hot loop)
 //   k_ar_back    a workgroup per block: unpack X_PACK pieces, copy X_CAT pieces, un-stripe, sizes and statuses
 //
-// The step (ar_symbol), where the models live (order 0: registers; run-length models: LDS; order-1 rows: LDS up to the
-// budget below, else a slot of the context's arena) and what was measured: DESIGN 4.6, profiles/arith.md.
+// The step (ar_symbol: r4x16_arith_step.h), where the models live (order 0: registers; run-length models: LDS; order-1
+// rows: LDS up to the budget, else a slot of the context's arena - the homes of r4x16_arith_model.h, which the encoder
+// shares) and what was measured: DESIGN 4.6, profiles/arith.md.  The device call and the host round trip are built on
+// r4x16_dev_call_args / r4x16_chunk_walk / r4x16_route_begin, _end / r4x16_host_trip (r4x16_host.h).
 //
 // Loops: every loop is bounded by the item's output size or input size (each trip writes an output byte or consumes an
 // input byte, or adds 3 to a run that ends the loop at the output size), both checked against max_in_size /
@@ -42,8 +44,6 @@ struct ArWs {
     u32 planes, stripe_out; // rans4x16_hip_set_dev_stripe_planes
 };
 
-__host__ __device__ static inline u32 ar_rows_bytes(u32 m) { return m * ar_row_stride(m) * 4u + m * 4u; }
-
 // ---- front ------------------------------------------------------------------------------------------------------
 struct ArDevSink {
     ArItem *items; u64 in_base; u32 lane; u32 need; const u8 *in;
@@ -58,11 +58,11 @@ struct ArDevSink {
         if (pc.kind == AR_K_O0 || pc.kind == AR_K_O0_RLE) it.home = AR_HOME_O0;
         else if (pc.kind == AR_K_O1 || pc.kind == AR_K_O1_RLE) {
             const u32 m = in[pc.in_pos] ? in[pc.in_pos] : 256u;
-            it.home = ar_rows_bytes(m) <= AR_ROWS_BYTES ? AR_HOME_O1_LDS : AR_HOME_O1_GLOBAL;
+            it.home = ar_lds_home(m) ? AR_HOME_O1_LDS : AR_HOME_O1_GLOBAL;
         }
         for (int k = 0; k < 16; k++) it.map[k] = pc.map[k];
         items[j] = it;
-        if (it.home != AR_HOME_NONE) need += (pc.dec_size + 15u) & ~15u;
+        if (it.home != AR_HOME_NONE) need += ar_r16(pc.dec_size);
     }
 };
 
@@ -138,17 +138,6 @@ __device__ __forceinline__ u32 ar_run_symbol(u32x4 &e, ArCoder &rc, u32 lane)
     return ent >> 16;
 }
 
-// The decoded bytes, four at a time: the stage slots are 16-byte aligned and hold their size rounded up to 16
-struct ArOut {
-    u32 *dst; u32 acc, n;
-    __device__ __forceinline__ void put(u32 b, u32 lane)
-    {
-        acc |= b << (8u * (n & 3u));
-        if ((++n & 3u) == 0) { if (lane == 0) dst[(n >> 2) - 1] = acc; acc = 0; }
-    }
-    __device__ __forceinline__ void flush(u32 lane) { if ((n & 3u) && lane == 0) dst[n >> 2] = acc; }
-};
-
 // HOME: AR_HOME_*.  One wave per item, the items of other homes passed over; the global home's waves stride over the items,
 // each with the row slot of its workgroup.
 template <int HOME>
@@ -165,22 +154,18 @@ __global__ __launch_bounds__(64) void k_ar_decode(const u8 *in, ArWs w, int nite
         const u32 out_sz = item->dec_size;
         const u32 m = src[0] ? src[0] : 256u;                        // the alphabet byte: 0 means 256
         const u32 stride = ar_row_stride(m);
-        u32 *rows = HOME == AR_HOME_O1_LDS ? lds + AR_RUN_BYTES / 4 : (u32 *)(w.rows + (size_t)blockIdx.x * AR_GLOBAL_ROW_BYTES);
-        u32 *tots = rows + (HOME == AR_HOME_O1_LDS ? m * stride : 256u * 256u);
-        if (rle) for (u32 k = lane; k < AR_NRUN * 4u; k += WAVE) lds[k] = 1u | ((k & 3u) << 16);
+        const ArHome h = ar_home(HOME == AR_HOME_O1_LDS, lds, w.rows, m, stride);
+        if (rle) ar_runs_init(lds, lane);
         u32x4 e = {0, 0, 0, 0};
         u32 tot = m;
-        if (HOME == AR_HOME_O0) {
-            const u32 p = 4u * lane;
-            e.x = p < m ? 1u | (p << 16) : 0u; e.y = p + 1 < m ? 1u | ((p + 1) << 16) : 0u;
-            e.z = p + 2 < m ? 1u | ((p + 2) << 16) : 0u; e.w = p + 3 < m ? 1u | ((p + 3) << 16) : 0u;
-        } else {
-            for (u32 k = lane; k < m * stride; k += WAVE) { const u32 s = k % stride; rows[k] = s < m ? 1u | (s << 16) : 0u; }
-            for (u32 k = lane; k < m; k += WAVE) tots[k] = m;
+        if (HOME == AR_HOME_O0) e = ar_fresh(4u * lane, m);
+        else {
+            for (u32 k = lane; k < m * stride; k += WAVE) { const u32 s = k % stride; h.rows[k] = s < m ? 1u | (s << 16) : 0u; }
+            for (u32 k = lane; k < m; k += WAVE) h.tots[k] = m;
         }
         wsync();
         ArCoder rc(src, item->in_size, lane);
-        ArOut out{(u32 *)(w.stage + item->stage), 0u, 0u};
+        ArBytes out{(u32 *)(w.stage + item->stage), 0u, 0u};
         u32 last = 0;
         const bool mine = 4u * lane < stride;
         while (out.n < out_sz) {
@@ -188,12 +173,12 @@ __global__ __launch_bounds__(64) void k_ar_decode(const u8 *in, ArWs w, int nite
             u32 c;
             if (HOME == AR_HOME_O0) c = ar_symbol(e, tot, rc, lane, &dirty);
             else {
-                u32x4 *row = (u32x4 *)(rows + last * stride);
+                u32x4 *row = (u32x4 *)(h.rows + last * stride);
                 e = mine ? row[lane] : u32x4{0, 0, 0, 0};
-                tot = tots[last];
+                tot = h.tots[last];
                 c = ar_symbol(e, tot, rc, lane, &dirty);
                 if (dirty && mine) row[lane] = e;
-                if (lane == 0) tots[last] = tot;
+                if (lane == 0) h.tots[last] = tot;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the next step's row may be this one
             }
             out.put(c, lane);
@@ -274,54 +259,37 @@ extern "C" int rans4x16_hip_arith_uncompress_dev(rans4x16_hip_ctx *c, int n,
                                                  uint32_t *d_out_size, int32_t *d_status,
                                                  uint32_t max_in_size, uint32_t max_out_size, uint64_t total_out_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "arith_uncompress_dev: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
+    BatchArgs a;
+    const int go = r4x16_dev_call_args(c, "arith_uncompress_dev: bad arguments", true, &a, n, d_in, d_in_off, d_in_size, d_out, d_out_off,
+                                       d_out_cap, d_out_size, d_status, 0, nullptr);
+    if (go <= 0) return go;
     hipStream_t s = (hipStream_t)stream;
     const size_t per = c->dev_stripe_planes > 0 ? (size_t)c->dev_stripe_planes : 1;
     // every item's decoded bytes wait in the stage arena, each rounded up to 16: the caller's total, or n x the largest
     const u64 total = total_out_size ? total_out_size : (u64)n * max_out_size;
     ArWs w;
-    auto bytes_for = [&](size_t nb) {
+    auto layout = [&](u8 *at, size_t nb) {
         const u64 tot = std::min<u64>(total, (u64)nb * max_out_size);
-        return ar_layout(nullptr, nb, per, tot + 16ull * nb * per, &w);
+        return ar_layout(at, nb, per, tot + 16ull * nb * per, &w);
     };
-    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / per, r4x16_room(c, A_BIT(A_AR)), bytes_for);
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_AR, bytes_for(nb), false); }) != 0) return -1;
-    BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
-    HIPCHK(c, hipMemsetAsync(c->at(A_AR), 0, 2 * sizeof(u64), s));
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const int nb = (int)std::min(chunk, (size_t)n - base);
-        const u64 tot = std::min<u64>(total, (u64)nb * max_out_size);
-        ar_layout(c->at(A_AR), (size_t)nb, per, tot + 16ull * nb * per, &w);
+    auto bytes_for = [&](size_t nb) { return layout(nullptr, nb); };
+    const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / per, r4x16_room(c, A_BIT(A_AR)), bytes_for);
+    return r4x16_chunk_walk(c, n, A_AR, chunk, s, bytes_for, [&](size_t base, int nb) {
+        if (base == 0) HIPCHK(c, hipMemsetAsync(c->at(A_AR), 0, 2 * sizeof(u64), s));
+        layout(c->at(A_AR), (size_t)nb);
         w.out_total = total;
         w.planes = (u32)c->dev_stripe_planes; w.stripe_out = c->dev_stripe_out;
         const int nitems = nb * (int)per;
-        const bool count = c->opts.v[OPT_ROUTE_COUNT] != 0;
         u32 *const d_route = w.route;
         HIPCHK(c, hipMemsetAsync(w.cursor, 0, sizeof(u64), s));
-        if (count) HIPCHK(c, hipMemsetAsync(d_route, 0, R4X16_ARITH_KINDS * sizeof(u32), s));
-        else w.route = nullptr;
+        if (r4x16_route_begin(c, &w.route, R4X16_ARITH_KINDS, s) != 0) return -1;
         hipLaunchKernelGGL(k_ar_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, w, (int)base, nb, max_in_size, max_out_size);
         hipLaunchKernelGGL(k_ar_decode<AR_HOME_O0>, dim3(nitems), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_ar_decode<AR_HOME_O1_LDS>, dim3(nitems), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_ar_decode<AR_HOME_O1_GLOBAL>, dim3(std::min(nitems, AR_GLOBAL_SLOTS)), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_ar_back, dim3(nb), dim3(256), 0, s, a, w, (int)base);
-        if (count) {
-            if (r4x16_route_snap(c, R4X16_ROUTE_ARITH, d_route, R4X16_ARITH_KINDS, s) != 0) return -1;
-            c->route[R4X16_ROUTE_LAUNCH][R4X16_LAUNCH_IN_ORDER]++;
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return r4x16_route_end(c, R4X16_ROUTE_ARITH, d_route, R4X16_ARITH_KINDS, s);
+    });
 }
 
 extern "C" int rans4x16_hip_arith_peek_dev(rans4x16_hip_ctx *c, int n,
@@ -334,10 +302,8 @@ extern "C" int rans4x16_hip_arith_peek_dev(rans4x16_hip_ctx *c, int n,
 }
 
 // ---- host buffers -------------------------------------------------------------------------------------------------
-// One upload, the device call, one download; not pipelined (a stream of this codec takes milliseconds per megabyte on
-// the device: the copies are a small share).  X_STRIPE blocks are decoded as after
-// rans4x16_hip_set_dev_stripe_planes(ctx, most planes of the batch, largest block); the caller's setting is put back.
-struct ArHostSrc { const u8 *p; u8 at(u32 i) const { return p[i]; } };
+// One round trip (r4x16_host_trip).  X_STRIPE blocks are decoded as after rans4x16_hip_set_dev_stripe_planes(ctx, most
+// planes of the batch, largest block); the caller's setting is put back.
 struct ArNoSink { void put(u32, const ArPiece &) {} };
 
 extern "C" int rans4x16_hip_arith_uncompress_batch(rans4x16_hip_ctx *c, int n,
@@ -347,54 +313,26 @@ extern "C" int rans4x16_hip_arith_uncompress_batch(rans4x16_hip_ctx *c, int n,
     if (!c) return -1;
     if (n < 0 || (n && (!in || !in_size || !out || !out_size || !status))) { c->err = "arith_uncompress_batch: bad arguments"; return -1; }
     if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
     // the host walk refuses what the device walk would refuse, before anything is uploaded, and gives the stripe limits
-    std::vector<u64> in_off(n), out_off(n);
     std::vector<u32> isz(n, 0), cap(n, 0);
+    std::vector<u8> take(n, 0);
     u32 max_in = 0, max_out = 0, planes = 0, stripe_out = 0;
     for (int i = 0; i < n; i++) {
-        ArHostSrc src{in[i]};
+        HostSrc src{in[i]};
         ArTop top;
         ArNoSink sink;
         status[i] = in[i] && out[i] ? ar_parse(src, in_size[i], out_size[i], 255u, 0xffffffffu, &top, sink) : R4X16_E_UNSUPPORTED;
         if (status[i] != AR_OK) { out_size[i] = 0; continue; }
-        isz[i] = in_size[i]; cap[i] = out_size[i];
+        take[i] = 1; isz[i] = in_size[i]; cap[i] = out_size[i];
         max_in = std::max(max_in, isz[i]); max_out = std::max(max_out, cap[i]);
         if (top.nplanes) { planes = std::max(planes, top.nplanes); stripe_out = std::max(stripe_out, top.out_size); }
     }
-    // slots of the size rounded up to 16; a refused block (size 0) takes none, its offsets are its successor's
-    const size_t in_total = r4x16_stage_slots(isz.data(), (size_t)n, 0, 16, in_off.data());
-    const size_t out_total = r4x16_stage_slots(cap.data(), (size_t)n, 0, 16, out_off.data());
-    if (in_total == 0) return n;                                     // nothing was accepted
-    hipStream_t s = c->stream;
-    StageLayout L;
-    if (r4x16_stage_begin(c, &L, (size_t)n, in_total + 16, 0, out_total + 16, 0,
-                          {in_off.data(), out_off.data(), isz.data(), cap.data(), nullptr}, s) != 0)
-        return -1;
-    std::vector<u8> up(in_total);
-    for (int i = 0; i < n; i++) if (isz[i]) memcpy(up.data() + in_off[i], in[i], isz[i]);
-    HIPCHK(c, hipMemcpyAsync(L.in, up.data(), in_total, hipMemcpyHostToDevice, s));
-    {
+    const HostTrip trip = {in, out, out_size, status, take.data(), isz.data(), cap.data(), nullptr, nullptr, 0, 0, nullptr};
+    return r4x16_host_trip(c, n, trip, [&](const StageLayout &L, size_t, size_t out_total, hipStream_t s) {
         StripeLimits limits(c, (int)planes, stripe_out);
-        if (rans4x16_hip_arith_uncompress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
-                                              max_in, max_out, out_total, s) != 0)
-            return -1;
-    }
-    std::vector<u8> down(out_total);
-    std::vector<u32> osz(n);
-    std::vector<i32> dstat(n);
-    HIPCHK(c, hipMemcpyAsync(down.data(), L.out, out_total, hipMemcpyDeviceToHost, s));
-    if (r4x16_stage_verdicts(c, L, (size_t)n, osz.data(), dstat.data(), s) != 0) return -1;
-    int bad = 0;
-    for (int i = 0; i < n; i++) {
-        if (isz[i]) {                                                // (a block the host walk refused was uploaded as an empty one)
-            status[i] = dstat[i];
-            out_size[i] = dstat[i] == 0 ? osz[i] : 0;
-            if (dstat[i] == 0 && osz[i]) memcpy(out[i], down.data() + out_off[i], osz[i]);
-        }
-        bad += status[i] != 0;
-    }
-    return bad;
+        return rans4x16_hip_arith_uncompress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status, max_in, max_out,
+                                                 out_total, s);
+    });
 }
 
 // ---- the reference's two calls (arith_dynamic.h), on the calling thread's context ---------------------------------
@@ -402,7 +340,7 @@ extern "C" unsigned char *rans4x16_hip_arith_uncompress_to(unsigned char *in, un
                                                           unsigned char *out, unsigned int *out_size)
 {
     if (!in || !out_size || in_size == 0) return nullptr;
-    ArHostSrc src{in};
+    HostSrc src{in};
     ArTop top;
     ArNoSink sink;
     if (ar_parse(src, in_size, out ? *out_size : AR_NO_CAP, 255u, 0xffffffffu, &top, sink) != AR_OK) return nullptr;

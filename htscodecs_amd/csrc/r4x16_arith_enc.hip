@@ -1,7 +1,9 @@
 // r4x16_arith_enc.hip - encoding with htscodecs' adaptive arithmetic codec (arith_dynamic.c:621-863 arith_compress_to, the
 // four core coders, c_simple_model.h, c_range_coder.h) on the device: include/rans4x16_hip.h part 2h.
 //
-// The mirror of r4x16_arith.hip, on its model layout (r4x16_arith_model.h) and with its three homes of the models:
+// The mirror of r4x16_arith.hip.  The model layout, the three homes of the models, the input window and the byte writer
+// are r4x16_arith_model.h's, shared with the decoder; the call's walk over chunks and the host round trip r4x16_host.h's.
+// Stages:
 //   k_are_front   one wave per block: what arith_compress_to decides before it codes - the flag rules, the items (one for
 //                 a plain block; for an X_STRIPE block every candidate method of every plane), the transposition, hts_pack,
 //                 the alphabet byte - and the items' places in the stage arena
@@ -52,8 +54,6 @@ struct AreWs {
     u32 planes;             // planes a stripe block may have (0: stripe blocks report UNSUPPORTED)
 };
 
-__host__ __device__ static inline u32 are_r16(u32 v) { return (v + 15u) & ~15u; }
-__host__ __device__ static inline bool are_lds_home(u32 m) { return m * ar_row_stride(m) * 4u + m * 4u <= AR_ROWS_BYTES; }
 // candidate c of plane j (:690-693), -1 past the last
 __host__ __device__ static inline int are_method(u32 j, u32 c)
 {
@@ -86,7 +86,7 @@ __host__ __device__ static inline u32 are_cap(u32 size, int order)
 // stage bytes of one plane of len bytes coded as candidates [0, nc): its copy (a stripe block's), its packed form, the bodies
 __host__ __device__ static inline u64 are_plane_need(u32 len, bool copy, bool pack, u32 nc)
 {
-    return (copy ? (u64)are_r16(len) : 0ull) + (pack ? (u64)are_r16((len + 1u) / 2u) : 0ull) + (u64)nc * ((u64)are_r16(len) + 16u);
+    return (copy ? (u64)ar_r16(len) : 0ull) + (pack ? (u64)ar_r16((len + 1u) / 2u) : 0ull) + (u64)nc * ((u64)ar_r16(len) + 16u);
 }
 
 // ---- front ------------------------------------------------------------------------------------------------------
@@ -160,8 +160,7 @@ __device__ __forceinline__ u32 are_var_len(u32 v)
 }
 __device__ __forceinline__ u32 are_var_put(u8 *cp, u32 v)
 {
-    u32 groups = 1;
-    for (u32 t = v >> 7; t; t >>= 7) groups++;
+    const u32 groups = are_var_len(v);
     for (u32 g = groups; g-- > 0;) *cp++ = (u8)(((v >> (7u * g)) & 0x7fu) | (g ? 0x80u : 0u));
     return groups;
 }
@@ -193,7 +192,7 @@ __device__ static u32 are_item(AreItem *dst, const ArePlane &P, u32 order, u64 i
     it.m = (u8)(n ? mx + 1u : 1u);
     it.rle = (flags & AR_X_RLE) != 0;
     const u32 m = it.m ? it.m : 256u;
-    it.home = ord == 1 ? (are_lds_home(m) ? R4X16_ARITH_ENC_O1_LDS : R4X16_ARITH_ENC_O1_GLOBAL) : R4X16_ARITH_ENC_O0;
+    it.home = ord == 1 ? (ar_lds_home(m) ? R4X16_ARITH_ENC_O1_LDS : R4X16_ARITH_ENC_O1_GLOBAL) : R4X16_ARITH_ENC_O0;
     it.state = (flags & AR_X_CAT) ? ARE_STORED : ARE_CODE;          // an explicit X_CAT stores the bytes
     for (u32 k = nm; k < ARE_META; k++) it.meta[k] = 0;
     if (lane == 0) {
@@ -238,7 +237,7 @@ __global__ __launch_bounds__(256) void k_are_front(BatchArgs a, AreWs w, int bas
     }
     u64 at = 0;
     if (st == AR_OK && lane == 0) at = atomicAdd((unsigned long long *)w.cursor, (unsigned long long)need);
-    at = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)at);
+    at = wave_uniform(at);
     if (st == AR_OK && at + need > w.stage_bytes) st = AR_E_UNSUPPORTED;             // (the arena holds what the host sized it for)
     u32 live = 0;
     if (st == AR_OK) {
@@ -258,13 +257,13 @@ __global__ __launch_bounds__(256) void k_are_front(BatchArgs a, AreWs w, int bas
             P.raw_at = at;
             u8 *copy = N ? w.stage + at : nullptr;
             P.max_raw = are_scan(in + (N ? j : 0u), N ? N : 1u, P.len, copy, pack ? seen : nullptr, lane);
-            if (N) at += are_r16(P.len);
+            if (N) at += ar_r16(P.len);
             wsync();                                                                 // the copy and the symbols seen, before they are read
             P.raw = N ? copy : in;
             if (!N ? (order & AR_X_PACK) != 0 : j >= 2) {
                 P.pk_at = at;
                 if (pack) are_pack(P, w.stage + at, seen, lane);
-                at += are_r16((P.len + 1u) / 2u);
+                at += ar_r16((P.len + 1u) / 2u);
                 wsync();
             }
             if (!N) { are_item(items, P, (u32)order & ~(u32)AR_X_STRIPE, a.in_off[g], at, lane, w.route); break; }   // (:634: 20 bytes and fewer are not striped)
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(256) void k_are_front(BatchArgs a, AreWs w, int bas
                 AreItem *dst = items + (size_t)j * ARE_CANDS + c;
                 if (mt < 0 || (even && (mt & 1))) { if (lane == 0) dst->state = ARE_NONE; continue; }
                 are_item(dst, P, (u32)mt | AR_X_NOSZ, 0, at, lane, w.route);
-                at += are_r16(P.len) + 16u;
+                at += ar_r16(P.len) + 16u;
             }
         }
     }
@@ -286,55 +285,19 @@ __global__ __launch_bounds__(256) void k_are_front(BatchArgs a, AreWs w, int bas
 }
 
 // ---- the step ---------------------------------------------------------------------------------------------------
-// The bytes to code: ArCoder's window (r4x16_arith.hip) - 1 KB in registers, 16 bytes a lane, read by a scalar lane read;
-// the last bytes, which fill no whole 16-byte piece, come from memory
-struct AreIn {
-    const u8 *base;
-    u32x4 held;
-    u32 wbase, wlen, end;
-    __device__ AreIn(const u8 *in, u32 n) : base(in), held{0, 0, 0, 0}, wbase(0), wlen(0), end(n) {}
-    __device__ __forceinline__ void fill(u32 p, u32 lane)
-    {
-        wbase = p & ~15u;
-        const u32 mine = wbase + 16u * lane;
-        held = u32x4{0, 0, 0, 0};
-        if (mine + 16u <= end) held = *(const u32x4_unaligned *)(base + mine);
-        const u32 room = (end - wbase) & ~15u;
-        wlen = room < 1024u ? room : 1024u;
-    }
-    __device__ __forceinline__ u32 byte(u32 p, u32 lane)           // p < end
-    {
-        if (p - wbase >= wlen) {
-            if (p + 16u > end) return base[p];
-            fill(p, lane);
-        }
-        const u32 so = (u32)__builtin_amdgcn_readfirstlane((int)(p - wbase));
-        const int ln = (int)(so >> 4);
-        const u32 d0 = (u32)__builtin_amdgcn_readlane((int)held.x, ln), d1 = (u32)__builtin_amdgcn_readlane((int)held.y, ln),
-                  d2 = (u32)__builtin_amdgcn_readlane((int)held.z, ln), d3 = (u32)__builtin_amdgcn_readlane((int)held.w, ln);
-        const u32 lo = (so & 4u) ? d1 : d0, hi = (so & 4u) ? d3 : d2;
-        return (((so & 8u) ? hi : lo) >> (8u * (so & 3u))) & 0xffu;
-    }
-};
-
-// The range coder (c_range_coder.h:42-110) and its bytes, four at a time as ArOut stores them.  All of it wave-uniform.
+// The range coder (c_range_coder.h:42-110) and its bytes (ArBytes; the alphabet byte is the first of them).  All of it
+// wave-uniform.
 struct AreCoder {
     u32 low, range, ffnum, carry, cache;
-    u32 *dst; u32 acc, n;
-    __device__ AreCoder(u32 *d, u32 first) : low(0), range(0xffffffffu), ffnum(0), carry(0), cache(0), dst(d), acc(first), n(1) {}
-    __device__ __forceinline__ void put(u32 b, u32 lane)
-    {
-        acc |= b << (8u * (n & 3u));
-        if ((++n & 3u) == 0) { if (lane == 0) dst[(n >> 2) - 1] = acc; acc = 0; }
-    }
-    __device__ __forceinline__ void flush(u32 lane) { if ((n & 3u) && lane == 0) dst[n >> 2] = acc; }
+    ArBytes out;
+    __device__ AreCoder(u32 *d, u32 first) : low(0), range(0xffffffffu), ffnum(0), carry(0), cache(0), out{d, first, 1u} {}
     // bytes the body has for certain: written, or pending behind the cache byte
-    __device__ __forceinline__ u32 sure() const { return n + ffnum; }
+    __device__ __forceinline__ u32 sure() const { return out.n + ffnum; }
     __device__ __forceinline__ void shift_low(u32 lane)             // RC_ShiftLow, :71-89
     {
         if (low < 0xff000000u || carry) {
-            put((cache + carry) & 0xffu, lane);
-            for (; ffnum; ffnum--) put((carry - 1u) & 0xffu, lane);
+            out.put((cache + carry) & 0xffu, lane);
+            for (; ffnum; ffnum--) out.put((carry - 1u) & 0xffu, lane);
             cache = low >> 24;
             carry = 0;
         } else ffnum++;
@@ -349,7 +312,7 @@ struct AreCoder {
         carry += low < old;
         while (range < AR_TOP) { range <<= 8; shift_low(lane); }
     }
-    __device__ __forceinline__ void finish(u32 lane) { for (int k = 0; k < 5; k++) shift_low(lane); flush(lane); }
+    __device__ __forceinline__ void finish(u32 lane) { for (int k = 0; k < 5; k++) shift_low(lane); out.flush(lane); }
 };
 
 // One symbol of a model that lies across the wave (SIMPLE_MODEL(256,_encodeSymbol), c_simple_model.h:100-135): ar_symbol's
@@ -365,8 +328,7 @@ __device__ __forceinline__ void are_symbol(u32x4 &e, u32 &tot, u32 c, AreCoder &
     const int L = (int)__builtin_ctzll(hit);
     const u32 j_l = k0 ? 0u : k1 ? 1u : k2 ? 2u : 3u;
     const u32 c0 = e.x & 0xffffu, c1 = c0 + (e.y & 0xffffu), c2 = c1 + (e.z & 0xffffu), c3 = c2 + (e.w & 0xffffu);
-    const u32 incl = wave_incl_scan(c3, lane);
-    const u32 cum_l = incl - c3 + (j_l == 0 ? 0u : j_l == 1 ? c0 : j_l == 2 ? c1 : c2);
+    const u32 cum_l = wave_incl_scan(c3, lane) - c3 + (j_l == 0 ? 0u : j_l == 1 ? c0 : j_l == 2 ? c1 : c2);
     const u32 j = (u32)__builtin_amdgcn_readlane((int)j_l, L);
     const u32 cum = (u32)__builtin_amdgcn_readlane((int)cum_l, L);
     const u32 ent = (u32)__builtin_amdgcn_readlane((int)ar_get(e, j_l), L);
@@ -430,21 +392,17 @@ __global__ __launch_bounds__(64) void k_are_encode(const u8 *in, AreWs w, int ni
         const u32 n = item->n;
         const u32 m = item->m ? item->m : 256u;
         const u32 stride = ar_row_stride(m);
-        u32 *rows = HOME == R4X16_ARITH_ENC_O1_LDS ? lds + AR_RUN_BYTES / 4 : (u32 *)(w.rows + (size_t)blockIdx.x * AR_GLOBAL_ROW_BYTES);
-        u32 *tots = rows + (HOME == R4X16_ARITH_ENC_O1_LDS ? m * stride : 256u * 256u);
-        if (rle) for (u32 k = lane; k < AR_NRUN * 4u; k += WAVE) lds[k] = 1u | ((k & 3u) << 16);
+        const ArHome h = ar_home(HOME == R4X16_ARITH_ENC_O1_LDS, lds, w.rows, m, stride);
+        if (rle) ar_runs_init(lds, lane);
         u32x4 e = {0, 0, 0, 0};
         u32 tot = m;
-        if (HOME == R4X16_ARITH_ENC_O0) {
-            const u32 p = 4u * lane;
-            e.x = p < m ? 1u | (p << 16) : 0u; e.y = p + 1 < m ? 1u | ((p + 1) << 16) : 0u;
-            e.z = p + 2 < m ? 1u | ((p + 2) << 16) : 0u; e.w = p + 3 < m ? 1u | ((p + 3) << 16) : 0u;
-        } else {
-            for (u32 k = lane; k < m * stride; k += WAVE) { const u32 s = k % stride; rows[k] = s < m ? 1u | (s << 16) : 0u; }
-            for (u32 k = lane; k < m; k += WAVE) tots[k] = m;
+        if (HOME == R4X16_ARITH_ENC_O0) e = ar_fresh(4u * lane, m);
+        else {
+            for (u32 k = lane; k < m * stride; k += WAVE) { const u32 s = k % stride; h.rows[k] = s < m ? 1u | (s << 16) : 0u; }
+            for (u32 k = lane; k < m; k += WAVE) h.tots[k] = m;
         }
         wsync();
-        AreIn src(item->src_stage ? w.stage + item->src : in + item->src, n);
+        ArWindow src(item->src_stage ? w.stage + item->src : in + item->src, n);
         AreCoder rc((u32 *)(w.stage + item->out), m & 0xffu);
         u32 last = 0, i = 0;
         const bool mine = 4u * lane < stride;
@@ -455,12 +413,12 @@ __global__ __launch_bounds__(64) void k_are_encode(const u8 *in, AreWs w, int ni
             const u32 c = src.byte(i++, lane);
             if (HOME == R4X16_ARITH_ENC_O0) are_symbol(e, tot, c, rc, lane, &dirty);
             else {
-                u32x4 *row = (u32x4 *)(rows + last * stride);
+                u32x4 *row = (u32x4 *)(h.rows + last * stride);
                 e = mine ? row[lane] : u32x4{0, 0, 0, 0};
-                tot = tots[last];
+                tot = h.tots[last];
                 are_symbol(e, tot, c, rc, lane, &dirty);
                 if (dirty && mine) row[lane] = e;
-                if (lane == 0) tots[last] = tot;
+                if (lane == 0) h.tots[last] = tot;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the next step's row may be this one
             }
             last = c;
@@ -486,9 +444,9 @@ __global__ __launch_bounds__(64) void k_are_encode(const u8 *in, AreWs w, int ni
                 } while (run && !stored);
             }
         }
-        if (!stored) { rc.finish(lane); stored = rc.n >= n; }
+        if (!stored) { rc.finish(lane); stored = rc.out.n >= n; }
         if (lane == 0) {
-            item->body = rc.n;
+            item->body = rc.out.n;
             if (stored) item->state = ARE_STORED;
             if (stored && w.route) atomicAdd(&w.route[R4X16_ARITH_ENC_STORED], 1u);
         }
@@ -601,13 +559,10 @@ extern "C" int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *c, int n,
                                                uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
                                                uint32_t max_in_size, uint64_t total_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "arith_compress_dev: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
+    BatchArgs a;
+    const int go = r4x16_dev_call_args(c, "arith_compress_dev: bad arguments", true, &a, n, d_in, d_in_off, d_in_size, d_out, d_out_off,
+                                       d_out_cap, d_out_size, d_status, order, d_order);
+    if (go <= 0) return go;
     hipStream_t s = (hipStream_t)stream;
     // the planes a stripe block may have: the one order's own, or what rans4x16_hip_set_dev_stripe_encode reserved
     u32 planes = 0;
@@ -618,37 +573,23 @@ extern "C" int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *c, int n,
     // a candidate (are_plane_need: 4.5 bytes a byte at most, and the roundings of every item)
     const u64 total = total_in_size ? total_in_size : (u64)n * max_in_size;
     AreWs w;
-    auto stage_for = [&](size_t nb) { return are_stage_bytes(nb, per, planes, total, max_in_size); };
-    auto bytes_for = [&](size_t nb) { return are_layout(nullptr, nb, per, stage_for(nb), &w); };
-    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / per, r4x16_room(c, A_BIT(A_AR)), bytes_for);
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_AR, bytes_for(nb), false); }) != 0) return -1;
-    BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const int nb = (int)std::min(chunk, (size_t)n - base);
-        are_layout(c->at(A_AR), (size_t)nb, per, stage_for((size_t)nb), &w);
+    auto layout = [&](u8 *at, size_t nb) { return are_layout(at, nb, per, are_stage_bytes(nb, per, planes, total, max_in_size), &w); };
+    auto bytes_for = [&](size_t nb) { return layout(nullptr, nb); };
+    const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / per, r4x16_room(c, A_BIT(A_AR)), bytes_for);
+    return r4x16_chunk_walk(c, n, A_AR, chunk, s, bytes_for, [&](size_t base, int nb) {
+        layout(c->at(A_AR), (size_t)nb);
         w.planes = planes;
         const int nitems = nb * (int)per;
-        const bool count = c->opts.v[OPT_ROUTE_COUNT] != 0;
         u32 *const d_route = w.route;
         HIPCHK(c, hipMemsetAsync(w.cursor, 0, sizeof(u64), s));
-        if (count) HIPCHK(c, hipMemsetAsync(d_route, 0, R4X16_ARITH_ENC_KINDS * sizeof(u32), s));
-        else w.route = nullptr;
+        if (r4x16_route_begin(c, &w.route, R4X16_ARITH_ENC_KINDS, s) != 0) return -1;
         hipLaunchKernelGGL(k_are_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, w, (int)base, nb, max_in_size);
         hipLaunchKernelGGL(k_are_encode<R4X16_ARITH_ENC_O0>, dim3(nitems), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_are_encode<R4X16_ARITH_ENC_O1_LDS>, dim3(nitems), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_are_encode<R4X16_ARITH_ENC_O1_GLOBAL>, dim3(std::min(nitems, AR_GLOBAL_SLOTS)), dim3(64), 0, s, d_in, w, nitems);
         hipLaunchKernelGGL(k_are_back, dim3(nb), dim3(256), 0, s, a, w, (int)base);
-        if (count) {
-            if (r4x16_route_snap(c, R4X16_ROUTE_ARITH_ENC, d_route, R4X16_ARITH_ENC_KINDS, s) != 0) return -1;
-            c->route[R4X16_ROUTE_LAUNCH][R4X16_LAUNCH_IN_ORDER]++;
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return r4x16_route_end(c, R4X16_ROUTE_ARITH_ENC, d_route, R4X16_ARITH_ENC_KINDS, s);
+    });
 }
 
 // ---- best of k, results back to back --------------------------------------------------------------------------------
@@ -687,7 +628,7 @@ __global__ __launch_bounds__(256) void k_ab_expand(const u64 *in_off, const u32 
     w.in_off[q] = in_off[g];
     w.in_size[q] = sz;
     w.order[q] = m;
-    w.need[q] = (sz > max_in || ab_skipped(sz, m)) ? 0u : are_r16(are_cap(sz, m));
+    w.need[q] = (sz > max_in || ab_skipped(sz, m)) ? 0u : ar_r16(are_cap(sz, m));
 }
 
 __global__ __launch_bounds__(256) void k_ab_admit(AbWs w, u32 items)
@@ -809,40 +750,31 @@ extern "C" int rans4x16_hip_arith_compress_best_packed_dev(rans4x16_hip_ctx *c, 
     AbWs w;
     auto slot_bytes = [&](size_t nb) { return ab_slot_bytes(p, nb, max_in_size); };
     auto mine = [&](size_t nb) { return ab_carve(&w, nullptr, nb, (size_t)k, slot_bytes(nb)); };
-    auto inner_total = [&](size_t nb) { return ab_inner_total(p, nb, max_in_size); };
-    size_t chunk = p.chunk;
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_PS, mine(nb), false); }) != 0) return -1;
     const PackedOut pk = {d_out, d_out_off, out_capacity};
-    const size_t keep_ws = c->max_ws;
-    const int keep_planes = c->dev_stripe_enc;
-    int rc = 0;
-    for (size_t base = 0; base < (size_t)n && rc == 0; base += chunk) {
-        const int nb = (int)std::min(chunk, (size_t)n - base);
+    return r4x16_chunk_walk(c, n, A_PS, p.chunk, s, mine, [&](size_t base, int nb) {
         const u32 items = (u32)nb * (u32)k;
         const size_t arena = ab_carve(&w, c->at(A_PS), (size_t)nb, (size_t)k, slot_bytes((size_t)nb));
         const dim3 per_item((items + 255) / 256);
         hipLaunchKernelGGL(k_ab_expand, per_item, dim3(256), 0, s, d_in_off, d_in_size, w, pm, (int)base, items, max_in_size);
         r4x16_launch_packed_scan(w.need, w.slot_off, 0, (int)items, s);
         hipLaunchKernelGGL(k_ab_admit, per_item, dim3(256), 0, s, w, items);
-        c->max_ws = keep_ws > arena + ((size_t)1 << 20) ? keep_ws - arena : (size_t)1 << 20;
-        c->dev_stripe_enc = (int)planes;
-        rc = rans4x16_hip_arith_compress_dev(c, (int)items, d_in, w.in_off, w.in_size, w.slots, w.slot_off, w.cap, w.out_size, w.status, 0,
-                                             w.order, max_in_size, inner_total((size_t)nb), s);
-        c->dev_stripe_enc = keep_planes;
-        c->max_ws = keep_ws;
-        if (rc != 0) break;
+        {
+            // the inner call: what is left of the ceiling beside this call's slots, and the planes the methods ask for
+            Keep<size_t> ceiling(c->max_ws, c->max_ws > arena + ((size_t)1 << 20) ? c->max_ws - arena : (size_t)1 << 20);
+            Keep<int> stripe(c->dev_stripe_enc, (int)planes);
+            if (rans4x16_hip_arith_compress_dev(c, (int)items, d_in, w.in_off, w.in_size, w.slots, w.slot_off, w.cap, w.out_size, w.status, 0,
+                                                w.order, max_in_size, ab_inner_total(p, (size_t)nb, max_in_size), s) != 0)
+                return -1;
+        }
         hipLaunchKernelGGL(k_ab_pick, dim3((u32)(nb + 255) / 256), dim3(256), 0, s, d_in_size, w, pm, d_out_size, d_status, d_chosen, (int)base, nb, max_in_size);
         r4x16_launch_packed_scan(d_out_size, d_out_off, (int)base, nb, s);
         hipLaunchKernelGGL(k_ab_gather, dim3((u32)nb), dim3(256), 0, s, pk, w, k, d_out_size, d_status, (int)base);
-    }
-    if (rc != 0) return -1;
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return 0;
+    });
 }
 
 // ---- host buffers -------------------------------------------------------------------------------------------------
-// One upload, the device call with per-block orders, one download; not pipelined.  Stripe encoding is switched on for the
+// One round trip (r4x16_host_trip) around the device call with per-block orders.  Stripe encoding is switched on for the
 // call (rans4x16_hip_set_dev_stripe_encode with the most planes of the batch) and the caller's setting put back.
 extern "C" int rans4x16_hip_arith_compress_batch(rans4x16_hip_ctx *c, int n,
                                                  const unsigned char *const *in, const unsigned int *in_size,
@@ -851,58 +783,27 @@ extern "C" int rans4x16_hip_arith_compress_batch(rans4x16_hip_ctx *c, int n,
     if (!c) return -1;
     if (n < 0 || (n && (!in || !in_size || !out || !out_size || !order || !status))) { c->err = "arith_compress_batch: bad arguments"; return -1; }
     if (n == 0) return 0;
-    // what the order word and the capacity refuse is refused here, before anything is uploaded
-    std::vector<u64> in_off(n), out_off(n);
+    // what the order word and the capacity refuse is refused here, before anything is uploaded; a refused block takes no
+    // slot (its capacity 0 refuses it on the device as well)
     std::vector<u32> isz(n, 0), cap(n, 0);
     std::vector<i32> ord(n, 0);
     std::vector<u8> take(n, 0);
     u32 max_in = 0, planes = 0;
-    int taken = 0, bad = 0;
     for (int i = 0; i < n; i++) {
         u32 N = 0;
         status[i] = (in[i] || !in_size[i]) && out[i] ? are_order_check(in_size[i], order[i], &N) : R4X16_E_UNSUPPORTED;
         if (status[i] == AR_OK && out_size[i] < are_cap(in_size[i], order[i])) status[i] = AR_E_CAPACITY;
-        if (status[i] != AR_OK) { out_size[i] = 0; bad++; continue; }
-        take[i] = 1; taken++;
+        if (status[i] != AR_OK) { out_size[i] = 0; continue; }
+        take[i] = 1;
         isz[i] = in_size[i]; cap[i] = are_cap(in_size[i], order[i]); ord[i] = order[i];
         max_in = std::max(max_in, isz[i]); planes = std::max(planes, N);
     }
-    if (!taken) return bad;
-    HIPCHK(c, hipSetDevice(c->device));
-    // slots of the size rounded up to 16; a refused block takes none (its capacity 0 refuses it on the device as well)
-    const size_t in_total = r4x16_stage_slots(isz.data(), (size_t)n, 0, 16, in_off.data());
-    const size_t out_total = r4x16_stage_slots(cap.data(), (size_t)n, 0, 16, out_off.data());
-    hipStream_t s = c->stream;
-    StageLayout L;
-    if (r4x16_stage_begin(c, &L, (size_t)n, in_total + 16, 0, out_total + 16, 0,
-                          {in_off.data(), out_off.data(), isz.data(), cap.data(), ord.data()}, s) != 0)
-        return -1;
-    std::vector<u8> up(in_total + 1);
-    for (int i = 0; i < n; i++) if (isz[i]) memcpy(up.data() + in_off[i], in[i], isz[i]);
-    if (in_total) HIPCHK(c, hipMemcpyAsync(L.in, up.data(), in_total, hipMemcpyHostToDevice, s));
-    {
-        const int keep = c->dev_stripe_enc;
-        c->dev_stripe_enc = (int)planes;
-        const int rc = rans4x16_hip_arith_compress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
-                                                       0, L.order, max_in, in_total, s);
-        c->dev_stripe_enc = keep;
-        if (rc != 0) return -1;
-    }
-    std::vector<u8> down(out_total);
-    std::vector<u32> osz(n);
-    std::vector<i32> dstat(n);
-    HIPCHK(c, hipMemcpyAsync(down.data(), L.out, out_total, hipMemcpyDeviceToHost, s));
-    if (r4x16_stage_verdicts(c, L, (size_t)n, osz.data(), dstat.data(), s) != 0) return -1;
-    bad = 0;
-    for (int i = 0; i < n; i++) {
-        if (take[i]) {
-            status[i] = dstat[i];
-            out_size[i] = dstat[i] == 0 ? osz[i] : 0;
-            if (dstat[i] == 0 && osz[i]) memcpy(out[i], down.data() + out_off[i], osz[i]);
-        }
-        bad += status[i] != 0;
-    }
-    return bad;
+    const HostTrip trip = {in, out, out_size, status, take.data(), isz.data(), cap.data(), ord.data(), nullptr, 0, 0, nullptr};
+    return r4x16_host_trip(c, n, trip, [&](const StageLayout &L, size_t in_total, size_t, hipStream_t s) {
+        Keep<int> stripe(c->dev_stripe_enc, (int)planes);
+        return rans4x16_hip_arith_compress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status, 0, L.order, max_in,
+                                               in_total, s);
+    });
 }
 
 // ---- the reference's calls (arith_dynamic.h), on the calling thread's context -------------------------------------

@@ -1,46 +1,18 @@
 // r4x16_arith_step.h - the decoding step the adaptive coders share on the device: the carry-less range coder of
-// c_range_coder.h with its input window in registers, and one symbol of a SIMPLE_MODEL whose list lies across the wave
-// (c_simple_model.h).  r4x16_arith.hip (arith_dynamic) and r4x16_fqz.hip (fqzcomp_qual) decode with it.
+// c_range_coder.h on the input window in registers, and one symbol of a SIMPLE_MODEL whose list lies across the wave
+// (c_simple_model.h).  r4x16_arith.hip (arith_dynamic) and r4x16_fqz.hip (fqzcomp_qual) decode with it; the window
+// is r4x16_arith_model.h's, which the encoder reads its input through as well.
 #pragma once
 #include "r4x16_arith_model.h"
 
 // ---- the step ---------------------------------------------------------------------------------------------------
 struct ArCoder {
-    u32 code, range, pos, end;      // wave-uniform
-    // the input: a window of 1 KB held in registers, 16 bytes a lane, read by a scalar lane read (WinSrc's scheme,
-    // r4x16_dev.h), so that the byte-wise renormalisation never waits for memory; the last bytes, which fill no whole
-    // 16-byte piece, are read from memory.  (Not WinSrc itself: it points at a ByteSrc, and the two as members of one
-    // object - the pointer to a sibling member - put the whole coder into scratch memory, 112 bytes a lane.)
-    const u8 *base;
-    u32x4 held;
-    u32 wbase, wlen;
-    __device__ ArCoder(const u8 *in, u32 in_size, u32 lane) : code(0), range(0xffffffffu), pos(1), end(in_size), base(in),
-                                                             held{0, 0, 0, 0}, wbase(0), wlen(0)
+    u32 code, range, pos;           // wave-uniform
+    ArWindow in;                    // the input in registers (r4x16_arith_model.h): held by value, never pointed at
+    __device__ ArCoder(const u8 *src, u32 in_size, u32 lane) : code(0), range(0xffffffffu), pos(1), in(src, in_size)
     {
-        if (pos + 5 >= end) pos = end;                              // c_range_coder.h:64-67: nothing is read, code stays 0
-        else for (int k = 0; k < 5; k++) code = (code << 8) | byte(pos++, lane);
-    }
-    __device__ __forceinline__ void fill(u32 p, u32 lane)
-    {
-        wbase = p & ~15u;
-        const u32 mine = wbase + 16u * lane;
-        held = u32x4{0, 0, 0, 0};
-        if (mine + 16u <= end) held = *(const u32x4_unaligned *)(base + mine);
-        const u32 room = (end - wbase) & ~15u;
-        wlen = room < 1024u ? room : 1024u;
-    }
-    __device__ __forceinline__ u32 byte(u32 p, u32 lane)           // p < end
-    {
-        if (p - wbase >= wlen) {
-            if (p + 16u > end) return base[p];
-            fill(p, lane);
-        }
-        const u32 so = (u32)__builtin_amdgcn_readfirstlane((int)(p - wbase));
-        const int ln = (int)(so >> 4);
-        const u32 d0 = (u32)__builtin_amdgcn_readlane((int)held.x, ln), d1 = (u32)__builtin_amdgcn_readlane((int)held.y, ln),
-                  d2 = (u32)__builtin_amdgcn_readlane((int)held.z, ln), d3 = (u32)__builtin_amdgcn_readlane((int)held.w, ln);
-        const u32 lo = (so & 4u) ? d1 : d0, hi = (so & 4u) ? d3 : d2;
-        return (((so & 8u) ? hi : lo) >> (8u * (so & 3u))) & 0xffu;
+        if (pos + 5 >= in.end) pos = in.end;                        // c_range_coder.h:64-67: nothing is read, code stays 0
+        else for (int k = 0; k < 5; k++) code = (code << 8) | in.byte(pos++, lane);
     }
     // RC_GetFreq: the guard included (c_range_coder.h:112-115)
     __device__ __forceinline__ u32 get_freq(u32 tot)
@@ -55,8 +27,8 @@ struct ArCoder {
         code -= cum * range;
         range *= f;
         while (range < AR_TOP) {
-            if (pos >= end) return;
-            code = (code << 8) + byte(pos++, lane);
+            if (pos >= in.end) return;
+            code = (code << 8) + in.byte(pos++, lane);
             range <<= 8;
         }
     }

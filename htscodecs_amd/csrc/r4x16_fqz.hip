@@ -3,7 +3,7 @@
 //
 // A stream is one serial chain: every base is one step of an adaptive model picked by a 16-bit context that the bases
 // before it made.  The parallelism is the arith decoder's (r4x16_arith.hip) - the model's list across the wave, one wave
-// per stream - and so is the step (r4x16_arith_step.h).  What is new is the size of the state: up to 65,536 models a
+// per stream - and so is the step (r4x16_arith_step.h, on r4x16_arith_model.h).  What is new is the size of the state: up to 65,536 models a
 // stream, held in a slot of the context's arena, and the per-record machinery around the step.  Stages:
 //   k_fq_front   one wave per block: the header walk (r4x16_fqz_parse.h), the block's flat tables and, under
 //                GFLAG_DO_REV, its record table claimed from the stage arena
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_fq_front(BatchArgs a, FqWs w, int base,
             const u64 rec_bytes = (top.gflags & FQ_GFLAG_DO_REV) ? ((u64)top.out_size * 4u + 15u) & ~15ull : 0ull;
             const u64 need = fq_tab_bytes(top.nparam) + rec_bytes;
             if (lane == 0) at = atomicAdd((unsigned long long *)w.cursor, (unsigned long long)need);
-            at = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)at);
+            at = wave_uniform(at);
             if (at + need > w.stage_bytes) st = FQ_E_UNSUPPORTED;    // the arena holds no more parameter blocks: DESIGN 4.8
             else {
                 rec = at + fq_tab_bytes(top.nparam);
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void k_fq_plan(BatchArgs a, FqWs w, FqLens ln, 
         if (lane == 0)
             for (u32 k = 0; k < WAVE; k++) { sum += sz[k]; ok[k] = sum <= w.out_total; }
         wsync();
-        sum = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(sum >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)sum);
+        sum = wave_uniform(sum);
         if (b < nb) {
             if (bk.status == FQ_OK && !ok[lane]) {
                 bk.status = FQ_E_UNSUPPORTED; bk.home = FQ_HOME_NONE;
@@ -342,14 +342,10 @@ extern "C" int rans4x16_hip_fqz_uncompress_dev(rans4x16_hip_ctx *c, int n,
                                                uint32_t *d_len, const uint64_t *d_len_off, const uint32_t *d_len_cap, uint32_t *d_nrec,
                                                uint32_t max_in_size, uint32_t max_out_size, uint64_t total_out_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status)) ||
-        (d_len && (!d_len_off || !d_len_cap))) {
-        c->err = "fqz_uncompress_dev: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
+    BatchArgs a;
+    const int go = r4x16_dev_call_args(c, "fqz_uncompress_dev: bad arguments", !d_len || (d_len_off && d_len_cap), &a, n, d_in, d_in_off,
+                                       d_in_size, d_out, d_out_off, d_out_cap, d_out_size, d_status, 0, nullptr);
+    if (go <= 0) return go;
     hipStream_t s = (hipStream_t)stream;
     const u64 total = total_out_size ? total_out_size : (u64)n * max_out_size;
     const u64 slot_bytes = fq_slot_bytes((u32)c->fqz_max_sym);
@@ -357,41 +353,28 @@ extern "C" int rans4x16_hip_fqz_uncompress_dev(rans4x16_hip_ctx *c, int n,
     FqWs w;
     // the stage arena: a selector table a block and room for four parameter blocks a block (256, one stream's most, at
     // least), and a record table as long as the output for the blocks under GFLAG_DO_REV - which only the device knows
-    auto stage_for = [&](size_t nb) {
+    auto layout = [&](u8 *at, size_t nb) {
         const u64 tot = std::min<u64>(total, (u64)nb * max_out_size);
-        return (u64)nb * FQ_STAB_BYTES + (u64)std::max<size_t>(4 * nb, 256) * FQ_PARAM_BYTES + 4ull * tot + 16ull * nb;
+        const u64 stage = (u64)nb * FQ_STAB_BYTES + (u64)std::max<size_t>(4 * nb, 256) * FQ_PARAM_BYTES + 4ull * tot + 16ull * nb;
+        return fq_layout(at, nb, stage, std::min(nb, max_slots), slot_bytes, &w);
     };
-    auto bytes_for = [&](size_t nb) { return fq_layout(nullptr, nb, stage_for(nb), std::min(nb, max_slots), slot_bytes, &w); };
-    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX, r4x16_room(c, A_BIT(A_AR)), bytes_for);
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_AR, bytes_for(nb), false); }) != 0) return -1;
-    BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
+    auto bytes_for = [&](size_t nb) { return layout(nullptr, nb); };
+    const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX, r4x16_room(c, A_BIT(A_AR)), bytes_for);
     const FqLens ln{d_len, d_len_off, d_len_cap, d_nrec};
-    HIPCHK(c, hipMemsetAsync(c->at(A_AR), 0, 2 * sizeof(u64), s));
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const int nb = (int)std::min(chunk, (size_t)n - base);
-        fq_layout(c->at(A_AR), (size_t)nb, stage_for((size_t)nb), std::min((size_t)nb, max_slots), slot_bytes, &w);
+    return r4x16_chunk_walk(c, n, A_AR, chunk, s, bytes_for, [&](size_t base, int nb) {
+        if (base == 0) HIPCHK(c, hipMemsetAsync(c->at(A_AR), 0, 2 * sizeof(u64), s));
+        layout(c->at(A_AR), (size_t)nb);
         w.out_total = total;
         w.max_sym = (u32)c->fqz_max_sym;
-        const bool count = c->opts.v[OPT_ROUTE_COUNT] != 0;
         u32 *const d_route = w.route;
         HIPCHK(c, hipMemsetAsync(w.cursor, 0, sizeof(u64), s));
-        if (count) HIPCHK(c, hipMemsetAsync(d_route, 0, R4X16_FQZ_KINDS * sizeof(u32), s));
-        else w.route = nullptr;
+        if (r4x16_route_begin(c, &w.route, R4X16_FQZ_KINDS, s) != 0) return -1;
         hipLaunchKernelGGL(k_fq_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, w, (int)base, nb, max_in_size, max_out_size);
         hipLaunchKernelGGL(k_fq_plan, dim3(1), dim3(64), 0, s, a, w, ln, (int)base, nb);
         hipLaunchKernelGGL(k_fq_decode<true>, dim3(w.slots), dim3(64), 0, s, a, w, ln, (int)base, nb);
         hipLaunchKernelGGL(k_fq_decode<false>, dim3(w.slots), dim3(64), 0, s, a, w, ln, (int)base, nb);
-        if (count) {
-            if (r4x16_route_snap(c, R4X16_ROUTE_FQZ, d_route, R4X16_FQZ_KINDS, s) != 0) return -1;
-            c->route[R4X16_ROUTE_LAUNCH][R4X16_LAUNCH_IN_ORDER]++;
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return r4x16_route_end(c, R4X16_ROUTE_FQZ, d_route, R4X16_FQZ_KINDS, s);
+    });
 }
 
 // the stored size of every block: the varint at byte 0 (there is no flag byte in this format)
@@ -428,13 +411,11 @@ extern "C" int rans4x16_hip_fqz_peek_dev(rans4x16_hip_ctx *c, int n,
 }
 
 // ---- the walk on host memory --------------------------------------------------------------------------------------
-struct FqHostSrc { const u8 *p; u8 at(u32 i) const { return p[i]; } };
-
 extern "C" int rans4x16_hip_fqz_scan(const unsigned char *in, unsigned int in_size, uint32_t *stored_size, uint32_t *header_bytes,
                                      uint32_t *gflags, uint32_t *nparam, uint32_t *max_sel, uint32_t *max_sym)
 {
     FqTop top = {0, 0, 0, 0, 0, 0};
-    FqHostSrc src{in};
+    HostSrc src{in};
     FqNoSink none;
     const int st = in ? fq_parse(src, in_size, FQ_NO_CAP, &top, none) : (int)FQ_E_EMPTY;
     if (stored_size) *stored_size = top.out_size;
@@ -447,17 +428,9 @@ extern "C" int rans4x16_hip_fqz_scan(const unsigned char *in, unsigned int in_si
 }
 
 // ---- host buffers -------------------------------------------------------------------------------------------------
-// One upload (the streams, and behind them the places of the lengths), the device call, one download (the outputs, and
-// behind them the record counts and the lengths); not pipelined, as the arith batch is not.  The model slots are sized
-// for the batch's largest max_sym, which the host walk knows; the caller's limits are put back.
-struct FqLimits {
-    rans4x16_hip_ctx *c; int slots, max_sym;
-    FqLimits(rans4x16_hip_ctx *c_, int max_sym_) : c(c_), slots(c_->fqz_slots), max_sym(c_->fqz_max_sym) { c->fqz_max_sym = max_sym_; }
-    ~FqLimits() { c->fqz_slots = slots; c->fqz_max_sym = max_sym; }
-    FqLimits(const FqLimits &) = delete;
-    FqLimits &operator=(const FqLimits &) = delete;
-};
-
+// One round trip (r4x16_host_trip): behind the streams go the places of the lengths, behind the outputs come the record
+// counts and the lengths.  The model slots are sized for the batch's largest max_sym, which the host walk knows; the
+// caller's limit is put back.
 extern "C" int rans4x16_hip_fqz_uncompress_batch(rans4x16_hip_ctx *c, int n,
                                                  const unsigned char *const *in, const unsigned int *in_size,
                                                  unsigned char *const *out, unsigned int *out_size, int *status,
@@ -469,65 +442,40 @@ extern "C" int rans4x16_hip_fqz_uncompress_batch(rans4x16_hip_ctx *c, int n,
         return -1;
     }
     if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<u64> in_off(n), out_off(n), len_off(n, 0);
-    std::vector<u32> isz(n, 0), cap(n, 0), len_cap(n, 0);
+    std::vector<u32> isz(n, 0), cap(n, 0);
+    std::vector<u8> take(n, 0), places(12 * (size_t)n, 0), tail;     // places: [n] offsets (8 bytes), [n] capacities (4) of the lengths
+    u64 *const len_off = (u64 *)places.data();
+    u32 *const len_cap = (u32 *)(places.data() + 8 * (size_t)n);
     u32 max_in = 0, max_out = 0, max_sym = 0;
     u64 nlen = 0;
     for (int i = 0; i < n; i++) {
-        FqHostSrc src{in[i]};
+        HostSrc src{in[i]};
         FqTop top;
         FqNoSink none;
         status[i] = in[i] && out[i] ? fq_parse(src, in_size[i], out_size[i], &top, none) : R4X16_E_UNSUPPORTED;
         if (nrec) nrec[i] = 0;
         if (status[i] != FQ_OK) { out_size[i] = 0; continue; }
-        isz[i] = in_size[i]; cap[i] = out_size[i];
+        take[i] = 1; isz[i] = in_size[i]; cap[i] = out_size[i];
         max_in = std::max(max_in, isz[i]); max_out = std::max(max_out, cap[i]); max_sym = std::max(max_sym, top.max_sym);
         if (lengths && lengths[i] && nlengths[i] > 0) { len_off[i] = nlen; len_cap[i] = (u32)nlengths[i]; nlen += len_cap[i]; }
     }
-    // slots of the size rounded up to 16; a refused block (size 0) takes none, its offsets are its successor's
-    const size_t in_total = r4x16_stage_slots(isz.data(), (size_t)n, 0, 16, in_off.data());
-    const size_t out_total = r4x16_stage_slots(cap.data(), (size_t)n, 0, 16, out_off.data());
-    if (in_total == 0) return n;                                     // nothing was accepted
-    const size_t up_bytes = in_total + 12 * (size_t)n, down_bytes = out_total + 4 * (size_t)n + 4 * (size_t)nlen;
-    hipStream_t s = c->stream;
-    StageLayout L;
-    if (r4x16_stage_begin(c, &L, (size_t)n, up_bytes + 16, 0, down_bytes + 16, 0,
-                          {in_off.data(), out_off.data(), isz.data(), cap.data(), nullptr}, s) != 0)
-        return -1;
-    std::vector<u8> up(up_bytes);
-    for (int i = 0; i < n; i++) if (isz[i]) memcpy(up.data() + in_off[i], in[i], isz[i]);
-    memcpy(up.data() + in_total, len_off.data(), 8 * (size_t)n);
-    memcpy(up.data() + in_total + 8 * (size_t)n, len_cap.data(), 4 * (size_t)n);
-    HIPCHK(c, hipMemcpyAsync(L.in, up.data(), up_bytes, hipMemcpyHostToDevice, s));
-    u32 *const d_nrec = (u32 *)(L.out + out_total);
-    {
-        FqLimits limits(c, (int)max_sym);
-        if (rans4x16_hip_fqz_uncompress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
-                                            d_nrec + n, (const u64 *)(L.in + in_total), (const u32 *)(L.in + in_total + 8 * (size_t)n), d_nrec,
-                                            max_in, max_out, out_total, s) != 0)
-            return -1;
-    }
-    std::vector<u8> down(down_bytes);
-    std::vector<u32> osz(n);
-    std::vector<i32> dstat(n);
-    HIPCHK(c, hipMemcpyAsync(down.data(), L.out, down_bytes, hipMemcpyDeviceToHost, s));
-    if (r4x16_stage_verdicts(c, L, (size_t)n, osz.data(), dstat.data(), s) != 0) return -1;
-    const u32 *h_nrec = (const u32 *)(down.data() + out_total);
-    int bad = 0;
-    for (int i = 0; i < n; i++) {
-        if (isz[i]) {                                                // (a block the host walk refused was uploaded as an empty one)
-            status[i] = dstat[i];
-            out_size[i] = dstat[i] == 0 ? osz[i] : 0;
-            if (dstat[i] == 0) {
-                if (osz[i]) memcpy(out[i], down.data() + out_off[i], osz[i]);
-                if (nrec) nrec[i] = h_nrec[i];
-                // the reference's lengths[rec] = len for rec < nlengths: the entries behind the last record stay as they were
-                if (len_cap[i]) memcpy(lengths[i], h_nrec + n + len_off[i], 4 * (size_t)std::min(h_nrec[i], len_cap[i]));
-            }
+    const HostTrip trip = {in, out, out_size, status, take.data(), isz.data(), cap.data(), nullptr,
+                           places.data(), places.size(), 4 * (size_t)n + 4 * (size_t)nlen, &tail};
+    const int bad = r4x16_host_trip(c, n, trip, [&](const StageLayout &L, size_t in_total, size_t out_total, hipStream_t s) {
+        Keep<int> limit(c->fqz_max_sym, (int)max_sym);
+        u32 *const d_nrec = (u32 *)(L.out + out_total);
+        return rans4x16_hip_fqz_uncompress_dev(c, n, L.in, L.in_off, L.in_size, L.out, L.out_off, L.cap, L.osz, L.status,
+                                               d_nrec + n, (const u64 *)(L.in + in_total), (const u32 *)(L.in + in_total + 8 * (size_t)n), d_nrec,
+                                               max_in, max_out, out_total, s);
+    });
+    if (bad < 0 || tail.empty()) return bad;                        // (empty: nothing was taken)
+    const u32 *h_nrec = (const u32 *)tail.data();
+    for (int i = 0; i < n; i++)
+        if (take[i] && status[i] == 0) {
+            if (nrec) nrec[i] = h_nrec[i];
+            // the reference's lengths[rec] = len for rec < nlengths: the entries behind the last record stay as they were
+            if (len_cap[i]) memcpy(lengths[i], h_nrec + n + len_off[i], 4 * (size_t)std::min(h_nrec[i], len_cap[i]));
         }
-        bad += status[i] != 0;
-    }
     return bad;
 }
 
@@ -535,7 +483,7 @@ extern "C" int rans4x16_hip_fqz_uncompress_batch(rans4x16_hip_ctx *c, int n,
 extern "C" char *rans4x16_hip_fqz_decompress(char *in, size_t comp_size, size_t *uncomp_size, int *lengths, int nlengths)
 {
     if (!in || !uncomp_size || comp_size > 0xffffffffull) return nullptr;
-    FqHostSrc src{(const u8 *)in};
+    HostSrc src{(const u8 *)in};
     FqTop top;
     FqNoSink none;
     const int st = fq_parse(src, (u32)comp_size, FQ_NO_CAP, &top, none);

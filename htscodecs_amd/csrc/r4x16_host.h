@@ -16,6 +16,7 @@
 #include <thread>
 #include <chrono>
 #include <algorithm>
+#include <functional>
 
 #include "../../include/rans4x16_hip.h"
 #include "../../include/rans4x8_hip.h"
@@ -147,6 +148,38 @@ struct StageArrays { const u64 *in_off, *out_off; const u32 *in_size, *cap; cons
 int r4x16_stage_begin(rans4x16_hip_ctx *c, StageLayout *L, size_t items, size_t in_bytes, size_t plane_bytes, size_t out_bytes,
                       size_t pk_count, const StageArrays &h, hipStream_t s);
 int r4x16_stage_verdicts(rans4x16_hip_ctx *c, const StageLayout &L, size_t items, u32 *osz, i32 *status, hipStream_t s);
+// The device calls of the adaptive coders (arith_dynamic either way, fqzcomp_qual) and what rides on them.
+// args: the start of such a call - the context and the eight slot arguments tested (`ok`: what else the call requires),
+// the device set, BatchArgs filled.  -1: refused, err = `bad`; 0: n == 0, nothing to do; 1: go on.
+int r4x16_dev_call_args(rans4x16_hip_ctx *c, const char *bad, bool ok, BatchArgs *a, int n, const u8 *d_in, const u64 *d_in_off,
+                        const u32 *d_in_size, u8 *d_out, const u64 *d_out_off, const u32 *d_out_cap, u32 *d_out_size, i32 *d_status,
+                        int order, const i32 *d_order);
+// walk: n blocks in chunks of `chunk` (what the caller's plan fitted), fewer where arena `which` cannot be had for as many
+// (bytes_for(nb): what a chunk of nb blocks takes of it), ordered on the context's arenas before and behind: run(base, nb)
+// enqueues one chunk, 0 or -1.
+int r4x16_chunk_walk(rans4x16_hip_ctx *c, int n, R4Arena which, size_t chunk, hipStream_t s,
+                     const std::function<size_t(size_t)> &bytes_for, const std::function<int(size_t, int)> &run);
+// The route counters of one chunk of launches.  begin: zeroed on `s` - or, option route_count off, *kernels = nullptr: the
+// kernels count nothing.  end (d_cnt: the counters, not the kernels' copy): read out into list `which`, the chunk counted
+// as launched in order.
+int r4x16_route_begin(rans4x16_hip_ctx *c, u32 **kernels, u32 words, hipStream_t s);
+int r4x16_route_end(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words, hipStream_t s);
+// One round trip of a host-buffer batch of these coders: the taken blocks' bytes in one upload (slots of the size rounded
+// up to 16 - a block that is not taken has size and capacity 0 and takes none - and up_tail behind them), the device
+// call on the staged layout, one download (the outputs, and down_tail bytes behind them, handed back in *down_tail), the
+// verdicts, and every taken block's status, size and bytes to the caller's arrays.  What the caller's walk said of a block
+// it did not take stays, and that block's buffer is not written.  Returns the blocks whose status is not 0: n without
+// touching the device where none is taken; -1 where the call itself failed.
+struct HostTrip {
+    const unsigned char *const *in; unsigned char *const *out;
+    unsigned int *out_size; int *status;
+    const u8 *take; const u32 *isz, *cap; const i32 *order;         // [n]; order: nullptr where the call takes none
+    const void *up_tail; size_t up_tail_bytes;
+    size_t down_tail_bytes; std::vector<u8> *down_tail;
+};
+// call(L, in_total, out_total, s): the device call; the tails lie at L.in + in_total and L.out + out_total
+typedef std::function<int(const StageLayout &, size_t, size_t, hipStream_t)> HostTripCall;
+int r4x16_host_trip(rans4x16_hip_ctx *c, int n, const HostTrip &t, const HostTripCall &call);
 // one staging pass (copy in, the device calls, sizes back, copy out) on the context's stream; x8: the rANS 4x8 calls
 int r4x16_run_slab(rans4x16_hip_ctx *c, int n, bool decode, bool x8,
                    const unsigned char *const *in, const unsigned int *in_size,
@@ -191,20 +224,23 @@ struct rans4x16_hip_ctx {
     std::vector<RouteSnap> route_pending;
 };
 
-// The X_STRIPE limits of the device-resident decode calls (rans4x16_hip_set_dev_stripe_planes) for one call made on the
-// caller's behalf: set here, and the caller's own put back when the scope ends, whichever way it ends.
+// a host buffer as the header walks read it (r4x16_arith_parse.h, r4x16_fqz_parse.h).  (r4x16_tok3_scan.hip has one of its
+// own in an anonymous namespace: that unit compiles without any HIP header and cannot include this one.)
+struct HostSrc { const u8 *p; u8 at(u32 i) const { return p[i]; } };
+
+// A setting of the context for one call made on the caller's behalf: set here, and the caller's own put back when the
+// scope ends, whichever way it ends.
+template <class T> struct Keep {
+    T &field; T was;
+    Keep(T &f, T v) : field(f), was(f) { f = v; }
+    ~Keep() { field = was; }
+    Keep(const Keep &) = delete;
+    Keep &operator=(const Keep &) = delete;
+};
+// the X_STRIPE limits of the device-resident decode calls (rans4x16_hip_set_dev_stripe_planes)
 struct StripeLimits {
-    rans4x16_hip_ctx *c;
-    int planes;
-    unsigned int out;
-    StripeLimits(rans4x16_hip_ctx *c_, int planes_, unsigned int out_) : c(c_), planes(c_->dev_stripe_planes), out(c_->dev_stripe_out)
-    {
-        c->dev_stripe_planes = planes_;
-        c->dev_stripe_out = out_;
-    }
-    ~StripeLimits() { c->dev_stripe_planes = planes; c->dev_stripe_out = out; }
-    StripeLimits(const StripeLimits &) = delete;
-    StripeLimits &operator=(const StripeLimits &) = delete;
+    Keep<int> planes; Keep<unsigned int> out;
+    StripeLimits(rans4x16_hip_ctx *c, int planes_, unsigned int out_) : planes(c->dev_stripe_planes, planes_), out(c->dev_stripe_out, out_) {}
 };
 
 #define HIPCHK(ctx, call)                                                                   \

@@ -38,6 +38,86 @@ int r4x16_stage_verdicts(rans4x16_hip_ctx *c, const StageLayout &L, size_t items
     return 0;
 }
 
+// The adaptive coders' device calls and host round trip (r4x16_host.h)
+int r4x16_dev_call_args(rans4x16_hip_ctx *c, const char *bad, bool ok, BatchArgs *a, int n, const u8 *d_in, const u64 *d_in_off,
+                        const u32 *d_in_size, u8 *d_out, const u64 *d_out_off, const u32 *d_out_cap, u32 *d_out_size, i32 *d_status,
+                        int order, const i32 *d_order)
+{
+    if (!c) return -1;
+    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status)) || !ok) {
+        c->err = bad;
+        return -1;
+    }
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    a->in = d_in; a->in_off = d_in_off; a->in_size = d_in_size;
+    a->out = d_out; a->out_off = d_out_off; a->out_cap = d_out_cap; a->out_size = d_out_size;
+    a->status = d_status; a->d_order = d_order; a->order = order; a->n = n;
+    return 1;
+}
+
+int r4x16_chunk_walk(rans4x16_hip_ctx *c, int n, R4Arena which, size_t chunk, hipStream_t s,
+                     const std::function<size_t(size_t)> &bytes_for, const std::function<int(size_t, int)> &run)
+{
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, which, bytes_for(nb), false); }) != 0) return -1;
+    for (size_t base = 0; base < (size_t)n; base += chunk)
+        if (run(base, (int)std::min(chunk, (size_t)n - base)) != 0) return -1;
+    HIPCHK(c, hipGetLastError());
+    return r4x16_ws_order_end(c, s);
+}
+
+int r4x16_route_begin(rans4x16_hip_ctx *c, u32 **kernels, u32 words, hipStream_t s)
+{
+    if (c->opts.v[OPT_ROUTE_COUNT]) HIPCHK(c, hipMemsetAsync(*kernels, 0, words * sizeof(u32), s));
+    else *kernels = nullptr;
+    return 0;
+}
+
+int r4x16_route_end(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words, hipStream_t s)
+{
+    if (!c->opts.v[OPT_ROUTE_COUNT]) return 0;
+    if (r4x16_route_snap(c, which, d_cnt, words, s) != 0) return -1;
+    c->route[R4X16_ROUTE_LAUNCH][R4X16_LAUNCH_IN_ORDER]++;
+    return 0;
+}
+
+// One upload, the device call, one download; not pipelined (a stream of these codecs takes milliseconds per megabyte on
+// the device: the copies are a small share)
+int r4x16_host_trip(rans4x16_hip_ctx *c, int n, const HostTrip &t, const HostTripCall &call)
+{
+    if (std::find(t.take, t.take + n, 1) == t.take + n) return n;    // nothing was accepted
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<u64> in_off(n), out_off(n);
+    const size_t in_total = r4x16_stage_slots(t.isz, (size_t)n, 0, 16, in_off.data());
+    const size_t out_total = r4x16_stage_slots(t.cap, (size_t)n, 0, 16, out_off.data());
+    const size_t up_bytes = in_total + t.up_tail_bytes, down_bytes = out_total + t.down_tail_bytes;
+    hipStream_t s = c->stream;
+    StageLayout L;
+    if (r4x16_stage_begin(c, &L, (size_t)n, up_bytes + 16, 0, down_bytes + 16, 0, {in_off.data(), out_off.data(), t.isz, t.cap, t.order}, s) != 0)
+        return -1;
+    std::vector<u8> up(up_bytes + 1), down(down_bytes + 1);
+    for (int i = 0; i < n; i++) if (t.isz[i]) memcpy(up.data() + in_off[i], t.in[i], t.isz[i]);
+    if (t.up_tail_bytes) memcpy(up.data() + in_total, t.up_tail, t.up_tail_bytes);
+    if (up_bytes) HIPCHK(c, hipMemcpyAsync(L.in, up.data(), up_bytes, hipMemcpyHostToDevice, s));   // (every taken block may be empty)
+    if (call(L, in_total, out_total, s) != 0) return -1;
+    std::vector<u32> osz(n);
+    std::vector<i32> dstat(n);
+    if (down_bytes) HIPCHK(c, hipMemcpyAsync(down.data(), L.out, down_bytes, hipMemcpyDeviceToHost, s));
+    if (r4x16_stage_verdicts(c, L, (size_t)n, osz.data(), dstat.data(), s) != 0) return -1;
+    int bad = 0;
+    for (int i = 0; i < n; i++) {
+        if (t.take[i]) {
+            t.status[i] = dstat[i];
+            t.out_size[i] = dstat[i] == 0 ? osz[i] : 0;
+            if (dstat[i] == 0 && osz[i]) memcpy(t.out[i], down.data() + out_off[i], osz[i]);
+        }
+        bad += t.status[i] != 0;
+    }
+    if (t.down_tail) t.down_tail->assign(down.begin() + out_total, down.begin() + down_bytes);
+    return bad;
+}
+
 // One slab of blocks: copy in, run the device path, copy out, all on the context's own stream.  x8: the rANS 4x8 pair of
 // device calls (they take no max_cap / sum_cap) instead of the 4x16 pair.
 int r4x16_run_slab(rans4x16_hip_ctx *c, int n, bool decode, bool x8,
