@@ -134,7 +134,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith", "arith_enc", "fqz") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc", "fqz", "encode_body") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -146,7 +146,7 @@ class _Ctx:
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
-               "arith_enc": 7, "fqz": 8}
+               "arith_enc": 7, "fqz": 8, "encode_body": 9}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -157,6 +157,7 @@ ROUTE_KINDS = {
     "arith": ("o0", "o1_lds", "o1_global", "rle"),
     "arith_enc": ("o0", "o1_lds", "o1_global", "rle", "stored"),
     "fqz": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
+    "encode_body": ("packed_affine",),
 }
 
 _tls = threading.local()

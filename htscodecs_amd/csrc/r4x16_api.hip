@@ -51,6 +51,8 @@ static const struct { const char *name, *env; long dflt, lo, hi; } OPT_TAB[OPT_C
     /* OPT_COMBINE_WORKERS   */ {"combine_workers", "R4X16_COMBINE_WORKERS", 1, 0, 4},
     /* OPT_COMBINE_MAX_MB    */ {"combine_max_mb", "R4X16_COMBINE_MAX_MB", 2048, 0, 1L << 20},
     /* OPT_NUMA              */ {"numa", "R4X16_NUMA", 1, 0, 1},
+    // not listed by rans4x16_hip_option_name (OPT_LISTED, r4x16_dev.h): per context, like the first group
+    /* OPT_ENC_AFFINE        */ {"enc_affine", "R4X16_ENC_AFFINE", 1, 0, 1},
 };
 // the process-wide defaults: the environment is read here, once, and nowhere else
 static std::mutex g_opts_mu;
@@ -106,7 +108,7 @@ extern "C" int rans4x16_hip_get_option(const rans4x16_hip_ctx *c, const char *na
     *value = d->v[i];
     return 0;
 }
-extern "C" const char *rans4x16_hip_option_name(int index) { return index >= 0 && index < OPT_COUNT ? OPT_TAB[index].name : nullptr; }
+extern "C" const char *rans4x16_hip_option_name(int index) { return index >= 0 && index < OPT_LISTED ? OPT_TAB[index].name : nullptr; }
 
 // ---- the context's arenas (r4x16_host.h) -----------------------------------------------------------------------
 static const char *const ARENA_NAME[A_COUNT] = {"workspace", "staging arena", "stripe / candidate arena", "packed calls' slot arena",
@@ -318,6 +320,7 @@ static int route_fold(rans4x16_hip_ctx *c)
                 const int k = r.which == 0 ? r4x16_enc_route_kind(ci, &freq_table) : r4x16_dec_route_kind(ci);
                 if (k >= 0 && r.cnt[ci]) c->route[r.which][k] += (long)r.cnt[ci];
                 if (freq_table && r.cnt[ci]) c->route[0][R4X16_ENC_PACKED_FREQ] += (long)r.cnt[ci];
+                if (r.which == 0 && ci == ENC_ROUTE_AFF_WORD) c->route[R4X16_ROUTE_ENCODE_BODY][R4X16_ENC_BODY_PACKED_AFFINE] += (long)r.cnt[ci];
             }
         (void)hipEventDestroy(r.ev);
         (void)hipHostFree(r.cnt);
@@ -339,7 +342,7 @@ int r4x16_route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words
     return 0;
 }
 static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS, R4X16_RESULT_KINDS,
-                                               R4X16_NAMES_KINDS, R4X16_ARITH_KINDS, R4X16_ARITH_ENC_KINDS, R4X16_FQZ_KINDS};
+                                               R4X16_NAMES_KINDS, R4X16_ARITH_KINDS, R4X16_ARITH_ENC_KINDS, R4X16_FQZ_KINDS, R4X16_ENC_BODY_KINDS};
 static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS && R4X16_NAMES_KINDS <= ROUTE_KINDS &&
               R4X16_ARITH_KINDS <= ROUTE_KINDS && R4X16_ARITH_KINDS <= CLS_MAX &&
               R4X16_ARITH_KINDS <= R4X16_ARITH_ENC_KINDS && R4X16_ARITH_ENC_KINDS <= R4X16_FQZ_KINDS && R4X16_FQZ_KINDS <= ROUTE_KINDS, "route kinds");

@@ -297,7 +297,8 @@ struct EncItem {
     u32 img_bytes;   // bytes of the image (what must sit in LDS)
     u32 packed;      // 0: u16 rows, 1: rows are 11-bit bit streams (below), 2: 16-byte symbol records (further below),
                      // ENC_KIND_PK_SHORT: packed rows behind a 128-byte index (below)
-    u32 affine;      // symbol records: c + 1 when compact index = byte - c for every byte of the data (no idx_of[] look-up), else 0
+    u32 affine;      // symbol records, packed rows of the short-index kind: c + 1 when compact index = byte - c for every byte of the
+                     // data (no idx_of[] look-up in the pipelined loop), else 0
 };
 // Packed encoder rows: order-1 streams with 10-bit tables and 20..64 symbols (the quality alphabets).  Row r is a
 // bit stream of 11-bit entries cum[r][0..ns] (11 bits hold the total 1024), entry j at bit 11 j; W = ceil(11 (ns + 1)

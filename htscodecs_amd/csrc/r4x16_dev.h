@@ -84,8 +84,12 @@ enum R4Opt {
     OPT_DEC_QPW, OPT_DEC_QPW_SMALL, OPT_DEC_QPW_PK, OPT_DEC_QPW_DIR,
     OPT_ENC_QPW, OPT_ENC_WAVES, OPT_ENC_QPW_REC, OPT_ENC_QPW_CAP, OPT_FRONT_LDS, OPT_ROUTE_COUNT,
     OPT_COMBINE, OPT_COMBINE_WINDOW_US, OPT_COMBINE_MAX, OPT_COMBINE_WORKERS, OPT_COMBINE_MAX_MB, OPT_NUMA,
+    // switches for A/B runs inside one library and for the tests: set and read by name like the others, but not part of
+    // the list that rans4x16_hip_option_name walks (include/rans4x16_hip.h part 2b)
+    OPT_ENC_AFFINE,
     OPT_COUNT
 };
+#define OPT_LISTED OPT_ENC_AFFINE
 struct R4Opts { long v[OPT_COUNT]; };
 extern "C" const R4Opts *r4x16_opts_defaults(void);
 

@@ -3,6 +3,7 @@
 // instantiation, compiled with another instruction scheduler).
 #pragma once
 #include <stdlib.h>
+#include <type_traits>
 #include "r4x16_dev.h"
 #include "r4x16_sched.h"
 #include "r4x16_enc_step.h"
@@ -248,9 +249,12 @@ typedef EncOutT<false> EncOut;
 // PK: packed rows (r4x16_common.h) and a reciprocal table of the 1,025 frequencies a 10-bit table can hold.
 // FT: the packed rows' short-index kind: idx_of[0..127] only, and `lrcp` is the frequency table (8-byte entries, read whole
 // where the reciprocal alone was read; EncOutT::step_freq).
+// aff_wave (FT only, the same in every lane): every stream of the wave has an affine alphabet, compact index = byte - c
+// (EncItem.affine = c + 1, `aff`): the pipelined loop computes its index words from the bytes, with no idx_of[] look-up.
 template <bool PK, bool BYTE = false, bool FT = false>
 __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, const u32 *lrcp, gcu8 *data, u32 n, u32 ns,
-                                                   u32 bits, gcu8 *safe, gu8 *scratch_end, gu8 *dump, bool active, u32 lane)
+                                                   u32 bits, gcu8 *safe, gu8 *scratch_end, gu8 *dump, bool active, u32 lane,
+                                                   bool aff_wave = false, u32 aff = 0u)
 {
     const u32 k = lane & 3;
     static_assert(!FT || (PK && !BYTE), "the frequency table serves the packed rows");
@@ -355,7 +359,10 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
     const u32 npair = main >> 3;                 // double trips
     const u32 ntrip = 2 * npair;
     cur = (active && q) ? idx[qbase[r0]] : 0u;
-    if (wave_any(npair > 0)) {
+    // AFF (the short-index kind, a wave whose streams all have affine alphabets): the loop's index words are computed from
+    // the bytes - idx4 below.
+    auto pipelined = [&](auto affc) {
+        constexpr bool AFF = decltype(affc)::value;
         // Software pipeline, every access issued at least one trip before its first use:
         //   input piece of double-trip D+3 (HBM, 8 bytes)   byte -> compact index of trip t+3 (LDS)
         //   cumulative pair of trip t+2 (LDS)               reciprocal of trip t+1 (LDS)      trip t: 4 state updates
@@ -373,7 +380,25 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             return *(GAS const u32x2_unaligned *)(lbase + loff);
         };
         struct I4 { u32 c0, c1, c2, c3; };       // the words of four compact indices
+        // AFF: word(byte - c) = byte * wmul + (wadd - c * wmul) mod 2^32 - one multiply-add of the byte with two constants
+        // of the lane, no idx_of[] read (both halves of the sum are in range, so what the addend borrows across bit 16
+        // comes back; tests/test_enc_affine_cpu.py).  That holds for a lane's own data, whose bytes are members of its
+        // alphabet - the pieces of its double trips, and its quarter's first bytes, which it reads again past its last one.
+        // A lane without a double trip reads `safe` or nothing of its own: its word must not depend on the byte, so its
+        // multiplier is 0 and its addend the word of index 0 in the image it holds - a valid pair address, whose pair
+        // real4 replaces by the neutral one.
+        u32 amul = 0u, aadd = wadd;
+        if (AFF && npair) { amul = wmul; aadd = wadd - __umul24(aff - 1u, wmul); }
+        auto aword = [&](u32 b) -> u32 {
+            u32 w = __umul24(b, amul) + aadd;
+            asm("" : "+v"(w));               // (one multiply-add, as in word())
+            return w;
+        };
         auto idx4 = [&](u32 ww) -> I4 {
+            if (AFF) {
+                I4 r = {aword(ww >> 24), aword((ww >> 16) & 0xff), aword((ww >> 8) & 0xff), aword(ww & 0xff)};
+                return r;
+            }
             I4 r = {word(idx[ww >> 24]), word(idx[(ww >> 16) & 0xff]), word(idx[(ww >> 8) & 0xff]), word(idx[ww & 0xff])};
             return r;
         };
@@ -453,6 +478,12 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
         o.flush();                               // fewer than 32 words may stay in the ring from here on
         // (packed rows: the loop does not carry the symbol that follows its last live trip - it is read again)
         if (PK) cur = (active && q) ? idx[qbase[r0 - 4 * ntrip]] : 0u;
+    };
+    if (wave_any(npair > 0)) {
+        if constexpr (FT) {
+            if (aff_wave) pipelined(std::true_type{});
+            else pipelined(std::false_type{});
+        } else pipelined(std::false_type{});
     }
     // (B') remaining walk steps, one at a time
     u32 r = r0 - 4 * ntrip, done = 4 * ntrip;
@@ -592,10 +623,12 @@ __device__ __forceinline__ u32 chain_encode_o0_pipe(const u8 *img_lds, u8 *ring,
 // owns lds_per_item bytes (image, then the word ring).  Waves never meet again after the set-up.
 // PK: the class holds packed order-1 streams only (10-bit tables): a 1,025-entry reciprocal table suffices.
 // FT: the class holds packed streams of the short-index kind: the frequency table in place of the reciprocals.
+// aff_on (option enc_affine): waves of the short-index kind whose streams all have affine alphabets (EncItem.affine) take
+// the pipelined loop's affine body; aff_count: where they count their streams for the route read-out (nullptr: not kept).
 #define ENC_LRCP_PK_BYTES 4112u      // 1,025 dwords, padded to 16
 template <bool LDS_IMG, bool PK, bool FT = false>
 __global__ __launch_bounds__(256) void k_enc_chain(EncItem *items, const u32 *rcptab_, u8 *dump_, const u32 *list, u32 *count,
-                                                   int qpw, int spw, u32 lds_per_item, int dyn)
+                                                   int qpw, int spw, u32 lds_per_item, int dyn, int aff_on, u32 *aff_count)
 {
     extern __shared__ __attribute__((aligned(16))) u8 lds[];
     const u32 tid = threadIdx.x;
@@ -658,7 +691,14 @@ __global__ __launch_bounds__(256) void k_enc_chain(EncItem *items, const u32 *rc
         const u8 *im = slots + (u64)slot * lds_per_item;
         u8 *ring = slots + (u64)slot * lds_per_item + (lds_per_item - ENC_RING_BYTES);
         gu8 *dump = to_global(dump_) + 16u * ((blockIdx.x * blockDim.x + tid) & (ENC_DUMP_BYTES / 16u - 1u));
-        pay = chain_encode_o1_lds<PK, false, FT>(im, ring, lrcp, data, n, ns, bits, (gcu8 *)rcptab, send, dump, order == 1, lane);
+        if (FT) {
+            // (a lane without a stream has no say; the same rule as k_enc_chain_rec's and the decoder's affine body)
+            const u32 aff = !aff_on ? 0u : active ? I->affine : 1u;
+            const bool aff_wave = !wave_any(aff == 0u);
+            pay = chain_encode_o1_lds<PK, false, FT>(im, ring, lrcp, data, n, ns, bits, (gcu8 *)rcptab, send, dump, order == 1, lane, aff_wave, aff);
+            const u32 nstreams = (u32)__popcll(__ballot(active) & 0x1111111111111111ull);
+            if (aff_count && aff_wave && lane == 0) atomicAdd(aff_count, nstreams);
+        } else pay = chain_encode_o1_lds<PK, false, FT>(im, ring, lrcp, data, n, ns, bits, (gcu8 *)rcptab, send, dump, order == 1, lane);
         if (!PK) pay |= chain_encode_o0_pipe(im, ring, lrcp, data, n, bits, (gcu8 *)rcptab, send, dump, order == 0, lane);
     } else {
         gcu8 *im = (gcu8 *)I->image;

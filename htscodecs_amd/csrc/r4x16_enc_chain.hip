@@ -157,8 +157,13 @@ extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t 
     u8 *dump = ws->dump;
     const u32 *list = ws->sched.list;
     u32 *cnt, bytes;
-    int qpw, spw, dyn = o->v[OPT_SCHED_CLAIM] != 0;
-    void *args[] = {(void *)&items, (void *)&rcptab, (void *)&dump, (void *)&list, (void *)&cnt, (void *)&qpw, (void *)&spw, (void *)&bytes, (void *)&dyn};
+    int qpw, spw, dyn = o->v[OPT_SCHED_CLAIM] != 0, aff_on = o->v[OPT_ENC_AFFINE] != 0;
+    // the streams coded by the affine body are counted in the last word of the per-class counts, which no class uses: it
+    // travels to the host with them (r4x16_route_snap)
+    static_assert(ENC_NCLS + 2u * ENC_PK_NCLS + ENC_REC_NCLS + 3u <= ENC_ROUTE_AFF_WORD, "a free word behind the classes' counts");
+    u32 *aff_count = o->v[OPT_ROUTE_COUNT] ? ws->sched.cnt + SCHED_COUNT + ENC_ROUTE_AFF_WORD : nullptr;
+    void *args[] = {(void *)&items, (void *)&rcptab, (void *)&dump, (void *)&list, (void *)&cnt, (void *)&qpw, (void *)&spw, (void *)&bytes, (void *)&dyn,
+                    (void *)&aff_on, (void *)&aff_count};
     sched_launch_classes(plan, SchedBatch{&ws->sched, nitems, s0, fk, o, hint, 1u, "encode"}, todo, ntodo, &tail, 1,
         [&] { hipLaunchKernelGGL(k_enc_classify, dim3((nitems + 255) / 256), dim3(256), 0, s0, (const EncItem *)ws->items, nitems, tab, ws->sched); },
         [&](const SchedLaunch &L) { cnt = ws->sched.cnt + L.ci; qpw = L.qpw; spw = L.spw; bytes = L.bytes; return args; });

@@ -297,7 +297,7 @@ __device__ __forceinline__ u32 chain_encode_rec(const u8 *img_lds, u8 *ring, gcu
 // class (see k_dec_chain).  A stream owns lds_per_item bytes: image (idx_of + records), then the word ring.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WAVE) void k_enc_chain_rec(EncItem *items, const u32 *safe_, u8 *dump_, const u32 *list, u32 *count,
-                                                        int qpw, int spw_unused, u32 lds_per_item, int dyn)
+                                                        int qpw, int spw_unused, u32 lds_per_item, int dyn, int aff_on_unused, u32 *aff_count_unused)
 {
     extern __shared__ __attribute__((aligned(16))) u8 lds[];
     const u32 lane = threadIdx.x;

@@ -1512,6 +1512,19 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
     if (packed && lane == 0) ((u32 *)(img + idxb))[ns * W] = 0;      // the pair window's second dword past the last row
     wsync();
 
+    // symbol records, and packed rows of the short-index kind (k_enc_chain's affine body): is the compact index an offset
+    // of the byte value?  (quality values are a run of consecutive bytes; byte 0, which every order-1 alphabet lists,
+    // must then not occur in the data unless the run starts right behind it)
+    // (here, ahead of the nested table: its order-0 table is written over the pair counters of an alphabet that keeps them
+    //  in global memory)
+    u32 aff = 0;
+    if ((recs || (packed && idxb == ENC_IMG_IDX_SHORT)) && ns >= 2) {
+        const u32 c = (u32)S.alpha[1] - 1u;
+        bool ok = true;
+        for (u32 j = lane; j < ns; j += WAVE) if (j >= 1 && (u32)S.alpha[j] != j + c) ok = false;
+        if (c != 0) for (u32 r = lane; r < ns; r += WAVE) if (Fp[r * ns] != 0) ok = false;      // byte 0 coded somewhere
+        aff = __ballot(!ok) ? 0u : c + 1u;
+    }
     TPROF(4);
     // ---- table into the stream (:766-780) -----------------------------------------------------------
     // A table of 1,000 bytes and more is also coded as an order-0 stream, and the shorter form goes out.  That
@@ -1535,16 +1548,6 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
         }
     }
     TPROF(5);
-    // symbol records: is the compact index an offset of the byte value?  (quality values are a run of consecutive bytes;
-    // byte 0, which every order-1 alphabet lists, must then not occur in the data unless the run starts right behind it)
-    u32 aff = 0;
-    if (recs && ns >= 2) {
-        const u32 c = (u32)S.alpha[1] - 1u;
-        bool ok = true;
-        for (u32 j = lane; j < ns; j += WAVE) if (j >= 1 && (u32)S.alpha[j] != j + c) ok = false;
-        if (c != 0) for (u32 r = lane; r < ns; r += WAVE) if (Fp[r * ns] != 0) ok = false;      // byte 0 coded somewhere
-        aff = __ballot(!ok) ? 0u : c + 1u;
-    }
     const u32 final_len = 1 + tlen;
     wsync();
     if (lane == 0) {

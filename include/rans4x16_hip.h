@@ -886,6 +886,10 @@ char *rans4x16_hip_fqz_decompress(char *in, size_t comp_size, size_t *uncomp_siz
  *   combine_workers       1     R4X16_COMBINE_WORKERS    worker threads per direction
  *   combine_max_mb     2048     R4X16_COMBINE_MAX_MB     buffer bytes per combined batch
  *   numa                  1     R4X16_NUMA               multi-device calls bind each device's worker to its NUMA node
+ *   switches for A/B runs inside one library and for the tests (per context; set and read by name like the others, range
+ *   0..1, but not in the list that rans4x16_hip_option_name walks - nothing to tune, the streams are the same either way):
+ *   enc_affine            1     R4X16_ENC_AFFINE         encode: packed rows of the short-index kind whose alphabet is a run of consecutive
+ *                                                        bytes compute their index words from the bytes (0: every wave looks them up)
  *
  * Every option has a range (0 keeps its meaning of "auto" / "never" where it has one; host_threads 1..32, host_lanes
  * 1..16, the dec_qpw* and enc_qpw_rec knobs 0..16, enc_qpw 0..31, enc_waves 0..4, enc_qpw_cap 1..64, switches 0..1,
@@ -900,7 +904,8 @@ char *rans4x16_hip_fqz_decompress(char *in, size_t comp_size, size_t *uncomp_siz
  */
 int rans4x16_hip_set_option(rans4x16_hip_ctx *ctx, const char *name, long value);
 int rans4x16_hip_get_option(const rans4x16_hip_ctx *ctx, const char *name, long *value);
-/* Name of option number `index` (0, 1, ..), NULL past the last: lets a caller list what this build knows. */
+/* Name of option number `index` (0, 1, ..), NULL past the last: lets a caller list what this build knows (the A/B switches
+ * at the end of the table above excepted). */
 const char *rans4x16_hip_option_name(int index);
 
 /* Bytes of device workspace the context currently holds (grows on demand, never shrinks). */
@@ -926,7 +931,8 @@ enum {
     R4X16_ROUTE_NAMES = 5,    /* host-buffer names batches (part 2f): chunks and blocks (R4X16_NAMES_*)                */
     R4X16_ROUTE_ARITH = 6,    /* arith_dynamic decoding (part 2g): streams per home of their models (R4X16_ARITH_*)    */
     R4X16_ROUTE_ARITH_ENC = 7,/* arith_dynamic encoding (part 2h): candidate streams (R4X16_ARITH_ENC_*)               */
-    R4X16_ROUTE_FQZ = 8       /* fqzcomp_qual decoding (part 2i): decoded streams (R4X16_FQZ_*)                        */
+    R4X16_ROUTE_FQZ = 8,      /* fqzcomp_qual decoding (part 2i): decoded streams (R4X16_FQZ_*)                        */
+    R4X16_ROUTE_ENCODE_BODY = 9 /* encode chain: streams per body of the pipelined loop (R4X16_ENC_BODY_*)               */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -944,6 +950,12 @@ enum {   /* R4X16_ROUTE_ENCODE: the encoder's row kinds */
     R4X16_ENC_PACKED_FREQ = 3,/* those of the packed streams (counted there too) whose highest byte is below 128: the image  */
                               /* with the 128-byte index, coded from the 8-byte frequency table                              */
     R4X16_ENC_KINDS = 4
+};
+enum {   /* R4X16_ROUTE_ENCODE_BODY */
+    R4X16_ENC_BODY_PACKED_AFFINE = 0, /* packed streams of the short-index kind (counted under R4X16_ROUTE_ENCODE too) in waves that  */
+                                      /* took the affine body: every stream of the wave has a run of consecutive bytes for its       */
+                                      /* alphabet, and option enc_affine is on                                                      */
+    R4X16_ENC_BODY_KINDS = 1
 };
 enum { R4X16_EXPAND_WAVE = 0, R4X16_EXPAND_WORKGROUP = 1, R4X16_EXPAND_KINDS = 2 };               /* R4X16_ROUTE_EXPAND */
 enum { R4X16_LAUNCH_IN_ORDER = 0, R4X16_LAUNCH_SIDE_BY_SIDE = 1, R4X16_LAUNCH_KINDS = 2 };        /* R4X16_ROUTE_LAUNCH */
