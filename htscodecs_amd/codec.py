@@ -134,7 +134,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith", "arith_enc", "fqz", "encode_body") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -146,7 +146,7 @@ class _Ctx:
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
-               "arith_enc": 7, "fqz": 8, "encode_body": 9}
+               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -158,6 +158,7 @@ ROUTE_KINDS = {
     "arith_enc": ("o0", "o1_lds", "o1_global", "rle", "stored"),
     "fqz": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
     "encode_body": ("packed_affine",),
+    "fqz_enc": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
 }
 
 _tls = threading.local()
@@ -571,6 +572,92 @@ def fqz_decompress(comp, nlengths=0):
     return res, list(lens)[:int(nlengths)]
 
 
+def fqz_pick_parameters(data, lens, flags, vers=4, strat=0, params_cap=None):
+    """rans4x16_hip_fqz_pick_parameters: the reference's parameter choice for one slice.  Returns (status, the parameter
+    bytes or None, lens, flags) - the lists as the call leaves them: the lengths after the reference's fix-ups, the selector
+    in flags[rec] >> 16.  params_cap: the room offered (default: enough); status 1 gives (1, the size needed, ..).  Needs no
+    GPU."""
+    L = _lib.load()
+    buf = bytes(data)
+    n = len(lens)
+    la = (C.c_uint32 * max(n, 1))(*[int(v) & 0xffffffff for v in lens])
+    fa = (C.c_uint32 * max(n, 1))(*[int(v) & 0xffffffff for v in flags])
+    cap = 4096 if params_cap is None else int(params_cap)
+    out = C.create_string_buffer(max(cap, 1))
+    size = C.c_uint(0)
+    st = L.rans4x16_hip_fqz_pick_parameters(int(vers), int(strat), n, la, fa, buf, len(buf), out, cap, C.byref(size))
+    if st == 1 and params_cap is None:
+        cap = size.value
+        out = C.create_string_buffer(max(cap, 1))
+        st = L.rans4x16_hip_fqz_pick_parameters(int(vers), int(strat), n, la, fa, buf, len(buf), out, cap, C.byref(size))
+    res = out.raw[:size.value] if st == 0 else (size.value if st == 1 else None)
+    return st, res, list(la)[:n], list(fa)[:n]
+
+
+def fqz_compress_cap(size, nrec, params_size):
+    """rans4x16_hip_fqz_compress_cap: a capacity with which a block of `size` bytes in `nrec` records never overflows."""
+    return _lib.load().rans4x16_hip_fqz_compress_cap(int(size), int(nrec), int(params_size))
+
+
+def fqz_compress_batch(blocks, lens, flags, vers=4, strat=0, params=None, caps=None, ctx=None):
+    """rans4x16_hip_fqz_compress_batch: quality blocks (bytes) with their record lengths and flags -> (list of bytes | None,
+    statuses, lens, flags as the call leaves them).  params: None, or per block None (picked on the host with vers and
+    strat) or its parameter bytes.  caps: the capacity of each output (default: fqz_compress_cap with 4096 parameter
+    bytes).  One upload, one device call, one download."""
+    ctx = ctx or _thread_ctx()
+    L = ctx.L
+    n = len(blocks)
+    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+    la = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in lens]
+    fa = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in flags]
+    pars = [None if params is None or p is None else np.frombuffer(bytes(p), dtype=np.uint8) for p in (params or [None] * n)]
+    if caps is None:
+        caps = [L.rans4x16_hip_fqz_compress_cap(len(s), len(l), 4096 if p is None else len(p)) for s, l, p in zip(srcs, la, pars)]
+    outs = [np.empty(max(int(c), 1), dtype=np.uint8) for c in caps]
+    dummy = np.zeros(4, dtype=np.uint8)
+    ptr = lambda a: a.ctypes.data if len(a) else dummy.ctypes.data
+    in_p = (C.c_void_p * n)(*[ptr(s) for s in srcs])
+    len_p = (C.c_void_p * n)(*[ptr(a) for a in la])
+    fl_p = (C.c_void_p * n)(*[ptr(a) for a in fa])
+    par_p = (C.c_void_p * n)(*[None if p is None else ptr(p) for p in pars])
+    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
+    nrec = (C.c_uint * n)(*[len(a) for a in la])
+    par_sz = (C.c_uint * n)(*[0 if p is None else len(p) for p in pars])
+    out_sz = (C.c_uint * n)(*[int(c) for c in caps])
+    status = (C.c_int * n)()
+    rc = L.rans4x16_hip_fqz_compress_batch(ctx.h, n, in_p, in_sz, nrec, len_p, fl_p, int(vers), int(strat),
+                                           None if params is None else par_p, par_sz, out_p, out_sz, status)
+    if rc < 0:
+        raise RuntimeError("fqz batch failed: " + ctx.error())
+    res = [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)]
+    return res, list(status), [a.tolist() for a in la], [a.tolist() for a in fa]
+
+
+class _FqzSlice(C.Structure):
+    _fields_ = [("num_records", C.c_int), ("len", C.POINTER(C.c_uint32)), ("flags", C.POINTER(C.c_uint32))]
+
+
+def fqz_compress(data, lens, flags, vers=4, strat=0, gp=None):
+    """The reference's fqz_compress(vers, slice, in, in_size, &out_size, strat, gp): (the stream, lens, flags as the call
+    leaves them), or None where it returns NULL (gp must be None: the parameter struct is not taken)."""
+    L = _lib.load()
+    buf = C.create_string_buffer(bytes(data), max(len(data), 1))
+    n = len(lens)
+    la = (C.c_uint32 * max(n, 1))(*[int(v) & 0xffffffff for v in lens])
+    fa = (C.c_uint32 * max(n, 1))(*[int(v) & 0xffffffff for v in flags])
+    s = _FqzSlice(n, la, fa)
+    size = C.c_size_t(0)
+    p = L.rans4x16_hip_fqz_compress(int(vers), C.byref(s), buf, len(data), C.byref(size), int(strat), gp)
+    if buf.raw[:len(data)] != bytes(data):
+        raise AssertionError("fqz_compress changed its input")
+    if not p:
+        return None
+    res = C.string_at(p, size.value)
+    _free(p)
+    return res, list(la)[:n], list(fa)[:n]
+
+
 def arith_compress_bound(size, order):
     """The reference's arith_compress_bound (host arithmetic)."""
     return _lib.load().rans4x16_hip_arith_compress_bound(int(size), int(order))
@@ -804,6 +891,27 @@ class DeviceCodec:
         (0: 255)."""
         if self.L.rans4x16_hip_set_fqz_limits(self.ctx.h, int(max_slots), int(max_sym)) != 0:
             raise ValueError("set_fqz_limits: " + self.ctx.error())
+
+    # ---- fqzcomp_qual encoding (include/rans4x16_hip.h part 2j) -------------------------------------------------------
+    def fqz_compress(self, d_in, in_off, in_size, d_params, par_off, par_size, d_len, d_flags, rec_off, nrec,
+                     d_out, out_off, out_cap, out_size, status, max_in_size, max_params_size, max_records):
+        """rans4x16_hip_fqz_compress_dev: per block the qualities, the parameter bytes (uint8 at par_off, int64, of par_size,
+        int32) and the records (nrec, int32, lengths and flags as int32 entries from rec_off, int64, in d_len / d_flags),
+        fqzcomp_qual streams out.  Enqueues only."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8 and d_params.dtype == t.uint8
+        assert in_off.dtype == t.int64 and out_off.dtype == t.int64 and par_off.dtype == t.int64 and rec_off.dtype == t.int64
+        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32 and par_size.dtype == t.int32 and nrec.dtype == t.int32
+        assert d_len.dtype == t.int32 and d_flags.dtype == t.int32
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        rc = self.L.rans4x16_hip_fqz_compress_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_params.data_ptr(), par_off.data_ptr(), par_size.data_ptr(),
+            d_len.data_ptr(), d_flags.data_ptr(), rec_off.data_ptr(), nrec.data_ptr(),
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            int(max_in_size), int(max_params_size), int(max_records), self._stream())
+        if rc != 0:
+            raise RuntimeError("fqz_compress_dev: " + self.ctx.error())
 
     # ---- packed calls (include/rans4x16_hip.h part 2a): one dense arena, offsets written by the device ----------
     def _packed_args(self, d_in, in_off, in_size, d_out, out_off, out_size, status):

@@ -1,7 +1,8 @@
 // r4x16_arith_model.h - what the adaptive coders share on the device, whichever way they code (r4x16_arith.hip decodes
-// arith_dynamic, r4x16_arith_enc.hip encodes it, r4x16_fqz.hip decodes fqzcomp_qual): the constants of c_simple_model.h
-// and c_range_coder.h, a model's entries (frequency | symbol << 16), the homes of arith_dynamic's models, the input
-// window in registers and the word-wise byte writer.  The decoding step on top of this: r4x16_arith_step.h.
+// arith_dynamic, r4x16_arith_enc.hip encodes it, r4x16_fqz.hip decodes fqzcomp_qual, r4x16_fqz_enc.hip encodes it): the
+// constants of c_simple_model.h and c_range_coder.h, a model's entries (frequency | symbol << 16), the homes of
+// arith_dynamic's models, the input window in registers and the word-wise byte writer.  The steps on top of this:
+// r4x16_arith_step.h (decoding), r4x16_arith_enc_step.h (encoding).
 // The update behind a coded symbol and a step's row traffic are NOT here: each symbol step keeps its own statements,
 // because as shared functions they changed the code of the hot kernels (profiles/adaptive_refactor.md).
 #pragma once

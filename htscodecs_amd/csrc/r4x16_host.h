@@ -68,7 +68,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 10
+#define ROUTE_WHICH 11
 // R4X16_ROUTE_ENCODE_BODY rides on the encode chain's copy: the word of the per-class counts that k_enc_chain's affine
 // waves count their streams in (no launch has that many classes; r4x16_enc_chain.hip)
 #define ENC_ROUTE_AFF_WORD (CLS_MAX - 1u)
@@ -87,7 +87,7 @@ enum R4Arena {
     A_T3,        // tok3 containers: the winners waiting to be framed / the directory of the columns to decode (r4x16_tok3.hip)
     A_TN,        // tok3 names: the names' histories; for the one-call form the columns in front of them (r4x16_tok3_names.hip)
     A_AR,        // the adaptive coders: arith_dynamic, either direction - items, stage arena, the order-1 rows that do not fit LDS
-                 // (r4x16_arith.hip, r4x16_arith_enc.hip); fqzcomp_qual - blocks, tables, record tables, model slots (r4x16_fqz.hip)
+                 // (r4x16_arith.hip, r4x16_arith_enc.hip); fqzcomp_qual, either direction - blocks, tables, record tables, model slots (r4x16_fqz.hip, r4x16_fqz_enc.hip)
     A_COUNT
 };
 #define A_BIT(a) (1u << (a))

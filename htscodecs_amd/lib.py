@@ -179,6 +179,18 @@ SIGNATURES = {
     "rans4x16_hip_fqz_uncompress_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rans4x16_hip_fqz_decompress": (C.c_void_p, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int]),
+    # fqzcomp_qual encoding (include/rans4x16_hip.h part 2j)
+    "rans4x16_hip_fqz_pick_parameters": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_uint, C.POINTER(C.c_uint)]),
+    "rans4x16_hip_fqz_compress_cap": (C.c_uint, [C.c_uint, C.c_uint, C.c_uint]),
+    "rans4x16_hip_fqz_compress_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rans4x16_hip_fqz_compress_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rans4x16_hip_fqz_compress": (C.c_void_p, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
     # rANS 4x8's packed and best-of-two device-resident calls (include/rans4x8_hip.h part 2a)
     "rans4x8_hip_compress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -8,8 +8,9 @@
  * stored size that the caller free()s, *out_size the stored size, lengths[rec] the length of record rec for
  * rec < nlengths (lengths may be NULL), NULL on failure.
  *
- * Decoding only: fqz_compress, fqz_pick_parameters and fqz_qual_stats are not built, and this header does not declare
- * them - a program that encodes keeps the reference for that.
+ * This header is the reader's: it declares the decoder alone.  A program that writes quality blocks includes
+ * fqzcomp_qual_enc_hip.h, which includes this header and adds the reference's encode call with fqz_slice, the FQZ_F*
+ * flags and FQZ_MAX_STRAT (include/rans4x16_hip.h part 2j).  fqz_qual_stats is not built.
  */
 #ifndef FQZCOMP_QUAL_HIP_H
 #define FQZCOMP_QUAL_HIP_H

@@ -768,8 +768,8 @@ unsigned char *rans4x16_hip_arith_compress(unsigned char *in, unsigned int in_si
 /* ---- 2i. fqzcomp_qual decoding (the CRAM 3.1 quality codec) ------------------------------------------------------
  * htscodecs/fqzcomp_qual.c's decoder on the device: the range coder and the adaptive models of parts 2g and 2h, with a
  * 16-bit context - up to 65,536 models a stream, in a slot of the context's arena - and the per-record machinery
- * (selector, lengths, reverse flag, duplicates, parameter blocks and their tables).  Decoding only: fqz_compress,
- * fqz_pick_parameters and fqz_qual_stats are not built.  DESIGN.md 4.8.
+ * (selector, lengths, reverse flag, duplicates, parameter blocks and their tables).  The encoder is part 2j.
+ * DESIGN.md 4.8.
  *
  * rans4x16_hip_fqz_scan: walks the header of one stream in HOST memory.  Pure host arithmetic, usable without a GPU.
  * Reports the stored size, the bytes in front of the range coder's input, gflags, nparam, max_sel and max_sym (the
@@ -839,6 +839,80 @@ int rans4x16_hip_fqz_uncompress_batch(rans4x16_hip_ctx *ctx, int n,
                                       unsigned char *const *out, unsigned int *out_size, int *status,
                                       int *const *lengths, const int *nlengths, unsigned int *nrec);
 char *rans4x16_hip_fqz_decompress(char *in, size_t comp_size, size_t *uncomp_size, int *lengths, int nlengths);
+
+/* ---- 2j. fqzcomp_qual encoding (fqz_compress) ---------------------------------------------------------------------
+ * htscodecs/fqzcomp_qual.c's encoder: the parameter choice on the host, the encode loop on the device.  DESIGN.md 4.9.
+ *
+ * PARAMETER BYTES are the parameter format of every call here: what fqz_store_parameters writes and a stream holds
+ * between its size varint and the range coder's bytes - the version byte (5), gflags, [nparam], [max_sel, the selector
+ * table], the parameter blocks.  They go into the stream verbatim, and the device reads them with the header walk of
+ * part 2i: parameter bytes it would refuse in a stream it refuses here, with the scan's statuses.
+ *
+ * rans4x16_hip_fqz_pick_parameters: fqz_pick_parameters and fqz_qual_stats(.., one_param = -1) in HOST memory.  Pure host
+ * arithmetic, usable without a GPU.  vers 3 sets GFLAG_DO_REV; strat 0..3 are the reference's strategies, 4 and above its
+ * all-zero row.  flags[rec] holds FQZ_FREVERSE (16), FQZ_FREAD2 (128) and, from bit 16 up, a selector of the caller's.
+ * On success (0) `params` holds *params_size parameter bytes, len[] is as the reference's fix-ups leave it (a list that
+ * overruns in_size is cut, the last record takes what is left over) and flags[rec] >> 16 holds the selector the
+ * statistics chose (the average-quality split, the READ1/READ2 split): the slice the encode calls take.
+ * R4X16_E_CAPACITY: params_cap is too small (or params NULL); *params_size is the size needed, len and flags are
+ * unchanged.  R4X16_E_UNSUPPORTED: a negative strat or nrec, a missing array, 2^31 bytes or more.  With nrec = 0 the
+ * reference reads len[0]; here that length counts as 0.
+ *
+ * rans4x16_hip_fqz_compress_dev has the contract of rans4x16_hip_arith_compress_dev: it only enqueues on `stream`, reads
+ * nothing back and writes nothing outside [d_out_off[i], d_out_off[i] + d_out_cap[i]).  Per block: the qualities
+ * (d_in, d_in_off, d_in_size), the parameter bytes (d_params, d_par_off, d_par_size), the records - d_nrec[i] lengths
+ * and flags as 32-bit entries from d_len[d_rec_off[i]] and d_flags[d_rec_off[i]] (the offset counts ENTRIES), flags
+ * with bit 4 = reversed and bits 16 and up = selector, the slice as the pick leaves it - and the slot.  Block i comes
+ * out as compress_block_fqz2f writes it under those parameters: varint(size), the parameter bytes, the coder's bytes.
+ * The caller's input is never modified.  d_status[i], besides the scan's statuses for the parameter bytes:
+ *   R4X16_E_CAPACITY     the stream is longer than d_out_cap[i]: nothing is written.  A slot of any size is accepted;
+ *                        one of rans4x16_hip_fqz_compress_cap(size, nrec, params_size) bytes never overflows
+ *   R4X16_E_SIZE         record lengths that do not sum to the size, a record of 0 bytes, no record for a block that
+ *                        has bytes (a block of size 0 reads no record)
+ *   R4X16_E_CONTEXT      where the reference is undefined: a selector above max_sel where selectors are
+ *                        coded, or one whose parameter block the bytes do not have; a quality that a stored qmap does
+ *                        not list, or - without a stored qmap - above max_sym
+ *   R4X16_E_TABLE        also: several parameter blocks with max_sel = 0 (no selector model to code with)
+ *   R4X16_E_TRUNCATED / R4X16_E_UNSUPPORTED  also: parameter bytes that end before / go on behind the walk's end
+ *   R4X16_E_UNSUPPORTED  a block above max_in_size, max_params_size or max_records, or of 2^31 bytes or more (not read),
+ *                        a max_sym above rans4x16_hip_set_fqz_limits's, no room for its parameter blocks (the arena holds
+ *                        four a block of the chunk and 256 at least)
+ * The model slots and rans4x16_hip_set_fqz_limits are part 2i's.
+ *
+ * rans4x16_hip_fqz_compress_batch: host buffers.  nrec[i], len[i], flags[i] describe block i's records; params may be
+ * NULL, and a block with params[i] == NULL is picked on the host with (vers, strat) - its len[i] and flags[i] change as
+ * the pick changes them.  out_size[i] holds the capacity of out[i] on entry and the size on return.  One upload, the
+ * device call with the slots sized for the batch's largest max_sym, one download.  On return flags[i][rec] &= 0xffff,
+ * as the reference leaves them.  Returns the number of failed blocks, -1 on a call error.
+ *
+ * rans4x16_hip_fqz_compress: the arguments and the ownership of the reference's fqz_compress (a malloc'd buffer, the
+ * caller's to free; NULL on failure; s->len and s->flags as the reference leaves them; `in` unchanged), on the calling
+ * thread's context.  gp != NULL returns NULL: the parameter struct is not taken - a caller with parameters of its own
+ * uses the batch call with parameter bytes.  include/fqzcomp_qual_enc_hip.h gives it the reference's name.
+ *
+ * Route read-out: R4X16_ROUTE_FQZ_ENC counts the streams that were encoded (R4X16_FQZ_ENC_*); each chunk of a call counts
+ * once as R4X16_LAUNCH_IN_ORDER under R4X16_ROUTE_LAUNCH. */
+typedef struct rans4x16_hip_fqz_slice { int num_records; uint32_t *len; uint32_t *flags; } rans4x16_hip_fqz_slice;
+struct rans4x16_hip_fqz_gparams;   /* opaque: never looked into */
+int rans4x16_hip_fqz_pick_parameters(int vers, int strat, int nrec, uint32_t *len, uint32_t *flags,
+                                     const unsigned char *in, size_t in_size,
+                                     unsigned char *params, unsigned int params_cap, unsigned int *params_size);
+unsigned int rans4x16_hip_fqz_compress_cap(unsigned int size, unsigned int nrec, unsigned int params_size);
+int rans4x16_hip_fqz_compress_dev(rans4x16_hip_ctx *ctx, int n,
+                                  const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                  const unsigned char *d_params, const uint64_t *d_par_off, const uint32_t *d_par_size,
+                                  const uint32_t *d_len, const uint32_t *d_flags, const uint64_t *d_rec_off, const uint32_t *d_nrec,
+                                  unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                  uint32_t *d_out_size, int32_t *d_status,
+                                  uint32_t max_in_size, uint32_t max_params_size, uint32_t max_records, void *stream);
+int rans4x16_hip_fqz_compress_batch(rans4x16_hip_ctx *ctx, int n,
+                                    const unsigned char *const *in, const unsigned int *in_size,
+                                    const unsigned int *nrec, uint32_t *const *len, uint32_t *const *flags,
+                                    int vers, int strat,
+                                    const unsigned char *const *params, const unsigned int *params_size,
+                                    unsigned char *const *out, unsigned int *out_size, int *status);
+char *rans4x16_hip_fqz_compress(int vers, rans4x16_hip_fqz_slice *s, char *in, size_t in_size, size_t *out_size, int strat,
+                                struct rans4x16_hip_fqz_gparams *gp);
 
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
@@ -932,7 +1006,8 @@ enum {
     R4X16_ROUTE_ARITH = 6,    /* arith_dynamic decoding (part 2g): streams per home of their models (R4X16_ARITH_*)    */
     R4X16_ROUTE_ARITH_ENC = 7,/* arith_dynamic encoding (part 2h): candidate streams (R4X16_ARITH_ENC_*)               */
     R4X16_ROUTE_FQZ = 8,      /* fqzcomp_qual decoding (part 2i): decoded streams (R4X16_FQZ_*)                        */
-    R4X16_ROUTE_ENCODE_BODY = 9 /* encode chain: streams per body of the pipelined loop (R4X16_ENC_BODY_*)               */
+    R4X16_ROUTE_ENCODE_BODY = 9,/* encode chain: streams per body of the pipelined loop (R4X16_ENC_BODY_*)               */
+    R4X16_ROUTE_FQZ_ENC = 10  /* fqzcomp_qual encoding (part 2j): encoded streams (R4X16_FQZ_ENC_*)                    */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -995,6 +1070,15 @@ enum {   /* R4X16_ROUTE_FQZ: streams rans4x16_hip_fqz_uncompress_dev sent to a d
     R4X16_FQZ_MULTI_PARAM = 4,  /* with more than one parameter block                                                  */
     R4X16_FQZ_DUP = 5,          /* accepted streams in which a duplicate record was copied                             */
     R4X16_FQZ_KINDS = 6
+};
+enum {   /* R4X16_ROUTE_FQZ_ENC: streams rans4x16_hip_fqz_compress_dev sent to an encode wave */
+    R4X16_FQZ_ENC_STREAMS = 0,      /* all of them                                                                     */
+    R4X16_FQZ_ENC_TAB_LDS = 1,      /* the parameter blocks' tables in LDS (up to eight parameter blocks)              */
+    R4X16_FQZ_ENC_TAB_GLOBAL = 2,   /* the tables read from the context's arena                                        */
+    R4X16_FQZ_ENC_DO_REV = 3,       /* with GFLAG_DO_REV: coded from the coder-order copy                              */
+    R4X16_FQZ_ENC_MULTI_PARAM = 4,  /* with more than one parameter block                                              */
+    R4X16_FQZ_ENC_DUP = 5,          /* accepted streams (status 0) in which a record was coded as a duplicate          */
+    R4X16_FQZ_ENC_KINDS = 6
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
