@@ -74,27 +74,39 @@ def rans_uncompress(comp):
     return res
 
 
+class _HostArrays:
+    """What every host-batch call takes - the blocks' pointers and sizes, an output buffer per block of its capacity, the
+    sizes coming back, the statuses - and what it leaves.  caps: a capacity per block, or a function of a block's index and
+    size that gives it."""
+
+    def __init__(self, blocks, caps):
+        n = self.n = len(blocks)
+        self.srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+        capv = [int(caps(i, len(x))) for i, x in enumerate(self.srcs)] if callable(caps) else [int(c) for c in caps]
+        self.outs = [np.empty(max(c, 1), dtype=np.uint8) for c in capv]
+        self.dummy = np.zeros(1, dtype=np.uint8)
+        self.in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else self.dummy.ctypes.data) for s in self.srcs])
+        self.out_p = (C.c_void_p * n)(*[o.ctypes.data for o in self.outs])
+        self.in_sz = (C.c_uint * n)(*[len(s) for s in self.srcs])
+        self.out_sz = (C.c_uint * n)(*capv)
+        self.status = (C.c_int * n)()
+
+    def results(self):
+        """(every block's bytes, None for a block that failed; the statuses)"""
+        return [self.outs[i][:self.out_sz[i]].tobytes() if self.status[i] == 0 else None for i in range(self.n)], list(self.status)
+
+
 def _host_batch8(blocks, decode, orders=None, caps=None):
     ctx = _thread_ctx()
     L = ctx.L
-    n = len(blocks)
-    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-    capv = list(caps) if decode else [L.rans4x8_hip_compress_bound(len(s)) for s in srcs]
-    outs = [np.empty(max(c, 1), dtype=np.uint8) for c in capv]
-    dummy = np.zeros(1, dtype=np.uint8)
-    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-    out_sz = (C.c_uint * n)(*capv)
-    status = (C.c_int * n)()
+    a = _HostArrays(blocks, caps if decode else lambda i, size: L.rans4x8_hip_compress_bound(size))
     if decode:
-        rc = L.rans4x8_hip_uncompress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, status)
+        rc = L.rans4x8_hip_uncompress_batch(ctx.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, a.status)
     else:
-        ords = (C.c_int * n)(*orders)
-        rc = L.rans4x8_hip_compress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, ords, status)
+        rc = L.rans4x8_hip_compress_batch(ctx.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, _methods(orders), a.status)
     if rc < 0:
         raise RuntimeError("rans4x8 batch call failed: " + ctx.error())
-    return [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)], list(status)
+    return a.results()
 
 
 def compress_batch_4x8(blocks, orders):
@@ -203,28 +215,14 @@ def set_default_option(name, value):
 def _host_batch(blocks, decode, orders=None, caps=None):
     ctx = _thread_ctx()
     L = ctx.L
-    n = len(blocks)
-    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+    a = _HostArrays(blocks, caps if decode else lambda i, size: L.rans_compress_bound_4x16(size, orders[i]))
     if decode:
-        capv = list(caps)
+        rc = L.rans4x16_hip_uncompress_batch(ctx.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, a.status)
     else:
-        capv = [L.rans_compress_bound_4x16(len(s), o) for s, o in zip(srcs, orders)]
-    outs = [np.empty(max(c, 1), dtype=np.uint8) for c in capv]
-    dummy = np.zeros(1, dtype=np.uint8)
-    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-    out_sz = (C.c_uint * n)(*capv)
-    status = (C.c_int * n)()
-    if decode:
-        rc = L.rans4x16_hip_uncompress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, status)
-    else:
-        ords = (C.c_int * n)(*orders)
-        rc = L.rans4x16_hip_compress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, ords, status)
+        rc = L.rans4x16_hip_compress_batch(ctx.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, _methods(orders), a.status)
     if rc < 0:
         raise RuntimeError("batch call failed: " + ctx.error())
-    res = [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)]
-    return res, list(status)
+    return a.results()
 
 
 class MultiCodec:
@@ -254,24 +252,14 @@ class MultiCodec:
 
     def _run(self, blocks, decode, orders=None, caps=None):
         L = self.L
-        n = len(blocks)
-        srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-        capv = list(caps) if decode else [L.rans_compress_bound_4x16(len(s), o) for s, o in zip(srcs, orders)]
-        outs = [np.empty(max(c, 1), dtype=np.uint8) for c in capv]
-        dummy = np.zeros(1, dtype=np.uint8)
-        in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-        out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-        out_sz = (C.c_uint * n)(*capv)
-        status = (C.c_int * n)()
+        a = _HostArrays(blocks, caps if decode else lambda i, size: L.rans_compress_bound_4x16(size, orders[i]))
         if decode:
-            rc = L.rans4x16_hip_uncompress_batch_multi(self.h, n, in_p, in_sz, out_p, out_sz, status)
+            rc = L.rans4x16_hip_uncompress_batch_multi(self.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, a.status)
         else:
-            ords = (C.c_int * n)(*orders)
-            rc = L.rans4x16_hip_compress_batch_multi(self.h, n, in_p, in_sz, out_p, out_sz, ords, status)
+            rc = L.rans4x16_hip_compress_batch_multi(self.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, _methods(orders), a.status)
         if rc < 0:
             raise RuntimeError("multi-device batch failed: " + L.rans4x16_hip_multi_last_error(self.h).decode())
-        return [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)], list(status)
+        return a.results()
 
     def compress_batch(self, blocks, orders):
         return self._run(blocks, False, orders=orders)
@@ -290,23 +278,13 @@ def compress_best_batch(blocks, methods):
     as one call: list of bytes, list of order values -> (list of bytes|None, chosen order per block, statuses)."""
     ctx = _thread_ctx()
     L = ctx.L
-    n, k = len(blocks), len(methods)
-    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-    capv = [max(L.rans_compress_bound_4x16(len(s), m) for m in methods) for s in srcs]
-    outs = [np.empty(max(c, 1), dtype=np.uint8) for c in capv]
-    dummy = np.zeros(1, dtype=np.uint8)
-    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-    out_sz = (C.c_uint * n)(*capv)
-    meth = (C.c_int * k)(*methods)
-    chosen = (C.c_int * n)()
-    status = (C.c_int * n)()
-    rc = L.rans4x16_hip_compress_best_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, k, meth, chosen, status)
+    a = _HostArrays(blocks, lambda i, size: max(L.rans_compress_bound_4x16(size, m) for m in methods))
+    chosen = (C.c_int * a.n)()
+    rc = L.rans4x16_hip_compress_best_batch(ctx.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, len(methods), _methods(methods), chosen, a.status)
     if rc < 0:
         raise RuntimeError("batch call failed: " + ctx.error())
-    res = [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)]
-    return res, list(chosen), list(status)
+    res, status = a.results()
+    return res, list(chosen), status
 
 
 def uncompress_batch(blocks, caps):
@@ -379,6 +357,11 @@ def tok3_level_methods(level):
     return list(m[:k])
 
 
+def _methods(methods):
+    """A list of order values as a C int array: the methods of a best-of-k call, the orders of a host batch."""
+    return (C.c_int * len(methods))(*[int(m) for m in methods])
+
+
 def _free(addr):
     libc = C.CDLL(None)
     libc.free.argtypes = [C.c_void_p]
@@ -415,7 +398,7 @@ def _names_batch(blocks, encode, methods=None, ctx=None, tok3_arith=None):
     a, b = (C.c_uint * n)(), (C.c_uint * n)()
     status = (C.c_int * n)()
     if encode:
-        meth = (C.c_int * len(methods))(*methods)
+        meth = _methods(methods)
         rc = L.rans4x16_hip_tok3_encode_names_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, len(methods), meth, a, b, status)
     else:
         rc = L.rans4x16_hip_tok3_decode_names_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, a, status)
@@ -483,20 +466,11 @@ def arith_uncompress_batch(blocks, caps, ctx=None):
     """rans4x16_hip_arith_uncompress_batch: arith_dynamic streams (bytes) and the capacity of each output ->
     (list of bytes | None, statuses).  One upload, one device call, one download."""
     ctx = ctx or _thread_ctx()
-    L = ctx.L
-    n = len(blocks)
-    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-    outs = [np.empty(max(int(c), 1), dtype=np.uint8) for c in caps]
-    dummy = np.zeros(1, dtype=np.uint8)
-    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-    out_sz = (C.c_uint * n)(*[int(c) for c in caps])
-    status = (C.c_int * n)()
-    rc = L.rans4x16_hip_arith_uncompress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, status)
+    a = _HostArrays(blocks, caps)
+    rc = ctx.L.rans4x16_hip_arith_uncompress_batch(ctx.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, a.status)
     if rc < 0:
         raise RuntimeError("arith batch failed: " + ctx.error())
-    return [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)], list(status)
+    return a.results()
 
 
 def arith_uncompress(comp, out_size=None):
@@ -537,24 +511,17 @@ def fqz_uncompress_batch(blocks, caps=None, nlengths=None, ctx=None):
     n = len(blocks)
     if caps is None:
         caps = [fqz_scan(b)[1]["stored_size"] for b in blocks]
-    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-    outs = [np.empty(max(int(c), 1), dtype=np.uint8) for c in caps]
+    a = _HostArrays(blocks, caps)
     nl = [0] * n if nlengths is None else [int(v) for v in nlengths]
     lens = [np.full(max(v, 1), -1, dtype=np.int32) for v in nl]
-    dummy = np.zeros(1, dtype=np.uint8)
-    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    len_p = (C.c_void_p * n)(*[a.ctypes.data for a in lens])
-    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-    out_sz = (C.c_uint * n)(*[int(c) for c in caps])
+    len_p = (C.c_void_p * n)(*[x.ctypes.data for x in lens])
     nl_a = (C.c_int * n)(*nl)
     nrec = (C.c_uint * n)()
-    status = (C.c_int * n)()
-    rc = L.rans4x16_hip_fqz_uncompress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, status, len_p, nl_a, nrec)
+    rc = L.rans4x16_hip_fqz_uncompress_batch(ctx.h, n, a.in_p, a.in_sz, a.out_p, a.out_sz, a.status, len_p, nl_a, nrec)
     if rc < 0:
         raise RuntimeError("fqz batch failed: " + ctx.error())
-    res = [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)]
-    return res, list(status), [lens[i][:min(nl[i], nrec[i])].tolist() for i in range(n)], list(nrec)
+    res, status = a.results()
+    return res, status, [lens[i][:min(nl[i], nrec[i])].tolist() for i in range(n)], list(nrec)
 
 
 def fqz_decompress(comp, nlengths=0):
@@ -607,31 +574,25 @@ def fqz_compress_batch(blocks, lens, flags, vers=4, strat=0, params=None, caps=N
     ctx = ctx or _thread_ctx()
     L = ctx.L
     n = len(blocks)
-    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
     la = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in lens]
     fa = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in flags]
     pars = [None if params is None or p is None else np.frombuffer(bytes(p), dtype=np.uint8) for p in (params or [None] * n)]
     if caps is None:
-        caps = [L.rans4x16_hip_fqz_compress_cap(len(s), len(l), 4096 if p is None else len(p)) for s, l, p in zip(srcs, la, pars)]
-    outs = [np.empty(max(int(c), 1), dtype=np.uint8) for c in caps]
+        caps = lambda i, size: L.rans4x16_hip_fqz_compress_cap(size, len(la[i]), 4096 if pars[i] is None else len(pars[i]))
+    a = _HostArrays(blocks, caps)
     dummy = np.zeros(4, dtype=np.uint8)
-    ptr = lambda a: a.ctypes.data if len(a) else dummy.ctypes.data
-    in_p = (C.c_void_p * n)(*[ptr(s) for s in srcs])
-    len_p = (C.c_void_p * n)(*[ptr(a) for a in la])
-    fl_p = (C.c_void_p * n)(*[ptr(a) for a in fa])
+    ptr = lambda x: x.ctypes.data if len(x) else dummy.ctypes.data
+    len_p = (C.c_void_p * n)(*[ptr(x) for x in la])
+    fl_p = (C.c_void_p * n)(*[ptr(x) for x in fa])
     par_p = (C.c_void_p * n)(*[None if p is None else ptr(p) for p in pars])
-    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-    nrec = (C.c_uint * n)(*[len(a) for a in la])
+    nrec = (C.c_uint * n)(*[len(x) for x in la])
     par_sz = (C.c_uint * n)(*[0 if p is None else len(p) for p in pars])
-    out_sz = (C.c_uint * n)(*[int(c) for c in caps])
-    status = (C.c_int * n)()
-    rc = L.rans4x16_hip_fqz_compress_batch(ctx.h, n, in_p, in_sz, nrec, len_p, fl_p, int(vers), int(strat),
-                                           None if params is None else par_p, par_sz, out_p, out_sz, status)
+    rc = L.rans4x16_hip_fqz_compress_batch(ctx.h, n, a.in_p, a.in_sz, nrec, len_p, fl_p, int(vers), int(strat),
+                                           None if params is None else par_p, par_sz, a.out_p, a.out_sz, a.status)
     if rc < 0:
         raise RuntimeError("fqz batch failed: " + ctx.error())
-    res = [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)]
-    return res, list(status), [a.tolist() for a in la], [a.tolist() for a in fa]
+    res, status = a.results()
+    return res, status, [x.tolist() for x in la], [x.tolist() for x in fa]
 
 
 class _FqzSlice(C.Structure):
@@ -673,22 +634,13 @@ def arith_compress_batch(blocks, orders, caps=None, ctx=None):
     caps: the capacity of each output (default: arith_compress_cap).  One upload, one device call, one download."""
     ctx = ctx or _thread_ctx()
     L = ctx.L
-    n = len(blocks)
     if caps is None:
         caps = [L.rans4x16_hip_arith_compress_cap(len(b), int(o)) for b, o in zip(blocks, orders)]
-    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-    outs = [np.empty(max(int(c), 1), dtype=np.uint8) for c in caps]
-    dummy = np.zeros(1, dtype=np.uint8)
-    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-    out_sz = (C.c_uint * n)(*[int(c) for c in caps])
-    ords = (C.c_int * n)(*[int(o) for o in orders])
-    status = (C.c_int * n)()
-    rc = L.rans4x16_hip_arith_compress_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, ords, status)
+    a = _HostArrays(blocks, caps)
+    rc = L.rans4x16_hip_arith_compress_batch(ctx.h, a.n, a.in_p, a.in_sz, a.out_p, a.out_sz, _methods(orders), a.status)
     if rc < 0:
         raise RuntimeError("arith batch failed: " + ctx.error())
-    return [outs[i][:out_sz[i]].tobytes() if status[i] == 0 else None for i in range(n)], list(status)
+    return a.results()
 
 
 def arith_compress(data, order, out_size=None):
@@ -758,19 +710,14 @@ class DeviceCodec:
 
     def compress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status, order,
                  max_in_size, d_order=None, total_in_size=0):
-        t = self.torch
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
-        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
         n = in_off.numel()
         rc = self.L.rans4x16_hip_compress_dev_sized(
             self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(),
             status.data_ptr(), int(order), d_order.data_ptr() if d_order is not None else None,
             int(max_in_size), int(total_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("compress_dev: " + self.ctx.error())
+        self._check(rc, "compress_dev")
 
     def set_stripe_encode(self, max_planes):
         """rans4x16_hip_set_dev_stripe_encode: `compress` with d_order encodes X_STRIPE blocks of up to max_planes
@@ -783,66 +730,51 @@ class DeviceCodec:
         """rans4x16_hip_compress_best_dev: every block with each of `methods` (a list of order values), the smallest
         result in its output slot, the winning method in `chosen` (int32 tensor, optional).  Enqueues only."""
         t = self.torch
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
-        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
         assert chosen is None or chosen.dtype == t.int32
         n = in_off.numel()
-        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        meth = _methods(methods)
         rc = self.L.rans4x16_hip_compress_best_dev(
             self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(),
             status.data_ptr(), len(methods), meth, chosen.data_ptr() if chosen is not None else None,
             int(max_in_size), int(total_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("compress_best_dev: " + self.ctx.error())
+        self._check(rc, "compress_best_dev")
 
     def uncompress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status,
                    max_in_size, max_out_cap, total_out_cap=0):
-        t = self.torch
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
         n = in_off.numel()
         rc = self.L.rans4x16_hip_uncompress_dev_sized(
             self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(),
             status.data_ptr(), int(max_in_size), int(max_out_cap), int(total_out_cap), self._stream())
-        if rc != 0:
-            raise RuntimeError("uncompress_dev: " + self.ctx.error())
+        self._check(rc, "uncompress_dev")
 
     # ---- arith_dynamic, both directions (include/rans4x16_hip.h parts 2g, 2h) --------------------------------------------------
     def arith_uncompress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status,
                          max_in_size, max_out_size, total_out_size=0):
         """rans4x16_hip_arith_uncompress_dev: uncompress()'s arguments over arith_dynamic streams.  Enqueues only."""
-        t = self.torch
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
-        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
         rc = self.L.rans4x16_hip_arith_uncompress_dev(
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(),
             status.data_ptr(), int(max_in_size), int(max_out_size), int(total_out_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("arith_uncompress_dev: " + self.ctx.error())
+        self._check(rc, "arith_uncompress_dev")
 
     def arith_compress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status, order,
                        max_in_size, d_order=None, total_in_size=0):
         """rans4x16_hip_arith_compress_dev: compress()'s arguments, arith_dynamic streams out.  Enqueues only.  X_STRIPE
         under d_order needs set_stripe_encode."""
         t = self.torch
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
-        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
         assert d_order is None or d_order.dtype == t.int32
         rc = self.L.rans4x16_hip_arith_compress_dev(
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(),
             status.data_ptr(), int(order), d_order.data_ptr() if d_order is not None else None,
             int(max_in_size), int(total_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("arith_compress_dev: " + self.ctx.error())
+        self._check(rc, "arith_compress_dev")
 
     def arith_peek(self, d_in, in_off, in_size, fmt, raw_size, status, max_in_size):
         """rans4x16_hip_arith_peek_dev: peek()'s arguments and results over arith_dynamic streams."""
@@ -851,8 +783,7 @@ class DeviceCodec:
         assert fmt.dtype == t.int32 and raw_size.dtype == t.int32 and status.dtype == t.int32
         rc = self.L.rans4x16_hip_arith_peek_dev(self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
                                                 fmt.data_ptr(), raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("arith_peek_dev: " + self.ctx.error())
+        self._check(rc, "arith_peek_dev")
 
     # ---- fqzcomp_qual decoding (include/rans4x16_hip.h part 2i) -------------------------------------------------------
     def fqz_uncompress(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status,
@@ -861,10 +792,7 @@ class DeviceCodec:
         ones: record lengths into d_len (int32) at len_off (int64, entries) up to len_cap (int32, entries), record counts
         into nrec (int32).  Enqueues only."""
         t = self.torch
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
-        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
         assert d_len is None or (d_len.dtype == t.int32 and len_off.dtype == t.int64 and len_cap.dtype == t.int32)
         assert nrec is None or nrec.dtype == t.int32
         ptr = lambda x: x.data_ptr() if x is not None else None
@@ -873,8 +801,7 @@ class DeviceCodec:
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             ptr(d_len), ptr(len_off), ptr(len_cap), ptr(nrec),
             int(max_in_size), int(max_out_size), int(total_out_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("fqz_uncompress_dev: " + self.ctx.error())
+        self._check(rc, "fqz_uncompress_dev")
 
     def fqz_peek(self, d_in, in_off, in_size, raw_size, status, max_in_size):
         """rans4x16_hip_fqz_peek_dev: the stored size of every fqzcomp_qual stream."""
@@ -883,8 +810,7 @@ class DeviceCodec:
         assert raw_size.dtype == t.int32 and status.dtype == t.int32
         rc = self.L.rans4x16_hip_fqz_peek_dev(self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
                                               raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("fqz_peek_dev: " + self.ctx.error())
+        self._check(rc, "fqz_peek_dev")
 
     def set_fqz_limits(self, max_slots=0, max_sym=0):
         """rans4x16_hip_set_fqz_limits: the model slots in flight at most (0: 1024) and the largest max_sym a slot holds
@@ -899,19 +825,28 @@ class DeviceCodec:
         int32) and the records (nrec, int32, lengths and flags as int32 entries from rec_off, int64, in d_len / d_flags),
         fqzcomp_qual streams out.  Enqueues only."""
         t = self.torch
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8 and d_params.dtype == t.uint8
-        assert in_off.dtype == t.int64 and out_off.dtype == t.int64 and par_off.dtype == t.int64 and rec_off.dtype == t.int64
-        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32 and par_size.dtype == t.int32 and nrec.dtype == t.int32
-        assert d_len.dtype == t.int32 and d_flags.dtype == t.int32
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
+        assert d_params.dtype == t.uint8 and par_off.dtype == t.int64 and rec_off.dtype == t.int64
+        assert par_size.dtype == t.int32 and nrec.dtype == t.int32 and d_len.dtype == t.int32 and d_flags.dtype == t.int32
         rc = self.L.rans4x16_hip_fqz_compress_dev(
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_params.data_ptr(), par_off.data_ptr(), par_size.data_ptr(),
             d_len.data_ptr(), d_flags.data_ptr(), rec_off.data_ptr(), nrec.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             int(max_in_size), int(max_params_size), int(max_records), self._stream())
+        self._check(rc, "fqz_compress_dev")
+
+    # ---- what the methods share: the dtypes of either form's arrays, and the end of every call ----------------------
+    def _slot_args(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status):
+        t = self.torch
+        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
+        assert in_off.dtype == t.int64 and out_off.dtype == t.int64
+        assert in_size.dtype == t.int32 and out_cap.dtype == t.int32
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+
+    def _check(self, rc, name):
         if rc != 0:
-            raise RuntimeError("fqz_compress_dev: " + self.ctx.error())
+            raise RuntimeError(name + ": " + self.ctx.error())
 
     # ---- packed calls (include/rans4x16_hip.h part 2a): one dense arena, offsets written by the device ----------
     def _packed_args(self, d_in, in_off, in_size, d_out, out_off, out_size, status):
@@ -932,8 +867,7 @@ class DeviceCodec:
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), int(order),
             d_order.data_ptr() if d_order is not None else None, int(max_in_size), int(total_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("compress_packed_dev: " + self.ctx.error())
+        self._check(rc, "compress_packed_dev")
 
     def compress_best_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size,
                              chosen=None, total_in_size=0, out_capacity=None):
@@ -942,13 +876,12 @@ class DeviceCodec:
         assert chosen is None or chosen.dtype == self.torch.int32
         cap = d_out.numel() if out_capacity is None else int(out_capacity)
         assert cap <= d_out.numel()
-        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        meth = _methods(methods)
         rc = self.L.rans4x16_hip_compress_best_packed_dev(
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), len(methods), meth,
             chosen.data_ptr() if chosen is not None else None, int(max_in_size), int(total_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("compress_best_packed_dev: " + self.ctx.error())
+        self._check(rc, "compress_best_packed_dev")
 
     def arith_compress_best_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size,
                                    chosen=None, total_in_size=0, out_capacity=None):
@@ -963,18 +896,17 @@ class DeviceCodec:
         room = d_out.numel() if d_out is not None else 0
         cap = room if out_capacity is None else int(out_capacity)
         assert cap <= room
-        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        meth = _methods(methods)
         rc = self.L.rans4x16_hip_arith_compress_best_packed_dev(
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             len(methods), meth, chosen.data_ptr() if chosen is not None else None, int(max_in_size), int(total_in_size),
             self._stream())
-        if rc != 0:
-            raise RuntimeError("arith_compress_best_packed_dev: " + self.ctx.error())
+        self._check(rc, "arith_compress_best_packed_dev")
 
     def arith_best_chunk_blocks(self, n, methods, max_in_size, total_in_size=0):
         """rans4x16_hip_arith_best_chunk_blocks: the blocks per chunk arith_compress_best_packed plans for these arguments."""
-        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        meth = _methods(methods)
         rc = self.L.rans4x16_hip_arith_best_chunk_blocks(self.ctx.h, int(n), len(methods), meth, int(max_in_size), int(total_in_size))
         if rc < 0:
             raise RuntimeError("arith_best_chunk_blocks: " + self.ctx.error())
@@ -992,8 +924,7 @@ class DeviceCodec:
         assert fmt.dtype == t.int32 and raw_size.dtype == t.int32 and status.dtype == t.int32
         rc = self.L.rans4x16_hip_peek_dev(self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
                                           fmt.data_ptr(), raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("peek_dev: " + self.ctx.error())
+        self._check(rc, "peek_dev")
 
     def uncompress_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, max_in_size, max_out_size,
                           nosz_size=None, out_capacity=None):
@@ -1013,8 +944,7 @@ class DeviceCodec:
             self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             nosz_size.data_ptr() if nosz_size is not None else None, int(max_in_size), int(max_out_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("uncompress_packed_dev: " + self.ctx.error())
+        self._check(rc, "uncompress_packed_dev")
 
     # ---- tok3 column containers (include/rans4x16_hip.h part 2c) -------------------------------------------------
     def tok3_pack(self, blk_first, d_in, col_off, col_size, col_id, last_start, nreads, d_out, out_off, out_size, status,
@@ -1033,14 +963,13 @@ class DeviceCodec:
         assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
         cap = (d_out.numel() if d_out is not None else 0) if out_capacity is None else int(out_capacity)
         assert cap <= (d_out.numel() if d_out is not None else 0)
-        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        meth = _methods(methods)
         rc = self.L.rans4x16_hip_tok3_pack_dev(
             self.ctx.h, nblk, n, blk_first.data_ptr(), d_in.data_ptr(), col_off.data_ptr(), col_size.data_ptr(),
             col_id.data_ptr(), last_start.data_ptr(), nreads.data_ptr(), d_out.data_ptr() if d_out is not None else None, cap,
             out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), len(methods), meth,
             chosen.data_ptr() if chosen is not None else None, int(max_col_size), int(total_col_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("tok3_pack_dev: " + self.ctx.error())
+        self._check(rc, "tok3_pack_dev")
 
     def tok3_unpack(self, d_in, in_off, in_size, d_out, out_off, out_size, status, ncol, last_start, nreads,
                     col_id, col_off, col_size, max_columns, max_in_size, max_col_size, out_capacity=None):
@@ -1064,8 +993,7 @@ class DeviceCodec:
             d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             ncol.data_ptr(), last_start.data_ptr(), nreads.data_ptr(), col_id.data_ptr(), col_off.data_ptr(), col_size.data_ptr(),
             int(max_columns), int(max_in_size), int(max_col_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("tok3_unpack_dev: " + self.ctx.error())
+        self._check(rc, "tok3_unpack_dev")
 
     # ---- tok3 name decoding (include/rans4x16_hip.h part 2d) ---------------------------------------------------------
     def _names_out(self, nblk, d_out, out_off, out_size, nnames, status, name_start, max_names, out_capacity):
@@ -1101,8 +1029,7 @@ class DeviceCodec:
             d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), nnames.data_ptr(),
             status.data_ptr(), name_start.data_ptr() if name_start is not None else None,
             int(max_columns), int(max_names), int(max_tokens), self._stream())
-        if rc != 0:
-            raise RuntimeError("tok3_names_dev: " + self.ctx.error())
+        self._check(rc, "tok3_names_dev")
 
     def tok3_decode_names(self, d_in, in_off, in_size, d_out, out_off, out_size, nnames, status, max_columns, max_in_size,
                           max_col_size, max_names, max_tokens=128, total_col_size=0, name_start=None, out_capacity=None):
@@ -1119,8 +1046,7 @@ class DeviceCodec:
             status.data_ptr(), name_start.data_ptr() if name_start is not None else None,
             int(max_columns), int(max_in_size), int(max_col_size), int(max_names), int(max_tokens), int(total_col_size),
             self._stream())
-        if rc != 0:
-            raise RuntimeError("tok3_decode_names_dev: " + self.ctx.error())
+        self._check(rc, "tok3_decode_names_dev")
 
     # ---- tok3 name encoding (include/rans4x16_hip.h part 2e) ---------------------------------------------------------
     def tok3_tokenise(self, d_in, in_off, in_size, d_cols, cols_off, cols_size, status, blk_first, col_id, col_off, col_size,
@@ -1149,8 +1075,7 @@ class DeviceCodec:
             blk_first.data_ptr(), col_id.data_ptr(), col_off.data_ptr(), col_size.data_ptr(), last_start.data_ptr(),
             nreads.data_ptr(), int(max_in_size), int(max_names), int(max_name_len), int(max_tokens), int(max_columns),
             int(total_in_size), int(search_slots), self._stream())
-        if rc != 0:
-            raise RuntimeError("tok3_tokenise_dev: " + self.ctx.error())
+        self._check(rc, "tok3_tokenise_dev")
 
     def tok3_encode_names(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size, max_names,
                           max_name_len, max_columns, max_tokens=128, max_col_size=0, total_in_size=0, search_slots=0,
@@ -1169,15 +1094,14 @@ class DeviceCodec:
         assert blk_first is None or (blk_first.dtype == t.int32 and blk_first.numel() == nblk + 1)
         cap = (d_out.numel() if d_out is not None else 0) if out_capacity is None else int(out_capacity)
         assert cap <= (d_out.numel() if d_out is not None else 0)
-        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        meth = _methods(methods)
         rc = self.L.rans4x16_hip_tok3_encode_names_dev(
             self.ctx.h, nblk, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             len(methods), meth, chosen.data_ptr() if chosen is not None else None,
             blk_first.data_ptr() if blk_first is not None else None, int(max_in_size), int(max_names), int(max_name_len),
             int(max_tokens), int(max_columns), int(max_col_size), int(total_in_size), int(search_slots), self._stream())
-        if rc != 0:
-            raise RuntimeError("tok3_encode_names_dev: " + self.ctx.error())
+        self._check(rc, "tok3_encode_names_dev")
 
     # ---- rANS 4x8 (CRAM 3.0), include/rans4x8_hip.h part 2a: the same surface, every result assembled in place -------
     def compress_packed_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, order, max_in_size,
@@ -1191,8 +1115,7 @@ class DeviceCodec:
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), int(order),
             d_order.data_ptr() if d_order is not None else None, int(max_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("rans4x8 compress_packed_dev: " + self.ctx.error())
+        self._check(rc, "rans4x8 compress_packed_dev")
 
     def compress_best_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size,
                           chosen=None, packed=False, out_cap=None, out_capacity=None):
@@ -1202,7 +1125,7 @@ class DeviceCodec:
         packed=True: rans4x8_hip_compress_best_packed_dev, the winners back to back (out_off: n + 1 entries, written)."""
         t = self.torch
         assert chosen is None or chosen.dtype == t.int32
-        meth = (C.c_int * len(methods))(*[int(m) for m in methods])
+        meth = _methods(methods)
         ch = chosen.data_ptr() if chosen is not None else None
         if packed:
             self._packed_args(d_in, in_off, in_size, d_out, out_off, out_size, status)
@@ -1213,16 +1136,13 @@ class DeviceCodec:
                 d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), len(methods), meth, ch,
                 int(max_in_size), self._stream())
         else:
-            assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-            assert in_off.dtype == t.int64 and out_off.dtype == t.int64 and out_off.numel() == in_off.numel()
-            assert in_size.dtype == t.int32 and out_cap is not None and out_cap.dtype == t.int32
-            assert out_size.dtype == t.int32 and status.dtype == t.int32
+            assert out_cap is not None and out_off.numel() == in_off.numel()
+            self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
             rc = self.L.rans4x8_hip_compress_best_dev(
                 self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
                 d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
                 len(methods), meth, ch, int(max_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("rans4x8 compress_best%s_dev: " % ("_packed" if packed else "") + self.ctx.error())
+        self._check(rc, "rans4x8 compress_best%s_dev" % ("_packed" if packed else ""))
 
     def peek_4x8(self, d_in, in_off, in_size, fmt, raw_size, status, max_in_size):
         """rans4x8_hip_peek_dev: byte 0 (fmt, int32; -1 = none) and bytes 5..8 (raw_size, int32 holding the unsigned value;
@@ -1232,8 +1152,7 @@ class DeviceCodec:
         assert fmt.dtype == t.int32 and raw_size.dtype == t.int32 and status.dtype == t.int32
         rc = self.L.rans4x8_hip_peek_dev(self.ctx.h, in_size.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
                                          fmt.data_ptr(), raw_size.data_ptr(), status.data_ptr(), int(max_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("rans4x8 peek_dev: " + self.ctx.error())
+        self._check(rc, "rans4x8 peek_dev")
 
     def uncompress_packed_4x8(self, d_in, in_off, in_size, d_out, out_off, out_size, status, max_in_size, max_out_size,
                               out_capacity=None):
@@ -1252,35 +1171,27 @@ class DeviceCodec:
             self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             int(max_in_size), int(max_out_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("rans4x8 uncompress_packed_dev: " + self.ctx.error())
+        self._check(rc, "rans4x8 uncompress_packed_dev")
 
     def compress_4x8(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status, order, max_in_size, d_order=None):
         """rans4x8_hip_compress_dev: the slot call (out_off: n entries, read; out_cap: int32, what each slot holds)."""
         t = self.torch
         n = in_off.numel()
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-        assert in_off.dtype == t.int64 and out_off.dtype == t.int64 and out_off.numel() == n
-        assert in_size.dtype == t.int32 and in_size.numel() == n and out_cap.dtype == t.int32 and out_cap.numel() == n
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
+        assert out_off.numel() == n and in_size.numel() == n and out_cap.numel() == n
         assert d_order is None or (d_order.dtype == t.int32 and d_order.numel() == n)
         rc = self.L.rans4x8_hip_compress_dev(
             self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(), int(order),
             d_order.data_ptr() if d_order is not None else None, int(max_in_size), self._stream())
-        if rc != 0:
-            raise RuntimeError("rans4x8 compress_dev: " + self.ctx.error())
+        self._check(rc, "rans4x8 compress_dev")
 
     def uncompress_4x8(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status):
         """rans4x8_hip_uncompress_dev: the slot call (in_off may have more than n entries; the block count is in_size's)."""
-        t = self.torch
         n = in_size.numel()
-        assert d_in.dtype == t.uint8 and d_out.dtype == t.uint8
-        assert in_off.dtype == t.int64 and in_off.numel() >= n and in_size.dtype == t.int32
-        assert out_off.dtype == t.int64 and out_off.numel() == n and out_cap.dtype == t.int32 and out_cap.numel() == n
-        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
+        assert in_off.numel() >= n and out_off.numel() == n and out_cap.numel() == n
         rc = self.L.rans4x8_hip_uncompress_dev(
             self.ctx.h, in_size.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError("rans4x8 uncompress_dev: " + self.ctx.error())
+        self._check(rc, "rans4x8 uncompress_dev")

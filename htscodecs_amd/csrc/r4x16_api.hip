@@ -476,34 +476,16 @@ extern "C" int rans4x16_hip_compress_dev_sized(rans4x16_hip_ctx *c, int n,
                                                int32_t *d_status, int order, const int32_t *d_order,
                                                uint32_t max_in_size, uint64_t total_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "compress_dev: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
+    BatchArgs a;
+    const int go = r4x16_dev_call_args(c, "compress_dev: bad arguments", true, &a, n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_out_cap,
+                                       d_out_size, d_status, order, d_order);
+    if (go <= 0) return go;
     hipStream_t s = (hipStream_t)stream;
     if (c->opts.v[OPT_ROUTE_COUNT] && !c->in_stripe && !c->in_packed) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_IN_SLOT] += n;
-    if (!d_order && (order & X_STRIPE)) {                 // one order for all blocks: N and the candidate methods are host knowledge
-        BatchArgs sa;
-        sa.in = d_in; sa.in_off = d_in_off; sa.in_size = d_in_size;
-        sa.out = d_out; sa.out_off = d_out_off; sa.out_cap = d_out_cap; sa.out_size = d_out_size;
-        sa.status = d_status; sa.d_order = nullptr; sa.order = order; sa.n = n;
-        return r4x16_stripe_compress_dev(c, n, sa, order, max_in_size, s);
-    }
-    if (d_order && c->dev_stripe_enc > 0 && !c->in_stripe) {   // per-block orders that may ask for X_STRIPE: N and the methods are read on the device
-        BatchArgs sa;
-        sa.in = d_in; sa.in_off = d_in_off; sa.in_size = d_in_size;
-        sa.out = d_out; sa.out_off = d_out_off; sa.out_cap = d_out_cap; sa.out_size = d_out_size;
-        sa.status = d_status; sa.d_order = d_order; sa.order = order; sa.n = n;
-        return r4x16_orders_stripe_compress_dev(c, n, sa, max_in_size, total_in_size, s);
-    }
-
-    BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
+    // one order for all blocks: N and the candidate methods are host knowledge
+    if (!d_order && (order & X_STRIPE)) return r4x16_stripe_compress_dev(c, n, a, order, max_in_size, s);
+    // per-block orders that may ask for X_STRIPE: N and the methods are read on the device
+    if (d_order && c->dev_stripe_enc > 0 && !c->in_stripe) return r4x16_orders_stripe_compress_dev(c, n, a, max_in_size, total_in_size, s);
     return r4x16_enc_run(c, a, max_in_size, total_in_size, s, nullptr);
 }
 
@@ -529,24 +511,23 @@ int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64
     PackedSlots p = {};
     const u64 slot_stride = pk ? r4x16_packed_stride(max_in_size, order, d_order != nullptr) : 0;
     auto slots_for = [&](size_t nb) -> size_t { return pk ? r4x16_packed_carve(&p, nullptr, (size_t)n, nb, slot_stride) : 0; };
-    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS) | (pk ? A_BIT(A_PS) : 0)),
-                                   [&](size_t nb) { return enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w) + 4096 + slots_for(nb); });
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) {
-            return r4x16_ensure(c, A_WS, enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w), false) == 0 &&
-                   (!pk || r4x16_ensure(c, A_PS, slots_for(nb), false) == 0) ? 0 : -1;
-        }) != 0) return -1;
-    enc_ws_layout(c->at(A_WS), chunk, scratch_stride, var_for(chunk), &w);
-    w.logtab = c->logtab;
-    w.rcptab = c->rcptab;
-    if (pk) {
-        r4x16_packed_carve(&p, c->at(A_PS), (size_t)n, chunk, slot_stride);
-        r4x16_launch_packed_slots(&a, &p, n, chunk, max_in_size, s);
-        a.out = p.slots; a.out_off = p.slot_off; a.out_cap = p.slot_cap;
-    }
-
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
+    const size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS) | (pk ? A_BIT(A_PS) : 0)),
+                                         [&](size_t nb) { return enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w) + 4096 + slots_for(nb); });
+    auto grab = [&](size_t nb) {
+        return r4x16_ensure(c, A_WS, enc_ws_layout(nullptr, nb, scratch_stride, var_for(nb), &w), false) == 0 &&
+               (!pk || r4x16_ensure(c, A_PS, slots_for(nb), false) == 0) ? 0 : -1;
+    };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
+        if (base == 0) {                               // the layout of the call: nb is the chunk size here
+            enc_ws_layout(c->at(A_WS), (size_t)nb, scratch_stride, var_for((size_t)nb), &w);
+            w.logtab = c->logtab;
+            w.rcptab = c->rcptab;
+            if (pk) {
+                r4x16_packed_carve(&p, c->at(A_PS), (size_t)n, (size_t)nb, slot_stride);
+                r4x16_launch_packed_slots(&a, &p, n, (size_t)nb, max_in_size, s);
+                a.out = p.slots; a.out_off = p.slot_off; a.out_cap = p.slot_cap;
+            }
+        }
         w.direct_budget = r4x16_enc_direct_budget(nb, &c->opts);       // few streams: LDS to spare, symbol records (r4x16_common.h)
         // (made at first use: not inside the timed region.  One small block is one payload class and a call of 0.4 ms: it
         //  stays on the caller's stream; one large block with X_RLE is two long streams - literals, run lengths - of
@@ -566,9 +547,8 @@ int r4x16_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, uint64
         }
         if (pk) r4x16_launch_enc_finish_dense(&a, &w, (int)base, nb, pk, s);
         else r4x16_launch_enc_finish(&a, &w, (int)base, nb, s);
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return 0;
+    });
 }
 
 // var_bytes: the staging regions of the blocks that carry X_PACK / X_RLE, together (0: the batch has none)
@@ -611,21 +591,12 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
                                                  int32_t *d_status, uint32_t max_in_size, uint32_t max_out_cap,
                                                  uint64_t total_out_cap, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "uncompress_dev: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
+    BatchArgs a;
+    const int go = r4x16_dev_call_args(c, "uncompress_dev: bad arguments", true, &a, n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_out_cap,
+                                       d_out_size, d_status, 0, nullptr);
+    if (go <= 0) return go;
     hipStream_t s = (hipStream_t)stream;
-    if (c->dev_stripe_planes > 0 && !c->in_stripe) {
-        BatchArgs sa;
-        sa.in = d_in; sa.in_off = d_in_off; sa.in_size = d_in_size;
-        sa.out = d_out; sa.out_off = d_out_off; sa.out_cap = d_out_cap; sa.out_size = d_out_size;
-        sa.status = d_status; sa.d_order = nullptr; sa.order = 0; sa.n = n;
-        return r4x16_stripe_uncompress_dev(c, n, sa, max_in_size, max_out_cap, c->dev_stripe_out, s);
-    }
+    if (c->dev_stripe_planes > 0 && !c->in_stripe) return r4x16_stripe_uncompress_dev(c, n, a, max_in_size, max_out_cap, c->dev_stripe_out, s);
 
     // PACK / RLE staging, only for the blocks whose flag byte asks for it: a buffer of the block's output size and room
     // for the decoded run-length meta (rANS_static4x16pr.c:1273: at most in_size + 257 bytes), laid out on the device
@@ -634,20 +605,11 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
     const u64 total_out = total_out_cap ? total_out_cap : (u64)n * max_out_cap;
     auto var_for = [&](size_t nb) -> u64 { return max_out_cap ? dec_var_bound(nb, std::min<u64>(total_out, (u64)nb * max_out_cap)) : 0; };
     DecWs w;
-    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS)),
-                                   [&](size_t nb) { return dec_ws_layout(nullptr, nb, var_for(nb), max_out_cap, &w) + 4096; });
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_WS, dec_ws_layout(nullptr, nb, var_for(nb), max_out_cap, &w), false); }) != 0)
-        return -1;
-    dec_ws_layout(c->at(A_WS), chunk, var_for(chunk), max_out_cap, &w);
-
-    BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
-
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
+    const size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS)),
+                                         [&](size_t nb) { return dec_ws_layout(nullptr, nb, var_for(nb), max_out_cap, &w) + 4096; });
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_WS, dec_ws_layout(nullptr, nb, var_for(nb), max_out_cap, &w), false); };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
+        if (base == 0) dec_ws_layout(c->at(A_WS), (size_t)nb, var_for((size_t)nb), max_out_cap, &w);      // the layout of the call: nb is the chunk size here
         w.direct_budget = r4x16_dec_direct_budget(nb, &c->opts);       // few streams: LDS to spare, the short-step rows (r4x16_common.h)
         w.mid_budget = r4x16_dec_mid_budget(nb, &c->opts);             // one partly filled round: the mid rows
         r4x16_launch_dec_front(&a, &w, (int)base, nb, s, &c->opts);
@@ -662,9 +624,8 @@ extern "C" int rans4x16_hip_uncompress_dev_sized(rans4x16_hip_ctx *c, int n,
         }
         const int wg = r4x16_launch_dec_back(&a, &w, (int)base, nb, s, &c->opts);
         if (c->opts.v[OPT_ROUTE_COUNT]) c->route[2][wg ? R4X16_EXPAND_WORKGROUP : R4X16_EXPAND_WAVE] += nb;
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return 0;
+    });
 }
 
 extern "C" int rans4x16_hip_residency(rans4x16_hip_ctx *c, int decode, unsigned int nsym, int order, unsigned int shift,
@@ -968,17 +929,10 @@ extern "C" int rans4x8_hip_compress_dev(rans4x16_hip_ctx *c, int n,
                                         uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
                                         uint32_t max_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "rans4x8 compress_dev: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
     BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
+    const int go = r4x16_dev_call_args(c, "rans4x8 compress_dev: bad arguments", true, &a, n, d_in, d_in_off, d_in_size, d_out, d_out_off,
+                                       d_out_cap, d_out_size, d_status, order, d_order);
+    if (go <= 0) return go;
     return r4x8_enc_run(c, a, max_in_size, (hipStream_t)stream, nullptr, nullptr);
 }
 
@@ -1007,20 +961,20 @@ int r4x8_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, hipStre
     Enc8Items it = {};
     auto items_for = [&](size_t nb) -> size_t { return slot_call ? 0 : enc8_items_carve(&it, nullptr, k * nb, nb); };
     // (INT_MAX / k: item indices j * nb + b < k * nb and the item count stay inside an int)
-    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / k, r4x16_room(c, A_BIT(A_WS) | (slot_call ? 0 : A_BIT(A_PS))),
-                                   [&](size_t nb) { return enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w) + 4096 + items_for(nb); });
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) {
-            return r4x16_ensure(c, A_WS, enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w), false) == 0 &&
-                   (slot_call || r4x16_ensure(c, A_PS, items_for(nb), false) == 0) ? 0 : -1;
-        }) != 0) return -1;
-    enc_ws_layout(c->at(A_WS), k * chunk, scratch_stride, 0, &w);
-    w.logtab = c->logtab;
-    w.rcptab = c->rcptab;
-    if (!slot_call) enc8_items_carve(&it, c->at(A_PS), k * chunk, chunk);
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
-        if (slot_call) { r4x8_launch_encode(&a, &w, (int)base, nb, s); continue; }
+    const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / k, r4x16_room(c, A_BIT(A_WS) | (slot_call ? 0 : A_BIT(A_PS))),
+                                         [&](size_t nb) { return enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w) + 4096 + items_for(nb); });
+    auto grab = [&](size_t nb) {
+        return r4x16_ensure(c, A_WS, enc_ws_layout(nullptr, k * nb, scratch_stride, 0, &w), false) == 0 &&
+               (slot_call || r4x16_ensure(c, A_PS, items_for(nb), false) == 0) ? 0 : -1;
+    };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
+        if (base == 0) {                               // the layout of the call: nb is the chunk size here
+            enc_ws_layout(c->at(A_WS), k * (size_t)nb, scratch_stride, 0, &w);
+            w.logtab = c->logtab;
+            w.rcptab = c->rcptab;
+            if (!slot_call) enc8_items_carve(&it, c->at(A_PS), k * (size_t)nb, (size_t)nb);
+        }
+        if (slot_call) { r4x8_launch_encode(&a, &w, (int)base, nb, s); return 0; }
         r4x8_launch_enc_items(&a, (int)base, nb, sel ? sel->k : 0, sel ? sel->m : nullptr, max_in_size, &it, s);
         BatchArgs ia = a;                              // the items: the same input bytes, their own offsets, sizes, orders and slots
         ia.in_off = it.in_off; ia.in_size = it.in_size; ia.out_cap = it.cap; ia.d_order = it.order; ia.n = (int)k * nb;
@@ -1028,9 +982,8 @@ int r4x8_enc_run(rans4x16_hip_ctx *c, BatchArgs a, uint32_t max_in_size, hipStre
         const Pick8Out po = {pk ? *pk : PackedOut{nullptr, nullptr, 0}, it.pick, sel ? sel->d_chosen : nullptr};
         r4x8_launch_enc_finish_pick(&a, &w, (int)base, nb, (int)k, &po, s);
         if (c->opts.v[OPT_ROUTE_COUNT]) c->route[R4X16_ROUTE_RESULT][pk ? R4X16_RESULT_DENSE : R4X16_RESULT_IN_SLOT] += nb;
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return 0;
+    });
 }
 
 extern "C" int rans4x8_hip_uncompress_dev(rans4x16_hip_ctx *c, int n,
@@ -1038,27 +991,17 @@ extern "C" int rans4x8_hip_uncompress_dev(rans4x16_hip_ctx *c, int n,
                                           unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                           uint32_t *d_out_size, int32_t *d_status, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "rans4x8 uncompress_dev: bad arguments";
-        return -1;
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS)), [&](size_t nb) { return r4x8_dec_ws_bytes(nb) + 4096; });
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_WS, r4x8_dec_ws_bytes(nb), false); }) != 0) return -1;
     BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const int nb = (int)((size_t)n - base < chunk ? (size_t)n - base : chunk);
-        r4x8_launch_decode(&a, c->at(A_WS), (int)base, nb, s);
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+    const int go = r4x16_dev_call_args(c, "rans4x8 uncompress_dev: bad arguments", true, &a, n, d_in, d_in_off, d_in_size, d_out, d_out_off,
+                                       d_out_cap, d_out_size, d_status, 0, nullptr);
+    if (go <= 0) return go;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, r4x16_room(c, A_BIT(A_WS)), [&](size_t nb) { return r4x8_dec_ws_bytes(nb) + 4096; });
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_WS, r4x8_dec_ws_bytes(nb), false); };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
+        r4x8_launch_decode(&a, c->at(A_WS), (int)base, nb, s);       // (the launcher lays the workspace out, per chunk)
+        return 0;
+    });
 }
 
 // host buffers: the argument check of the 4x8 calls, then one staging pass on the context's stream (r4x16_run_slab) -

@@ -506,7 +506,8 @@ extern "C" int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *c, int n,
     auto layout = [&](u8 *at, size_t nb) { return are_layout(at, nb, per, are_stage_bytes(nb, per, planes, total, max_in_size), &w); };
     auto bytes_for = [&](size_t nb) { return layout(nullptr, nb); };
     const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / per, r4x16_room(c, A_BIT(A_AR)), bytes_for);
-    return r4x16_chunk_walk(c, n, A_AR, chunk, s, bytes_for, [&](size_t base, int nb) {
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_AR, bytes_for(nb), false); };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
         layout(c->at(A_AR), (size_t)nb);
         w.planes = planes;
         const int nitems = nb * (int)per;
@@ -622,7 +623,8 @@ static u64 ab_slot_bytes(const AbPlan &p, size_t nb, u32 max_in)
 }
 static u64 ab_inner_total(const AbPlan &p, size_t nb, u32 max_in) { return (u64)p.pm.k * std::min<u64>(p.total, (u64)nb * max_in); }
 
-static int ab_plan(rans4x16_hip_ctx *c, int n, int k, const int *methods, uint32_t max_in_size, uint64_t total_in_size, AbPlan *p)
+// the methods alone: what a call refuses before it asks for the device
+static int ab_methods(rans4x16_hip_ctx *c, int k, const int *methods, AbPlan *p)
 {
     p->pm = AbMethods{};
     p->pm.k = k;
@@ -633,11 +635,16 @@ static int ab_plan(rans4x16_hip_ctx *c, int n, int k, const int *methods, uint32
         p->planes = std::max(p->planes, N);
         p->pm.m[j] = methods[j];
     }
-    HIPCHK(c, hipSetDevice(c->device));
+    return 0;
+}
+
+// the rest, on the context's device
+static void ab_fit(rans4x16_hip_ctx *c, int n, int k, uint32_t max_in_size, uint64_t total_in_size, AbPlan *p)
+{
     p->per = p->planes ? (size_t)p->planes * ARE_CANDS : 1;
     p->total = total_in_size ? total_in_size : (u64)n * max_in_size;
     p->chunk = 0;
-    if (n == 0) return 0;
+    if (n == 0) return;
     AbWs w;
     AreWs iw;
     auto bytes = [&](size_t nb) {
@@ -645,7 +652,6 @@ static int ab_plan(rans4x16_hip_ctx *c, int n, int k, const int *methods, uint32
                are_layout(nullptr, nb * k, p->per, are_stage_bytes(nb * k, p->per, p->planes, ab_inner_total(*p, nb, max_in_size), max_in_size), &iw);
     };
     p->chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / (p->per * k), r4x16_room(c, A_BIT(A_PS) | A_BIT(A_AR)), bytes);
-    return 0;
 }
 
 extern "C" int rans4x16_hip_arith_best_chunk_blocks(rans4x16_hip_ctx *c, int n, int k, const int *methods, uint32_t max_in_size,
@@ -654,7 +660,9 @@ extern "C" int rans4x16_hip_arith_best_chunk_blocks(rans4x16_hip_ctx *c, int n, 
     if (!c) return -1;
     if (n < 0 || k < 1 || k > AB_MAX_K || !methods) { c->err = "arith_best_chunk_blocks: bad arguments"; return -1; }
     AbPlan p;
-    if (ab_plan(c, n, k, methods, max_in_size, total_in_size, &p) != 0) return -1;
+    if (ab_methods(c, k, methods, &p) != 0) return -1;
+    HIPCHK(c, hipSetDevice(c->device));
+    ab_fit(c, n, k, max_in_size, total_in_size, &p);
     return (int)p.chunk;
 }
 
@@ -665,23 +673,21 @@ extern "C" int rans4x16_hip_arith_compress_best_packed_dev(rans4x16_hip_ctx *c, 
                                                            int k, const int *methods, int32_t *d_chosen,
                                                            uint32_t max_in_size, uint64_t total_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || k < 1 || k > AB_MAX_K || !methods || !d_out_off ||
-        (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
-        c->err = "arith_compress_best_packed_dev: bad arguments";
-        return -1;
-    }
+    hipStream_t s = (hipStream_t)stream;
     AbPlan p;
-    if (ab_plan(c, n, k, methods, max_in_size, total_in_size, &p) != 0) return -1;
+    BatchArgs a;                                   // (filled, not read: the items of the inner call are this call's own)
+    PackedOut pk;
+    const int go = r4x16_packed_call_args(c, "arith_compress_best_packed_dev: bad arguments", k >= 1 && k <= AB_MAX_K && methods, &a, &pk, n,
+                                          d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, 0, nullptr, s,
+                                          [&] { return ab_methods(c, k, methods, &p); });
+    if (go <= 0) return go;
+    ab_fit(c, n, k, max_in_size, total_in_size, &p);
     const AbMethods &pm = p.pm;
     const u32 planes = p.planes;
-    hipStream_t s = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
     AbWs w;
     auto slot_bytes = [&](size_t nb) { return ab_slot_bytes(p, nb, max_in_size); };
-    auto mine = [&](size_t nb) { return ab_carve(&w, nullptr, nb, (size_t)k, slot_bytes(nb)); };
-    const PackedOut pk = {d_out, d_out_off, out_capacity};
-    return r4x16_chunk_walk(c, n, A_PS, p.chunk, s, mine, [&](size_t base, int nb) {
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_PS, ab_carve(&w, nullptr, nb, (size_t)k, slot_bytes(nb)), false); };
+    return r4x16_chunk_walk(c, n, p.chunk, s, grab, [&](size_t base, int nb) {
         const u32 items = (u32)nb * (u32)k;
         const size_t arena = ab_carve(&w, c->at(A_PS), (size_t)nb, (size_t)k, slot_bytes((size_t)nb));
         const dim3 per_item((items + 255) / 256);

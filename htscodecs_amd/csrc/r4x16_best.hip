@@ -304,24 +304,22 @@ static int best_run(rans4x16_hip_ctx *c, int n, const BatchArgs &a, BestArgs *e,
     BestWs w;
     auto bytes = [&](size_t nb) { return best_carve(&w, nullptr, nb, *e) + r4x16_enc_ws_bytes(nb * P, max_in_size, inner_total(nb)); };
     // (INT_MAX / P: the inner call counts its items in an int)
-    size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / P, r4x16_room(c, A_BIT(A_WS) | A_BIT(A_XS)), bytes);
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / P, r4x16_room(c, A_BIT(A_WS) | A_BIT(A_XS)), bytes);
     // (no refusal above half of the free memory here, unlike r4x16_stripe.hip on the same arena: the chunk was planned
     //  under r4x16_room a moment ago, and a chunk that does not fit after all is halved, not refused)
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_XS, best_carve(&w, nullptr, nb, *e), false); }) != 0) return -1;
-    best_carve(&w, c->at(A_XS), chunk, *e);
-    for (size_t base = 0; base < (size_t)n; base += chunk) {
-        const size_t nb = std::min(chunk, (size_t)n - base);
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_XS, best_carve(&w, nullptr, nb, *e), false); };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
+        if (base == 0) best_carve(&w, c->at(A_XS), (size_t)nb, *e);                   // the layout of the call: nb is the chunk size here
         hipLaunchKernelGGL(k_best_prepare, dim3((u32)nb), dim3(256), 0, s, a, w, *e, (int)base);
-        c->in_stripe = true;
-        const int rc = rans4x16_hip_compress_dev_sized(c, (int)(nb * P), w.planes, w.in_off, w.in_size, w.out, w.out_off, w.out_cap,
-                                                       w.out_size, w.status, 0, w.order, max_in_size, inner_total(nb), s);
-        c->in_stripe = false;
-        if (rc != 0) return -1;
+        {
+            Keep<bool> inner(c->in_stripe, true);
+            if (rans4x16_hip_compress_dev_sized(c, nb * (int)P, w.planes, w.in_off, w.in_size, w.out, w.out_off, w.out_cap, w.out_size,
+                                                w.status, 0, w.order, max_in_size, inner_total((size_t)nb), s) != 0)
+                return -1;
+        }
         hipLaunchKernelGGL(k_best_pick, dim3((u32)nb), dim3(256), 0, s, a, w, *e, d_chosen, (int)base);
-    }
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return 0;
+    });
 }
 
 int r4x16_orders_stripe_compress_dev(rans4x16_hip_ctx *c, int n, const BatchArgs &a, uint32_t max_in_size, uint64_t total_in_size,
@@ -340,24 +338,19 @@ extern "C" int rans4x16_hip_compress_best_dev(rans4x16_hip_ctx *c, int n,
                                               int k, const int *methods, int32_t *d_chosen,
                                               uint32_t max_in_size, uint64_t total_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || k < 1 || k > BEST_MAX_K || !methods ||
-        (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "compress_best_dev: bad arguments";
-        return -1;
-    }
     BestArgs e = {};
     e.k = k; e.by_order = 0; e.max_planes = 255;
-    for (int j = 0; j < k; j++) {
-        if ((methods[j] & X_STRIPE) && ((unsigned)methods[j] >> 8) > 255) { c->err = "compress_best_dev: more than 255 stripes"; return -1; }   // :1158
-        e.m[j].method = methods[j];
-    }
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->opts.v[OPT_ROUTE_COUNT] && !c->in_packed) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_IN_SLOT] += n;
+    auto table = [&] {
+        for (int j = 0; j < k; j++) {
+            if ((methods[j] & X_STRIPE) && ((unsigned)methods[j] >> 8) > 255) { c->err = "compress_best_dev: more than 255 stripes"; return -1; }   // :1158
+            e.m[j].method = methods[j];
+        }
+        return 0;
+    };
     BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
+    const int go = r4x16_dev_call_args(c, "compress_best_dev: bad arguments", k >= 1 && k <= BEST_MAX_K && methods, &a, n, d_in, d_in_off,
+                                       d_in_size, d_out, d_out_off, d_out_cap, d_out_size, d_status, 0, nullptr, table);
+    if (go <= 0) return go;
+    if (c->opts.v[OPT_ROUTE_COUNT] && !c->in_packed) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_IN_SLOT] += n;
     return best_run(c, n, a, &e, d_chosen, 0, max_in_size, total_in_size, (hipStream_t)stream);
 }

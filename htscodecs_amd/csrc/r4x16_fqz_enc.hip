@@ -407,7 +407,8 @@ extern "C" int rans4x16_hip_fqz_compress_dev(rans4x16_hip_ctx *c, int n,
     };
     auto bytes_for = [&](size_t nb) { return layout(nullptr, nb); };
     const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX, r4x16_room(c, A_BIT(A_AR)), bytes_for);
-    return r4x16_chunk_walk(c, n, A_AR, chunk, s, bytes_for, [&](size_t base, int nb) {
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_AR, bytes_for(nb), false); };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
         layout(c->at(A_AR), (size_t)nb);
         w.max_sym = (u32)c->fqz_max_sym;
         u32 *const d_route = w.route;

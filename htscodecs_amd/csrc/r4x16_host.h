@@ -151,17 +151,26 @@ struct StageArrays { const u64 *in_off, *out_off; const u32 *in_size, *cap; cons
 int r4x16_stage_begin(rans4x16_hip_ctx *c, StageLayout *L, size_t items, size_t in_bytes, size_t plane_bytes, size_t out_bytes,
                       size_t pk_count, const StageArrays &h, hipStream_t s);
 int r4x16_stage_verdicts(rans4x16_hip_ctx *c, const StageLayout &L, size_t items, u32 *osz, i32 *status, hipStream_t s);
-// The device calls of the adaptive coders (arith_dynamic either way, fqzcomp_qual) and what rides on them.
-// args: the start of such a call - the context and the eight slot arguments tested (`ok`: what else the call requires),
-// the device set, BatchArgs filled.  -1: refused, err = `bad`; 0: n == 0, nothing to do; 1: go on.
+// How every codec's device calls start and walk their batch (the tok3 calls and the single-shot stripe calls apart), and
+// what rides on them.
+// args: the start of a slot call - the context and the eight slot arguments tested (`ok`: what else the call requires),
+// `check` run where the call has one (its method table: check leaves its own text in err), n == 0 answered, the device
+// set, BatchArgs filled.  -1: refused, err = `bad` or check's; 0: n == 0, nothing to do; 1: go on.
 int r4x16_dev_call_args(rans4x16_hip_ctx *c, const char *bad, bool ok, BatchArgs *a, int n, const u8 *d_in, const u64 *d_in_off,
                         const u32 *d_in_size, u8 *d_out, const u64 *d_out_off, const u32 *d_out_cap, u32 *d_out_size, i32 *d_status,
-                        int order, const i32 *d_order);
-// walk: n blocks in chunks of `chunk` (what the caller's plan fitted), fewer where arena `which` cannot be had for as many
-// (bytes_for(nb): what a chunk of nb blocks takes of it), ordered on the context's arenas before and behind: run(base, nb)
-// enqueues one chunk, 0 or -1.
-int r4x16_chunk_walk(rans4x16_hip_ctx *c, int n, R4Arena which, size_t chunk, hipStream_t s,
-                     const std::function<size_t(size_t)> &bytes_for, const std::function<int(size_t, int)> &run);
+                        int order, const i32 *d_order, const std::function<int()> &check = {});
+// The same for a packed call, whose results lie back to back at d_out + d_out_off[i]: d_out_off is required whatever n
+// is, d_out may be null with capacity 0 (the sizing pass).  check, then the device set; n == 0 zeroes d_out_off[0] on `s`.
+// BatchArgs filled but for out / out_off / out_cap (null: the route sets them), and *pk.
+int r4x16_packed_call_args(rans4x16_hip_ctx *c, const char *bad, bool ok, BatchArgs *a, PackedOut *pk, int n, const u8 *d_in,
+                           const u64 *d_in_off, const u32 *d_in_size, u8 *d_out, u64 out_capacity, u64 *d_out_off, u32 *d_out_size,
+                           i32 *d_status, int order, const i32 *d_order, hipStream_t s, const std::function<int()> &check = {});
+// walk: n blocks in chunks of `chunk` (what the caller's plan fitted), fewer where grab(nb) - r4x16_ensure on every arena a
+// chunk of nb blocks takes, 0 or -1 - cannot have them for as many, ordered on the context's arenas before and behind:
+// run(base, nb) enqueues one chunk, 0 or -1 (the walk ends there, the order left open).  The first chunk is a full one:
+// a call that lays its arenas out once does so in run at base == 0, where nb is the chunk size the back-off ended on, and
+// enqueues its once-per-call work there.
+// r4x16_chunk_walk is a template over its two callables and needs the context's members: it stands at the end of this file.
 // The route counters of one chunk of launches.  begin: zeroed on `s` - or, option route_count off, *kernels = nullptr: the
 // kernels count nothing.  end (d_cnt: the counters, not the kernels' copy): read out into list `which`, the chunk counted
 // as launched in order.
@@ -254,3 +263,14 @@ struct StripeLimits {
             return -1;                                                                      \
         }                                                                                   \
     } while (0)
+
+template <class Grab, class Run>
+static inline int r4x16_chunk_walk(rans4x16_hip_ctx *c, int n, size_t chunk, hipStream_t s, Grab grab, Run run)
+{
+    if (r4x16_ws_order_begin(c, s) != 0) return -1;
+    if (r4x16_backoff(chunk, grab) != 0) return -1;
+    for (size_t base = 0; base < (size_t)n; base += chunk)
+        if (run(base, (int)std::min(chunk, (size_t)n - base)) != 0) return -1;
+    HIPCHK(c, hipGetLastError());
+    return r4x16_ws_order_end(c, s);
+}

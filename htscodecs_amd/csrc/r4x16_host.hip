@@ -38,33 +38,46 @@ int r4x16_stage_verdicts(rans4x16_hip_ctx *c, const StageLayout &L, size_t items
     return 0;
 }
 
-// The adaptive coders' device calls and host round trip (r4x16_host.h)
+// How a device call starts and walks its batch, and the adaptive coders' host round trip (r4x16_host.h)
+static void fill_args(BatchArgs *a, int n, const u8 *d_in, const u64 *d_in_off, const u32 *d_in_size, u8 *d_out, const u64 *d_out_off,
+                      const u32 *d_out_cap, u32 *d_out_size, i32 *d_status, int order, const i32 *d_order)
+{
+    a->in = d_in; a->in_off = d_in_off; a->in_size = d_in_size;
+    a->out = d_out; a->out_off = d_out_off; a->out_cap = d_out_cap; a->out_size = d_out_size;
+    a->status = d_status; a->d_order = d_order; a->order = order; a->n = n;
+}
+
 int r4x16_dev_call_args(rans4x16_hip_ctx *c, const char *bad, bool ok, BatchArgs *a, int n, const u8 *d_in, const u64 *d_in_off,
                         const u32 *d_in_size, u8 *d_out, const u64 *d_out_off, const u32 *d_out_cap, u32 *d_out_size, i32 *d_status,
-                        int order, const i32 *d_order)
+                        int order, const i32 *d_order, const std::function<int()> &check)
 {
     if (!c) return -1;
     if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status)) || !ok) {
         c->err = bad;
         return -1;
     }
+    if (check && check() != 0) return -1;
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
-    a->in = d_in; a->in_off = d_in_off; a->in_size = d_in_size;
-    a->out = d_out; a->out_off = d_out_off; a->out_cap = d_out_cap; a->out_size = d_out_size;
-    a->status = d_status; a->d_order = d_order; a->order = order; a->n = n;
+    fill_args(a, n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_out_cap, d_out_size, d_status, order, d_order);
     return 1;
 }
 
-int r4x16_chunk_walk(rans4x16_hip_ctx *c, int n, R4Arena which, size_t chunk, hipStream_t s,
-                     const std::function<size_t(size_t)> &bytes_for, const std::function<int(size_t, int)> &run)
+int r4x16_packed_call_args(rans4x16_hip_ctx *c, const char *bad, bool ok, BatchArgs *a, PackedOut *pk, int n, const u8 *d_in,
+                           const u64 *d_in_off, const u32 *d_in_size, u8 *d_out, u64 out_capacity, u64 *d_out_off, u32 *d_out_size,
+                           i32 *d_status, int order, const i32 *d_order, hipStream_t s, const std::function<int()> &check)
 {
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, which, bytes_for(nb), false); }) != 0) return -1;
-    for (size_t base = 0; base < (size_t)n; base += chunk)
-        if (run(base, (int)std::min(chunk, (size_t)n - base)) != 0) return -1;
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+    if (!c) return -1;
+    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status)) || !ok) {
+        c->err = bad;
+        return -1;
+    }
+    if (check && check() != 0) return -1;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(u64), s)); return 0; }
+    fill_args(a, n, d_in, d_in_off, d_in_size, nullptr, nullptr, nullptr, d_out_size, d_status, order, d_order);   // (the internal slots: set by the route)
+    *pk = PackedOut{d_out, d_out_off, out_capacity};
+    return 1;
 }
 
 int r4x16_route_begin(rans4x16_hip_ctx *c, u32 **kernels, u32 words, hipStream_t s)

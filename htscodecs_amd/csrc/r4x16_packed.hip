@@ -233,40 +233,37 @@ static int gathered(rans4x16_hip_ctx *c, int n, const BatchArgs &a, const Packed
     else
         for (int j = 0; j < pm.k; j++) stride = std::max(stride, r4x16_packed_stride(max_in_size, pm.m[j], false));
     PackedSlots p;
-    const size_t keep_ws = c->max_ws;
+    size_t arena = 0;
     auto slots_for = [&](size_t nb) { return r4x16_packed_carve(&p, nullptr, (size_t)n, nb, stride); };
     const size_t room = r4x16_room(c, A_BIT(A_WS) | A_BIT(A_XS) | A_BIT(A_PS));
-    size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, room / 4, slots_for);
-    if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    if (r4x16_backoff(chunk, [&](size_t nb) { return r4x16_ensure(c, A_PS, slots_for(nb), false); }) != 0) return -1;
-    const size_t arena = r4x16_packed_carve(&p, c->at(A_PS), (size_t)n, chunk, stride);
-    hipLaunchKernelGGL(k_pk_slots, dim3((n + 255) / 256), dim3(256), 0, s, a.in_size, a.d_order, a.order, pm, n, (u32)chunk, stride,
-                       max_in_size, p.slot_off, p.slot_cap);
-    int rc = 0;
-    for (size_t base = 0; base < (size_t)n && rc == 0; base += chunk) {
-        const int nb = (int)std::min(chunk, (size_t)n - base);
+    const size_t chunk = r4x16_fit_chunk((size_t)n, SIZE_MAX, room / 4, slots_for);
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_PS, slots_for(nb), false); };
+    return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
+        if (base == 0) {                               // the layout of the call: nb is the chunk size here
+            arena = r4x16_packed_carve(&p, c->at(A_PS), (size_t)n, (size_t)nb, stride);
+            hipLaunchKernelGGL(k_pk_slots, dim3((n + 255) / 256), dim3(256), 0, s, a.in_size, a.d_order, a.order, pm, n, (u32)nb, stride,
+                               max_in_size, p.slot_off, p.slot_cap);
+        }
         const u64 total = total_in_size ? std::min<u64>(total_in_size, (u64)nb * max_in_size) : 0;
-        c->max_ws = keep_ws > arena + ((size_t)1 << 20) ? keep_ws - arena : (size_t)1 << 20;
-        c->in_packed = true;
-        if (pm.k)
-            rc = rans4x16_hip_compress_best_dev(c, nb, a.in, a.in_off + base, a.in_size + base, p.slots, p.slot_off + base, p.slot_cap + base,
-                                                a.out_size + base, a.status + base, pm.k, pm.m, d_chosen ? d_chosen + base : nullptr,
-                                                max_in_size, total, s);
-        else
-            rc = rans4x16_hip_compress_dev_sized(c, nb, a.in, a.in_off + base, a.in_size + base, p.slots, p.slot_off + base, p.slot_cap + base,
-                                                 a.out_size + base, a.status + base, a.order, a.d_order ? a.d_order + base : nullptr,
-                                                 max_in_size, total, s);
-        c->in_packed = false;
-        c->max_ws = keep_ws;
-        if (rc != 0) break;
+        {
+            // the inner call: what is left of the ceiling beside this call's slots
+            Keep<size_t> ceiling(c->max_ws, c->max_ws > arena + ((size_t)1 << 20) ? c->max_ws - arena : (size_t)1 << 20);
+            Keep<bool> inner(c->in_packed, true);
+            const int rc = pm.k
+                ? rans4x16_hip_compress_best_dev(c, nb, a.in, a.in_off + base, a.in_size + base, p.slots, p.slot_off + base, p.slot_cap + base,
+                                                 a.out_size + base, a.status + base, pm.k, pm.m, d_chosen ? d_chosen + base : nullptr,
+                                                 max_in_size, total, s)
+                : rans4x16_hip_compress_dev_sized(c, nb, a.in, a.in_off + base, a.in_size + base, p.slots, p.slot_off + base, p.slot_cap + base,
+                                                  a.out_size + base, a.status + base, a.order, a.d_order ? a.d_order + base : nullptr,
+                                                  max_in_size, total, s);
+            if (rc != 0) return -1;
+        }
         hipLaunchKernelGGL(k_pk_scan, dim3(1), dim3(1024), 0, s, (const u32 *)a.out_size, pk.off, (int)base, nb);
         hipLaunchKernelGGL(k_pk_gather, dim3((u32)nb), dim3(256), 0, s, pk, (const u8 *)p.slots, (const u64 *)p.slot_off,
                            (const u32 *)p.slot_cap, a.out_size, a.status, (int)base);
         if (c->opts.v[OPT_ROUTE_COUNT]) c->route[R4X16_ROUTE_RESULT][R4X16_RESULT_GATHERED] += nb;
-    }
-    if (rc != 0) return -1;
-    HIPCHK(c, hipGetLastError());
-    return r4x16_ws_order_end(c, s);
+        return 0;
+    });
 }
 
 extern "C" int rans4x16_hip_compress_packed_dev(rans4x16_hip_ctx *c, int n,
@@ -275,19 +272,12 @@ extern "C" int rans4x16_hip_compress_packed_dev(rans4x16_hip_ctx *c, int n,
                                                 uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
                                                 uint32_t max_in_size, uint64_t total_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
-        c->err = "compress_packed_dev: bad arguments";
-        return -1;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
     BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = nullptr; a.out_off = nullptr; a.out_cap = nullptr; a.out_size = d_out_size;      // (the internal slots: set by the route)
-    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
-    const PackedOut pk = {d_out, d_out_off, out_capacity};
+    PackedOut pk;
+    const int go = r4x16_packed_call_args(c, "compress_packed_dev: bad arguments", true, &a, &pk, n, d_in, d_in_off, d_in_size, d_out,
+                                          out_capacity, d_out_off, d_out_size, d_status, order, d_order, s);
+    if (go <= 0) return go;
     const bool stripes = d_order ? c->dev_stripe_enc > 0 : (order & X_STRIPE) != 0;
     if (!stripes) return r4x16_enc_run(c, a, max_in_size, total_in_size, s, &pk);
     if (!d_order && ((unsigned)order >> 8) > 255) { c->err = "compress_packed_dev: more than 255 stripes"; return -1; }
@@ -302,26 +292,21 @@ extern "C" int rans4x16_hip_compress_best_packed_dev(rans4x16_hip_ctx *c, int n,
                                                      int k, const int *methods, int32_t *d_chosen,
                                                      uint32_t max_in_size, uint64_t total_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || k < 1 || k > PK_MAX_K || !methods || !d_out_off ||
-        (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
-        c->err = "compress_best_packed_dev: bad arguments";
-        return -1;
-    }
-    PkMethods pm = {};
-    pm.k = k;
-    for (int j = 0; j < k; j++) {
-        if ((methods[j] & X_STRIPE) && ((unsigned)methods[j] >> 8) > 255) { c->err = "compress_best_packed_dev: more than 255 stripes"; return -1; }
-        pm.m[j] = methods[j];
-    }
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
+    PkMethods pm = {};
+    auto table = [&] {
+        pm.k = k;
+        for (int j = 0; j < k; j++) {
+            if ((methods[j] & X_STRIPE) && ((unsigned)methods[j] >> 8) > 255) { c->err = "compress_best_packed_dev: more than 255 stripes"; return -1; }
+            pm.m[j] = methods[j];
+        }
+        return 0;
+    };
     BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = nullptr; a.out_off = nullptr; a.out_cap = nullptr; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = nullptr; a.order = 0; a.n = n;
-    const PackedOut pk = {d_out, d_out_off, out_capacity};
+    PackedOut pk;
+    const int go = r4x16_packed_call_args(c, "compress_best_packed_dev: bad arguments", k >= 1 && k <= PK_MAX_K && methods, &a, &pk, n, d_in,
+                                          d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, 0, nullptr, s, table);
+    if (go <= 0) return go;
     return gathered(c, n, a, pk, pm, d_chosen, max_in_size, total_in_size, s);
 }
 
@@ -345,31 +330,30 @@ extern "C" int rans4x16_hip_peek_dev(rans4x16_hip_ctx *c, int n,
 
 // The packed decode of either codec: claims, offsets, admission, the slot call with capacity = claim, verdicts.
 template <bool X8>
-static int unpack_run(rans4x16_hip_ctx *c, int n, const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
-                      unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off, uint32_t *d_out_size, int32_t *d_status,
-                      const uint32_t *d_nosz_size, uint32_t max_in_size, uint32_t max_out_size, hipStream_t s)
+static int unpack_run(rans4x16_hip_ctx *c, const BatchArgs &a, const PackedOut &pk, const uint32_t *d_nosz_size, uint32_t max_in_size,
+                      uint32_t max_out_size, hipStream_t s)
 {
+    const int n = a.n;
     // the layout's own arrays: 12 bytes per block in the packed arena (ordered between streams like the workspace)
     if (r4x16_ensure(c, A_PS, 3 * align_up((size_t)n * 4, 256), false) != 0) return -1;
     Carver cv(c->at(A_PS));
     UnpkWs w;
     w.claim = cv.take<u32>(n); w.in_size = cv.take<u32>(n); w.pre = cv.take<i32>(n);
     if (r4x16_ws_order_begin(c, s) != 0) return -1;
-    const PackedOut pk = {d_out, d_out_off, out_capacity};
     const dim3 grid((n + 255) / 256), wg(256);
-    hipLaunchKernelGGL(k_unpk_claim<X8>, grid, wg, 0, s, d_in, d_in_off, d_in_size, d_nosz_size, w, n, max_in_size, max_out_size);
-    hipLaunchKernelGGL(k_pk_scan, dim3(1), dim3(1024), 0, s, (const u32 *)w.claim, d_out_off, 0, n);
-    hipLaunchKernelGGL(k_unpk_admit, grid, wg, 0, s, d_in_size, w, pk, n);
+    hipLaunchKernelGGL(k_unpk_claim<X8>, grid, wg, 0, s, a.in, a.in_off, a.in_size, d_nosz_size, w, n, max_in_size, max_out_size);
+    hipLaunchKernelGGL(k_pk_scan, dim3(1), dim3(1024), 0, s, (const u32 *)w.claim, pk.off, 0, n);
+    hipLaunchKernelGGL(k_unpk_admit, grid, wg, 0, s, a.in_size, w, pk, n);
     // every admitted block ends inside the capacity, so the capacities of the transformed blocks together do too
-    const u64 total = std::max<u64>(std::min<u64>(out_capacity, (u64)n * max_out_size), 1);
+    const u64 total = std::max<u64>(std::min<u64>(pk.capacity, (u64)n * max_out_size), 1);
     // rANS 4x8's sizing pass (no arena, capacity 0): only blocks that claim 0 bytes are admitted and nothing is written,
     // but the slot call wants a pointer - the packed arena's own
-    unsigned char *out8 = d_out ? d_out : c->at(A_PS);
-    const int rc = X8 ? rans4x8_hip_uncompress_dev(c, n, d_in, d_in_off, w.in_size, out8, d_out_off, w.claim, d_out_size, d_status, s)
-                      : rans4x16_hip_uncompress_dev_sized(c, n, d_in, d_in_off, w.in_size, d_out, d_out_off, w.claim, d_out_size, d_status,
+    unsigned char *out8 = pk.out ? pk.out : c->at(A_PS);
+    const int rc = X8 ? rans4x8_hip_uncompress_dev(c, n, a.in, a.in_off, w.in_size, out8, pk.off, w.claim, a.out_size, a.status, s)
+                      : rans4x16_hip_uncompress_dev_sized(c, n, a.in, a.in_off, w.in_size, pk.out, pk.off, w.claim, a.out_size, a.status,
                                                           max_in_size, max_out_size, total, s);
     if (rc != 0) return -1;
-    hipLaunchKernelGGL(k_unpk_verdict, grid, wg, 0, s, w, d_out_size, d_status, n);
+    hipLaunchKernelGGL(k_unpk_verdict, grid, wg, 0, s, w, a.out_size, a.status, n);
     HIPCHK(c, hipGetLastError());
     return r4x16_ws_order_end(c, s);
 }
@@ -380,16 +364,13 @@ extern "C" int rans4x16_hip_uncompress_packed_dev(rans4x16_hip_ctx *c, int n,
                                                   uint32_t *d_out_size, int32_t *d_status, const uint32_t *d_nosz_size,
                                                   uint32_t max_in_size, uint32_t max_out_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
-        c->err = "uncompress_packed_dev: bad arguments";
-        return -1;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
-    return unpack_run<false>(c, n, d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, d_nosz_size,
-                             max_in_size, max_out_size, s);
+    BatchArgs a;
+    PackedOut pk;
+    const int go = r4x16_packed_call_args(c, "uncompress_packed_dev: bad arguments", true, &a, &pk, n, d_in, d_in_off, d_in_size, d_out,
+                                          out_capacity, d_out_off, d_out_size, d_status, 0, nullptr, s);
+    if (go <= 0) return go;
+    return unpack_run<false>(c, a, pk, d_nosz_size, max_in_size, max_out_size, s);
 }
 
 // ---- rANS 4x8 (include/rans4x8_hip.h) --------------------------------------------------------------------------
@@ -404,32 +385,19 @@ static int pick8_methods(rans4x16_hip_ctx *c, int k, const int *methods, Enc8Sel
     return 0;
 }
 
-static BatchArgs enc8_args(int n, const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size, uint32_t *d_out_size,
-                           int32_t *d_status, int order, const int32_t *d_order)
-{
-    BatchArgs a;
-    a.in = d_in; a.in_off = d_in_off; a.in_size = d_in_size;
-    a.out = nullptr; a.out_off = nullptr; a.out_cap = nullptr; a.out_size = d_out_size;
-    a.status = d_status; a.d_order = d_order; a.order = order; a.n = n;
-    return a;
-}
-
 extern "C" int rans4x8_hip_compress_packed_dev(rans4x16_hip_ctx *c, int n,
                                                const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
                                                unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
                                                uint32_t *d_out_size, int32_t *d_status, int order, const int32_t *d_order,
                                                uint32_t max_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
-        c->err = "rans4x8 compress_packed_dev: bad arguments";
-        return -1;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
-    const PackedOut pk = {d_out, d_out_off, out_capacity};
-    return r4x8_enc_run(c, enc8_args(n, d_in, d_in_off, d_in_size, d_out_size, d_status, order, d_order), max_in_size, s, &pk, nullptr);
+    BatchArgs a;
+    PackedOut pk;
+    const int go = r4x16_packed_call_args(c, "rans4x8 compress_packed_dev: bad arguments", true, &a, &pk, n, d_in, d_in_off, d_in_size, d_out,
+                                          out_capacity, d_out_off, d_out_size, d_status, order, d_order, s);
+    if (go <= 0) return go;
+    return r4x8_enc_run(c, a, max_in_size, s, &pk, nullptr);
 }
 
 extern "C" int rans4x8_hip_compress_best_dev(rans4x16_hip_ctx *c, int n,
@@ -438,18 +406,13 @@ extern "C" int rans4x8_hip_compress_best_dev(rans4x16_hip_ctx *c, int n,
                                              uint32_t *d_out_size, int32_t *d_status,
                                              int k, const int *methods, int32_t *d_chosen, uint32_t max_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || (n && (!d_in || !d_in_off || !d_in_size || !d_out || !d_out_off || !d_out_cap || !d_out_size || !d_status))) {
-        c->err = "rans4x8 compress_best_dev: bad arguments";
-        return -1;
-    }
     Enc8Sel sel = {};
-    if (pick8_methods(c, k, methods, &sel, "rans4x8 compress_best_dev") != 0) return -1;
-    if (n == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
+    BatchArgs a;
+    const int go = r4x16_dev_call_args(c, "rans4x8 compress_best_dev: bad arguments", true, &a, n, d_in, d_in_off, d_in_size, d_out, d_out_off,
+                                       d_out_cap, d_out_size, d_status, 0, nullptr,
+                                       [&] { return pick8_methods(c, k, methods, &sel, "rans4x8 compress_best_dev"); });
+    if (go <= 0) return go;
     sel.d_chosen = d_chosen;
-    BatchArgs a = enc8_args(n, d_in, d_in_off, d_in_size, d_out_size, d_status, 0, nullptr);
-    a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap;
     return r4x8_enc_run(c, a, max_in_size, (hipStream_t)stream, nullptr, &sel);
 }
 
@@ -459,19 +422,16 @@ extern "C" int rans4x8_hip_compress_best_packed_dev(rans4x16_hip_ctx *c, int n,
                                                     uint32_t *d_out_size, int32_t *d_status,
                                                     int k, const int *methods, int32_t *d_chosen, uint32_t max_in_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
-        c->err = "rans4x8 compress_best_packed_dev: bad arguments";
-        return -1;
-    }
-    Enc8Sel sel = {};
-    if (pick8_methods(c, k, methods, &sel, "rans4x8 compress_best_packed_dev") != 0) return -1;
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
+    Enc8Sel sel = {};
+    BatchArgs a;
+    PackedOut pk;
+    const int go = r4x16_packed_call_args(c, "rans4x8 compress_best_packed_dev: bad arguments", true, &a, &pk, n, d_in, d_in_off, d_in_size,
+                                          d_out, out_capacity, d_out_off, d_out_size, d_status, 0, nullptr, s,
+                                          [&] { return pick8_methods(c, k, methods, &sel, "rans4x8 compress_best_packed_dev"); });
+    if (go <= 0) return go;
     sel.d_chosen = d_chosen;
-    const PackedOut pk = {d_out, d_out_off, out_capacity};
-    return r4x8_enc_run(c, enc8_args(n, d_in, d_in_off, d_in_size, d_out_size, d_status, 0, nullptr), max_in_size, s, &pk, &sel);
+    return r4x8_enc_run(c, a, max_in_size, s, &pk, &sel);
 }
 
 extern "C" int rans4x8_hip_peek_dev(rans4x16_hip_ctx *c, int n,
@@ -497,14 +457,11 @@ extern "C" int rans4x8_hip_uncompress_packed_dev(rans4x16_hip_ctx *c, int n,
                                                  uint32_t *d_out_size, int32_t *d_status,
                                                  uint32_t max_in_size, uint32_t max_out_size, void *stream)
 {
-    if (!c) return -1;
-    if (n < 0 || !d_out_off || (n && (!d_in || !d_in_off || !d_in_size || (!d_out && out_capacity) || !d_out_size || !d_status))) {
-        c->err = "rans4x8 uncompress_packed_dev: bad arguments";
-        return -1;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(c, hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s)); return 0; }
-    return unpack_run<true>(c, n, d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, nullptr,
-                            max_in_size, max_out_size, s);
+    BatchArgs a;
+    PackedOut pk;
+    const int go = r4x16_packed_call_args(c, "rans4x8 uncompress_packed_dev: bad arguments", true, &a, &pk, n, d_in, d_in_off, d_in_size,
+                                          d_out, out_capacity, d_out_off, d_out_size, d_status, 0, nullptr, s);
+    if (go <= 0) return go;
+    return unpack_run<true>(c, a, pk, nullptr, max_in_size, max_out_size, s);
 }
