@@ -230,12 +230,24 @@ struct DecItem {
     u32 active;      // 0 = nothing to do (failed block, CAT, empty)
     u32 blk;         // owning block (errors are reported there)
     u32 nsym;        // compact alphabet size n (decides the tree depth and the row size)
-    u32 packed;      // 0: u16 rows of img_levels(nsym) levels, 1: packed 10-bit rows (level 1 / 5), 2: direct rows (level 6), 3: mid rows (level 10)
+    u32 packed;      // the image's format, DEC_FMT_*
     u32 affine;      // direct rows: c + 1 when byte = compact index + c for every symbol with a frequency, else 0
 };
-static inline __host__ __device__ u32 item_levels(u32 nsym, u32 packed)
+// The format of a decode image (DecItem.packed): u16 rows of img_levels(nsym) reads, packed 10-bit rows (wide beyond
+// PK_MAX_NSYM symbols), direct rows, mid rows.
+enum { DEC_FMT_U16 = 0, DEC_FMT_PACKED = 1, DEC_FMT_DIRECT = 2, DEC_FMT_MID = 3 };
+// The kind of a class of the chain decoder: a format (u16 rows: one kind per depth, the depth itself), or a variant of
+// another kind that has classes of its own and runs on that kind's kernel - the order-0 streams of the direct rows and
+// of the two-read u16 rows, the packed rows on the short word ring.  The values are the "levels" 1..10 of older
+// profiles, and the LV of k_dec_chain<LDS_IMG, LV, TRIP>.  (r4x16_decode.hip DEC_KINDS: what the launcher does per kind.)
+enum {
+    DEC_KIND_PACKED = 1, DEC_KIND_U16_2 = 2, DEC_KIND_U16_3 = 3, DEC_KIND_U16_4 = 4, DEC_KIND_WIDE = 5, DEC_KIND_DIRECT = 6,
+    DEC_KIND_DIRECT_O0 = 7, DEC_KIND_U16_2_O0 = 8, DEC_KIND_PACKED_SHORT = 9, DEC_KIND_MID = 10, DEC_KIND_COUNT = 11
+};
+// the kind an image has by its format alone (the variants: dec_class_of, r4x16_decode.hip)
+static inline __host__ __device__ u32 item_levels(u32 nsym, u32 fmt)
 {
-    return packed == 3u ? 10u : packed == 2u ? 6u : packed ? (nsym > PK_MAX_NSYM ? 5u : 1u) : img_levels(nsym);
+    return fmt == DEC_FMT_MID ? DEC_KIND_MID : fmt == DEC_FMT_DIRECT ? DEC_KIND_DIRECT : fmt ? (nsym > PK_MAX_NSYM ? DEC_KIND_WIDE : DEC_KIND_PACKED) : img_levels(nsym);
 }
 
 // Per-block record of the decode pipeline.
@@ -295,8 +307,8 @@ struct EncItem {
     u32 blk;
     u32 ns;          // symbols per image row (a row is ns+1 u16)
     u32 img_bytes;   // bytes of the image (what must sit in LDS)
-    u32 packed;      // 0: u16 rows, 1: rows are 11-bit bit streams (below), 2: 16-byte symbol records (further below),
-                     // ENC_KIND_PK_SHORT: packed rows behind a 128-byte index (below)
+    u32 packed;      // ENC_KIND_U16: u16 rows, _PACKED: rows are 11-bit bit streams (below), _RECORDS: 16-byte symbol records
+                     // (further below), _PK_SHORT: packed rows behind a 128-byte index (below)
     u32 affine;      // symbol records, packed rows of the short-index kind: c + 1 when compact index = byte - c for every byte of the
                      // data (no idx_of[] look-up in the pipelined loop), else 0
 };
@@ -313,7 +325,15 @@ struct EncItem {
 #define ENC_PK_MIN_NS 20u
 #define ENC_PK_MAX_NS 64u
 #define ENC_IMG_IDX_SHORT 128u
-#define ENC_KIND_PK_SHORT 5u                               // (3 and 4 are the classifier's kinds of order-0 streams)
+// The kind of an encode image (EncItem.packed: u16 rows, packed rows, symbol records, packed rows behind the short
+// index) and of a class of the chain encoder: those, and the classes that the order-0 streams of the u16 rows and of the
+// records have to themselves (k_enc_classify; ENC_GROUPS, r4x16_enc_chain.hip).
+#define ENC_KIND_U16        0u
+#define ENC_KIND_PACKED     1u
+#define ENC_KIND_RECORDS    2u
+#define ENC_KIND_U16_O0     3u
+#define ENC_KIND_RECORDS_O0 4u
+#define ENC_KIND_PK_SHORT   5u
 static inline __host__ __device__ u32 enc_pk_row_dwords(u32 ns) { return (11u * (ns + 1u) + 31u) / 32u; }
 static inline __host__ __device__ u32 enc_pk_img_bytes(u32 ns, u32 idx_bytes = ENC_IMG_IDX) { return idx_bytes + 4u * ns * enc_pk_row_dwords(ns) + 4u; }
 

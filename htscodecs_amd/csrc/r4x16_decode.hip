@@ -17,8 +17,6 @@
 #include "r4x16_sched.h"
 #include "r4x16_host.h"
 
-static inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // ---- image access: global memory or LDS ------------------------------------------------------
 struct GImg {
     gcu8 *p;
@@ -71,7 +69,7 @@ __device__ __forceinline__ u32 lookup_step(const IMG &img, u32 row, u32 look, u3
     const u32 m = x & mask;
     const u32 mm = __umul24(m, 0x10001u) + 0x80008000u;     // m | m << 16 | flags (m < 2^15: no overlap)
     u32 e, c0, c1, c2;
-    if (LV == 3) {
+    if (LV == DEC_KIND_U16_3) {
         const u32 a = count_le(mm, img.ld64(row));
         const u32 b = count_le(mm, img.ld64(row + 8 + 8 * a));
         const u32 g = row + 48u + 60u * a + 12u * b;
@@ -83,7 +81,7 @@ __device__ __forceinline__ u32 lookup_step(const IMG &img, u32 row, u32 look, u3
         if (dd >= 2) { Ed = E2; En = E3; }
         e = 30 * a + 6 * b + 2 * dd;
         c0 = Ed & 0xffffu; c1 = Ed >> 16; c2 = En & 0xffffu;
-    } else if (LV == 4) {
+    } else if (LV == DEC_KIND_U16_4) {
         const u32 a = count_le(mm, img.ld64(row)) + count_le(mm, img.ld64(row + 8));
         const u32 b = count_le(mm, img.ld64(row + 16 + 8 * a));
         const u32 dd = count_le(mm, img.ld64(row + 64 + 8 * (5 * a + b)));
@@ -357,9 +355,9 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
     const LImg img0{0u};                                   // row reads: `row` is an absolute LDS address
     const u32 k = lane & 3;
     const u32 mask = (1u << look) - 1;
-    constexpr bool PKD = LV == 1 || LV == 5, WIDE = LV == 5;       // packed rows (r4x16_common.h), with the 16-byte root
-    static_assert(LV != 6 && LV != 10, "direct blocks and mid rows have their own loops: chain_decode_dir, chain_decode_mid");
-    constexpr bool PK2 = LV == 1;                                  // layout 2 of the packed rows: 8-byte head entries (root, alpha word)
+    constexpr bool PKD = LV == DEC_KIND_PACKED || LV == DEC_KIND_WIDE, WIDE = LV == DEC_KIND_WIDE;       // packed rows (r4x16_common.h), with the 16-byte root
+    static_assert(LV != DEC_KIND_DIRECT && LV != DEC_KIND_MID, "direct blocks and mid rows have their own loops: chain_decode_dir, chain_decode_mid");
+    constexpr bool PK2 = LV == DEC_KIND_PACKED;                    // layout 2 of the packed rows: 8-byte head entries (root, alpha word)
     const u32 rows = lds_addr(img_lds) + (PKD ? pk_head_bytes(nsym) : img_alpha_bytes(nsym)), roww = PKD ? pk_row_bytes(nsym) : img_row_bytes(nsym);
     const u32 nwords = BYTE ? words_len : words_len >> 1;  // units of the cursor: 16-bit words (bytes for rANS 4x8)
     const u32 below = (1u << k) - 1u;                      // quad lanes below this one
@@ -405,7 +403,7 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
     u32 row = rows, cursor = 0, bad = 0, t = 0;
     // root separators of `row`, read as soon as the row is known (one step ahead of their use,
     // so that this LDS round trip runs beside the renormalisation instead of after it)
-    u32x2 root = PK2 ? u32x2{img.ld32(0), 0u} : LV == 1 ? u32x2{img0.ld32(row), 0u} : img0.ld64(row);
+    u32x2 root = PK2 ? u32x2{img.ld32(0), 0u} : LV == DEC_KIND_PACKED ? u32x2{img0.ld32(row), 0u} : img0.ld64(row);
     u32x2 root2 = WIDE ? img0.ld64(row + 8) : u32x2{0u, 0u};
     u32 acc = 0;                                          // order-1: the last (up to) 4 decoded bytes
     u32 a0 = 0, a1 = 0, a2 = 0, a3 = 0;                   // order-1: completed dwords not yet stored (a3 newest)
@@ -512,7 +510,7 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
             u32 xn = x;
             RootSpec spec;
             spec.rows = rows; spec.roww = roww;
-            const bool speculate = ORDER == 1 && LV == 2;
+            const bool speculate = ORDER == 1 && LV == DEC_KIND_U16_2;
             u32 s, rown1 = 0;
             u32x2 rootn1 = {0u, 0u}, rootn2 = {0u, 0u};
             if (PKD) {
@@ -525,7 +523,7 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
                 } else
                     rootn1.x = *(LAS const volatile u32 *)(unsigned long)rown1;
             } else {
-                s = lookup_step<(PKD ? 2 : LV)>(img0, row, look, mask, xn, LV == 2 ? &root : nullptr, speculate ? &spec : nullptr);
+                s = lookup_step<(PKD ? DEC_KIND_U16_2 : LV)>(img0, row, look, mask, xn, LV == DEC_KIND_U16_2 ? &root : nullptr, speculate ? &spec : nullptr);
             }
             const u32 hn = img.ld16(2 * s);   // byte value | ROW_EMPTY of the new context
             if (BYTE) badb |= (FAST || live) ? hn : 0u;   // rANS 4x8: ROW_BAD on ANY decoded symbol, the last one included
@@ -1769,7 +1767,7 @@ __device__ void o1_tables(const u8 *in, ByteSrc &src, const u8 *tbuf, bool compr
             I0->out = D->s1; I0->out_sz = s1_size; I0->image = (u64)img;
             I0->img_bytes = direct ? dir_img_bytes(nsym, nsym, look) : mid ? mid_img_bytes(nsym) : packed ? pk_img_bytes(nsym) : img_bytes(nsym, nsym);
             I0->nsym = nsym;
-            I0->packed = direct ? 2u : mid ? 3u : packed ? 1u : 0u;
+            I0->packed = direct ? DEC_FMT_DIRECT : mid ? DEC_FMT_MID : packed ? DEC_FMT_PACKED : DEC_FMT_U16;
             I0->affine = affine;
             I0->look = look; I0->order = 1;
             I0->active = s1_size != 0;
@@ -1826,7 +1824,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(PHASE ? 8 
         DecItem *I2 = &ws.items[2 * gridDim.x + b];
         I0->active = 0; I1->active = 0; I2->active = 0;
         I0->blk = b; I1->blk = b; I2->blk = b;
-        I0->packed = 0; I1->packed = 0; I2->packed = 0;
+        I0->packed = DEC_FMT_U16; I1->packed = DEC_FMT_U16; I2->packed = DEC_FMT_U16;
         I0->affine = 0; I1->affine = 0; I2->affine = 0;
         ws.resume[b].pending = 0;
         D->status = ST_OK; D->cat_src = 0; D->cat_len = 0; D->osz = 0; D->s1_size = 0;
@@ -1944,7 +1942,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(PHASE ? 8 
             I1->words_len = H.meta_pos + H.meta_slen - S.words_pos;
             I1->out = (u64)metabuf; I1->out_sz = H.meta_len; I1->image = (u64)imgm;
             I1->img_bytes = meta_direct ? dir_img_bytes(S.nsym, 1u, O0_BITS) : img_bytes(S.nsym, 1); I1->nsym = S.nsym;
-            I1->packed = meta_direct ? 2u : 0u;
+            I1->packed = meta_direct ? DEC_FMT_DIRECT : DEC_FMT_U16;
             I1->affine = meta_direct ? meta_direct - 1u : 0u;
             I1->look = O0_BITS; I1->order = 0;
             for (int k = 0; k < 4; k++) I1->R[k] = S.R[k];
@@ -1967,7 +1965,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(PHASE ? 8 
                 I0->words_len = pay_pos + pay_len - S.words_pos;
                 I0->out = D->s1; I0->out_sz = s1_size; I0->image = (u64)img;
                 I0->img_bytes = o0_direct ? dir_img_bytes(S.nsym, 1u, O0_BITS) : img_bytes(S.nsym, 1); I0->nsym = S.nsym;
-                I0->packed = o0_direct ? 2u : 0u;
+                I0->packed = o0_direct ? DEC_FMT_DIRECT : DEC_FMT_U16;
                 I0->affine = o0_direct ? o0_direct - 1u : 0u;
                 I0->look = O0_BITS; I0->order = 0;
                 for (int k = 0; k < 4; k++) I0->R[k] = S.R[k];
@@ -2256,9 +2254,9 @@ __global__ __launch_bounds__(WAVE) void k_dec_chain(const DecItem *items, DecDes
         const u8 *im = lds + (u64)quad * lds_per_item + (flip ? ringb : 0u);
         u8 *ring = lds + (u64)quad * lds_per_item + (flip ? 0u : lds_per_item - ringb);
         // order-0 and order-1 streams may share a wave: run the two loops back to back
-        if constexpr (LV == 10) {
+        if constexpr (LV == DEC_KIND_MID) {
             bad = chain_decode_mid(im, nsym, ring, words, words_len, out, out_sz, x0, active && order == 1, lane);
-        } else if constexpr (LV == 6) {
+        } else if constexpr (LV == DEC_KIND_DIRECT) {
             // (affine alphabets - byte = index + c - skip the alpha[] read per symbol; a wave takes that body only if
             //  all its streams are affine)
             const u32 aff = active ? I->affine : 1u;
@@ -2270,17 +2268,19 @@ __global__ __launch_bounds__(WAVE) void k_dec_chain(const DecItem *items, DecDes
                 bad |= chain_decode_dir<0, false>(im, nsym, ring, words, words_len, out, out_sz, x0, look, 0u, active && order == 0, lane);
             }
         } else {
-        if constexpr (LV == 1 && TRIP == TRIP_STEPS)
+        constexpr bool PKD = LV == DEC_KIND_PACKED || LV == DEC_KIND_WIDE;      // packed rows exist for order-1 streams only
+        if constexpr (LV == DEC_KIND_PACKED && TRIP == TRIP_STEPS)
             bad = chain_decode_pk2(im, nsym, ring, words, words_len, out, out_sz, x0, active && order == 1, lane);
         else
         bad = chain_decode_lds<1, LV, TRIP>(im, nsym, ring, words, words_len, out, out_sz, x0, look, active && order == 1, lane);
-        if (LV != 1 && LV != 5)                               // packed rows exist for order-1 streams only
-            bad |= chain_decode_lds<0, ((LV == 1 || LV == 5) ? 2 : LV)>(im, nsym, ring, words, words_len, out, out_sz, x0, look, active && order == 0, lane);
+        if (!PKD)
+            bad |= chain_decode_lds<0, (PKD ? DEC_KIND_U16_2 : LV)>(im, nsym, ring, words, words_len, out, out_sz, x0, look, active && order == 0, lane);
         }
     } else {
-        GImg im{(gcu8 *)I->image};                            // (never level 1: packed images always fit a class)
-        bad = chain_decode<1, ((LV == 1 || LV == 5) ? 2 : LV)>(im, nsym, words, words_len, out, out_sz, x0, look, active && order == 1, lane);
-        bad |= chain_decode<0, ((LV == 1 || LV == 5) ? 2 : LV)>(im, nsym, words, words_len, out, out_sz, x0, look, active && order == 0, lane);
+        constexpr int DEPTH = (LV == DEC_KIND_PACKED || LV == DEC_KIND_WIDE) ? DEC_KIND_U16_2 : LV;
+        GImg im{(gcu8 *)I->image};                            // (never packed rows: packed images always fit a class)
+        bad = chain_decode<1, DEPTH>(im, nsym, words, words_len, out, out_sz, x0, look, active && order == 1, lane);
+        bad |= chain_decode<0, DEPTH>(im, nsym, words, words_len, out, out_sz, x0, look, active && order == 0, lane);
     }
     if (active && bad) desc[I->blk].status = ST_CONTEXT;
     __syncthreads();                                       // LDS is reused by the next share
@@ -3006,27 +3006,55 @@ extern "C" void r4x16_launch_dec_front(const BatchArgs *a, const DecWs *ws, int 
     launch_dec_chain_of(ws, ws->items + 2 * (size_t)nblk, nblk, true, s, nullptr, o, nullptr);        // nested order-1 tables
     hipLaunchKernelGGL(k_dec_front<1>, dim3(nblk), dim3(WAVE), 0, s, *a, *ws, base);
 }
-// LDS size classes: {bytes per stream (image + word ring), streams per wave, tree depth}.
+// ---- what the launcher does per class kind (r4x16_common.h DEC_KIND_*) ------------------------------------------------
+// One row per kind, indexed by it: the chain kernel of its classes (a variant kind runs on the kernel of the kind it
+// varies; TRIP 4 is the short word ring), what the route read-out counts its streams as (include/rans4x16_hip.h), when
+// its classes are launched at all, which of them the launch for nested order-1 tables takes (its items are order-0
+// streams, one-row images: at most IMG_O0_BYTES, four reads only as the lone row of an alphabet beyond 150 symbols), and
+// the tuning aids that override a class's streams per wave.
+typedef void (*dec_chain_fn)(const DecItem *, DecDesc *, const u32 *, u32 *, int, u32, int);
+enum { DEC_GATE_ALWAYS, DEC_GATE_DIRECT, DEC_GATE_MID, DEC_GATE_SHORT_RING };    // always / DecWs.direct_budget / DecWs.mid_budget / option dec_short_ring
+#define DEC_ONE_ROW_BYTES (IMG_O0_BYTES + RING_BYTES + 128u)
+struct DecKind {
+    dec_chain_fn kern; int route, gate;
+    u32 one_row_max;                        // nested tables: classes of up to this many bytes go out (0: none)
+    u32 tuned; int opt_tuned, opt_below;    // option opt_tuned, if set, gives the streams per wave of the class of `tuned` bytes, opt_below of the smaller ones,
+    int opt_cap;                            // opt_cap caps them in every class (-1: no such option)
+};
+static const DecKind DEC_KINDS[DEC_KIND_COUNT] = {
+    {},
+    /* DEC_KIND_PACKED       */ {k_dec_chain<true, DEC_KIND_PACKED>,    R4X16_DEC_L1,         DEC_GATE_ALWAYS,     0u,                3584u, OPT_DEC_QPW_PK, -1, -1},
+    /* DEC_KIND_U16_2        */ {k_dec_chain<true, DEC_KIND_U16_2>,     R4X16_DEC_L2,         DEC_GATE_ALWAYS,     0u,                5360u, OPT_DEC_QPW, OPT_DEC_QPW_SMALL, -1},
+    /* DEC_KIND_U16_3        */ {k_dec_chain<true, DEC_KIND_U16_3>,     R4X16_DEC_L3,         DEC_GATE_ALWAYS,     DEC_ONE_ROW_BYTES, 0u, -1, -1, -1},
+    /* DEC_KIND_U16_4        */ {k_dec_chain<true, DEC_KIND_U16_4>,     R4X16_DEC_L4,         DEC_GATE_ALWAYS,     22528u,            0u, -1, -1, -1},
+    /* DEC_KIND_WIDE         */ {k_dec_chain<true, DEC_KIND_WIDE>,      R4X16_DEC_L5,         DEC_GATE_ALWAYS,     0u,                0u, -1, -1, -1},
+    /* DEC_KIND_DIRECT       */ {k_dec_chain<true, DEC_KIND_DIRECT>,    R4X16_DEC_DIRECT,     DEC_GATE_DIRECT,     0u,                0u, -1, -1, OPT_DEC_QPW_DIR},
+    /* DEC_KIND_DIRECT_O0    */ {k_dec_chain<true, DEC_KIND_DIRECT>,    R4X16_DEC_DIRECT,     DEC_GATE_DIRECT,     0u,                0u, -1, -1, OPT_DEC_QPW_DIR},
+    /* DEC_KIND_U16_2_O0     */ {k_dec_chain<true, DEC_KIND_U16_2>,     R4X16_DEC_L2,         DEC_GATE_ALWAYS,     DEC_ONE_ROW_BYTES, 0u, -1, -1, -1},
+    /* DEC_KIND_PACKED_SHORT */ {k_dec_chain<true, DEC_KIND_PACKED, 4>, R4X16_DEC_SHORT_RING, DEC_GATE_SHORT_RING, 0u,                0u, -1, -1, -1},
+    /* DEC_KIND_MID          */ {k_dec_chain<true, DEC_KIND_MID>,       R4X16_DEC_MID,        DEC_GATE_MID,        0u,                0u, -1, -1, -1},
+};
+// LDS size classes: {bytes per stream (image + word ring), streams per wave, kind}.
 // LDS is allocated in 1,280-byte granules; streams per CU = floor(160 KB / granules(qpw * bytes)) * qpw.
 // Sizes are 16 mod 128, so that consecutive streams start four LDS banks apart.  For the 46-symbol
 // quality alphabets three waves of ten streams measured best (2 x 15: -8 %, 4 x 7: -12 %, 5 x 6: -24 %).
-// 2-read images are at most 6 KB, 4-level
-// images at least 21 KB (or the lone 1.3 KB row of a large order-0 alphabet), so the two groups of
-// classes are walked separately.
-static const struct { u32 bytes; int qpw; int lv; } DEC_CLASSES[] = {
-    // packed rows (level 1): 13..36 symbols in rows of up to 56 bytes, 37..48 of up to 72 (46 symbols: 68-byte rows,
-    // 3,496 bytes with alphabet and ring: 3 x 15 streams per CU)
+#define DEC_SHORT_CLASS_BYTES 3360u     // the class of the packed rows on the short ring, and what decides who takes it (dec_class_of)
+struct DecClass { u32 bytes; int qpw; u32 kind; };
+static const DecClass DEC_CLASSES[] = {
+    // packed rows: 13..36 symbols in rows of up to 56 bytes, 37..48 of up to 72
     // (layout 2: 46 symbols = 3,312 bytes of image, 3,584 with the ring: 15 streams = 42 LDS granules of 1,280 bytes exactly)
-    {1424, 16, 1}, {2448, 16, 1}, {3360, 16, 1}, {3584, 15, 1}, {3840, 14, 1}, {4128, 13, 1}, {4880, 11, 1},
-    // wide packed rows (level 5): 49..96 symbols, rows of 84..148 bytes; three workgroups per CU
-    {5520, 9, 5}, {7184, 7, 5}, {8912, 6, 5}, {10640, 5, 5}, {13200, 4, 5}, {14736, 3, 5},
-    {656, 16, 2}, {1296, 16, 2}, {2576, 16, 2}, {3856, 16, 2}, {5008, 16, 2}, {5360, 10, 2}, {5392, 15, 2}, {6416, 12, 2},
+    {1424, 16, DEC_KIND_PACKED}, {2448, 16, DEC_KIND_PACKED}, {3360, 16, DEC_KIND_PACKED}, {3584, 15, DEC_KIND_PACKED}, {3840, 14, DEC_KIND_PACKED}, {4128, 13, DEC_KIND_PACKED}, {4880, 11, DEC_KIND_PACKED},
+    // wide packed rows: 49..96 symbols, rows of 84..148 bytes; three workgroups per CU
+    {5520, 9, DEC_KIND_WIDE}, {7184, 7, DEC_KIND_WIDE}, {8912, 6, DEC_KIND_WIDE}, {10640, 5, DEC_KIND_WIDE}, {13200, 4, DEC_KIND_WIDE}, {14736, 3, DEC_KIND_WIDE},
+    // u16 rows of two reads: images of at most 6 KB
+    {656, 16, DEC_KIND_U16_2}, {1296, 16, DEC_KIND_U16_2}, {2576, 16, DEC_KIND_U16_2}, {3856, 16, DEC_KIND_U16_2}, {5008, 16, DEC_KIND_U16_2}, {5360, 10, DEC_KIND_U16_2}, {5392, 15, DEC_KIND_U16_2}, {6416, 12, DEC_KIND_U16_2},
     // 51..150 symbols, 3 reads: one-row order-0 images, then order-1 images of 9..55 KB (one stream per wave,
     // as many waves per CU as LDS granules allow)
-    {1296, 16, 3}, {10256, 1, 3}, {12816, 1, 3}, {16656, 1, 3}, {20496, 1, 3}, {25616, 1, 3}, {32016, 1, 3},
-    {40976, 1, 3}, {53648, 1, 3}, {64016, 1, 3},
-    {22528, 1, 4}, {32768, 1, 4}, {53248, 1, 4}, {81920, 1, 4}, {163840, 1, 4},
-    // direct blocks (level 6; only batches that leave LDS to spare make such images, r4x16_dec_direct_budget): four
+    {1296, 16, DEC_KIND_U16_3}, {10256, 1, DEC_KIND_U16_3}, {12816, 1, DEC_KIND_U16_3}, {16656, 1, DEC_KIND_U16_3}, {20496, 1, DEC_KIND_U16_3}, {25616, 1, DEC_KIND_U16_3}, {32016, 1, DEC_KIND_U16_3},
+    {40976, 1, DEC_KIND_U16_3}, {53648, 1, DEC_KIND_U16_3}, {64016, 1, DEC_KIND_U16_3},
+    // four reads: images of at least 21 KB, or the lone 1.3 KB row of a large order-0 alphabet
+    {22528, 1, DEC_KIND_U16_4}, {32768, 1, DEC_KIND_U16_4}, {53248, 1, DEC_KIND_U16_4}, {81920, 1, DEC_KIND_U16_4}, {163840, 1, DEC_KIND_U16_4},
+    // direct blocks (only batches that leave LDS to spare make such images, r4x16_dec_direct_budget): four
     // workgroups per CU and more - a wave per SIMD at least - with up to eight streams per wave, then one stream per wave.  Few
     // classes on purpose: every class is a launch, classes with streams run one after the other, and a batch that mixes
     // alphabets (q4 / q8 / q40) should not fall into more classes than it did with the compressed rows
@@ -3034,31 +3062,53 @@ static const struct { u32 bytes; int qpw; int lv; } DEC_CLASSES[] = {
     //  lanes pays for both halves - 4,096 x 1 MiB q8 literal streams: 481 cycles per step at nine streams per wave,
     //  372 at eight; the compressed rows' loop gains 2 % from the same change.  Seven per wave and five workgroups per CU
     //  - 35 streams instead of 32 - put two waves on one SIMD: 26.1 ms again, and 8,192 q8 streams 39.5 instead of 33.5)
-    {2576, 8, 6}, {4112, 8, 6}, {8080, 5, 6}, {13584, 3, 6}, {20368, 2, 6}, {32000, 1, 6}, {40960, 1, 6}, {53760, 1, 6},
-    {81920, 1, 6}, {163840, 1, 6},
-    // the same for order-0 streams (level 7 = level 6's kernel; images of at most 2,820 bytes).  A wave walks its order-1
+    {2576, 8, DEC_KIND_DIRECT}, {4112, 8, DEC_KIND_DIRECT}, {8080, 5, DEC_KIND_DIRECT}, {13584, 3, DEC_KIND_DIRECT}, {20368, 2, DEC_KIND_DIRECT}, {32000, 1, DEC_KIND_DIRECT}, {40960, 1, DEC_KIND_DIRECT}, {53760, 1, DEC_KIND_DIRECT},
+    {81920, 1, DEC_KIND_DIRECT}, {163840, 1, DEC_KIND_DIRECT},
+    // the same for order-0 streams (the direct rows' kernel; images of at most 2,820 bytes).  A wave walks its order-1
     // quads, then its order-0 quads: the run lengths of a block with X_RLE in a launch of their own run beside the
     // block's literals where launches run side by side (one 1 MiB q8 block: 25.0 -> 18.7 ms), not behind them in the
     // same wave (only where launches do run side by side, DecClassTab.split_o0)
-    {2576, 8, 7}, {4112, 8, 7},
-    // order-0 streams with compressed rows of up to 50 symbols (level 8 = level 2's kernel; such an image and its ring
+    {2576, 8, DEC_KIND_DIRECT_O0}, {4112, 8, DEC_KIND_DIRECT_O0},
+    // order-0 streams with compressed rows of up to 50 symbols (the two-read rows' kernel; such an image and its ring
     // take at most 516 bytes).  The kernel runs a wave's order-1 streams, then its order-0 streams: in a class that
     // holds both kinds - q4 / q8 order-1 tables are this small too - a wave of long streams of both kinds took twice
     // the chain latency (round 4's heterogeneous batch: the class of its 1 MiB streams 104 ms instead of 50).
-    {656, 16, 8},
-    // packed rows of 43..46 symbols with the short ring (level 9 = level 1's rows, four-step trips: chain_decode_lds):
-    // 3,224 bytes of image + 136 of ring = 3,360, 16 x 3,360 = 42 LDS granules exactly - three workgroups of SIXTEEN
+    {656, 16, DEC_KIND_U16_2_O0},
+    // packed rows with the short ring (the packed rows' images, four-step trips: chain_decode_lds): an image of up to
+    // 3,224 bytes + 136 of ring = 3,360, 16 x 3,360 = 42 LDS granules exactly - three workgroups of SIXTEEN
     // streams per CU where the long ring allows fifteen
-    {3360, 16, 9},
-    // mid rows (level 10; only batches of one partly filled round make such images, r4x16_dec_mid_budget): four streams
+    {DEC_SHORT_CLASS_BYTES, 16, DEC_KIND_PACKED_SHORT},
+    // mid rows (only batches of one partly filled round make such images, r4x16_dec_mid_budget): four streams
     // per wave - the loop is two LDS round trips per step, few lanes per access - and four waves per CU, one per SIMD:
     // sixteen streams of up to 47 symbols (8,640 bytes with the word ring; 48 take 9,008) per CU, 4,096 per chip
-    {8976, 4, 10},
+    {8976, 4, DEC_KIND_MID},
 };
-// ---- streams -> classes, on the device ---------------------------------------------------------
-// class ids: index into DEC_CLASSES, then one catch-all per tree depth (images too large for LDS)
+// ---- streams -> classes: one rule for the device and for the host's residency answers ------------
+// class ids: index into DEC_CLASSES, then one catch-all per depth of the u16 rows (images too large for LDS)
 #define DEC_NCLS ((u32)(sizeof(DEC_CLASSES) / sizeof(DEC_CLASSES[0])))
-struct DecClassTab { u32 n; u32 split_o0; u32 sort; u32 short_ring; u32 bytes[CLS_MAX]; u32 lv[CLS_MAX]; };
+static_assert(DEC_NCLS + 3u <= CLS_MAX, "the classes and their three catch-alls have a count each");
+struct DecClassTab { u32 n; u32 split_o0; u32 sort; u32 short_ring; DecClass cls[CLS_MAX]; };      // (the launcher's copy of DEC_CLASSES and the call's switches)
+// The kind of the class a stream belongs in, and the LDS bytes it needs there: the kind of its image's format, or one of
+// the variants - order-0 streams have classes of their own for the direct rows (split_o0: where launches run side by
+// side) and for the two-read rows; with short_ring, the packed images that fit the short ring's class with that ring and
+// not with the long one (layout 2: 43 and 44 symbols) take it.
+struct DecNeed { u32 kind, bytes; };
+static inline __host__ __device__ DecNeed dec_class_of(u32 fmt, u32 nsym, u32 order, u32 img_bytes, bool split_o0, bool short_ring)
+{
+    const u32 kind = item_levels(nsym, fmt), need = img_bytes + RING_BYTES, need_short = img_bytes + RING_BYTES_SHORT;
+    if (kind == DEC_KIND_DIRECT && order == 0 && split_o0) return {DEC_KIND_DIRECT_O0, need};
+    if (kind == DEC_KIND_U16_2 && order == 0) return {DEC_KIND_U16_2_O0, need};
+    if (kind == DEC_KIND_PACKED && short_ring && need > DEC_SHORT_CLASS_BYTES && need_short <= DEC_SHORT_CLASS_BYTES) return {DEC_KIND_PACKED_SHORT, need_short};
+    return {kind, need};
+}
+// Its class id: the first class of the kind that holds it, else the catch-all of its depth (tables stay in global memory;
+// only u16 images can be that large - the other kinds are made to fit a class, and would land on the first catch-all).
+static inline __host__ __device__ u32 dec_class_find(const DecClass *cls, u32 n, DecNeed w)
+{
+    for (u32 k = 0; k < n; k++)
+        if (cls[k].kind == w.kind && w.bytes <= cls[k].bytes) return k;
+    return n + ((w.kind < DEC_KIND_U16_2 || w.kind > DEC_KIND_U16_4) ? 0u : w.kind - DEC_KIND_U16_2);
+}
 // class, length bucket and the class's work per item (r4x16_sched.h); per-class counts go through LDS first: a whole
 // batch is usually one class, and 30,000 atomics on one global word took 0.18 ms
 __global__ __launch_bounds__(256) void k_dec_classify(const DecItem *items, int nitems, DecClassTab tab, SchedWs sw)
@@ -3072,11 +3122,7 @@ __global__ __launch_bounds__(256) void k_dec_classify(const DecItem *items, int 
     if (i < nitems) {
         const DecItem *I = &items[i];
         if (I->active) {
-            const u32 need = I->img_bytes + RING_BYTES, lv0 = item_levels(I->nsym, I->packed), lv = (lv0 == 6u && I->order == 0 && tab.split_o0) ? 7u : (lv0 == 2u && I->order == 0) ? 8u :
-                                                                 (lv0 == 1u && tab.short_ring && need > 3344u && I->img_bytes + RING_BYTES_SHORT <= 3360u) ? 9u : lv0;
-            c = tab.n + ((lv < 2u || lv > 4u) ? 0u : lv - 2u);  // catch-all of this depth (packed levels 1 and 5 always fit a class)
-            for (u32 k = 0; k < tab.n; k++)
-                if (tab.lv[k] == lv && (lv == 9u ? I->img_bytes + RING_BYTES_SHORT : need) <= tab.bytes[k]) { c = k; break; }   // classes of a depth ascend
+            c = dec_class_find(tab.cls, tab.n, dec_class_of(I->packed, I->nsym, I->order, I->img_bytes, tab.split_o0 != 0, tab.short_ring != 0));
             len = I->out_sz;
         }
     }
@@ -3119,61 +3165,51 @@ extern "C" void r4x16_launch_cls_group(const u32 *cls, int nitems, u32 *count, u
     hipLaunchKernelGGL(k_cls_scatter, dim3((nitems + 255) / 256), dim3(256), 0, s, cls, nitems, count, list);
 }
 extern "C" void r4x16_launch_dec_chain(const DecWs *ws, int nitems, hipStream_t s, const R4Fork *fk, const R4Opts *o, SchedHint *hint) { launch_dec_chain_of(ws, ws->items, nitems, false, s, fk, o, hint); }
-static int dec_class_qpw(u32 ci, const R4Opts *o)
+static int dec_class_waves(const DecClass &c) { return sched_resident_per_cu((size_t)c.qpw * c.bytes, 1); }     // per CU, at the table's streams per wave
+static int dec_class_qpw(const DecClass &c, const R4Opts *o)
 {
-    const auto &c = DEC_CLASSES[ci];
-    const int force_qpw = (int)o->v[OPT_DEC_QPW], force_small = (int)o->v[OPT_DEC_QPW_SMALL], force_pk = (int)o->v[OPT_DEC_QPW_PK],
-              force_dir = (int)o->v[OPT_DEC_QPW_DIR];                                                    // tuning aids
-    int qpw = (c.lv == 1 && force_pk && (c.bytes == 3496 || c.bytes == 3584)) ? force_pk :
-              c.lv != 2 ? c.qpw : (force_qpw && c.bytes == 5360) ? force_qpw : (force_small && c.bytes < 5360) ? force_small : c.qpw;
-    if ((c.lv == 6 || c.lv == 7) && force_dir > 0 && qpw > force_dir) qpw = force_dir;
-    return qpw;
+    const DecKind &d = DEC_KINDS[c.kind];
+    auto opt = [o](int i) { return i < 0 ? 0 : (int)o->v[i]; };                                        // tuning aids
+    const int qpw = (c.bytes == d.tuned && opt(d.opt_tuned)) ? opt(d.opt_tuned) : (c.bytes < d.tuned && opt(d.opt_below)) ? opt(d.opt_below) : c.qpw;
+    return (opt(d.opt_cap) > 0 && qpw > opt(d.opt_cap)) ? opt(d.opt_cap) : qpw;
 }
 // one_row_only: the items are order-0 streams (one-row images): only the classes such an image can fall into are launched
 static void launch_dec_chain_of(const DecWs *ws, const DecItem *items, int nitems, bool one_row_only, hipStream_t s0, const R4Fork *fk, const R4Opts *o, SchedHint *hint)
 {
     // the classes go out side by side or in stream order: sched_launch_classes (r4x16_sched.hip)
-    typedef void (*chain_fn)(const DecItem *, DecDesc *, const u32 *, u32 *, int, u32, int);
     SchedLaunch todo[CLS_MAX];
     int ntodo = 0;
     SchedPlan plan;
     DecClassTab tab;
     tab.n = DEC_NCLS;
+    memcpy(tab.cls, DEC_CLASSES, sizeof(DEC_CLASSES));
     tab.split_o0 = fk != nullptr;           // (launches in stream order: a wave takes both kinds, 4,096 x 1 MiB q8 with X_RLE 26.7 against 28.2 ms)
     tab.sort = o->v[OPT_SCHED_SORT] != 0;
     tab.short_ring = o->v[OPT_DEC_SHORT_RING] != 0;
     sched_plan_init(plan, fk ? fk->n + 1 : 1, o);
     plan.ncls = DEC_NCLS;
     const int cus = r4x16_cu_count();
+    const bool open[] = {true, ws->direct_budget != 0, ws->mid_budget != 0, tab.short_ring != 0};      // by DEC_GATE_*: did the front make such images?
     for (u32 ci = 0; ci < DEC_NCLS; ci++) {
-        const auto &c = DEC_CLASSES[ci];
-        tab.bytes[ci] = c.bytes; tab.lv[ci] = (u32)c.lv;
-        const int qpw = dec_class_qpw(ci, o);
+        const DecClass &c = DEC_CLASSES[ci];
+        const DecKind &d = DEC_KINDS[c.kind];
+        const int qpw = dec_class_qpw(c, o);
         const size_t ldsb = (size_t)qpw * c.bytes;
         plan.qpw[ci] = (u16)qpw;
         plan.wgs_full[ci] = (u16)(cus * sched_resident_per_cu(ldsb, 1));
         plan.rate[ci] = sched_rate(qpw, 1, sched_resident_per_cu(ldsb, 1), cus);
-        // (an order-0 image: at most IMG_O0_BYTES; depth 4 only as the lone row of an alphabet beyond 150 symbols)
-        const bool skip = (c.lv == 9 && !tab.short_ring) || (c.lv == 10 && !ws->mid_budget) ||
-                          (one_row_only && (c.lv == 1 || c.lv == 2 || (c.lv >= 5 && c.lv != 8) || c.bytes > (c.lv == 4 ? 22528u : IMG_O0_BYTES + RING_BYTES + 128u))) ||
-                          ((c.lv == 6 || c.lv == 7) && !ws->direct_budget);      // (no stream of this batch was given direct blocks)
-        if (skip) continue;
-        chain_fn kern =
-            c.lv == 10 ? k_dec_chain<true, 10> : c.lv == 9 ? k_dec_chain<true, 1, 4> : c.lv == 1 ? k_dec_chain<true, 1> : c.lv == 5 ? k_dec_chain<true, 5> : (c.lv == 2 || c.lv == 8) ? k_dec_chain<true, 2> : c.lv == 3 ? k_dec_chain<true, 3> :
-            (c.lv == 6 || c.lv == 7) ? k_dec_chain<true, 6> : k_dec_chain<true, 4>;
-        todo[ntodo++] = SchedLaunch{(const void *)kern, r4x16_resident_grid(ldsb, 1, (nitems + qpw - 1) / qpw), WAVE, ldsb, ci, qpw, qpw, c.bytes};
+        if (!open[d.gate] || (one_row_only && c.bytes > d.one_row_max)) continue;
+        todo[ntodo++] = SchedLaunch{(const void *)d.kern, r4x16_resident_grid(ldsb, 1, (nitems + qpw - 1) / qpw), WAVE, ldsb, ci, qpw, qpw, c.bytes};
     }
     if (r4x16_first_on_device(FIRST_DEC_CHAIN))
-        for (chain_fn k : std::initializer_list<chain_fn>{k_dec_chain<true, 1>, k_dec_chain<true, 1, 4>, k_dec_chain<true, 10>, k_dec_chain<true, 5>,
-                                                          k_dec_chain<true, 2>, k_dec_chain<true, 3>, k_dec_chain<true, 4>, k_dec_chain<true, 6>})
-            sched_lds_limit((const void *)k, 163840);
-    // images that fit no LDS class: tables stay in global memory (L2); one catch-all per tree depth
+        for (int k = 1; k < DEC_KIND_COUNT; k++) sched_lds_limit((const void *)DEC_KINDS[k].kern, 163840);       // (a variant's kernel twice: harmless)
+    // images that fit no LDS class: tables stay in global memory (L2); one catch-all per depth, in dec_class_find's order
     // (one_row_only: such an image always fits a class)
     const int grid = (nitems + 15) / 16;
     const SchedLaunch tail[3] = {
-        {(const void *)(chain_fn)k_dec_chain<false, 2>, grid, WAVE, 0, DEC_NCLS + 0, 16, 16, 0u},
-        {(const void *)(chain_fn)k_dec_chain<false, 3>, grid, WAVE, 0, DEC_NCLS + 1, 16, 16, 0u},
-        {(const void *)(chain_fn)k_dec_chain<false, 4>, grid, WAVE, 0, DEC_NCLS + 2, 16, 16, 0u},
+        {(const void *)(dec_chain_fn)k_dec_chain<false, DEC_KIND_U16_2>, grid, WAVE, 0, DEC_NCLS + 0, 16, 16, 0u},
+        {(const void *)(dec_chain_fn)k_dec_chain<false, DEC_KIND_U16_3>, grid, WAVE, 0, DEC_NCLS + 1, 16, 16, 0u},
+        {(const void *)(dec_chain_fn)k_dec_chain<false, DEC_KIND_U16_4>, grid, WAVE, 0, DEC_NCLS + 2, 16, 16, 0u},
     };
     DecDesc *desc = ws->desc;
     const u32 *list = ws->sched.list;
@@ -3184,7 +3220,7 @@ static void launch_dec_chain_of(const DecWs *ws, const DecItem *items, int nitem
         [&] { hipLaunchKernelGGL(k_dec_classify, dim3((nitems + 255) / 256), dim3(256), 0, s0, items, nitems, tab, ws->sched); },
         [&](const SchedLaunch &L) { cnt = ws->sched.cnt + L.ci; qpw = L.qpw; bytes = L.bytes; return args; });
 }
-// LDS bytes a stream may spend on direct blocks (level 6) when `nblk` streams are to be resident at once: the largest
+// LDS bytes a stream may spend on direct blocks when `nblk` streams are to be resident at once: the largest
 // direct class that still holds the batch in ONE round of the chip (0: none does - the batch is large enough to be
 // bound by resident streams, which is what the compressed rows are for).
 //   R4X16_DEC_DIRECT=0  never;  =N (N >= 1)  accept up to N rounds of direct streams (default 1)
@@ -3196,77 +3232,57 @@ extern "C" u32 r4x16_dec_direct_budget(int nblk, const R4Opts *o)
     const long per_cu = (nblk + cus * rounds - 1) / (cus * rounds);
     u32 best = 0;
     for (const auto &c : DEC_CLASSES)
-        if (c.lv == 6 && (long)sched_resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw >= per_cu && c.bytes > best) best = c.bytes;
+        if (c.kind == DEC_KIND_DIRECT && (long)dec_class_waves(c) * c.qpw >= per_cu && c.bytes > best) best = c.bytes;
     return best;
 }
-// LDS bytes a stream may spend on mid rows (level 10): the mid class's, if `nblk` streams fit `dec_mid` rounds of it
+// LDS bytes a stream may spend on mid rows: the mid class's, if `nblk` streams fit `dec_mid` rounds of it
 // (sixteen per CU), else 0.
 extern "C" u32 r4x16_dec_mid_budget(int nblk, const R4Opts *o)
 {
     const long rounds = o->v[OPT_DEC_MID];
     if (rounds <= 0 || nblk <= 0) return 0u;
     for (const auto &c : DEC_CLASSES)
-        if (c.lv == 10 && (long)nblk <= rounds * r4x16_cu_count() * sched_resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw) return c.bytes;
+        if (c.kind == DEC_KIND_MID && (long)nblk <= rounds * r4x16_cu_count() * dec_class_waves(c) * c.qpw) return c.bytes;
     return 0u;
 }
-// Streams of one kind that a CU holds at once in the chain decoder (host arithmetic on the class table above).
+// The shape of the class that an image of this format lands in (dec_class_of, dec_class_find; launches in stream order);
+// false: none holds it.
+static bool dec_residency_of(u32 fmt, u32 nsym, int order, u32 img, bool short_ring, int *streams_per_wave, int *waves_per_cu)
+{
+    const u32 ci = dec_class_find(DEC_CLASSES, DEC_NCLS, dec_class_of(fmt, nsym, (u32)order, img, false, short_ring));
+    if (ci >= DEC_NCLS) return false;
+    *streams_per_wave = DEC_CLASSES[ci].qpw;
+    *waves_per_cu = dec_class_waves(DEC_CLASSES[ci]);
+    return true;
+}
+// Streams of one kind that a CU holds at once in the chain decoder, with the rows that every batch gets (the front's
+// choice between packed and u16 rows, o1_tables).
 extern "C" int r4x16_dec_residency(u32 nsym, int order, u32 bits, int *streams_per_wave, int *waves_per_cu, int short_ring)
 {
     if (nsym == 0 || nsym > 256) return -1;
     const bool packed = order == 1 && bits == 10 && nsym >= PK_MIN_NSYM && nsym <= PKW_MAX_NSYM;
-    u32 lv = packed ? item_levels(nsym, 1u) : (order == 0 && img_levels(nsym) == 2u) ? 8u : item_levels(nsym, 0u);
     const u32 img = packed ? pk_img_bytes(nsym) : img_bytes(nsym, order ? nsym : 1u);
-    u32 need = img + RING_BYTES;
-    if (lv == 1u && short_ring && need > 3344u && img + RING_BYTES_SHORT <= 3360u) { lv = 9u; need = img + RING_BYTES_SHORT; }
-    for (const auto &c : DEC_CLASSES) {
-        if ((u32)c.lv != lv || need > c.bytes) continue;
-        *streams_per_wave = c.qpw;
-        *waves_per_cu = sched_resident_per_cu((size_t)c.qpw * c.bytes, 1);
-        return 0;
+    if (!dec_residency_of(packed ? DEC_FMT_PACKED : DEC_FMT_U16, nsym, order, img, short_ring != 0, streams_per_wave, waves_per_cu)) {
+        *streams_per_wave = 16; *waves_per_cu = 8;          // tables in global memory: bounded by wave slots
     }
-    *streams_per_wave = 16; *waves_per_cu = 8;              // tables in global memory: bounded by wave slots
     return 0;
 }
-// The row kind of a class id of the chain decoder (its position in DEC_CLASSES, then the catch-alls of depths 2, 3, 4), as
-// the route read-out counts it (include/rans4x16_hip.h R4X16_DEC_*); -1 for ids beyond the catch-alls.
+// The row kind of a class id of the chain decoder (its position in DEC_CLASSES, then the catch-alls of the u16 rows' three
+// depths), as the route read-out counts it (include/rans4x16_hip.h R4X16_DEC_*); -1 for ids beyond the catch-alls.
 extern "C" int r4x16_dec_route_kind(u32 ci)
 {
-    if (ci >= DEC_NCLS) return ci - DEC_NCLS < 3u ? 1 + (int)(ci - DEC_NCLS) : -1;
-    switch (DEC_CLASSES[ci].lv) {
-    case 1: return 0;
-    case 2: case 8: return 1;                    // (level 8: level 2's kernel for order-0 streams)
-    case 3: return 2;
-    case 4: return 3;
-    case 5: return 4;
-    case 6: case 7: return 5;                    // (level 7: level 6's kernel for order-0 streams)
-    case 10: return 6;
-    case 9: return 7;
-    }
-    return -1;
+    if (ci >= DEC_NCLS + 3u) return -1;
+    return DEC_KINDS[ci < DEC_NCLS ? DEC_CLASSES[ci].kind : DEC_KIND_U16_2 + (int)(ci - DEC_NCLS)].route;
 }
 // Streams per CU of the class a stream of this kind lands in when the batch's budget admits it: the direct rows (short) /
-// the mid rows (!short).  Mirrors the front's choice (o1_tables, o0_front) and the class tables; -1 where the stream can
-// never take that kind.
+// the mid rows (!short), for the streams the front gives them to (o1_tables, o0_front); -1 where the stream can never
+// take that kind.
 extern "C" int r4x16_dec_residency_kind(u32 nsym, int order, u32 bits, bool short_step, int *streams_per_wave, int *waves_per_cu)
 {
     if (nsym == 0 || nsym > 256) return -1;
-    u32 need, lv;
-    if (short_step) {
-        if ((order && bits != 10 && bits != 12) || nsym > DIR_MAX_NSYM) return -1;
-        need = (order ? dir_img_bytes(nsym, nsym, bits) : dir_img_bytes(nsym, 1u, O0_BITS)) + RING_BYTES;
-        lv = 6u;
-    } else {
-        if (!order || bits != 10 || nsym < MID_MIN_NSYM || nsym > MID_MAX_NSYM) return -1;
-        need = mid_img_bytes(nsym) + RING_BYTES;
-        lv = 10u;
-    }
-    for (const auto &c : DEC_CLASSES) {
-        if ((u32)c.lv != lv || need > c.bytes) continue;
-        *streams_per_wave = c.qpw;
-        *waves_per_cu = sched_resident_per_cu((size_t)c.qpw * c.bytes, 1);
-        return 0;
-    }
-    return -1;
+    if (short_step ? ((order && bits != 10 && bits != 12) || nsym > DIR_MAX_NSYM) : (!order || bits != 10 || nsym < MID_MIN_NSYM || nsym > MID_MAX_NSYM)) return -1;
+    const u32 img = !short_step ? mid_img_bytes(nsym) : order ? dir_img_bytes(nsym, nsym, bits) : dir_img_bytes(nsym, 1u, O0_BITS);
+    return dec_residency_of(short_step ? DEC_FMT_DIRECT : DEC_FMT_MID, nsym, order, img, false, streams_per_wave, waves_per_cu) ? 0 : -1;
 }
 // returns the expansion kernel it launched: 0 one wave per block, 1 a workgroup per block (R4X16_EXPAND_*)
 extern "C" int r4x16_launch_dec_back(const BatchArgs *a, const DecWs *ws, int base, int nblk, hipStream_t s, const R4Opts *o)
@@ -3659,14 +3675,14 @@ __global__ __launch_bounds__(WAVE) void k8_dec_chain(const X8Item *items, BatchA
         // (the 4x16 decoder's loop with rANS 4x8's byte renormalisation: full trips without liveness selects,
         //  speculative roots, gathered stores)
 #define X8_RUN(O, L) bad |= chain_decode_lds<O, L, TRIP_STEPS, true>(im, nsym, ring, bytes, blen, out, osz, x0, X8_BITS, active && order == O && lv == L, lane)
-        X8_RUN(0, 2); X8_RUN(0, 3); X8_RUN(0, 4);
-        X8_RUN(1, 2);                                          // (X8_SLOT1 holds 2-read images only: up to 50 symbols)
+        X8_RUN(0, DEC_KIND_U16_2); X8_RUN(0, DEC_KIND_U16_3); X8_RUN(0, DEC_KIND_U16_4);
+        X8_RUN(1, DEC_KIND_U16_2);                                          // (X8_SLOT1 holds 2-read images only: up to 50 symbols)
 #undef X8_RUN
     } else {
         GImg im{(gcu8 *)I->image};
 #define X8_RUN(O, L) bad |= chain_decode8<O, L>(im, nsym, bytes, blen, out, osz, x0, active && order == O && lv == L, lane)
-        X8_RUN(0, 2); X8_RUN(0, 3); X8_RUN(0, 4);
-        X8_RUN(1, 2); X8_RUN(1, 3); X8_RUN(1, 4);
+        X8_RUN(0, DEC_KIND_U16_2); X8_RUN(0, DEC_KIND_U16_3); X8_RUN(0, DEC_KIND_U16_4);
+        X8_RUN(1, DEC_KIND_U16_2); X8_RUN(1, DEC_KIND_U16_3); X8_RUN(1, DEC_KIND_U16_4);
 #undef X8_RUN
     }
     if (active && bad) {
@@ -3675,32 +3691,33 @@ __global__ __launch_bounds__(WAVE) void k8_dec_chain(const X8Item *items, BatchA
     }
 }
 
-extern "C" size_t r4x8_dec_ws_bytes(size_t nblk)
+struct X8Ws { X8Item *items; u8 *images; u32 *cls, *list, *count; size_t bytes; };
+static X8Ws x8_layout(u8 *base, size_t nblk)
 {
-    return align_up_sz(nblk * sizeof(X8Item), 256) + nblk * (size_t)IMG8_SLOT + 2 * align_up_sz(nblk * 4, 256) + align_up_sz(3 * CLS_MAX * 4, 256);
+    Carver cv(base);
+    X8Ws w = {cv.take<X8Item>(nblk), cv.take<u8>(nblk * (size_t)IMG8_SLOT), cv.take<u32>(nblk), cv.take<u32>(nblk), cv.take<u32>(3 * CLS_MAX), 0};
+    w.bytes = cv.total();
+    return w;
 }
+extern "C" size_t r4x8_dec_ws_bytes(size_t nblk) { return x8_layout(nullptr, nblk).bytes; }
 extern "C" void r4x8_launch_decode(const BatchArgs *a, u8 *ws, int base, int nblk, hipStream_t s)
 {
-    X8Item *items = (X8Item *)ws;
-    u8 *images = ws + align_up_sz((size_t)nblk * sizeof(X8Item), 256);
-    u32 *cls = (u32 *)(images + (size_t)nblk * IMG8_SLOT);
-    u32 *cls_list = (u32 *)((u8 *)cls + align_up_sz((size_t)nblk * 4, 256));
-    u32 *cls_count = (u32 *)((u8 *)cls_list + align_up_sz((size_t)nblk * 4, 256));
-    hipLaunchKernelGGL(k8_dec_front, dim3(nblk), dim3(WAVE), 0, s, *a, items, images, base);
-    r4x16_launch_cls_zero(cls_count, s);
-    hipLaunchKernelGGL(k8_classify, dim3((nblk + 255) / 256), dim3(256), 0, s, (const X8Item *)items, nblk, cls, cls_count);
-    r4x16_launch_cls_group(cls, nblk, cls_count, cls_list, s);
+    const X8Ws w = x8_layout(ws, (size_t)nblk);
+    hipLaunchKernelGGL(k8_dec_front, dim3(nblk), dim3(WAVE), 0, s, *a, w.items, w.images, base);
+    r4x16_launch_cls_zero(w.count, s);
+    hipLaunchKernelGGL(k8_classify, dim3((nblk + 255) / 256), dim3(256), 0, s, (const X8Item *)w.items, nblk, w.cls, w.count);
+    r4x16_launch_cls_group(w.cls, nblk, w.count, w.list, s);
     if (r4x16_first_on_device(FIRST_DEC8_CHAIN)) sched_lds_limit((const void *)k8_dec_chain<true>, 163840);
     // (measured with the shape as a launch parameter, gpurun_out/r04_ab_x8*.txt, 11,520 x 1 MiB q40: a round takes ~58 ms whatever the wave holds - 12, 14 or 15 streams in
     //  each of two waves per CU: 100 GB/s; 8 x 3 waves: 87; 10 per wave does NOT make three waves: 54,560 bytes round up
     //  past a third of the LDS - so the class holds as many streams as two waves can: 2 x 15 x 5,456 = 163,680 bytes)
     const int q0 = 16, q1a = 15, q1 = 12;
-    hipLaunchKernelGGL(k8_dec_chain<true>, dim3((nblk + q0 - 1) / q0), dim3(WAVE), (size_t)q0 * X8_SLOT0, s, (const X8Item *)items, *a, base,
-                       (const u32 *)cls_list, (const u32 *)(cls_count + 0), q0, X8_SLOT0);
-    hipLaunchKernelGGL(k8_dec_chain<true>, dim3((nblk + q1a - 1) / q1a), dim3(WAVE), (size_t)q1a * X8_SLOT1A, s, (const X8Item *)items, *a, base,
-                       (const u32 *)cls_list, (const u32 *)(cls_count + 1), q1a, X8_SLOT1A);
-    hipLaunchKernelGGL(k8_dec_chain<true>, dim3((nblk + q1 - 1) / q1), dim3(WAVE), (size_t)q1 * X8_SLOT1, s, (const X8Item *)items, *a, base,
-                       (const u32 *)cls_list, (const u32 *)(cls_count + 2), q1, X8_SLOT1);
-    hipLaunchKernelGGL(k8_dec_chain<false>, dim3((nblk + 15) / 16), dim3(WAVE), 0, s, (const X8Item *)items, *a, base,
-                       (const u32 *)cls_list, (const u32 *)(cls_count + 3), 16, 0u);
+    hipLaunchKernelGGL(k8_dec_chain<true>, dim3((nblk + q0 - 1) / q0), dim3(WAVE), (size_t)q0 * X8_SLOT0, s, (const X8Item *)w.items, *a, base,
+                       (const u32 *)w.list, (const u32 *)(w.count + 0), q0, X8_SLOT0);
+    hipLaunchKernelGGL(k8_dec_chain<true>, dim3((nblk + q1a - 1) / q1a), dim3(WAVE), (size_t)q1a * X8_SLOT1A, s, (const X8Item *)w.items, *a, base,
+                       (const u32 *)w.list, (const u32 *)(w.count + 1), q1a, X8_SLOT1A);
+    hipLaunchKernelGGL(k8_dec_chain<true>, dim3((nblk + q1 - 1) / q1), dim3(WAVE), (size_t)q1 * X8_SLOT1, s, (const X8Item *)w.items, *a, base,
+                       (const u32 *)w.list, (const u32 *)(w.count + 2), q1, X8_SLOT1);
+    hipLaunchKernelGGL(k8_dec_chain<false>, dim3((nblk + 15) / 16), dim3(WAVE), 0, s, (const X8Item *)w.items, *a, base,
+                       (const u32 *)w.list, (const u32 *)(w.count + 3), 16, 0u);
 }

@@ -24,26 +24,40 @@ extern "C" const void *r4x16_enc_chain_rec_kernel(void);
 // (round 3: the steps above 12,816 were 33,296 and 73,616 - the 13 KB image of a 79-symbol alphabet, what X_PACK|X_RLE
 //  makes of four-letter quality values, sat in the 33 KB class at four streams per CU: 11.8 ms for 4,096 such streams.
 //  Now every count of streams per CU from nine to one has its class: 147,344 bytes beside the reciprocal table / k.)
-static const u32 ENC_CLASSES[] = {656, 1296, 2576, 4752, 6416, 12816, 16272, 24464, 36752, 49040, 73616, 147344};
+// {LDS bytes per stream, streams per wave - rows: 0, as many streams per workgroup as fit (enc_class_qpw)}
+struct EncClass { u32 bytes; int qpw; };
+static constexpr EncClass ENC_CLASSES[] = {{656}, {1296}, {2576}, {4752}, {6416}, {12816}, {16272}, {24464}, {36752}, {49040}, {73616}, {147344}};
 // packed rows (20..64 symbols, 10-bit tables): 46 symbols need 3,532 bytes -> 45 streams per CU beside the small
 // reciprocal table (3,536 is 80 mod 128: consecutive streams start 20 banks apart)
-static const u32 ENC_PK_CLASSES[] = {1168, 2064, 2832, 3536, 3728, 4752, 6416};
+static constexpr EncClass ENC_PK_CLASSES[] = {{1168}, {2064}, {2832}, {3536}, {3728}, {4752}, {6416}};
 // the short-index kind of the packed rows (r4x16_common.h: highest byte below 128): class k is packed class k less the
 // half of the index its images leave out - 46 symbols: 3,408 bytes, 45 streams per CU beside the 8,208-byte frequency
 // table (80 mod 128 like 3,536)
 #define ENC_PKS_LESS (ENC_IMG_IDX - ENC_IMG_IDX_SHORT)
-static u32 enc_pks_class(u32 k) { return ENC_PK_CLASSES[k] - ENC_PKS_LESS; }
-// symbol records (kind 2, r4x16_enc_chain_rec.hip; only batches that leave LDS to spare make such images): one wave
-// per workgroup, {LDS bytes per stream, streams per wave}; four workgroups per CU, then fewer
-struct EncRecClass { u32 bytes; int qpw; };
-static const EncRecClass ENC_REC_CLASSES[] = {
+// symbol records (r4x16_enc_chain_rec.hip; only batches that leave LDS to spare make such images): one wave
+// per workgroup; four workgroups per CU, then fewer
+static constexpr EncClass ENC_REC_CLASSES[] = {
     {2576, 15}, {4112, 9}, {8080, 5}, {13584, 3}, {20368, 2}, {32000, 1}, {40960, 1}, {53760, 1}, {81920, 1}, {163840, 1},
 };
-#define ENC_REC_NCLS ((u32)(sizeof(ENC_REC_CLASSES) / sizeof(ENC_REC_CLASSES[0])))
-#define ENC_NCLS    ((u32)(sizeof(ENC_CLASSES) / sizeof(ENC_CLASSES[0])))
-#define ENC_PK_NCLS ((u32)(sizeof(ENC_PK_CLASSES) / sizeof(ENC_PK_CLASSES[0])))
-// (kind: 0 u16 rows, 1 packed rows, ENC_KIND_PK_SHORT their short-index kind)
-static u32 enc_table_bytes(u32 kind) { return kind == ENC_KIND_PK_SHORT ? ENC_LFREQ_BYTES : kind == 1u ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES; }
+// the order-0 streams of the u16 rows (a 770-byte image and the ring) and of the records (a 4,352-byte image and the
+// ring) have a class of their own each: the kernels run a wave's order-1 streams, then its order-0 streams, and a class
+// that holds both - small order-1 alphabets make images as small as a one-row image - would pay both latencies
+static constexpr EncClass ENC_O0_ROWS[] = {{1296}}, ENC_O0_REC[] = {{8080, 5}};
+// The classes, group by group in the order of their ids: the kind the classifier matches (r4x16_common.h ENC_KIND_*),
+// the group's table (less: taken off every entry), what the route read-out counts its streams as (R4X16_ENC_*; freq: as
+// R4X16_ENC_PACKED_FREQ too).  Behind them the catch-all of images too large for LDS.
+struct EncGroup { u32 kind; const EncClass *cls; u32 n, less; int route; bool freq; };
+template <u32 N> static constexpr EncGroup enc_group(u32 kind, const EncClass (&cls)[N], u32 less, int route, bool freq = false) { return {kind, cls, N, less, route, freq}; }
+static constexpr EncGroup ENC_GROUPS[] = {
+    enc_group(ENC_KIND_U16, ENC_CLASSES, 0u, R4X16_ENC_U16),
+    enc_group(ENC_KIND_PACKED, ENC_PK_CLASSES, 0u, R4X16_ENC_PACKED),
+    enc_group(ENC_KIND_PK_SHORT, ENC_PK_CLASSES, ENC_PKS_LESS, R4X16_ENC_PACKED, true),
+    enc_group(ENC_KIND_RECORDS, ENC_REC_CLASSES, 0u, R4X16_ENC_RECORDS),
+    enc_group(ENC_KIND_U16_O0, ENC_O0_ROWS, 0u, R4X16_ENC_U16),
+    enc_group(ENC_KIND_RECORDS_O0, ENC_O0_REC, 0u, R4X16_ENC_RECORDS),
+};
+static constexpr u32 enc_ncls() { u32 n = 0; for (const EncGroup &g : ENC_GROUPS) n += g.n; return n; }
+static u32 enc_table_bytes(u32 kind) { return kind == ENC_KIND_PK_SHORT ? ENC_LFREQ_BYTES : kind == ENC_KIND_PACKED ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES; }
 static int enc_class_qpw(u32 bytes, u32 kind, const R4Opts *o)
 {
     const u32 room = 163840u - enc_table_bytes(kind);
@@ -61,11 +75,9 @@ __global__ __launch_bounds__(256) void k_enc_classify(const EncItem *items, int 
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     u32 c = CLS_NONE, len = 0;
     if (i < nitems && items[i].active) {
-        // kinds: 0 u16 rows, 1 packed rows, 2 symbol records; the order-0 streams of kinds 0 and 2 have classes of their
-        // own (kinds 3 and 4): the kernels run a wave's order-1 streams, then its order-0 streams, and a class that holds
-        // both kinds - small order-1 alphabets make images as small as a one-row image - would pay both latencies
+        // the kind of the image; the order-0 streams of the u16 rows and of the records have classes of their own (ENC_GROUPS)
         const u32 need = items[i].img_bytes + ENC_RING_BYTES, raw = items[i].packed,
-                  pk = items[i].order != 0 ? raw : raw == 0u ? 3u : raw == 2u ? 4u : raw;
+                  pk = items[i].order != 0 ? raw : raw == ENC_KIND_U16 ? ENC_KIND_U16_O0 : raw == ENC_KIND_RECORDS ? ENC_KIND_RECORDS_O0 : raw;
         c = tab.n;                                         // images too large for LDS (never a packed one)
         for (u32 k = 0; k < tab.n; k++) if (tab.pk[k] == pk && need <= tab.bytes[k]) { c = k; break; }
         len = items[i].n;
@@ -76,15 +88,10 @@ __global__ __launch_bounds__(256) void k_enc_classify(const EncItem *items, int 
 }
 // the shape of a class's launch: streams per workgroup, waves, streams per wave, LDS bytes
 struct EncShape { int qpw, waves, spw; size_t ldsb; u32 bytes; };
-#define ENC_O0_ROWS_BYTES 1296u      // order-0 streams with u16 rows: a 770-byte image and the ring
-#define ENC_O0_REC_BYTES  8080u      // order-0 streams with symbol records: a 4,352-byte image and the ring
-#define ENC_O0_REC_QPW    5
-// (cls: u16 classes, then the packed ones, then the packed ones of the short-index kind)
-static EncShape enc_rows_shape(u32 cls, int nitems, const R4Opts *o, u32 bytes_o0 = 0)
+// (kind: u16 rows of either order, packed rows, their short-index kind)
+static EncShape enc_rows_shape(u32 kind, u32 bytes, int nitems, const R4Opts *o)
 {
-    const u32 kind = bytes_o0 || cls < ENC_NCLS ? 0u : cls < ENC_NCLS + ENC_PK_NCLS ? 1u : ENC_KIND_PK_SHORT;
-    const u32 bytes = bytes_o0 ? bytes_o0 : kind == 0u ? ENC_CLASSES[cls] : kind == 1u ? ENC_PK_CLASSES[cls - ENC_NCLS] : enc_pks_class(cls - ENC_NCLS - ENC_PK_NCLS);
-    const u32 tuned = kind == 0u ? 4752u : kind == 1u ? 3536u : 3536u - ENC_PKS_LESS;       // the class of the 46-symbol quality tables
+    const u32 tuned = kind == ENC_KIND_PACKED ? 3536u : kind == ENC_KIND_PK_SHORT ? 3536u - ENC_PKS_LESS : 4752u;    // the class of the 46-symbol quality tables
     const int force_qpw = (int)o->v[OPT_ENC_QPW], force_waves = (int)o->v[OPT_ENC_WAVES];   // tuning aids
     int qpw = (force_qpw && bytes == tuned) ? force_qpw : enc_class_qpw(bytes, kind, o);
     // One workgroup per CU is the best shape (measured: 30 streams per CU as 1 x 32 beat 2 x 16 by a
@@ -104,10 +111,8 @@ static EncShape enc_rows_shape(u32 cls, int nitems, const R4Opts *o, u32 bytes_o
     sh.ldsb = (size_t)enc_table_bytes(kind) + (size_t)qpw * bytes;
     return sh;
 }
-static EncShape enc_rec_shape(u32 r, const R4Opts *o, bool o0 = false)
+static EncShape enc_rec_shape(const EncClass &c, const R4Opts *o)
 {
-    const EncRecClass c0 = {ENC_O0_REC_BYTES, ENC_O0_REC_QPW};
-    const EncRecClass &c = o0 ? c0 : ENC_REC_CLASSES[r];
     const int force_rec = (int)o->v[OPT_ENC_QPW_REC];     // tuning aid
     EncShape sh;
     sh.qpw = (force_rec > 0 && c.qpw > force_rec) ? force_rec : c.qpw;
@@ -118,7 +123,7 @@ static EncShape enc_rec_shape(u32 r, const R4Opts *o, bool o0 = false)
 extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t s0, const R4Fork *fk, const R4Opts *o, SchedHint *hint)
 {
     // the classes go out side by side or in stream order: sched_launch_classes (r4x16_sched.hip); class index ci =
-    // position in the classify table: u16 classes, packed classes, short-index packed classes, record classes
+    // position in the classify table: ENC_GROUPS' classes, group by group
     SchedLaunch todo[CLS_MAX];
     int ntodo = 0;
     EncClassTab tab;
@@ -137,13 +142,13 @@ extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t 
         if (!kern) return;
         todo[ntodo++] = SchedLaunch{kern, r4x16_resident_grid(sh.ldsb, sh.waves, (nitems + sh.qpw - 1) / sh.qpw), WAVE * sh.waves, sh.ldsb, ci, sh.qpw, sh.spw, sh.bytes};
     };
-    for (u32 k = 0; k < ENC_NCLS; k++) add(0, ENC_CLASSES[k], enc_rows_shape(k, nitems, o), (const void *)k_enc_chain<true, false>);
-    for (u32 k = 0; k < ENC_PK_NCLS; k++) add(1, ENC_PK_CLASSES[k], enc_rows_shape(ENC_NCLS + k, nitems, o), r4x16_enc_chain_pk_kernel(0));
-    for (u32 k = 0; k < ENC_PK_NCLS; k++) add(ENC_KIND_PK_SHORT, enc_pks_class(k), enc_rows_shape(ENC_NCLS + ENC_PK_NCLS + k, nitems, o), r4x16_enc_chain_pk_kernel(1));
-    // (record classes: only batches that leave LDS to spare make such images)
-    for (u32 k = 0; k < ENC_REC_NCLS; k++) add(2, ENC_REC_CLASSES[k].bytes, enc_rec_shape(k, o), ws->direct_budget ? r4x16_enc_chain_rec_kernel() : nullptr);
-    add(3, ENC_O0_ROWS_BYTES, enc_rows_shape(0, nitems, o, ENC_O0_ROWS_BYTES), (const void *)k_enc_chain<true, false>);
-    add(4, ENC_O0_REC_BYTES, enc_rec_shape(0, o, true), ws->direct_budget ? r4x16_enc_chain_rec_kernel() : nullptr);
+    for (const EncGroup &g : ENC_GROUPS) {
+        const bool rec = g.route == R4X16_ENC_RECORDS;       // (record classes: only batches that leave LDS to spare make such images)
+        const void *kern = rec ? (ws->direct_budget ? r4x16_enc_chain_rec_kernel() : nullptr) :
+                           g.route == R4X16_ENC_PACKED ? r4x16_enc_chain_pk_kernel(g.freq) : (const void *)k_enc_chain<true, false>;
+        for (u32 k = 0; k < g.n; k++)
+            add(g.kind, g.cls[k].bytes - g.less, rec ? enc_rec_shape(g.cls[k], o) : enc_rows_shape(g.kind, g.cls[k].bytes - g.less, nitems, o), kern);
+    }
     plan.ncls = tab.n;
     if (r4x16_first_on_device(FIRST_ENC_CHAIN)) {
         sched_lds_limit((const void *)k_enc_chain<true, false>, 163840);
@@ -160,7 +165,7 @@ extern "C" void r4x16_launch_enc_chain(const EncWs *ws, int nitems, hipStream_t 
     int qpw, spw, dyn = o->v[OPT_SCHED_CLAIM] != 0, aff_on = o->v[OPT_ENC_AFFINE] != 0;
     // the streams coded by the affine body are counted in the last word of the per-class counts, which no class uses: it
     // travels to the host with them (r4x16_route_snap)
-    static_assert(ENC_NCLS + 2u * ENC_PK_NCLS + ENC_REC_NCLS + 3u <= ENC_ROUTE_AFF_WORD, "a free word behind the classes' counts");
+    static_assert(enc_ncls() + 1u <= ENC_ROUTE_AFF_WORD, "a free word behind the counts of the classes and the catch-all");
     u32 *aff_count = o->v[OPT_ROUTE_COUNT] ? ws->sched.cnt + SCHED_COUNT + ENC_ROUTE_AFF_WORD : nullptr;
     void *args[] = {(void *)&items, (void *)&rcptab, (void *)&dump, (void *)&list, (void *)&cnt, (void *)&qpw, (void *)&spw, (void *)&bytes, (void *)&dyn,
                     (void *)&aff_on, (void *)&aff_count};
@@ -181,20 +186,17 @@ extern "C" u32 r4x16_enc_direct_budget(int nblk, const R4Opts *o)
         if ((long)sched_resident_per_cu((size_t)c.qpw * c.bytes, 1) * c.qpw >= per_cu && c.bytes > best) best = c.bytes;
     return best;
 }
-// The row kind of a class id of r4x16_launch_enc_chain's table (u16 classes, packed classes of both kinds, record classes,
-// then the order-0 u16 class, the order-0 record class and the catch-all of images too large for LDS) as the route read-out
-// counts it (include/rans4x16_hip.h R4X16_ENC_*: 0 u16 rows, 1 packed rows, 2 symbol records); -1 beyond the table.
+// The row kind of a class id of r4x16_launch_enc_chain's table (ENC_GROUPS' classes, then the catch-all of images too
+// large for LDS: u16 rows) as the route read-out counts it (include/rans4x16_hip.h R4X16_ENC_*); -1 beyond the table.
 // *freq_table: the class is of the short-index kind (counted as R4X16_ENC_PACKED_FREQ as well).
 extern "C" int r4x16_enc_route_kind(u32 ci, int *freq_table)
 {
-    *freq_table = ci >= ENC_NCLS + ENC_PK_NCLS && ci < ENC_NCLS + 2u * ENC_PK_NCLS;
-    if (ci < ENC_NCLS) return 0;
-    ci -= ENC_NCLS;
-    if (ci < 2u * ENC_PK_NCLS) return 1;
-    ci -= 2u * ENC_PK_NCLS;
-    if (ci < ENC_REC_NCLS) return 2;
-    ci -= ENC_REC_NCLS;
-    return ci == 0 ? 0 : ci == 1 ? 2 : ci == 2 ? 0 : -1;
+    *freq_table = 0;
+    for (const EncGroup &g : ENC_GROUPS) {
+        if (ci < g.n) { *freq_table = g.freq; return g.route; }
+        ci -= g.n;
+    }
+    return ci == 0 ? R4X16_ENC_U16 : -1;
 }
 // Streams per CU of the record class a stream lands in when the batch's budget admits records (r4x16_enc_direct_budget and
 // the front's choice, r4x16_encode.hip); -1 where its image can never be records.
@@ -220,11 +222,12 @@ extern "C" int r4x16_enc_residency(u32 nsym, int order, int *streams_per_wave, i
     //  hold as many streams or more)
     const bool pk = order && nsym >= ENC_PK_MIN_NS && nsym <= ENC_PK_MAX_NS;
     const u32 need = (pk ? enc_pk_img_bytes(nsym) : order ? ENC_IMG_IDX + 2u * nsym * (nsym + 1) : ENC_IMG_IDX + 2u * 257u) + ENC_RING_BYTES;
-    for (u32 cls = 0; cls < ENC_NCLS + ENC_PK_NCLS; cls++) {
-        if ((cls >= ENC_NCLS) != pk) continue;
-        const u32 bytes = pk ? ENC_PK_CLASSES[cls - ENC_NCLS] : ENC_CLASSES[cls];
-        if (need > bytes) continue;
-        const int qpw = enc_class_qpw(bytes, pk ? 1u : 0u, r4x16_opts_defaults());
+    const EncGroup &g = ENC_GROUPS[pk ? 1 : 0];
+    static_assert(ENC_GROUPS[0].kind == ENC_KIND_U16 && ENC_GROUPS[1].kind == ENC_KIND_PACKED, "the groups of order-1 rows come first");
+    for (u32 k = 0; k < g.n; k++) {
+        const EncClass &c = g.cls[k];
+        if (need > c.bytes) continue;
+        const int qpw = enc_class_qpw(c.bytes, g.kind, r4x16_opts_defaults());
         int waves = (qpw + 7) / 8;
         if (waves > 4) waves = 4;
         *streams_per_wave = (qpw + waves - 1) / waves;

@@ -1159,7 +1159,7 @@ __global__ __launch_bounds__(FRONT_THREADS) void k_enc_front(BatchArgs a, EncWs 
                         if (S.status != ST_OK) D->status = S.status;
                         I1->data = (u64)m; I1->n = mlen; I1->image = (u64)imgm; I1->bits = O0_BITS; I1->order = 0;
                         I1->ns = 256; I1->img_bytes = mrec ? enc_rec_img_bytes(256u, 1u) : ENC_IMG_IDX + 2u * 257u;
-                        I1->packed = mrec ? 2u : 0u; I1->affine = mrec ? 1u : 0u;
+                        I1->packed = mrec ? ENC_KIND_RECORDS : ENC_KIND_U16; I1->affine = mrec ? 1u : 0u;
                         I1->scratch_end = (u64)(var + V.total);
                         I1->active = S.status == ST_OK;
                     }
@@ -1328,7 +1328,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
             D->tab_len = S.tab_len;
             I0->data = (u64)data; I0->n = n; I0->image = (u64)img; I0->bits = O0_BITS; I0->order = 0;
             I0->ns = 256; I0->img_bytes = rec ? enc_rec_img_bytes(256u, 1u) : ENC_IMG_IDX + 2u * 257u;
-            I0->packed = rec ? 2u : 0u;
+            I0->packed = rec ? ENC_KIND_RECORDS : ENC_KIND_U16;
             I0->affine = rec ? 1u : 0u;                    // order 0: symbols index the records directly
             I0->scratch_end = (u64)scratch_end;
             I0->active = S.status == ST_OK;
@@ -1554,7 +1554,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_tables(BatchArgs a, EncWs ws, int 
         D->tab_len = final_len;
         I0->data = (u64)data; I0->n = n; I0->image = (u64)img; I0->bits = bits; I0->order = 1;
         I0->ns = ns; I0->img_bytes = recs ? enc_rec_img_bytes(ns, ns) : packed ? enc_pk_img_bytes(ns, idxb) : ENC_IMG_IDX + 2u * ns * (ns + 1);
-        I0->packed = recs ? 2u : !packed ? 0u : idxb == ENC_IMG_IDX_SHORT ? ENC_KIND_PK_SHORT : 1u;
+        I0->packed = recs ? ENC_KIND_RECORDS : !packed ? ENC_KIND_U16 : idxb == ENC_IMG_IDX_SHORT ? ENC_KIND_PK_SHORT : ENC_KIND_PACKED;
         I0->affine = aff;
         I0->scratch_end = (u64)scratch_end;
         I0->active = 1;
