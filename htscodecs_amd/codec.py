@@ -146,7 +146,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc", "fqz_pick") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -158,7 +158,7 @@ class _Ctx:
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
-               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10}
+               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10, "fqz_pick": 11}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -171,6 +171,7 @@ ROUTE_KINDS = {
     "fqz": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
     "encode_body": ("packed_affine",),
     "fqz_enc": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
+    "fqz_pick": ("blocks", "sel", "split", "dedup", "undecided", "host"),
 }
 
 _tls = threading.local()
@@ -566,6 +567,11 @@ def fqz_compress_cap(size, nrec, params_size):
     return _lib.load().rans4x16_hip_fqz_compress_cap(int(size), int(nrec), int(params_size))
 
 
+def fqz_pick_cap():
+    """rans4x16_hip_fqz_pick_cap: a parameter slot of this many bytes holds whatever the device pick writes."""
+    return _lib.load().rans4x16_hip_fqz_pick_cap()
+
+
 def fqz_compress_batch(blocks, lens, flags, vers=4, strat=0, params=None, caps=None, ctx=None):
     """rans4x16_hip_fqz_compress_batch: quality blocks (bytes) with their record lengths and flags -> (list of bytes | None,
     statuses, lens, flags as the call leaves them).  params: None, or per block None (picked on the host with vers and
@@ -835,6 +841,51 @@ class DeviceCodec:
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             int(max_in_size), int(max_params_size), int(max_records), self._stream())
         self._check(rc, "fqz_compress_dev")
+
+    # ---- fqzcomp_qual encoding: the parameter choice on the device (include/rans4x16_hip.h part 2k) -----------------------
+    def set_fqz_pick(self, mode=0, guard_bits=0):
+        """rans4x16_hip_set_fqz_pick: mode 1 makes fqz_compress_batch on this context pick on the device; guard_bits
+        widens the guard of every device pick by 2^guard_bits."""
+        if self.L.rans4x16_hip_set_fqz_pick(self.ctx.h, int(mode), int(guard_bits)) != 0:
+            raise ValueError("set_fqz_pick: " + self.ctx.error())
+
+    def _pick_args(self, d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_strat):
+        t = self.torch
+        assert d_in.dtype == t.uint8 and in_off.dtype == t.int64 and in_size.dtype == t.int32 and rec_off.dtype == t.int64
+        assert nrec.dtype == t.int32 and d_len.dtype == t.int32 and d_flags.dtype == t.int32
+        assert d_strat is None or d_strat.dtype == t.int32
+
+    def fqz_pick(self, d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_params, par_off, par_cap, par_size,
+                 d_len_out, d_flags_out, status, max_in_size, max_records, vers=4, strat=0, d_strat=None):
+        """rans4x16_hip_fqz_pick_dev: per block the qualities and the records (as in fqz_compress) -> its parameter bytes
+        (uint8 at par_off, int64, up to par_cap, int32; the size in par_size) and its slice as the pick leaves it in
+        d_len_out / d_flags_out (int32; may be d_len / d_flags).  d_strat: per-block strategies (int32).  Enqueues only."""
+        t = self.torch
+        self._pick_args(d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_strat)
+        assert d_params.dtype == t.uint8 and par_off.dtype == t.int64 and par_cap.dtype == t.int32 and par_size.dtype == t.int32
+        assert d_len_out.dtype == t.int32 and d_flags_out.dtype == t.int32 and status.dtype == t.int32
+        rc = self.L.rans4x16_hip_fqz_pick_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_len.data_ptr(), d_flags.data_ptr(), rec_off.data_ptr(), nrec.data_ptr(),
+            int(vers), int(strat), d_strat.data_ptr() if d_strat is not None else None,
+            d_params.data_ptr(), par_off.data_ptr(), par_cap.data_ptr(), par_size.data_ptr(),
+            d_len_out.data_ptr(), d_flags_out.data_ptr(), status.data_ptr(),
+            int(max_in_size), int(max_records), self._stream())
+        self._check(rc, "fqz_pick_dev")
+
+    def fqz_compress_pick(self, d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_out, out_off, out_cap, out_size,
+                          status, max_in_size, max_records, vers=4, strat=0, d_strat=None):
+        """rans4x16_hip_fqz_compress_pick_dev: the device pick and fqz_compress in one call; the caller's records are only
+        read.  Enqueues only."""
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
+        self._pick_args(d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_strat)
+        rc = self.L.rans4x16_hip_fqz_compress_pick_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_len.data_ptr(), d_flags.data_ptr(), rec_off.data_ptr(), nrec.data_ptr(),
+            int(vers), int(strat), d_strat.data_ptr() if d_strat is not None else None,
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            int(max_in_size), int(max_records), self._stream())
+        self._check(rc, "fqz_compress_pick_dev")
 
     # ---- what the methods share: the dtypes of either form's arrays, and the end of every call ----------------------
     def _slot_args(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status):

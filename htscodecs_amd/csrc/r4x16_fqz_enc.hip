@@ -23,10 +23,6 @@
 #include "r4x16_fqz_pick.h"
 #include "r4x16_arith_enc_step.h"
 
-struct FqeIn {              // what the call takes beside the slot arguments
-    const u8 *par; const u64 *par_off; const u32 *par_size;
-    const u32 *len, *flags; const u64 *rec_off; const u32 *nrec;
-};
 struct FqeBlk {
     i32 status; u32 size, gflags, nparam;
     u32 max_sel, max_sym, home, nrec;
@@ -374,6 +370,39 @@ static size_t fqe_layout(u8 *base, size_t nb, u64 stage_bytes, size_t slots, u64
     return cv.total();
 }
 
+// One chunk of nb blocks, blocks base .. base + nb of the arrays in `a` and `in`, laid out at `at` (r4x16_host.h: the
+// device call below, and the one-call form of r4x16_fqz_pick.hip behind its pick).  The stage arena: a selector table a
+// block, room for four parameter blocks a block with their inverse maps (256, one block's most, at least), and a block's
+// coder-order copy and its body at the bound.
+static size_t fqe_chunk_layout(rans4x16_hip_ctx *c, u8 *at, size_t nb, u32 max_in_size, u32 max_records, FqeWs *w)
+{
+    const u64 slot_bytes = fq_slot_bytes((u32)c->fqz_max_sym);
+    const size_t max_slots = c->fqz_slots > 0 ? (size_t)c->fqz_slots : (size_t)FQ_MAX_SLOTS;
+    const u64 per_block = (u64)ar_r16(max_in_size) + ((fqe_body_bound(max_in_size, max_records) + 48u + 15u) & ~15ull) + 64u;
+    const u64 stage = (u64)nb * FQ_STAB_BYTES + (u64)std::max<size_t>(4 * nb, 256) * (FQ_PARAM_BYTES + 256u) + (u64)nb * per_block;
+    return fqe_layout(at, nb, stage, std::min(nb, max_slots), slot_bytes, w);
+}
+size_t r4x16_fqe_chunk_bytes(rans4x16_hip_ctx *c, size_t nb, u32 max_in_size, u32 max_records)
+{
+    FqeWs w;
+    return fqe_chunk_layout(c, nullptr, nb, max_in_size, max_records, &w);
+}
+int r4x16_fqe_chunk(rans4x16_hip_ctx *c, const BatchArgs &a, const FqeIn &in, u8 *at, int base, int nb, u32 max_in_size, u32 max_params_size,
+                    u32 max_records, hipStream_t s)
+{
+    FqeWs w;
+    fqe_chunk_layout(c, at, (size_t)nb, max_in_size, max_records, &w);
+    w.max_sym = (u32)c->fqz_max_sym;
+    u32 *const d_route = w.route;
+    HIPCHK(c, hipMemsetAsync(w.cursor, 0, sizeof(u64), s));
+    if (r4x16_route_begin(c, &w.route, R4X16_FQZ_ENC_KINDS, s) != 0) return -1;
+    hipLaunchKernelGGL(k_fqe_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, in, w, base, nb, max_in_size, max_params_size, max_records);
+    hipLaunchKernelGGL(k_fqe_encode<true>, dim3(w.slots), dim3(64), 0, s, a, in, w, base, nb);
+    hipLaunchKernelGGL(k_fqe_encode<false>, dim3(w.slots), dim3(64), 0, s, a, in, w, base, nb);
+    hipLaunchKernelGGL(k_fqe_back, dim3(nb), dim3(256), 0, s, a, in, w, base);
+    return r4x16_route_end(c, R4X16_ROUTE_FQZ_ENC, d_route, R4X16_FQZ_ENC_KINDS, s);
+}
+
 extern "C" unsigned int rans4x16_hip_fqz_compress_cap(unsigned int size, unsigned int nrec, unsigned int params_size)
 {
     const u64 v = fqe_cap(size, nrec, params_size);
@@ -395,30 +424,11 @@ extern "C" int rans4x16_hip_fqz_compress_dev(rans4x16_hip_ctx *c, int n,
     if (go <= 0) return go;
     hipStream_t s = (hipStream_t)stream;
     const FqeIn in{d_params, d_par_off, d_par_size, d_len, d_flags, d_rec_off, d_nrec};
-    const u64 slot_bytes = fq_slot_bytes((u32)c->fqz_max_sym);
-    const size_t max_slots = c->fqz_slots > 0 ? (size_t)c->fqz_slots : (size_t)FQ_MAX_SLOTS;
-    // the stage arena: a selector table a block, room for four parameter blocks a block with their inverse maps (256,
-    // one block's most, at least), and a block's coder-order copy and its body at the bound
-    const u64 per_block = (u64)ar_r16(max_in_size) + ((fqe_body_bound(max_in_size, max_records) + 48u + 15u) & ~15ull) + 64u;
-    FqeWs w;
-    auto layout = [&](u8 *at, size_t nb) {
-        const u64 stage = (u64)nb * FQ_STAB_BYTES + (u64)std::max<size_t>(4 * nb, 256) * (FQ_PARAM_BYTES + 256u) + (u64)nb * per_block;
-        return fqe_layout(at, nb, stage, std::min(nb, max_slots), slot_bytes, &w);
-    };
-    auto bytes_for = [&](size_t nb) { return layout(nullptr, nb); };
+    auto bytes_for = [&](size_t nb) { return r4x16_fqe_chunk_bytes(c, nb, max_in_size, max_records); };
     const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX, r4x16_room(c, A_BIT(A_AR)), bytes_for);
     auto grab = [&](size_t nb) { return r4x16_ensure(c, A_AR, bytes_for(nb), false); };
     return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
-        layout(c->at(A_AR), (size_t)nb);
-        w.max_sym = (u32)c->fqz_max_sym;
-        u32 *const d_route = w.route;
-        HIPCHK(c, hipMemsetAsync(w.cursor, 0, sizeof(u64), s));
-        if (r4x16_route_begin(c, &w.route, R4X16_FQZ_ENC_KINDS, s) != 0) return -1;
-        hipLaunchKernelGGL(k_fqe_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, in, w, (int)base, nb, max_in_size, max_params_size, max_records);
-        hipLaunchKernelGGL(k_fqe_encode<true>, dim3(w.slots), dim3(64), 0, s, a, in, w, (int)base, nb);
-        hipLaunchKernelGGL(k_fqe_encode<false>, dim3(w.slots), dim3(64), 0, s, a, in, w, (int)base, nb);
-        hipLaunchKernelGGL(k_fqe_back, dim3(nb), dim3(256), 0, s, a, in, w, (int)base);
-        return r4x16_route_end(c, R4X16_ROUTE_FQZ_ENC, d_route, R4X16_FQZ_ENC_KINDS, s);
+        return r4x16_fqe_chunk(c, a, in, c->at(A_AR), (int)base, nb, max_in_size, max_params_size, max_records, s);
     });
 }
 
@@ -437,6 +447,57 @@ extern "C" int rans4x16_hip_fqz_pick_parameters(int vers, int strat, int nrec, u
     if (out.size() > params_cap || !params) return R4X16_E_CAPACITY;
     memcpy(params, out.data(), out.size());
     for (int i = 0; i < nrec; i++) { len[i] = L[i]; flags[i] = F[i]; }
+    return 0;
+}
+
+// ---- host buffers: the trip with the device pick (rans4x16_hip_set_fqz_pick mode 1) -------------------------------
+// The blocks of `todo` in one round trip of their own: behind the inputs go the places of the records (8 bytes each),
+// the record counts, the lengths and the flags (4 bytes each); behind the outputs come the lengths as the pick left
+// them.  A block the device pick leaves undecided goes back into todo with its capacity, for the host; every other
+// block of the trip is done, whatever its status.  The model slots are as rans4x16_hip_set_fqz_limits sized them: the
+// pick's max_sym is not known here.
+static int fqe_pick_trip(rans4x16_hip_ctx *c, int n, const unsigned char *const *in, const unsigned int *in_size, const unsigned int *nrec,
+                         uint32_t *const *len, uint32_t *const *flags, int vers, int strat, unsigned char *const *out, unsigned int *out_size,
+                         int *status, std::vector<int> &todo, std::vector<u8> &done)
+{
+    const size_t N = (size_t)n;
+    std::vector<u32> isz(n, 0), cap(n, 0), nr(n, 0);
+    std::vector<u8> take(n, 0);
+    u32 max_in = 0, max_rec = 0;
+    u64 nrecs = 0;
+    for (int i : todo) {
+        take[i] = 1; isz[i] = in_size[i]; cap[i] = out_size[i]; nr[i] = nrec[i];
+        max_in = std::max(max_in, isz[i]); max_rec = std::max(max_rec, nr[i]);
+        nrecs += nr[i];
+    }
+    std::vector<u8> tail(12 * N + 8 * (size_t)nrecs, 0), back;
+    u64 *const t_rec_off = (u64 *)tail.data();
+    u32 *const t_nrec = (u32 *)(t_rec_off + N), *const t_len = t_nrec + N, *const t_flags = t_len + nrecs;
+    u64 at_rec = 0;
+    for (int i = 0; i < n; i++) {
+        t_rec_off[i] = at_rec;
+        if (!take[i]) continue;
+        t_nrec[i] = nr[i];
+        if (nr[i]) { memcpy(t_len + at_rec, len[i], 4 * (size_t)nr[i]); memcpy(t_flags + at_rec, flags[i], 4 * (size_t)nr[i]); }
+        at_rec += nr[i];
+    }
+    const HostTrip trip = {in, out, out_size, status, take.data(), isz.data(), cap.data(), nullptr, tail.data(), tail.size(), 4 * (size_t)nrecs, &back};
+    const int rc = r4x16_host_trip(c, n, trip, [&](const StageLayout &L, size_t in_total, size_t out_total, hipStream_t s) {
+        const u8 *d_tail = L.in + in_total;
+        const u64 *d_rec_off = (const u64 *)d_tail;
+        const u32 *d_nrec = (const u32 *)(d_rec_off + N), *d_len = d_nrec + N, *d_flags = d_len + nrecs;
+        return r4x16_fqz_compress_pick_run(c, n, L.in, L.in_off, L.in_size, d_len, d_flags, d_rec_off, d_nrec, vers, strat, nullptr, L.out,
+                                           L.out_off, L.cap, L.osz, L.status, (u32 *)(L.out + out_total), max_in, max_rec, s);
+    });
+    if (rc < 0) return -1;
+    std::vector<int> host;
+    for (int i : todo) {
+        if (status[i] == R4X16_E_UNDECIDED) { status[i] = 0; out_size[i] = cap[i]; host.push_back(i); continue; }
+        done[i] = 1;
+        if (status[i] == 0 && nr[i] && back.size() >= 4 * (size_t)nrecs) memcpy(len[i], back.data() + 4 * t_rec_off[i], 4 * (size_t)nr[i]);
+    }
+    if (c->opts.v[OPT_ROUTE_COUNT]) c->route[R4X16_ROUTE_FQZ_PICK][R4X16_FQZ_PICK_HOST] += (long)host.size();
+    todo.swap(host);
     return 0;
 }
 
@@ -461,6 +522,7 @@ extern "C" int rans4x16_hip_fqz_compress_batch(rans4x16_hip_ctx *c, int n,
     std::vector<std::vector<uint8_t>> picked(n);
     std::vector<const u8 *> par(n, nullptr);
     std::vector<u32> psz(n, 0);
+    std::vector<u8> done(n, 0);                                      // coded by the trip with the device pick
     // the picks
     {
         std::vector<int> todo;
@@ -470,6 +532,8 @@ extern "C" int rans4x16_hip_fqz_compress_batch(rans4x16_hip_ctx *c, int n,
             else if (params && params[i]) { par[i] = params[i]; psz[i] = params_size[i]; }
             else todo.push_back(i);
         }
+        // rans4x16_hip_set_fqz_pick mode 1: one trip picks and codes them on the device; what it leaves undecided the host picks
+        if (c->fqz_pick == 1 && !todo.empty() && fqe_pick_trip(c, n, in, in_size, nrec, len, flags, vers, strat, out, out_size, status, todo, done) != 0) return -1;
         std::atomic<size_t> next{0};
         auto work = [&]() {
             for (size_t k; (k = next.fetch_add(1)) < todo.size();) {
@@ -493,6 +557,7 @@ extern "C" int rans4x16_hip_fqz_compress_batch(rans4x16_hip_ctx *c, int n,
     for (int i = 0; i < n; i++) {
         FqTop top;
         FqNoSink none;
+        if (done[i]) continue;
         if (status[i] == 0) status[i] = fqe_parse(par[i], psz[i], &top, none);
         if (status[i] != 0) { out_size[i] = 0; continue; }
         take[i] = 1; isz[i] = in_size[i]; cap[i] = out_size[i];
@@ -518,7 +583,7 @@ extern "C" int rans4x16_hip_fqz_compress_batch(rans4x16_hip_ctx *c, int n,
         at_rec += nr[i]; at_par += psz[i];
     }
     const HostTrip trip = {in, out, out_size, status, take.data(), isz.data(), cap.data(), nullptr, tail.data(), tail.size(), 0, nullptr};
-    const int bad = r4x16_host_trip(c, n, trip, [&](const StageLayout &L, size_t in_total, size_t, hipStream_t s) {
+    int bad = r4x16_host_trip(c, n, trip, [&](const StageLayout &L, size_t in_total, size_t, hipStream_t s) {
         Keep<int> limit(c->fqz_max_sym, (int)std::max(max_sym, 1u));
         const u8 *d_tail = L.in + in_total;                          // (in_total: a multiple of 16 in an arena aligned to 256)
         const u64 *d_par_off = (const u64 *)d_tail, *d_rec_off = d_par_off + N;
@@ -530,6 +595,7 @@ extern "C" int rans4x16_hip_fqz_compress_batch(rans4x16_hip_ctx *c, int n,
     // the reference clears the selectors it kept in the flags (:1142-1144)
     for (int i = 0; i < n; i++)
         if (len[i] && flags[i]) for (u32 r = 0; r < nrec[i]; r++) flags[i][r] &= 0xffffu;
+    if (bad >= 0 && std::find(done.begin(), done.end(), 1) != done.end()) bad = (int)(n - std::count(status, status + n, 0));
     return bad;
 }
 

@@ -206,6 +206,13 @@ static inline void fqp_qual_stats(int nrec, const uint32_t *len, uint32_t *flags
     }
 }
 
+// pshift where the strategy leaves it to the first record's length (:840-841)
+static inline int fqp_pshift(uint32_t first_len, int pbits)
+{
+    const double v = log((double)first_len / (1 << pbits)) / log(2) + .5;
+    return (int)(0 > v ? 0 : v);
+}
+
 // fqz_pick_parameters + fqz_store_parameters.  len and flags are the caller's and are only read: L and F take the slice as
 // the reference leaves it (on success), out the parameter bytes.
 static inline int fqp_pick(int vers, int strat, int nrec, const uint32_t *len, const uint32_t *flags, const uint8_t *in, size_t in_size,
@@ -254,10 +261,7 @@ static inline int fqp_pick(int vers, int strat, int nrec, const uint32_t *len, c
     pm->fixed_len = (i == (size_t)nrec);                             // (no record at all: 1 != 0, not fixed)
     pm->use_qtab = 0;
     if (strat < FQP_NSTRATS - 1) {
-        if (pm->pshift < 0) {
-            const double v = log((double)first_len / (1 << pm->pbits)) / log(2) + .5;
-            pm->pshift = (int)(0 > v ? 0 : v);
-        }
+        if (pm->pshift < 0) pm->pshift = fqp_pshift(first_len, pm->pbits);
         if (pm->nsym <= 4) {
             pm->qshift = 2;
             if (in_size < 5000000) { pm->pbits = 2; pm->pshift = 5; }

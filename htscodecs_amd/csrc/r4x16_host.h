@@ -68,7 +68,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 11
+#define ROUTE_WHICH 12
 // R4X16_ROUTE_ENCODE_BODY rides on the encode chain's copy: the word of the per-class counts that k_enc_chain's affine
 // waves count their streams in (no launch has that many classes; r4x16_enc_chain.hip)
 #define ENC_ROUTE_AFF_WORD (CLS_MAX - 1u)
@@ -176,6 +176,22 @@ int r4x16_packed_call_args(rans4x16_hip_ctx *c, const char *bad, bool ok, BatchA
 // as launched in order.
 int r4x16_route_begin(rans4x16_hip_ctx *c, u32 **kernels, u32 words, hipStream_t s);
 int r4x16_route_end(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words, hipStream_t s);
+// fqzcomp_qual encoding (r4x16_fqz_enc.hip): what the call takes beside the slot arguments, the arena bytes of a chunk of nb
+// blocks, and one chunk's front / encode / back stages laid out at `at` - the device call's, and what the one-call form
+// with the pick in front (r4x16_fqz_pick.hip) runs behind its pick
+struct FqeIn {
+    const u8 *par; const u64 *par_off; const u32 *par_size;
+    const u32 *len, *flags; const u64 *rec_off; const u32 *nrec;
+};
+size_t r4x16_fqe_chunk_bytes(rans4x16_hip_ctx *c, size_t nb, u32 max_in_size, u32 max_records);
+int r4x16_fqe_chunk(rans4x16_hip_ctx *c, const BatchArgs &a, const FqeIn &in, u8 *at, int base, int nb, u32 max_in_size, u32 max_params_size,
+                    u32 max_records, hipStream_t s);
+// the device pick with the lengths' way back (r4x16_fqz_pick.hip): rans4x16_hip_fqz_compress_pick_dev, and d_len_out
+// (may be null) for the host-buffer batch
+int r4x16_fqz_compress_pick_run(rans4x16_hip_ctx *c, int n, const u8 *d_in, const u64 *d_in_off, const u32 *d_in_size, const u32 *d_len,
+                                const u32 *d_flags, const u64 *d_rec_off, const u32 *d_nrec, int vers, int strat, const i32 *d_strat,
+                                u8 *d_out, const u64 *d_out_off, const u32 *d_out_cap, u32 *d_out_size, i32 *d_status, u32 *d_len_out,
+                                u32 max_in_size, u32 max_records, hipStream_t s);
 // One round trip of a host-buffer batch of these coders: the taken blocks' bytes in one upload (slots of the size rounded
 // up to 16 - a block that is not taken has size and capacity 0 and takes none - and up_tail behind them), the device
 // call on the staged layout, one download (the outputs, and down_tail bytes behind them, handed back in *down_tail), the
@@ -217,6 +233,7 @@ struct rans4x16_hip_ctx {
     bool in_stripe = false;                 // inside the recursive call over the internal items
     bool in_packed = false;                 // inside a packed call's slot call over its internal slots (r4x16_packed.hip)
     int tok3_arith = 0;                     // tok3 calls: R4X16_TOK3_ARITH_* (rans4x16_hip_set_tok3_arith); 0: the rANS flavour alone
+    int fqz_pick = 0, fqz_guard_bits = 0;   // fqzcomp_qual encoding: 1: host batches pick on the device; the guard times 2^guard_bits (rans4x16_hip_set_fqz_pick)
     int fqz_slots = 0, fqz_max_sym = 255;   // fqzcomp_qual: model slots in flight at most (0: 1024), the largest max_sym a slot holds (rans4x16_hip_set_fqz_limits)
     int names_chunk_blocks = 0;             // host-buffer names batches: blocks per chunk at most (rans4x16_hip_set_names_chunk_blocks)
     // calls on different streams are ordered on the one workspace through this event

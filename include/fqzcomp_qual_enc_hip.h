@@ -13,8 +13,9 @@
  * `in` is not modified.
  * gp must be NULL, as htslib passes it: fqz_gparams is opaque here, and a non-NULL gp returns NULL.  A caller with
  * parameters of its own hands them to rans4x16_hip_fqz_compress_batch as parameter bytes.
- * fqz_qual_stats and the test program's fqz_manual_parameters are not built; the parameter choice alone is
- * rans4x16_hip_fqz_pick_parameters.
+ * fqz_qual_stats as a call of its own and the test program's fqz_manual_parameters are not built; the parameter choice
+ * alone is rans4x16_hip_fqz_pick_parameters, and over slices in device memory rans4x16_hip_fqz_pick_dev
+ * (include/rans4x16_hip.h part 2k).  This call picks on the host whatever rans4x16_hip_set_fqz_pick says.
  */
 #ifndef FQZCOMP_QUAL_ENC_HIP_H
 #define FQZCOMP_QUAL_ENC_HIP_H

@@ -10,7 +10,7 @@
  *
  * This header is the reader's: it declares the decoder alone.  A program that writes quality blocks includes
  * fqzcomp_qual_enc_hip.h, which includes this header and adds the reference's encode call with fqz_slice, the FQZ_F*
- * flags and FQZ_MAX_STRAT (include/rans4x16_hip.h part 2j).  fqz_qual_stats is not built.
+ * flags and FQZ_MAX_STRAT (include/rans4x16_hip.h part 2j).  fqz_qual_stats as a call of its own is not built (the pick runs it: part 2j on the host, part 2k on the device).
  */
 #ifndef FQZCOMP_QUAL_HIP_H
 #define FQZCOMP_QUAL_HIP_H

@@ -66,7 +66,8 @@ enum {
     R4X16_E_UNSUPPORTED = 6,   /* valid-looking stream this build does not handle */
     R4X16_E_CONTEXT     = 7,   /* order-1 stream used a context that has no table row             */
     R4X16_E_RLE         = 8,   /* run-length expansion overran the output                         */
-    R4X16_E_EMPTY       = 9    /* zero-length compressed input                                    */
+    R4X16_E_EMPTY       = 9,   /* zero-length compressed input                                    */
+    R4X16_E_UNDECIDED   = 10   /* fqz pick on the device: a decision too close to call (part 2k)  */
 };
 
 /* One context per (host thread, device).  device < 0 selects the current HIP device.
@@ -841,7 +842,8 @@ int rans4x16_hip_fqz_uncompress_batch(rans4x16_hip_ctx *ctx, int n,
 char *rans4x16_hip_fqz_decompress(char *in, size_t comp_size, size_t *uncomp_size, int *lengths, int nlengths);
 
 /* ---- 2j. fqzcomp_qual encoding (fqz_compress) ---------------------------------------------------------------------
- * htscodecs/fqzcomp_qual.c's encoder: the parameter choice on the host, the encode loop on the device.  DESIGN.md 4.9.
+ * htscodecs/fqzcomp_qual.c's encoder: the parameter choice on the host (on the device: part 2k), the encode loop on the
+ * device.  DESIGN.md 4.9.
  *
  * PARAMETER BYTES are the parameter format of every call here: what fqz_store_parameters writes and a stream holds
  * between its size varint and the range coder's bytes - the version byte (5), gflags, [nparam], [max_sel, the selector
@@ -913,6 +915,69 @@ int rans4x16_hip_fqz_compress_batch(rans4x16_hip_ctx *ctx, int n,
                                     unsigned char *const *out, unsigned int *out_size, int *status);
 char *rans4x16_hip_fqz_compress(int vers, rans4x16_hip_fqz_slice *s, char *in, size_t in_size, size_t *out_size, int strat,
                                 struct rans4x16_hip_fqz_gparams *gp);
+
+/* ---- 2k. fqzcomp_qual encoding: the parameter choice on the device ---------------------------------------------------
+ * fqz_qual_stats(.., one_param = -1), fqz_pick_parameters and fqz_store_parameters over slices in DEVICE memory: what
+ * rans4x16_hip_fqz_pick_parameters computes, byte for byte - the parameter bytes, the lengths after the fix-ups, the
+ * selector in flags[rec] >> 16 - or no answer at all.  DESIGN.md 4.9 and 5.
+ *
+ * The choice compares sums of v * log(v / c) in doubles.  The device's log and its order of summation are not the
+ * host's, so the device takes a comparison only where its two sides differ by more than a guard that bounds both
+ * errors (2^-20 of the sum of the terms' magnitudes; a comparison of exact zeros is exact), and `pshift` of strategy 0
+ * only for a first record below 2^22 bytes.  Otherwise the block's status is R4X16_E_UNDECIDED, nothing is written for
+ * it, and the caller picks that block with rans4x16_hip_fqz_pick_parameters.
+ *
+ * rans4x16_hip_fqz_pick_dev only enqueues on `stream` and reads nothing back.  Inputs and records as in
+ * rans4x16_hip_fqz_compress_dev, flags as the caller has them (a selector of the caller's from bit 16 up is kept and
+ * OR-ed onto, as the reference does).  vers, strat as in rans4x16_hip_fqz_pick_parameters; d_strat (may be NULL) gives
+ * block i the strategy d_strat[i] - one call can hold the same slice under several.  Block i gets its parameter bytes in
+ * [d_par_off[i], + d_par_cap[i]) of d_params and their size in d_par_size[i], and its slice as the pick leaves it in
+ * d_len_out / d_flags_out at the entries d_rec_off[i] .. + d_nrec[i].  d_len_out / d_flags_out may be the very pointers
+ * d_len / d_flags; they may not overlap the inputs otherwise.  d_status[i]:
+ *   R4X16_E_CAPACITY     d_par_cap[i] is too small: d_par_size[i] is the size needed, nothing else is written.
+ *                        rans4x16_hip_fqz_pick_cap() bytes always do
+ *   R4X16_E_UNSUPPORTED  a block above max_in_size or max_records, of 2^31 bytes or more, a negative strategy (not read)
+ *   R4X16_E_UNDECIDED    see above
+ * On any status but 0 the block's d_len_out / d_flags_out entries and its parameter slot are untouched, and
+ * d_par_size[i] is 0 (the size needed under R4X16_E_CAPACITY).
+ *
+ * rans4x16_hip_fqz_compress_pick_dev: the pick and rans4x16_hip_fqz_compress_dev in one enqueue-only call.  The picked
+ * parameter bytes, lengths and flags stay in the context's arena; the caller's input and records are never written.
+ * d_out, d_out_off, d_out_cap, d_out_size, d_status as in rans4x16_hip_fqz_compress_dev; a block the pick refuses keeps
+ * the pick's status (R4X16_E_UNSUPPORTED, R4X16_E_UNDECIDED) and codes nothing.  The encoder gets the records the
+ * reference's encode loop reaches: those that the fix-ups leave behind the last byte (a list that over-runs) are never
+ * coded, and the stream is the reference's.  A record of 0 bytes in front of the last byte, and bytes without a record,
+ * are R4X16_E_SIZE as in part 2j.  The model slots are sized by rans4x16_hip_set_fqz_limits.
+ *
+ * rans4x16_hip_set_fqz_pick(ctx, mode, guard_bits): mode 0 (the default) changes nothing anywhere.  mode 1 makes
+ * rans4x16_hip_fqz_compress_batch pick and code the blocks that come without parameter bytes in one round trip on the
+ * device (the blocks that come with parameter bytes take the trip of mode 0 behind it); blocks the device leaves
+ * R4X16_E_UNDECIDED are then picked on the host and coded in a second trip of those blocks alone.  The results are those
+ * of mode 0: the streams, len[i] as the fix-ups leave them, flags[i][rec] &= 0xffff (an over-running list apart: mode 0
+ * refuses its records of 0 bytes with R4X16_E_SIZE, the device trip codes it as the reference does).  The device trip's model slots are
+ * as rans4x16_hip_set_fqz_limits sized them (mode 0 sizes them for the batch's largest max_sym, which the host pick
+ * knows).  guard_bits (0 .. 64, default 0)
+ * multiplies the guard by 2^guard_bits in every call of part 2k on this context: a test reaches the undecided path with
+ * it.  Returns 0, -1 out of range.
+ *
+ * Route read-out: R4X16_ROUTE_FQZ_PICK (R4X16_FQZ_PICK_*); each chunk of a call counts once as R4X16_LAUNCH_IN_ORDER
+ * under R4X16_ROUTE_LAUNCH (the one-call form: once for its pick, once for its encoder). */
+unsigned int rans4x16_hip_fqz_pick_cap(void);
+int rans4x16_hip_set_fqz_pick(rans4x16_hip_ctx *ctx, int mode, int guard_bits);
+int rans4x16_hip_fqz_pick_dev(rans4x16_hip_ctx *ctx, int n,
+                              const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                              const uint32_t *d_len, const uint32_t *d_flags, const uint64_t *d_rec_off, const uint32_t *d_nrec,
+                              int vers, int strat, const int32_t *d_strat,
+                              unsigned char *d_params, const uint64_t *d_par_off, const uint32_t *d_par_cap, uint32_t *d_par_size,
+                              uint32_t *d_len_out, uint32_t *d_flags_out, int32_t *d_status,
+                              uint32_t max_in_size, uint32_t max_records, void *stream);
+int rans4x16_hip_fqz_compress_pick_dev(rans4x16_hip_ctx *ctx, int n,
+                                       const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                       const uint32_t *d_len, const uint32_t *d_flags, const uint64_t *d_rec_off, const uint32_t *d_nrec,
+                                       int vers, int strat, const int32_t *d_strat,
+                                       unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                       uint32_t *d_out_size, int32_t *d_status,
+                                       uint32_t max_in_size, uint32_t max_records, void *stream);
 
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
@@ -1007,7 +1072,8 @@ enum {
     R4X16_ROUTE_ARITH_ENC = 7,/* arith_dynamic encoding (part 2h): candidate streams (R4X16_ARITH_ENC_*)               */
     R4X16_ROUTE_FQZ = 8,      /* fqzcomp_qual decoding (part 2i): decoded streams (R4X16_FQZ_*)                        */
     R4X16_ROUTE_ENCODE_BODY = 9,/* encode chain: streams per body of the pipelined loop (R4X16_ENC_BODY_*)               */
-    R4X16_ROUTE_FQZ_ENC = 10  /* fqzcomp_qual encoding (part 2j): encoded streams (R4X16_FQZ_ENC_*)                    */
+    R4X16_ROUTE_FQZ_ENC = 10, /* fqzcomp_qual encoding (part 2j): encoded streams (R4X16_FQZ_ENC_*)                    */
+    R4X16_ROUTE_FQZ_PICK = 11 /* fqzcomp_qual's parameter choice on the device (part 2k): blocks (R4X16_FQZ_PICK_*)    */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -1079,6 +1145,15 @@ enum {   /* R4X16_ROUTE_FQZ_ENC: streams rans4x16_hip_fqz_compress_dev sent to a
     R4X16_FQZ_ENC_MULTI_PARAM = 4,  /* with more than one parameter block                                              */
     R4X16_FQZ_ENC_DUP = 5,          /* accepted streams (status 0) in which a record was coded as a duplicate          */
     R4X16_FQZ_ENC_KINDS = 6
+};
+enum {   /* R4X16_ROUTE_FQZ_PICK: blocks of rans4x16_hip_fqz_pick_dev / _compress_pick_dev */
+    R4X16_FQZ_PICK_BLOCKS = 0,      /* picked (status 0)                                                               */
+    R4X16_FQZ_PICK_SEL = 1,         /* picked with selectors coded (PFLAG_DO_SEL): the bins, the split or the caller's  */
+    R4X16_FQZ_PICK_SPLIT = 2,       /* picked with the READ1 / READ2 split taken                                       */
+    R4X16_FQZ_PICK_DEDUP = 3,       /* picked with PFLAG_DO_DEDUP                                                      */
+    R4X16_FQZ_PICK_UNDECIDED = 4,   /* left to the host: R4X16_E_UNDECIDED                                             */
+    R4X16_FQZ_PICK_HOST = 5,        /* blocks of a host-buffer batch picked on the host behind an undecided device pick */
+    R4X16_FQZ_PICK_KINDS = 6
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
