@@ -180,7 +180,7 @@ struct EncOutT {
         x = ALL || live ? xn : xs;
     }
     // The step of the short-index packed rows (10-bit tables): {m, w} is the frequency table's entry of f (r4x16_api.hip),
-    // w = (1024 - f) | s << 24, and nothing is derived from f here but x_max.  The same x as step(), bit for bit:
+    // w = (1024 - f) | s << 24, and nothing is derived from f here, not even x_max.  The same x as step(), bit for bit:
     // both compute xs + start + (xs / f) * (1024 - f) with the exact quotient of a state xs < 2^31.
     //   q: m is the low word of the round-up reciprocal ceil(2^(32 + s) / f), s = ceil(log2 f), which lies in
     //      [2^32, 2^33): (mulhi(xs, m) + xs) >> s = floor(xs * (2^32 + m) / 2^(32 + s)) = xs / f for every 32-bit xs; the
@@ -189,13 +189,71 @@ struct EncOutT {
     //      f = 2 (any power of two): m = 0, q = xs >> s.      f = 3 (no power of two): m = ceil(2^(32 + s) / f) - 2^32 > 0.
     //   q * (1024 - f): q < 2^21 and 1024 - f < 2^10, a 24-bit multiply that does not look at the shift in w's top byte
     //      (the symbol records' trick, r4x16_common.h).  f = 1024: w's low bits are 0, the product is 0 and x = xs + start.
+    // X is x_max = f << 21 as it comes out of the row (chain_encode_o1_lds' topk): the compare takes it as it is.
     template <bool ALL = false>
-    __device__ __forceinline__ void step_freq(u32 &x, bool live, u32 m, u32 w, u32 start, u32 f)
+    __device__ __forceinline__ void step_freq(u32 &x, bool live, u32 m, u32 w, u32 start, u32 X)
     {
-        const u32 xs = emit16q<ALL>(x, live, x >= (f << 21));
+        const u32 xs = emit16q<ALL>(x, live, x >= X);
         const u32 q = (__umulhi(xs, m) + xs) >> ((w >> 24) & 31u);
         const u32 xn = __umul24(q, w) + (xs + start);
         x = ALL || live ? xn : xs;
+    }
+    // step_freq<true> for the four steps of a trip of the pipelined loop, written out as ONE statement because the order
+    // is the change.  The same x and the same words at the same places:
+    //  - `emit ? x >> 16 : x` is ONE select with a word pick (SDWA), which takes its condition from vcc only - the C++ form
+    //    has the compare as a bool beside a ballot and gets a shift and a select;
+    //  - a vector instruction reads vcc two slots behind the compare that wrote it at the earliest.  Nothing of the step
+    //    itself can stand there (all of it hangs on the compare), so the PREVIOUS step's ring address and ring write do;
+    //    the first step has the starts of two of the next trip's symbols there, and the last one's write stands at the end;
+    //  - one statement, not one per step: the compiler puts an idle slot between a statement and the next instruction
+    //    or statement that reads one of its outputs, and every piece of a step reads the one before.
+    // The state alternates between two registers (xa, xb), so the one a step started from is still there when the next
+    // step writes its low word out.  The quad's mask is a 64-bit shift whose low half alone is used, and a statement
+    // cannot name half an operand: it goes through a fixed register pair (ENC_TRIP_EM), declared as clobbered.
+    // The ring writes are not counted by the compiler's LDS waits, which is safe: LDS operations return in order and a
+    // wait for "at most N outstanding" can only cover more with an operation it does not know of.
+    // Hazards inside (gfx950): vcc written by a compare is read 3 slots later at the earliest; the SDWA forms write
+    // whole dwords (no forwarding hazard); nothing else here is on the list.
+#define ENC_TRIP_EM    "v[30:31]"
+#define ENC_TRIP_EM_LO "v30"
+#define ENC_TRIP_EM_CLOBBER "v30", "v31"
+#define ENC_TRIP_WRITE(xp) \
+        "v_mad_i32_i24 %[q], %[pj], -2, %[r126]\n\t" \
+        "ds_write_b16 %[q], %[" xp "]\n\t"
+#define ENC_TRIP_STEP(gap, xi, xo, n) \
+        "v_cmp_ge_u32_e32 vcc, %[" xi "], %[X" n "]\n\t" \
+        gap \
+        "v_lshrrev_b64 " ENC_TRIP_EM ", %[sh], vcc\n\t" \
+        "v_cndmask_b32_sdwa %[xs], %[" xi "], %[" xi "], vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t" \
+        "v_and_b32_e32 %[t], %[above], " ENC_TRIP_EM_LO "\n\t" \
+        "v_mul_hi_u32 %[q], %[xs], %[m" n "]\n\t" \
+        "v_and_b32_e32 " ENC_TRIP_EM_LO ", 15, " ENC_TRIP_EM_LO "\n\t" \
+        "v_bcnt_u32_b32 %[t], %[t], %[wr]\n\t" \
+        "v_add_u32_e32 %[q], %[xs], %[q]\n\t" \
+        "v_bcnt_u32_b32 %[wr], " ENC_TRIP_EM_LO ", %[wr]\n\t" \
+        "v_lshrrev_b32_sdwa %[q], %[w" n "], %[q] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD\n\t" \
+        "v_and_b32_e32 %[t], 63, %[t]\n\t" \
+        "v_mul_u32_u24_e32 %[q], %[q], %[w" n "]\n\t" \
+        "v_cndmask_b32_e32 %[pj], -1, %[t], vcc\n\t" \
+        "v_add3_u32 %[" xo "], %[xs], %[s" n "], %[q]\n\t"
+    // na, nb: two pairs of the NEXT trip as they come out of the row; their starts (the low eleven bits) are taken in the
+    // two slots behind the first compare, where the first step has no ring write to place.
+    __device__ __forceinline__ void trip_freq(u32 &x, u32x4 m, u32x4 w, u32 s0, u32 s1, u32 s2, u32 s3, u32 X0, u32 X1, u32 X2, u32 X3,
+                                              u32 &na, u32 &nb)
+    {
+        u32 xb, xs, t, q, pj;
+        const u32 sh = lane & ~3u;
+        asm volatile(ENC_TRIP_STEP("v_and_b32_e32 %[na], 0x7ff, %[na]\n\t"
+                                   "v_and_b32_e32 %[nb], 0x7ff, %[nb]\n\t", "xa", "xb", "0")
+                     ENC_TRIP_STEP(ENC_TRIP_WRITE("xa"), "xb", "xa", "1")
+                     ENC_TRIP_STEP(ENC_TRIP_WRITE("xb"), "xa", "xb", "2")
+                     ENC_TRIP_STEP(ENC_TRIP_WRITE("xa"), "xb", "xa", "3")
+                     ENC_TRIP_WRITE("xb")
+                     : [xa] "+v"(x), [wr] "+v"(written), [na] "+v"(na), [nb] "+v"(nb), [xb] "=&v"(xb), [xs] "=&v"(xs), [t] "=&v"(t), [q] "=&v"(q), [pj] "=&v"(pj)
+                     : [sh] "v"(sh), [above] "v"(above), [r126] "v"(ring126),
+                       [m0] "v"(m.x), [w0] "v"(w.x), [s0] "v"(s0), [X0] "v"(X0), [m1] "v"(m.y), [w1] "v"(w.y), [s1] "v"(s1), [X1] "v"(X1),
+                       [m2] "v"(m.z), [w2] "v"(w.z), [s2] "v"(s2), [X2] "v"(X2), [m3] "v"(m.w), [w3] "v"(w.w), [s3] "v"(s3), [X3] "v"(X3)
+                     : "vcc", "memory", ENC_TRIP_EM_CLOBBER);
     }
     // conditional form: copy out the half that has just been completed, if any
     __device__ __forceinline__ void flush()
@@ -276,10 +334,13 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
         asm("" : "+v"(w));               // one word: without this the low half is multiplied a second time, without the add
         return w;
     };
+    auto pairr = [&](u32 wc, u32 ws) -> u32x2 {          // packed rows: the two dwords that hold the pair
+        const u32 a = ((wc >> 16) + __builtin_amdgcn_ubfe(ws, 5, 5)) << 2;
+        return *(LAS const u32x2_a4 *)(unsigned long)a;
+    };
     auto pairw = [&](u32 wc, u32 ws) -> u32 {
         if (PK) {
-            const u32 a = ((wc >> 16) + __builtin_amdgcn_ubfe(ws, 5, 5)) << 2;
-            const u32x2 d = *(LAS const u32x2_a4 *)(unsigned long)a;
+            const u32x2 d = pairr(wc, ws);
             return __builtin_amdgcn_alignbit(d.y, d.x, ws);                  // (the shift uses the low five bits of ws)
         }
         return *(LAS const u32 *)(cumb + 2u * (__umul24(wc, rs) + ws));
@@ -294,22 +355,41 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
     //    other phases fetch() for live lanes only.
     const u32 neutral = 1024u << 11;
     const u32 rcp_last = RCPTAB_ENTRIES - 1u;
-    // A symbol on its way to its step: pk = start | freq << 16; FT: pk = start and f = freq, apart as they come out of the row
+    // A symbol on its way to its step: pk = start | freq << 16; FT: pk = start and f = x_max = freq << 21, which is all the
+    // step and the table read want of the frequency (topk below)
     // (every instruction of the loop is issue time, on the dependent path or off it: no packing that a step undoes again)
     struct PF { u32 pk, f; };
     // {reciprocal, 0}, or the frequency table's entry  (u16 rows clamp: their idle lanes hold garbage; packed rows: above)
+    // FT: entry f is 8 bytes at LDS byte address 8 f = x_max >> 18, one shift - the frequency table stands at LDS address
+    // 0: k_enc_chain puts it at the start of its dynamic LDS and has no static LDS in front of it (the flag of "does
+    // anybody have work" lives in the dynamic LDS for that reason; the parent's listing formed this address with a
+    // literal 0 already).  A table anywhere else needs its address added here - one instruction per symbol.
     auto rcpof = [&](PF s) -> u32x2 {
-        if (FT) return ((const u32x2 *)lrcp)[s.f];
+        if (FT) return *(LAS const u32x2 *)(unsigned long)(s.f >> 18);
         const u32 f = s.pk >> 16;
         u32x2 r = {lrcp[PK ? f : f < rcp_last ? f : rcp_last], 0u};
         return r;
     };
     // pair -> start | freq << 16.  u16 rows: a shift and a subtract (the empty asm keeps it from becoming a
-    // quarter-rate multiply by 0xFFFF0001); packed rows: two field extractions, a subtract, a shift-or (FT: none)
-    auto topk = [&](u32 p) -> PF {
+    // quarter-rate multiply by 0xFFFF0001); packed rows: two field extractions, a subtract, a shift-or.
+    // FT: start, and x_max = (next - start) << 21 by ONE multiply.  p is what v_alignbit delivers: start in bits 0..10, next
+    // in bits 11..21, the row's following fields above.  p * (2^10 - 2^21) = start * 2^10 + (next - start) * 2^21 mod 2^32:
+    // p * 2^10 carries next to bit 21, p * 2^21 carries start there, and whatever p holds above bit 21 - the sign bit of
+    // the 24-bit operand included - lands on multiples of 2^32.  start * 2^10 < 2^21 stays below the field and is masked
+    // off.  The neutral pair gives 2^31.  (tests/test_enc_xmax_cpu.py: every pair, any upper bits.)  Written as asm: the
+    // multiplier is hidden from the compiler, which makes two shifts and a subtract of a constant one.
+    int xmul = 1024 - 2097152;
+    if (FT) asm("" : "+s"(xmul));
+    // late: the start stays unmasked, EncOutT::trip_freq takes it.
+    auto topk = [&](u32 p, bool late = false) -> PF {
+        if (FT) {
+            const u32 X = (u32)__mul24((int)p, xmul);
+            PF r = {late ? p : p & 2047u, X & 0xffe00000u};
+            return r;
+        }
         if (PK) {
             const u32 st = p & 2047u, f = __builtin_amdgcn_ubfe(p, 11, 11) - st;
-            PF r = {FT ? st : st | (f << 16), f};
+            PF r = {st | (f << 16), f};
             return r;
         }
         u32 hi = p << 16; asm("" : "+v"(hi));
@@ -403,6 +483,21 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             return r;
         };
         auto cum4 = [&](const I4 &c, u32 sym) -> u32x4 {     // raw pairs start | next << 16
+            if (FT) {
+                // the four funnel shifts as one statement: the compiler then waits ONCE for the four reads (they return
+                // in order, and it gives each shift a counted wait of its own - three issue slots per trip).  Nothing
+                // reads the pairs before the next trip, so no idle slot follows the statement.
+                const u32x2 d0 = pairr(c.c0, sym), d1 = pairr(c.c1, c.c0), d2 = pairr(c.c2, c.c1), d3 = pairr(c.c3, c.c2);
+                u32x4 r;
+                asm("v_alignbit_b32 %0, %4, %5, %6\n\t"
+                    "v_alignbit_b32 %1, %7, %8, %9\n\t"
+                    "v_alignbit_b32 %2, %10, %11, %12\n\t"
+                    "v_alignbit_b32 %3, %13, %14, %15"
+                    : "=&v"(r.x), "=&v"(r.y), "=&v"(r.z), "=v"(r.w)
+                    : "v"(d0.y), "v"(d0.x), "v"(sym), "v"(d1.y), "v"(d1.x), "v"(c.c0), "v"(d2.y), "v"(d2.x), "v"(c.c1),
+                      "v"(d3.y), "v"(d3.x), "v"(c.c2));
+                return r;
+            }
             u32x4 r = {pairw(c.c0, sym), pairw(c.c1, c.c0), pairw(c.c2, c.c1), pairw(c.c3, c.c2)};
             return r;
         };
@@ -412,8 +507,8 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             return r;
         };
         struct P4 { PF x, y, z, w; };
-        auto topk4 = [&](u32x4 p) -> P4 {
-            P4 r = {topk(p.x), topk(p.y), topk(p.z), topk(p.w)};
+        auto topk4 = [&](u32x4 p, bool late = false) -> P4 {     // late: the first two starts are left to the trip's statement
+            P4 r = {topk(p.x, late), topk(p.y, late), topk(p.z), topk(p.w)};
             return r;
         };
         struct R4 { u32x4 rcp, w; };
@@ -444,12 +539,14 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
             const bool live = t < ntrip;
             const I4 In = idx4(wnext3);              // bytes of trip t+3
             const u32x4 Pn = cum4(I2, cur2);         // pairs of trip t+2
-            const P4 P1 = topk4(real4(Praw, t + 1 < ntrip));     // trip t+1, read during the previous trip
+            P4 P1 = topk4(real4(Praw, t + 1 < ntrip), FT);       // trip t+1, read during the previous trip
             const R4 Rn = rcp4(P1);
             // the look-ups above belong to later trips: keep the scheduler from pulling next trip's
             // (which depend on them) up behind them, which would put their latency on this trip
             __builtin_amdgcn_sched_barrier(0);
-            if (PK) {
+            if (FT) {
+                o.trip_freq(x, R0.rcp, R0.w, P0.x.pk, P0.y.pk, P0.z.pk, P0.w.pk, P0.x.f, P0.y.f, P0.z.f, P0.w.f, P1.x.pk, P1.y.pk);
+            } else if (PK) {
                 step_all(o, x, R0.rcp.x, R0.w.x, P0.x.pk, P0.x.f);
                 step_all(o, x, R0.rcp.y, R0.w.y, P0.y.pk, P0.y.f);
                 step_all(o, x, R0.rcp.z, R0.w.z, P0.z.pk, P0.z.f);
@@ -670,7 +767,7 @@ __global__ __launch_bounds__(256) void k_enc_chain(EncItem *items, const u32 *rc
     const u32 n = I->n, ns = I->ns, bits = active ? I->bits : 12u;
     u32 pay;
     if (LDS_IMG) {
-        u32 *lrcp = (u32 *)lds;
+        u32 *lrcp = (u32 *)lds;                            // FT: LDS address 0, which chain_encode_o1_lds' rcpof relies on
         u8 *slots = lds + (FT ? ENC_LFREQ_BYTES : PK ? ENC_LRCP_PK_BYTES : ENC_LRCP_BYTES);
         if (FT) for (u32 j = tid; j < 2u * ENC_FREQTAB_ENTRIES; j += blockDim.x) lrcp[j] = rcptab[ENC_FREQTAB_OFF + j];
         else for (u32 j = tid; j < (PK ? 1025u : RCPTAB_ENTRIES); j += blockDim.x) lrcp[j] = rcptab[j];
