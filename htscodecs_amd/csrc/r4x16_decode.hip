@@ -191,14 +191,15 @@ __device__ __forceinline__ u32 lookup_step_pk(u32 row, u32 root, u32 hdr, u32 &x
     if (pin) { symbol(s); __builtin_amdgcn_sched_barrier(0); }
     const u32 r11 = 22u - 11u * rneg;
     // the candidates in stride-11 order: P = L[3q], L[3q + 1], L[3q + 2];  C = L[3q + 1], L[3q + 2], L[3q + 3]
-    const u32 P = (D << 11) | (D >> 22);                      // (not a rotation: bit 21 is a guard bit, the top field must land on bit 0)
+    // (not a rotation: bit 21 is a guard bit, the top field must land on bit 0.)  L[c] is the end of the symbol before,
+    // 1023 standing for -1: one added to all three fields at once - the carries land in bits 10, 21 (zero: the guard
+    // bits of the stored dword) and off the top, outside every extract - gives the symbol's start, and no mask is needed
+    // behind the differences (the pick returns the first field >= m, so cum <= m <= cur: tests/test_dec_state_cpu.py)
+    const u32 P = ((D << 11) | (D >> 22)) + 0x00400801u;
     const u32 Cc = (D & 0x003fffffu) | (Dn & 0xffc00000u);    // (one v_bfi_b32)
-    const u32 prev = __builtin_amdgcn_ubfe(P, r11, 10);       // L[c]: end of the symbol before (1023 stands for -1)
+    const u32 cum = __builtin_amdgcn_ubfe(P, r11, 10);        // L[c] + 1 mod 1024: start of this symbol
     const u32 cur = __builtin_amdgcn_ubfe(Cc, r11, 10);       // L[c + 1]: end of this symbol
-    const u32 np = ~prev;
-    const u32 fm1 = (cur + np) & 1023u;                       // freq - 1
-    const u32 off = (m + np) & 1023u;                         // m - start
-    x = __umul24(fm1, xs) + xs + off;                         // freq <= 1024, x >> 10 < 2^22: exact mod 2^32
+    x = __umul24(cur - cum, xs) + ((m + xs) - cum);           // freq <= 1024, x >> 10 < 2^22: exact mod 2^32
     if (!pin) symbol(s);
     return s;
 }
@@ -702,6 +703,12 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
 // The step itself differs from lookup_step_pk's in two places, both written out in `issue` and `finish` below: the group
 // count takes the top field's compare as a borrow, and the pivot pick is a two-level search; with the three idle slots
 // (s_nop) of the step gone as well, a step is 67.8 instructions for 74.8 (profiles/dec_pivot.md).
+// The state update is lookup_step_pk's mask-free one, with m + (x >> 10) made in the group read's shadow (issue_end), and
+// the body of sixteen books a step's byte (one v_alignbit_b32) and every second step the flags of two rows (one
+// v_or3_b32) as asm volatile between the next step's group read and its wait: written as plain C++ in the same place,
+// the compiler kept the sixteen hdr words and did all of it in the blocks behind the body, where a lone wave pays every
+// slot (a fence does not stop a sink at the IR level).  A trip from header to back edge: 1,062 instructions for 1,096;
+// headline step 133.8 -> 129.8 ms (profiles/dec_state.md).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 *ring, gcu8 *words, u32 words_len,
                                                 gu8 *out, u32 out_sz, u32 x, bool active, u32 lane)
@@ -752,7 +759,7 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
 
     // ---- the step, in its three pieces -----------------------------------------------------------
     // carried from a step's issue half to its finish half (across the back edge for a trip's first step)
-    u32 m = 0, m22 = 0, GM = 0, t12 = 0, xs = 0, D0 = 0, D1 = 0, D2 = 0, D3 = 0, D4 = 0, d0 = 0, d1 = 0, d2 = 0, cb = 0, g = 0;
+    u32 m = 0, m22 = 0, GM = 0, t12 = 0, xs = 0, D0 = 0, D1 = 0, D2 = 0, D3 = 0, D4 = 0, d0 = 0, d1 = 0, d2 = 0, cb = 0, g = 0, mxs = 0, fs = 0;
     // issue half of the step after one whose word requests were `wq`; the caller's bookkeeping follows, then issue_end
     auto issue = [&](u32 wq, bool adv) __attribute__((always_inline)) {
         m = x & 1023u;
@@ -773,19 +780,20 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
         const u32x4 Dq = *(LAS const volatile u32x4 *)(unsigned long)ga;
         D0 = Dq.x; D1 = Dq.y; D2 = Dq.z; D3 = Dq.w; D4 = *(LAS const volatile u32 *)(unsigned long)(ga + 16u);
         __builtin_amdgcn_sched_barrier(0);
-        if (adv) {
-            asm volatile("" : "+v"(wq));                  // (holds the mask and the count behind the fence)
-            cursor += __popc(wq & 0xfu);
-        }
+        // (no empty asm on wq: the fence alone holds the mask and the count behind the group read, and the compiler pads
+        //  every asm with an s_nop in front of the reader of its output - the shift of xs used to stand in that slot)
+        fs = hdr >> PK_FIRST_SHIFT;
+        if (adv) cursor += __popc(wq & 0xfu);
         cb = off0 + 2 * cursor;
         const u32 ra = cb & (RB - 4u);
         const u32x2 d01 = *(LAS const volatile u32x2_a4 *)(ring + ra);
         d0 = d01.x; d1 = d01.y; d2 = *(lvcu32 *)(ring + ra + 8);
     };
     auto issue_end = [&]() __attribute__((always_inline)) {
-        xs = x >> 10;
-        asm volatile("" : "+v"(xs));                      // (a plain shift is not held by the fences: it sinks to its use)
-        asm("v_mad_u32_u24 %0, %1, 12, %2" : "=v"(t12) : "v"(g), "v"(hdr >> PK_FIRST_SHIFT));
+        // x >> 10 and m + (x >> 10), all of the state update that needs x alone (plain arithmetic is not held by the
+        // fences: it sinks to its use; and the sum behind an empty asm on the shift gets that asm's pad)
+        asm volatile("v_lshrrev_b32_e32 %0, 10, %2\n\tv_add_u32_e32 %1, %3, %0" : "=&v"(xs), "=v"(mxs) : "v"(x), "v"(m));
+        asm("v_mad_u32_u24 %0, %1, 12, %2" : "=v"(t12) : "v"(g), "v"(fs));
         __builtin_amdgcn_sched_barrier(0);
     };
     // finish half, state update and renormalisation; returns the quad's word requests in bits 0..3
@@ -829,14 +837,11 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
         __builtin_amdgcn_sched_barrier(0);
         u32 r11;                                          // 22 - 11 rneg (rneg comes out of an asm: the compiler no longer
         asm("v_mad_i32_i24 %0, %1, -11, 22" : "=v"(r11) : "v"(rneg));     //  knows it small and would multiply in 64 bits)
-        const u32 P = (D << 11) | (D >> 22);
+        const u32 P = ((D << 11) | (D >> 22)) + 0x00400801u;         // every field + 1: the symbol's start (lookup_step_pk)
         const u32 Cc = (D & 0x003fffffu) | (Dn & 0xffc00000u);
-        const u32 prev = __builtin_amdgcn_ubfe(P, r11, 10);
+        const u32 cum = __builtin_amdgcn_ubfe(P, r11, 10);
         const u32 cur = __builtin_amdgcn_ubfe(Cc, r11, 10);
-        const u32 np = ~prev;
-        const u32 fm1 = (cur + np) & 1023u;
-        const u32 off = (m + np) & 1023u;
-        const u32 xn = __umul24(fm1, xs) + xs + off;
+        const u32 xn = __umul24(cur - cum, xs) + (mxs - cum);
         u32 rown1;
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(rown1) : "v"(s), "v"(roww), "v"(rows));
         hdr = live ? h.y : hdr;
@@ -868,12 +873,14 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
                     const u32 wq = finish(std::true_type{}, true);
                     issue(wq, true);
                     // flags of the row now in use (ROW_EMPTY is tested after the loop), two steps per three-way or;
-                    // the row in use at t + 16 counts only if that step exists
+                    // the row in use at t + 16 counts only if that step exists.  The or and the byte's shift are PINNED
+                    // here, in the group read's shadow (asm volatile: as plain C++ the compiler sinks both behind the
+                    // body); each is read a step or more later, so neither gets an asm's pad
+                    u32 &A = u <= 4 ? b0 : u <= 8 ? b1 : u <= 12 ? b2 : acc;
                     if (u == 16) bad |= hdr_even | (t + 16u < count ? hdr : 0u);
                     else if (u & 1) hdr_even = hdr;
-                    else bad |= hdr | hdr_even;
-                    u32 &A = u <= 4 ? b0 : u <= 8 ? b1 : u <= 12 ? b2 : acc;
-                    A = __builtin_amdgcn_alignbit(hdr, A, 8);
+                    else asm volatile("v_or3_b32 %0, %0, %1, %2" : "+v"(bad) : "v"(hdr), "v"(hdr_even));
+                    asm volatile("v_alignbit_b32 %0, %1, %0, 8" : "+v"(A) : "v"(hdr));
                     issue_end();
                 }
                 t += 16u;

@@ -2,7 +2,8 @@
 """Instruction mix of the hot-loop bodies in build/asm/*.s (made by `make -C htscodecs_amd/csrc asm`).
 usage: tools/isa_count.py <kernel-name-substring> [block-label-substring]
        tools/isa_count.py --json <out>     the hot bodies' counts (and, for the decode chain on packed rows, the number of
-                                           instructions in the shadow of each step's group read and head read)"""
+                                           instructions in the shadow of each step's group read and head read, and the
+                                           instructions of one 16-step trip from loop header to back edge: trip_path)"""
 import re
 import sys
 from collections import Counter
@@ -63,6 +64,51 @@ def shadows(b, first, second=None):
     return out
 
 
+def trip_path(src, name, header, marker, steps):
+    """Instructions that a full trip issues from the loop header `header` (a block label) to the back edge: the body and
+    the blocks behind it (the store, the flags, the loop control), which the per-label block above does not hold, without
+    what the body's label holds but the trip does not run (the refill).  The function is cut into basic blocks at labels
+    and branches; the path is the shortest one from the header back to it that issues `marker` at least `steps` times
+    (leaving the loop and coming back in is shorter, but runs no step), taken with some lane live: s_cbranch_execz falls
+    through and s_cbranch_execnz is taken, so the code under a lane mask counts.  Returns the count and the labels met."""
+    import heapq
+    i = src.index(name + ':')
+    ins, label_at = [], {}
+    for l in src[i:src.index('.Lfunc_end', i)].split('\n'):
+        lm = re.match(r'^(\.LBB\d+_\d+):', l)
+        if lm:
+            label_at[lm.group(1)] = len(ins)
+        elif l.strip() and not l.strip().startswith(('.', ';')):
+            ins.append(l.strip())
+    starts = sorted(set(label_at.values()) | {k + 1 for k, x in enumerate(ins) if x.startswith(('s_branch', 's_cbranch'))} | {0})
+    starts = [s for s in starts if s < len(ins)]
+    nxt = dict(zip(starts, starts[1:] + [None]))
+    def succ(s):
+        e = (nxt[s] or len(ins)) - 1
+        op, *arg = ins[e].split()
+        if op == 's_endpgm': return []
+        if op == 's_branch' or op == 's_cbranch_execnz': return [label_at[arg[0]]]
+        if op.startswith('s_cbranch') and op != 's_cbranch_execz': return [label_at[arg[0]], nxt[s]]
+        return [nxt[s]]
+    size = lambda s: (nxt[s] or len(ins)) - s
+    marks = lambda s: sum(1 for x in ins[s:s + size(s)] if x.split()[0] == marker)
+    h = label_at[re.match(r'\.LBB\d+_\d+', header).group(0)]
+    heap, seen = [(size(h), h, min(marks(h), steps), (h,))], set()
+    while heap:
+        cost, s, mk, path = heapq.heappop(heap)
+        if (s, mk) in seen: continue
+        seen.add((s, mk))
+        for n in succ(s):
+            if n is None: continue
+            if n == h:
+                if mk >= steps:
+                    at = {v: k for k, v in label_at.items()}
+                    return cost, [at[p] for p in path if p in at]
+                continue
+            heapq.heappush(heap, (cost + size(n), n, min(mk + marks(n), steps), path + (n,)))
+    return None, []
+
+
 GROUP_READ = ("ds_read_b128", r"ds_read_b32 .*offset:16\b")      # lookup_step_pk's group: 16 bytes + the dword after them
 HEAD_READ = ("ds_read_b64", None)                                 # the head entry of the symbol just decoded
 
@@ -100,6 +146,9 @@ def to_json(out_path):
                                             "s_nop_in_block": c["s_nop"],
                                             "group_shadow_per_step": shadows(b, *GROUP_READ),
                                             "head_shadow_per_step": shadows(b, *HEAD_READ)})
+                            if least:                                    # the 16-step trip: header to back edge, no refill
+                                n, labs = trip_path(src, name, lab, marker, least[0])
+                                best[1].update({"trip_path_instructions": n, "trip_path_blocks": labs})
                 if best:
                     res["kernels"][label] = best[1]
     with open(out_path, 'w') as f:
@@ -127,6 +176,9 @@ def main():
                 print('  ', c.most_common(50))
                 if c["ds_read_b128"]:
                     print('   group shadow per step', shadows(b, *GROUP_READ), ' head shadow per step', shadows(b, *HEAD_READ))
+                    steps = c["ds_read_b128"]
+                    if steps >= 16:
+                        print('   trip path, header to back edge without the refill', trip_path(src, name, lab, "v_lshrrev_b64", steps))
 
 if __name__ == '__main__':
     main()
