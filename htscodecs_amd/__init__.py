@@ -18,7 +18,7 @@ from .codec import (  # noqa: F401
     arith_uncompress, arith_uncompress_batch,
     arith_compress, arith_compress_batch, arith_compress_bound, arith_compress_cap,
     fqz_scan, fqz_decompress, fqz_uncompress_batch,
-    fqz_pick_parameters, fqz_compress, fqz_compress_batch, fqz_compress_cap, fqz_pick_cap,
+    fqz_pick_parameters, fqz_compress, fqz_compress_batch, fqz_compress_best_batch, fqz_compress_cap, fqz_pick_cap,
 )
 
 __all__ = [
@@ -31,5 +31,5 @@ __all__ = [
     "arith_uncompress", "arith_uncompress_batch",
     "arith_compress", "arith_compress_batch", "arith_compress_bound", "arith_compress_cap",
     "fqz_scan", "fqz_decompress", "fqz_uncompress_batch",
-    "fqz_pick_parameters", "fqz_compress", "fqz_compress_batch", "fqz_compress_cap", "fqz_pick_cap",
+    "fqz_pick_parameters", "fqz_compress", "fqz_compress_batch", "fqz_compress_best_batch", "fqz_compress_cap", "fqz_pick_cap",
 ]

@@ -146,7 +146,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc", "fqz_pick") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc", "fqz_pick", "fqz_best") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -158,7 +158,7 @@ class _Ctx:
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
-               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10, "fqz_pick": 11}
+               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10, "fqz_pick": 11, "fqz_best": 12}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -172,6 +172,7 @@ ROUTE_KINDS = {
     "encode_body": ("packed_affine",),
     "fqz_enc": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
     "fqz_pick": ("blocks", "sel", "split", "dedup", "undecided", "host"),
+    "fqz_best": ("blocks", "candidates", "counted", "undecided", "refused"),
 }
 
 _tls = threading.local()
@@ -601,6 +602,34 @@ def fqz_compress_batch(blocks, lens, flags, vers=4, strat=0, params=None, caps=N
     return res, status, [x.tolist() for x in la], [x.tolist() for x in fa]
 
 
+def fqz_compress_best_batch(blocks, lens, flags, strats, vers=4, caps=None, ctx=None):
+    """rans4x16_hip_fqz_compress_best_batch: quality blocks (bytes) with their record lengths and flags, each coded under
+    every strategy of `strats` and the smallest stream kept -> (list of bytes | None, statuses, the winners' indices into
+    strats (-1: none), lens, flags as the call leaves them).  caps: the capacity of each output (default: fqz_compress_cap
+    with fqz_pick_cap parameter bytes).  One upload, one device call, one download."""
+    ctx = ctx or _thread_ctx()
+    L = ctx.L
+    n = len(blocks)
+    la = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in lens]
+    fa = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in flags]
+    if caps is None:
+        caps = lambda i, size: L.rans4x16_hip_fqz_compress_cap(size, len(la[i]), L.rans4x16_hip_fqz_pick_cap())
+    a = _HostArrays(blocks, caps)
+    dummy = np.zeros(4, dtype=np.uint8)
+    ptr = lambda x: x.ctypes.data if len(x) else dummy.ctypes.data
+    len_p = (C.c_void_p * n)(*[ptr(x) for x in la])
+    fl_p = (C.c_void_p * n)(*[ptr(x) for x in fa])
+    nrec = (C.c_uint * n)(*[len(x) for x in la])
+    chosen = (C.c_int * n)(*([-1] * n))
+    st = (C.c_int * len(strats))(*[int(v) for v in strats])
+    rc = L.rans4x16_hip_fqz_compress_best_batch(ctx.h, n, a.in_p, a.in_sz, nrec, len_p, fl_p, int(vers), len(strats), st,
+                                                a.out_p, a.out_sz, chosen, a.status)
+    if rc < 0:
+        raise RuntimeError("fqz best batch failed: " + ctx.error())
+    res, status = a.results()
+    return res, status, list(chosen), [x.tolist() for x in la], [x.tolist() for x in fa]
+
+
 class _FqzSlice(C.Structure):
     _fields_ = [("num_records", C.c_int), ("len", C.POINTER(C.c_uint32)), ("flags", C.POINTER(C.c_uint32))]
 
@@ -886,6 +915,56 @@ class DeviceCodec:
             d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             int(max_in_size), int(max_records), self._stream())
         self._check(rc, "fqz_compress_pick_dev")
+
+    # ---- fqzcomp_qual encoding: best of several strategies (include/rans4x16_hip.h part 2l) -----------------------------
+    def fqz_compress_best(self, d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_out, out_off, out_cap, out_size,
+                          status, strats, max_in_size, max_records, vers=4, chosen=None, d_len_out=None):
+        """rans4x16_hip_fqz_compress_best_dev: fqz_compress_pick under every strategy of `strats` (a host list), the smallest
+        stream into the slot; chosen (int32): the winner's index into strats, d_len_out (int32): the lengths as the fix-ups
+        leave them.  Enqueues only."""
+        t = self.torch
+        self._slot_args(d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status)
+        self._pick_args(d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, None)
+        assert chosen is None or chosen.dtype == t.int32
+        assert d_len_out is None or d_len_out.dtype == t.int32
+        st = (C.c_int * max(len(strats), 1))(*[int(v) for v in strats])
+        rc = self.L.rans4x16_hip_fqz_compress_best_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_len.data_ptr(), d_flags.data_ptr(), rec_off.data_ptr(), nrec.data_ptr(), int(vers), len(strats), st,
+            d_out.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            chosen.data_ptr() if chosen is not None else None, d_len_out.data_ptr() if d_len_out is not None else None,
+            int(max_in_size), int(max_records), self._stream())
+        self._check(rc, "fqz_compress_best_dev")
+
+    def fqz_compress_best_packed(self, d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_out, out_off, out_size, status,
+                                 strats, max_in_size, max_records, vers=4, chosen=None, d_len_out=None, out_capacity=None):
+        """rans4x16_hip_fqz_compress_best_packed_dev: the same with the winners back to back in d_out and out_off (int64,
+        n + 1) written on the device.  d_out None (with out_capacity 0 or None) is the sizing pass."""
+        t = self.torch
+        assert d_out is None or d_out.dtype == t.uint8
+        assert out_off.dtype == t.int64 and out_off.numel() == in_off.numel() + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        self._pick_args(d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, None)
+        assert chosen is None or chosen.dtype == t.int32
+        assert d_len_out is None or d_len_out.dtype == t.int32
+        room = d_out.numel() if d_out is not None else 0
+        cap = room if out_capacity is None else int(out_capacity)
+        assert cap <= room
+        st = (C.c_int * max(len(strats), 1))(*[int(v) for v in strats])
+        rc = self.L.rans4x16_hip_fqz_compress_best_packed_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_len.data_ptr(), d_flags.data_ptr(), rec_off.data_ptr(), nrec.data_ptr(), int(vers), len(strats), st,
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            chosen.data_ptr() if chosen is not None else None, d_len_out.data_ptr() if d_len_out is not None else None,
+            int(max_in_size), int(max_records), self._stream())
+        self._check(rc, "fqz_compress_best_packed_dev")
+
+    def fqz_best_chunk_blocks(self, n, k, max_in_size, max_records):
+        """rans4x16_hip_fqz_best_chunk_blocks: the blocks per chunk fqz_compress_best plans for these arguments."""
+        rc = self.L.rans4x16_hip_fqz_best_chunk_blocks(self.ctx.h, int(n), int(k), int(max_in_size), int(max_records))
+        if rc < 0:
+            raise RuntimeError("fqz_best_chunk_blocks: " + self.ctx.error())
+        return rc
 
     # ---- what the methods share: the dtypes of either form's arrays, and the end of every call ----------------------
     def _slot_args(self, d_in, in_off, in_size, d_out, out_off, out_cap, out_size, status):

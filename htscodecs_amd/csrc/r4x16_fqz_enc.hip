@@ -10,6 +10,8 @@
 //                 and every byte checked against its record's parameter block, under GFLAG_DO_REV the coder-order copy
 //   k_fqe_encode  one wave per model slot, striding over the chunk's blocks: fill the slot, encode into the stage arena
 //   k_fqe_back    a workgroup per block: size, parameter bytes and body into the caller's slot, the verdict
+// (r4x16_fqe_stages is the first two for a caller with a back end of its own: r4x16_fqz_best.hip, which assembles only
+// the smallest of a block's candidates; the work areas are declared in r4x16_fqz_best.h)
 //
 // Loops: the encode loop consumes at least one input byte a trip (a duplicate: `len` >= 1 bytes) and ends at the block's
 // size; the front's loops run over the records (nrec <= max_records) and their bytes, whose lengths it has summed to
@@ -18,30 +20,11 @@
 // has outgrown it for certain (16 bytes a trip at most, five to finish).  Only k_fqe_back writes into the caller's slot,
 // after it has tested the capacity.  All stores are plain vector stores.
 #include "r4x16_host.h"
+#include "r4x16_fqz_best.h"
 #include "r4x16_fqz_parse.h"
 #include "r4x16_fqz_model.h"
 #include "r4x16_fqz_pick.h"
 #include "r4x16_arith_enc_step.h"
-
-struct FqeBlk {
-    i32 status; u32 size, gflags, nparam;
-    u32 max_sel, max_sym, home, nrec;
-    u32 body, lim, uses_sel, dups;      // dups: records coded as duplicates (k_fqe_encode)
-    u64 tab;                // in the stage arena: the selector table, then nparam x FQ_PARAM_BYTES
-    u64 inv;                // nparam x 256: quality -> symbol
-    u64 cod;                // the block in coder order (GFLAG_DO_REV only)
-    u64 out;                // the coder's bytes: 16-byte aligned, lim + 48 rounded up to 16
-};
-struct FqeWs {
-    FqeBlk *blk;            // [nb]
-    u64 *cursor;            // bytes of the stage arena handed out (a chunk's)
-    u32 *route;             // [R4X16_FQZ_ENC_KINDS]; nullptr in the kernels' copy: option route_count is off
-    u8 *stage;
-    u64 stage_bytes;
-    u8 *rows;               // [slots] x slot_bytes
-    u64 slot_bytes;
-    u32 slots, max_sym;
-};
 
 // The parameter bytes as the walk reads a stream: a size byte of 0 in front, and behind them the nine bytes a stream
 // has at least (the coder's five, and the walk asks for ten behind the size).  The walk must end where the bytes end.
@@ -61,12 +44,6 @@ AR_HD static inline int fqe_parse(const u8 *par, u32 psz, FqTop *top, SINK &sink
     return st;
 }
 
-AR_HD static inline u32 fqe_var_len(u32 v)
-{
-    u32 groups = 1;
-    for (u32 t = v >> 7; t; t >>= 7) groups++;
-    return groups;
-}
 // the body's bound: a symbol shifts out two bytes at most, a record has seven symbols beside its qualities, five to finish
 AR_HD static inline u64 fqe_body_bound(u32 size, u32 nrec) { return 2ull * ((u64)size + 7ull * nrec) + 5ull; }
 AR_HD static inline u64 fqe_cap(u32 size, u32 nrec, u32 psz) { return 5ull + psz + fqe_body_bound(size, nrec); }
@@ -123,7 +100,7 @@ __global__ __launch_bounds__(256) void k_fqe_front(BatchArgs a, FqeIn in, FqeWs 
                 wsync();
                 uses_sel = (top.gflags & FQ_GFLAG_MULTI_PARAM) || (((const FqParam *)(tab + FQ_STAB_BYTES))->pflags & FQ_PFLAG_DO_SEL);
                 const u16 *stab = (const u16 *)tab;
-                const u32 *len = in.len + in.rec_off[g], *fl = in.flags + in.rec_off[g];
+                const u32 *len = in.len + (in.len_off ? in.len_off : in.rec_off)[g], *fl = in.flags + in.rec_off[g];
                 // the records: lengths that sum to the size, none of 0; selectors inside the model, with a parameter block
                 u64 sum = 0;
                 bool bad_len = false, bad_sel = false;
@@ -257,7 +234,7 @@ __global__ __launch_bounds__(64) void k_fqe_encode(BatchArgs a, FqeIn in, FqeWs 
         wsync();
         const u8 *const params = TAB_LDS ? (const u8 *)(lds + (FQ_LDS_MODELS + FQ_STAB_BYTES) / 4) : w.stage + bk.tab + FQ_STAB_BYTES;
         const u8 *const data = (bk.gflags & FQ_GFLAG_DO_REV) ? w.stage + bk.cod : a.in + a.in_off[g];
-        const u32 *const lens = in.len + in.rec_off[g], *const fls = in.flags + in.rec_off[g];
+        const u32 *const lens = in.len + (in.len_off ? in.len_off : in.rec_off)[g], *const fls = in.flags + in.rec_off[g];
         u32 tot_len[4] = {256u, 256u, 256u, 256u}, tot_sel = bk.max_sel + 1u;
         u32 rev0 = 1u, rev1 = 1u | (1u << 16), dup0 = 1u, dup1 = 1u | (1u << 16);
         ArWindow src(data, n);
@@ -387,18 +364,25 @@ size_t r4x16_fqe_chunk_bytes(rans4x16_hip_ctx *c, size_t nb, u32 max_in_size, u3
     FqeWs w;
     return fqe_chunk_layout(c, nullptr, nb, max_in_size, max_records, &w);
 }
+int r4x16_fqe_stages(rans4x16_hip_ctx *c, const BatchArgs &a, const FqeIn &in, u8 *at, int base, int nb, u32 max_in_size, u32 max_params_size,
+                     u32 max_records, hipStream_t s, FqeWs *w, u32 **d_route)
+{
+    fqe_chunk_layout(c, at, (size_t)nb, max_in_size, max_records, w);
+    w->max_sym = (u32)c->fqz_max_sym;
+    *d_route = w->route;
+    HIPCHK(c, hipMemsetAsync(w->cursor, 0, sizeof(u64), s));
+    if (r4x16_route_begin(c, &w->route, R4X16_FQZ_ENC_KINDS, s) != 0) return -1;
+    hipLaunchKernelGGL(k_fqe_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, in, *w, base, nb, max_in_size, max_params_size, max_records);
+    hipLaunchKernelGGL(k_fqe_encode<true>, dim3(w->slots), dim3(64), 0, s, a, in, *w, base, nb);
+    hipLaunchKernelGGL(k_fqe_encode<false>, dim3(w->slots), dim3(64), 0, s, a, in, *w, base, nb);
+    return 0;
+}
 int r4x16_fqe_chunk(rans4x16_hip_ctx *c, const BatchArgs &a, const FqeIn &in, u8 *at, int base, int nb, u32 max_in_size, u32 max_params_size,
                     u32 max_records, hipStream_t s)
 {
     FqeWs w;
-    fqe_chunk_layout(c, at, (size_t)nb, max_in_size, max_records, &w);
-    w.max_sym = (u32)c->fqz_max_sym;
-    u32 *const d_route = w.route;
-    HIPCHK(c, hipMemsetAsync(w.cursor, 0, sizeof(u64), s));
-    if (r4x16_route_begin(c, &w.route, R4X16_FQZ_ENC_KINDS, s) != 0) return -1;
-    hipLaunchKernelGGL(k_fqe_front, dim3((nb + 3) / 4), dim3(256), 0, s, a, in, w, base, nb, max_in_size, max_params_size, max_records);
-    hipLaunchKernelGGL(k_fqe_encode<true>, dim3(w.slots), dim3(64), 0, s, a, in, w, base, nb);
-    hipLaunchKernelGGL(k_fqe_encode<false>, dim3(w.slots), dim3(64), 0, s, a, in, w, base, nb);
+    u32 *d_route;
+    if (r4x16_fqe_stages(c, a, in, at, base, nb, max_in_size, max_params_size, max_records, s, &w, &d_route) != 0) return -1;
     hipLaunchKernelGGL(k_fqe_back, dim3(nb), dim3(256), 0, s, a, in, w, base);
     return r4x16_route_end(c, R4X16_ROUTE_FQZ_ENC, d_route, R4X16_FQZ_ENC_KINDS, s);
 }

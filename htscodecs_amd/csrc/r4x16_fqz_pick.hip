@@ -1,7 +1,8 @@
 // r4x16_fqz_pick.hip - the parameter choice of htscodecs' quality encoder on the device: fqz_qual_stats(.., -1),
 // fqz_pick_parameters and fqz_store_parameters (fqzcomp_qual.c:418-945) over slices in device memory:
 // include/rans4x16_hip.h part 2k.  The host's restatement is r4x16_fqz_pick.h; the decisions and the store are
-// r4x16_fqz_pick_dec.h, the same code on both sides.
+// r4x16_fqz_pick_dec.h, the same code on both sides.  The work areas and the statistics stages (r4x16_fqp_stats: the
+// first five kernels) are declared in r4x16_fqz_best.h: the best-of-several call runs them once for all its candidates.
 //
 // Everything fqz_qual_stats counts is a marginal of one joint histogram J[dir][bin][x][q]: dir READ2 or not,
 // bin the record's average-quality bin, x = j & 127 with j counting down from the record's length, q the quality.  A
@@ -11,6 +12,7 @@
 //   k_fqp_recs    one wave per record: its `tot` and avg_qual, the duplicate test against the record before, the
 //                 2,560-entry avg histogram, which qualities occur
 //   k_fqp_bins    one wave per block: nsym and max_sym, the thresholds (avg -> bin map), each record's (dir, bin) class
+//                 (the bins where the block's strategy - or, best of several, any candidate's: FqpIn.any_qa - asks)
 //   k_fqp_count   one wave per record: J, one atomic a byte
 //   k_fqp_sums    eight workgroups per block, sixteen x each: the row totals, then the entropy terms of the non-zero cells
 //   k_fqp_store   one wave per block: the decisions, the flags' largest selector, the parameter bytes into the stage,
@@ -21,43 +23,8 @@
 // tested in k_fqp_lens before anything is read; only k_fqp_store writes to the caller's memory, after it has tested
 // the slot's capacity, and only for a block whose status is 0.  All stores are plain vector stores or vector atomics.
 #include "r4x16_host.h"
-#include "r4x16_fqz_pick_dec.h"
+#include "r4x16_fqz_best.h"
 
-#define FQP_J_CELLS (2u * 4u * FQD_NP * 256u)
-#define FQP_PARTS 8u                        // workgroups of k_fqp_sums per block
-#define FQP_STAGE ((fqd_cap() + 15u) & ~15u)
-#define FQP_REC_GROUPS 256u                 // workgroups per block of the record kernels, at most
-
-struct FqpIn {
-    const u32 *len, *flags; const u64 *rec_off; const u32 *nrec; const i32 *d_strat;
-    int vers, strat, guard_bits;
-    u32 *len_out, *flags_out; const u64 *out_rec_off;    // out_rec_off and the slot arrays: indexed from obase
-};
-struct FqpBlk {
-    i32 status, strat;
-    u32 size, nrec, nw;                     // nw: the records worked on - nrec, or 1 for bytes without a record
-    u32 first_len, fixed_len, has_r2, caller_max_sel, visited, dups;
-    u32 nsym, max_sym, need_j;
-    u32 qmask[8];
-};
-struct FqpWs {
-    FqpBlk *blk;                            // [nb]
-    u32 *route;                             // [R4X16_FQZ_PICK_KINDS]; nullptr in the kernels' copy: option route_count is off
-    u32 *wlen, *wstart, *wavg;              // [nb] x rec_stride: fixed length, first byte, avg_qual
-    u8 *wcls;                               // [nb] x rec_stride: dir * 4 + bin
-    u32 *avg;                               // [nb] x 2560
-    u32 *J;                                 // [nb] x FQP_J_CELLS
-    double *part;                           // [nb] x FQP_PARTS x 5
-    u8 *par;                                // [nb] x FQP_STAGE
-    u64 rec_stride;
-};
-
-__device__ __forceinline__ u32 fqp_wave_max(u32 v)
-{
-#pragma unroll
-    for (int m = 32; m; m >>= 1) { const u32 o = (u32)__shfl_xor((int)v, m); v = v > o ? v : o; }
-    return v;
-}
 __device__ __forceinline__ double fqp_wave_dsum(double v)
 {
 #pragma unroll
@@ -174,8 +141,8 @@ __global__ __launch_bounds__(256) void k_fqp_bins(FqpIn in, FqpWs w, int base, i
     const u32 max_sym = fqp_wave_max(m ? lane * 32u + 31u - (u32)__clz(m) : 0u);
     FqdParam pm;
     fqd_strat(bk->strat, &pm);
-    const bool qa = pm.do_qa != 0;
-    if (lane == 0) { bk->nsym = nsym; bk->max_sym = max_sym; bk->need_j = qa || bk->has_r2 || pm.do_r2; }
+    const bool qa = pm.do_qa != 0 || in.any_qa;
+    if (lane == 0) { bk->nsym = nsym; bk->max_sym = max_sym; bk->need_j = qa || bk->has_r2 || pm.do_r2 || in.any_r2; }
     if (qa) {
         const u32 *avg = w.avg + (u64)b * FQD_AVG;
         for (u32 k = lane; k < FQD_AVG; k += WAVE) bins[wv][k] = avg[k];
@@ -282,16 +249,8 @@ __global__ __launch_bounds__(256) void k_fqp_store(BatchArgs a, FqpIn in, FqpWs 
     FqdStats fs;
     u32 psize = 0;
     if (st == 0) {
-        fs.nrec = (int)bk->nrec; fs.in_size = bk->size; fs.first_len = bk->first_len; fs.fixed_len = (int)bk->fixed_len;
-        fs.has_r2 = (int)bk->has_r2; fs.caller_max_sel = (int)bk->caller_max_sel; fs.visited = bk->visited; fs.dups = bk->dups;
-        fs.nsym = (int)bk->nsym; fs.max_sym = (int)bk->max_sym;
-        FqdSums sm = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (bk->need_j) {
-            const double *p = w.part + (u64)b * FQP_PARTS * 5u;
-            for (u32 k = 0; k < FQP_PARTS; k++) { sm.e1 += p[5 * k]; sm.e2 += p[5 * k + 1]; sm.e4 += p[5 * k + 2]; sm.r1 += p[5 * k + 3]; sm.r2 += p[5 * k + 4]; }
-            // every term is <= 0: the sum of the |terms| is the sum's own magnitude
-            sm.a1 = -sm.e1; sm.a2 = -sm.e2; sm.a4 = -sm.e4; sm.ra1 = -sm.r1; sm.ra2 = -sm.r2;
-        }
+        FqdSums sm;
+        fqp_stats_of(bk, w.part + (u64)b * FQP_PARTS * 5u, &fs, &sm);
         fqd_strat(bk->strat, &pm);
         st = fqd_decide(&pm, &fs, &sm, in.guard_bits, &ch);
     }
@@ -357,6 +316,20 @@ static u32 fqp_groups(u32 max_rec) { return std::min<u32>(FQP_REC_GROUPS, (max_r
 // a chunk holds at most this many blocks: the record kernels' grids are blocks x groups
 static size_t fqp_chunk_limit(u32 max_rec) { return (size_t)INT_MAX / std::max<u32>(fqp_groups(max_rec), FQP_PARTS); }
 
+size_t r4x16_fqp_layout(u8 *base, size_t nb, u32 max_rec, FqpWs *w) { return fqp_layout(base, nb, max_rec, w); }
+size_t r4x16_fqp_chunk_limit(u32 max_rec) { return fqp_chunk_limit(max_rec); }
+int r4x16_fqp_stats(rans4x16_hip_ctx *c, const BatchArgs &a, const FqpIn &in, const FqpWs &w, int base, int nb, u32 max_in, u32 max_rec, hipStream_t s)
+{
+    const u32 groups = fqp_groups(max_rec);
+    HIPCHK(c, hipMemsetAsync(w.avg, 0, (size_t)((u8 *)(w.J + (size_t)nb * FQP_J_CELLS) - (u8 *)w.avg), s));
+    hipLaunchKernelGGL(k_fqp_lens, dim3((nb + 3) / 4), dim3(256), 0, s, a, in, w, base, nb, max_in, max_rec);
+    hipLaunchKernelGGL(k_fqp_recs, dim3((u32)nb * groups), dim3(256), 0, s, a, w, base, groups);
+    hipLaunchKernelGGL(k_fqp_bins, dim3((nb + 3) / 4), dim3(256), 0, s, in, w, base, nb);
+    hipLaunchKernelGGL(k_fqp_count, dim3((u32)nb * groups), dim3(256), 0, s, a, w, base, groups);
+    hipLaunchKernelGGL(k_fqp_sums, dim3((u32)nb * FQP_PARTS), dim3(256), 0, s, w);
+    return 0;
+}
+
 // one chunk's pick, laid out at `at`: blocks base .. base + nb of the inputs, results at obase .. of the outputs
 static int fqp_chunk(rans4x16_hip_ctx *c, const BatchArgs &a, const FqpIn &in, u8 *at, int base, int obase, int nb, u32 max_in, u32 max_rec,
                      hipStream_t s)
@@ -364,14 +337,8 @@ static int fqp_chunk(rans4x16_hip_ctx *c, const BatchArgs &a, const FqpIn &in, u
     FqpWs w;
     fqp_layout(at, (size_t)nb, max_rec, &w);
     u32 *const d_route = w.route;
-    const u32 groups = fqp_groups(max_rec);
-    HIPCHK(c, hipMemsetAsync(w.avg, 0, (size_t)((u8 *)(w.J + (size_t)nb * FQP_J_CELLS) - (u8 *)w.avg), s));
     if (r4x16_route_begin(c, &w.route, R4X16_FQZ_PICK_KINDS, s) != 0) return -1;
-    hipLaunchKernelGGL(k_fqp_lens, dim3((nb + 3) / 4), dim3(256), 0, s, a, in, w, base, nb, max_in, max_rec);
-    hipLaunchKernelGGL(k_fqp_recs, dim3((u32)nb * groups), dim3(256), 0, s, a, w, base, groups);
-    hipLaunchKernelGGL(k_fqp_bins, dim3((nb + 3) / 4), dim3(256), 0, s, in, w, base, nb);
-    hipLaunchKernelGGL(k_fqp_count, dim3((u32)nb * groups), dim3(256), 0, s, a, w, base, groups);
-    hipLaunchKernelGGL(k_fqp_sums, dim3((u32)nb * FQP_PARTS), dim3(256), 0, s, w);
+    if (r4x16_fqp_stats(c, a, in, w, base, nb, max_in, max_rec, s) != 0) return -1;
     hipLaunchKernelGGL(k_fqp_store, dim3((nb + 3) / 4), dim3(256), 0, s, a, in, w, base, obase, nb);
     return r4x16_route_end(c, R4X16_ROUTE_FQZ_PICK, d_route, R4X16_FQZ_PICK_KINDS, s);
 }

@@ -68,7 +68,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 12
+#define ROUTE_WHICH 13
 // R4X16_ROUTE_ENCODE_BODY rides on the encode chain's copy: the word of the per-class counts that k_enc_chain's affine
 // waves count their streams in (no launch has that many classes; r4x16_enc_chain.hip)
 #define ENC_ROUTE_AFF_WORD (CLS_MAX - 1u)
@@ -178,10 +178,11 @@ int r4x16_route_begin(rans4x16_hip_ctx *c, u32 **kernels, u32 words, hipStream_t
 int r4x16_route_end(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words, hipStream_t s);
 // fqzcomp_qual encoding (r4x16_fqz_enc.hip): what the call takes beside the slot arguments, the arena bytes of a chunk of nb
 // blocks, and one chunk's front / encode / back stages laid out at `at` - the device call's, and what the one-call form
-// with the pick in front (r4x16_fqz_pick.hip) runs behind its pick
+// with the pick in front (r4x16_fqz_pick.hip) runs behind its pick.  (r4x16_fqz_best.h: the same without the back end.)
 struct FqeIn {
     const u8 *par; const u64 *par_off; const u32 *par_size;
     const u32 *len, *flags; const u64 *rec_off; const u32 *nrec;
+    const u64 *len_off;     // where a block's lengths start, if not at rec_off (nullptr): several blocks may share one list
 };
 size_t r4x16_fqe_chunk_bytes(rans4x16_hip_ctx *c, size_t nb, u32 max_in_size, u32 max_records);
 int r4x16_fqe_chunk(rans4x16_hip_ctx *c, const BatchArgs &a, const FqeIn &in, u8 *at, int base, int nb, u32 max_in_size, u32 max_params_size,

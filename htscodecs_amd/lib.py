@@ -202,6 +202,18 @@ SIGNATURES = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_uint32, C.c_uint32, C.c_void_p]),
+    # fqzcomp_qual encoding: best of several strategies (include/rans4x16_hip.h part 2l)
+    "rans4x16_hip_fqz_compress_best_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rans4x16_hip_fqz_compress_best_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                            C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rans4x16_hip_fqz_best_chunk_blocks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32]),
+    "rans4x16_hip_fqz_compress_best_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # rANS 4x8's packed and best-of-two device-resident calls (include/rans4x8_hip.h part 2a)
     "rans4x8_hip_compress_packed_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

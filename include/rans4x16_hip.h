@@ -979,6 +979,68 @@ int rans4x16_hip_fqz_compress_pick_dev(rans4x16_hip_ctx *ctx, int n,
                                        uint32_t *d_out_size, int32_t *d_status,
                                        uint32_t max_in_size, uint32_t max_records, void *stream);
 
+/* ---- 2l. fqzcomp_qual encoding: best of several strategies ---------------------------------------------------------
+ * The rows of strat_opts are alternatives for different instruments, and a CRAM writer offers them as so many methods and
+ * keeps the smallest block.  These calls are that loop in one enqueue: block i is coded under each of the k strategies
+ * strats[0 .. k) (a HOST array; 1 <= k <= 16, an entry >= 0, entries of 4 and above the all-zero row, entries may repeat;
+ * anything else returns -1) and comes out as rans4x16_hip_fqz_compress_pick_dev(.., vers, strats[j], ..) writes it for the
+ * j whose stream is smallest, the earlier j on a tie - the bytes and d_out_size[i] are that call's.  The statistics of part
+ * 2k are counted once per slice, whatever k is; only the decisions and the store run per candidate.  DESIGN.md 4.9.
+ *
+ * Inputs and records as in rans4x16_hip_fqz_compress_pick_dev; the caller's input, lengths and flags are never written.
+ * d_chosen (may be NULL): d_chosen[i] = the winner's index j into strats, -1 where the block has no winner (a winner that
+ * the capacity refuses keeps its index).  d_len_out (may be NULL): for a block with a winner the entries d_rec_off[i] ..
+ * + d_nrec[i] get the lengths as the fix-ups leave them.  d_status[i]:
+ *   R4X16_E_UNDECIDED    the device pick cannot decide one of the candidates (part 2k): nothing is written for the block -
+ *                        the smallest of the others would not be the smallest of the list
+ *   R4X16_E_UNSUPPORTED  a block above max_in_size or max_records, of 2^31 bytes or more, a max_sym above
+ *                        rans4x16_hip_set_fqz_limits's, or a candidate that found no room in the arena
+ *   R4X16_E_CAPACITY     the WINNER is longer than d_out_cap[i] (it is tested alone: a loser that would fit is not taken),
+ *                        or ends beyond the packed arena: nothing is written
+ *   a candidate whose parameter bytes the encoder's front end refuses (R4X16_E_TABLE for a pshift the header walk cannot
+ *   read back, ..) is out of the running; where no candidate is left - the records' own refusals, R4X16_E_SIZE and
+ *   R4X16_E_CONTEXT, are every candidate's - the block has the status of the first candidate in list order.
+ *
+ * rans4x16_hip_fqz_compress_best_dev writes the winner into the caller's slot [d_out_off[i], + d_out_cap[i]).
+ * rans4x16_hip_fqz_compress_best_packed_dev has the contract of rans4x16_hip_arith_compress_best_packed_dev: the winners lie
+ * back to back in d_out, d_out_off ([n + 1]) is written on the device, a block that would end beyond out_capacity is
+ * R4X16_E_CAPACITY with size 0 (its offsets stand), and nothing is written at or beyond d_out_off[n].  Both only enqueue on
+ * `stream`, read nothing back and write nothing outside the results' ranges.  No candidate stream is copied twice and no
+ * loser is copied at all: the winner is assembled at its final place from the encoder's stage.
+ *
+ * rans4x16_hip_fqz_best_chunk_blocks: the blocks per chunk these calls plan for n blocks under k strategies (n: one
+ * chunk) - the pick's layout, the candidates' hand-over and the encoder's layout for k items a block fit
+ * max_workspace_mb together.  Host arithmetic; -1 on bad arguments.
+ *
+ * rans4x16_hip_fqz_compress_best_batch: host buffers, as rans4x16_hip_fqz_compress_batch without parameter bytes: one
+ * upload, the device call, one download of the winners.  chosen (may be NULL) as d_chosen.  len[i] comes back as the fix-ups
+ * leave it (status 0) and flags[i][rec] &= 0xffff.  A block the device leaves R4X16_E_UNDECIDED has all its k candidates
+ * picked on the host (rans4x16_hip_fqz_pick_parameters) and is coded in a second trip of those blocks alone, counted
+ * under R4X16_FQZ_PICK_HOST.  Returns the number of failed blocks, -1 on a call error.
+ *
+ * Route read-out: R4X16_ROUTE_FQZ_BEST (R4X16_FQZ_BEST_*); R4X16_ROUTE_FQZ_PICK and R4X16_ROUTE_FQZ_ENC count what they
+ * count, per candidate. */
+int rans4x16_hip_fqz_compress_best_dev(rans4x16_hip_ctx *ctx, int n,
+                                       const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                       const uint32_t *d_len, const uint32_t *d_flags, const uint64_t *d_rec_off, const uint32_t *d_nrec,
+                                       int vers, int k, const int *strats,
+                                       unsigned char *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                       uint32_t *d_out_size, int32_t *d_status, int32_t *d_chosen, uint32_t *d_len_out,
+                                       uint32_t max_in_size, uint32_t max_records, void *stream);
+int rans4x16_hip_fqz_compress_best_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                              const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                              const uint32_t *d_len, const uint32_t *d_flags, const uint64_t *d_rec_off, const uint32_t *d_nrec,
+                                              int vers, int k, const int *strats,
+                                              unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                              uint32_t *d_out_size, int32_t *d_status, int32_t *d_chosen, uint32_t *d_len_out,
+                                              uint32_t max_in_size, uint32_t max_records, void *stream);
+int rans4x16_hip_fqz_best_chunk_blocks(rans4x16_hip_ctx *ctx, int n, int k, uint32_t max_in_size, uint32_t max_records);
+int rans4x16_hip_fqz_compress_best_batch(rans4x16_hip_ctx *ctx, int n,
+                                         const unsigned char *const *in, const unsigned int *in_size,
+                                         const unsigned int *nrec, uint32_t *const *len, uint32_t *const *flags,
+                                         int vers, int k, const int *strats,
+                                         unsigned char *const *out, unsigned int *out_size, int *chosen, int *status);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
@@ -1073,7 +1135,8 @@ enum {
     R4X16_ROUTE_FQZ = 8,      /* fqzcomp_qual decoding (part 2i): decoded streams (R4X16_FQZ_*)                        */
     R4X16_ROUTE_ENCODE_BODY = 9,/* encode chain: streams per body of the pipelined loop (R4X16_ENC_BODY_*)               */
     R4X16_ROUTE_FQZ_ENC = 10, /* fqzcomp_qual encoding (part 2j): encoded streams (R4X16_FQZ_ENC_*)                    */
-    R4X16_ROUTE_FQZ_PICK = 11 /* fqzcomp_qual's parameter choice on the device (part 2k): blocks (R4X16_FQZ_PICK_*)    */
+    R4X16_ROUTE_FQZ_PICK = 11,/* fqzcomp_qual's parameter choice on the device (part 2k): blocks (R4X16_FQZ_PICK_*)    */
+    R4X16_ROUTE_FQZ_BEST = 12 /* fqzcomp_qual's best of several strategies (part 2l): R4X16_FQZ_BEST_*                  */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -1154,6 +1217,14 @@ enum {   /* R4X16_ROUTE_FQZ_PICK: blocks of rans4x16_hip_fqz_pick_dev / _compres
     R4X16_FQZ_PICK_UNDECIDED = 4,   /* left to the host: R4X16_E_UNDECIDED                                             */
     R4X16_FQZ_PICK_HOST = 5,        /* blocks of a host-buffer batch picked on the host behind an undecided device pick */
     R4X16_FQZ_PICK_KINDS = 6
+};
+enum {   /* R4X16_ROUTE_FQZ_BEST: rans4x16_hip_fqz_compress_best_dev / _best_packed_dev / _best_batch */
+    R4X16_FQZ_BEST_BLOCKS = 0,      /* blocks whose winner was written (status 0)                                      */
+    R4X16_FQZ_BEST_CANDIDATES = 1,  /* candidate streams the encoder accepted, of the blocks that were decided          */
+    R4X16_FQZ_BEST_COUNTED = 2,     /* slices whose histogram was counted: once each, whatever k is                     */
+    R4X16_FQZ_BEST_UNDECIDED = 3,   /* blocks left R4X16_E_UNDECIDED by one of their candidates                         */
+    R4X16_FQZ_BEST_REFUSED = 4,     /* candidates out of the running, of the blocks that were decided                   */
+    R4X16_FQZ_BEST_KINDS = 5
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
