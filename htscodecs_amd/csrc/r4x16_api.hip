@@ -886,10 +886,11 @@ extern "C" unsigned char *rans_compress_4x16(unsigned char *in, unsigned int in_
 }
 
 // uncompressed size stored in the container header (host read of <= 6 bytes; needed to size the
-// malloc the reference API promises when out == NULL, rANS_static4x16pr.c:1459-1462)
+// malloc the reference API promises when out == NULL, rANS_static4x16pr.c:1459-1462).  A stripe stream always
+// stores its size and the reference never looks at its X_NOSZ bit (:1360-1378 come before :1439)
 static int peek_size(const unsigned char *in, unsigned int in_size, unsigned int *usz)
 {
-    if (in_size < 1 || (in[0] & X_NOSZ)) return -1;
+    if (in_size < 1 || ((in[0] & X_NOSZ) && !(in[0] & X_STRIPE))) return -1;
     unsigned int v = 0, i = 1;
     unsigned char ch;
     if (i >= in_size) { *usz = 0; return 0; }

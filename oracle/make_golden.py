@@ -10,13 +10,16 @@ Two kinds of vectors, and they do not have the same standing:
     oracle at sizes and shapes the fixtures do not have; they pin nothing about the reference by themselves.  (Rounds
     1-3 generated them with a build of the reference sources against an empty stand-in config.h; that build is not the
     reference's own and was removed in round 4 - see oracle/Makefile.  The oracle reproduces every one of those vectors
-    byte for byte, which is how this script was checked when it was switched over.)
+    byte for byte, which is how this script was checked when it was switched over.)  oracle/make_rans_edge.py sends
+    every entry of edge.json through the reference's unchanged sources (oracle/_ref/rans_ref) each time it runs and
+    fails unless all are reproduced by length and MD5; the count stands in tests/golden/rans/README.edge.md.  The
+    reference-MADE edge and damaged vectors are tests/golden/rans/edge.bin.
 
 What is written (data only — no reference source):
   tests/golden/dat/<name>.nl      the reference's own test inputs, first column with newlines
                                   removed, i.e. exactly what tests/rans4x16.test:11 feeds the codec
   tests/golden/r4x16/<name>.<o>   the reference's committed compressed fixtures (tests/dat/r4x16)
-  tests/golden/edge.json          generated edge cases: [input spec, order] -> reference output
+  tests/golden/edge.json          generated edge cases: [input spec, order] -> the oracle's output
                                   (base64 when small, md5+length always)
 """
 import base64

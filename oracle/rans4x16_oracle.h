@@ -10,9 +10,11 @@
  * Parity pin: tests/test_oracle.py checks this restatement against all 24 reference-held
  * fixtures (tests/golden/r4x16/ = tests/dat/r4x16/ of the reference: decode AND byte-identical
  * re-encode) and the varint known-answer tables of tests/varint_test.c.  The reference itself
- * is not built here (its sources need an autotools-generated config.h, oracle/Makefile); the
+ * is not built into this library (its sources need an autotools-generated config.h, oracle/Makefile); the
  * generated edge vectors of tests/golden/edge.json carry THIS restatement's outputs and are
- * regression vectors for the HIP path, not a second pin.
+ * regression vectors for the HIP path, not a second pin.  The second pin is tests/golden/rans/edge.bin: streams and
+ * answers to damaged streams made by the reference's unchanged sources behind oracle/rans_ref_driver.c
+ * (tests/test_rans_edge_cpu.py; oracle/make_rans_edge.py also shows that the reference reproduces all of edge.json).
  *
  * Symbols carry an orc_ prefix so the oracle and the product library can live in one process.  Signatures mirror htscodecs/rANS_static4x16.h:41-50.
  */

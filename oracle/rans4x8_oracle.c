@@ -22,10 +22,16 @@
  * decoder accepts 4095 and 4096.
  *
  * Where the reference is undefined on damaged input this restatement FAILS instead (and so does the device):
- *   - a lookup of slot 4095 in a table that sums to 4095 (the reference reads an unwritten table entry,
- *     rANS_static.c:257-259 / a byte written into another context's row, :807-808);
- *   - an order-1 context that has no table (the reference reads per-thread tables left by earlier calls, :685-706);
+ *   - a lookup of slot 4095 in a table that sums to 4095 (order 0: the reference reads an entry of a stack array it never
+ *     wrote, rANS_static.c:237-239; order 1: it numbers its rows by first appearance, :751-759, and copies slot 4094 of
+ *     row <context BYTE> to that row's slot 4095, :799-800, which is the table's own row only where number and byte agree);
+ *   - an order-1 context that has no table and is used (the reference decodes it from a row of its per-thread tables
+ *     that this call never wrote, :685-706) - and with it the one case in which the reference is defined: a stream that
+ *     lists byte 0 nowhere starts its quarters in the row of the first context listed (map[0] falls back to 0, :814-816);
  *   - in_size == 0 on encode (the reference divides by zero, :108).
+ * tests/rans_edge_cases.py (DEVIATIONS) holds the three as predicates over a stream's bytes, and tests/golden/rans/edge.bin
+ * holds the reference's answers to 600 damaged streams: where its answer does not depend on what the call never wrote, this
+ * restatement gives it, or one of those predicates holds (tests/test_rans_edge_cpu.py).
  */
 #include <stdint.h>
 #include <stdlib.h>

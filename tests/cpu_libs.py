@@ -1,5 +1,6 @@
-"""ctypes access to the CPU checkers: the oracle (our C restatement) and, when it has been
-built from /root/reference by `make -C oracle ref`, the real reference library.
+"""ctypes access to the CPU checker: the oracle (our C restatement, oracle/liboracle4x16.so).  The reference itself is
+never loaded into python: where a reference tree is present, `make -C oracle` links it behind stand-alone drivers
+(oracle/_ref/rans_ref, oracle/_ref/tok3_ref) that tests/rans_edge_cases.py and tests/test_tok3_edge_cpu.py start.
 
 Test infrastructure only: nothing in htscodecs_amd/ imports this module.
 """

@@ -1,8 +1,11 @@
 """Pins the CPU oracle (oracle/rans4x16_oracle.c) to the reference's own golden data:
 the 24 committed fixtures of tests/dat/r4x16 (decode AND byte-identical re-encode, as
 SURVEY.md §8c established for the reference itself), the varint known-answer values of
-tests/varint_test.c:145-155, and the generated edge vectors in tests/golden/edge.json
-(made from the real reference by oracle/make_golden.py)."""
+tests/varint_test.c:145-155, and the generated edge vectors in tests/golden/edge.json.  Those are ORACLE-made
+(oracle/make_golden.py writes the oracle's own output): regression vectors, no second pin.  What holds them to the
+reference is oracle/make_rans_edge.py, which sends every entry through the reference and records in
+tests/golden/rans/README.edge.md that it reproduces all 420 by length and MD5; the reference-made vectors are
+tests/golden/rans/edge.bin (tests/test_rans_edge_cpu.py)."""
 import base64
 import ctypes as C
 import hashlib
