@@ -146,7 +146,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc", "fqz_pick", "fqz_best") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc", "fqz_pick", "fqz_best", "best_any") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -158,7 +158,7 @@ class _Ctx:
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
-               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10, "fqz_pick": 11, "fqz_best": 12}
+               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10, "fqz_pick": 11, "fqz_best": 12, "best_any": 13}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -173,7 +173,13 @@ ROUTE_KINDS = {
     "fqz_enc": ("streams", "tab_lds", "tab_global", "do_rev", "multi_param", "dup"),
     "fqz_pick": ("blocks", "sel", "split", "dedup", "undecided", "host"),
     "fqz_best": ("blocks", "candidates", "counted", "undecided", "refused"),
+    "best_any": ("rans", "arith", "tie", "failed", "chunks"),
 }
+
+# include/rans4x16_hip.h part 2m: a method of the cross-codec calls is a codec tag OR-ed with that codec's order word
+CODEC_RANS4X16 = 0
+CODEC_ARITH = 1 << 24
+CODEC_MASK = 0x0F000000
 
 _tls = threading.local()
 
@@ -696,6 +702,53 @@ def arith_compress(data, order, out_size=None):
     return out.raw[:n.value] if p else None
 
 
+def compress_best_any_batch(blocks, methods, caps=None, ctx=None):
+    """rans4x16_hip_compress_best_any_batch: every block under a list of tagged methods (CODEC_ARITH | order for
+    arith_dynamic, a plain order word for rANS 4x16), the smallest stream kept.  caps None: the library allocates exactly
+    the result; else a capacity per block.  Returns (the streams, None for a block that failed; the chosen methods; the
+    statuses)."""
+    ctx = ctx or _thread_ctx()
+    L = ctx.L
+    n = len(blocks)
+    meth = _methods(methods)
+    chosen = (C.c_int * n)()
+    if caps is None:
+        srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+        dummy = np.zeros(1, dtype=np.uint8)
+        in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
+        in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
+        out_p = (C.c_void_p * n)()
+        out_sz = (C.c_uint * n)()
+        status = (C.c_int * n)()
+        rc = L.rans4x16_hip_compress_best_any_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, len(methods), meth, chosen, status)
+        outs = []
+        for i in range(n):
+            outs.append(C.string_at(out_p[i], out_sz[i]) if status[i] == 0 and out_p[i] else None)
+            if out_p[i]:
+                _free(out_p[i])
+        if rc < 0:
+            raise RuntimeError("compress_best_any_batch: " + ctx.error())
+        return outs, list(chosen), list(status)
+    a = _HostArrays(blocks, caps)
+    rc = L.rans4x16_hip_compress_best_any_batch(ctx.h, n, a.in_p, a.in_sz, a.out_p, a.out_sz, len(methods), meth, chosen, a.status)
+    if rc < 0:
+        raise RuntimeError("compress_best_any_batch: " + ctx.error())
+    outs, status = a.results()
+    return outs, list(chosen), status
+
+
+def uncompress_any_batch(blocks, methods, caps, ctx=None):
+    """rans4x16_hip_uncompress_any_batch: streams of either codec, methods[i] saying which (only its codec tag is looked
+    at; negative: a block that was never written), into buffers of caps[i] bytes.  Returns (the blocks, None where one
+    failed; the statuses)."""
+    ctx = ctx or _thread_ctx()
+    a = _HostArrays(blocks, caps)
+    rc = ctx.L.rans4x16_hip_uncompress_any_batch(ctx.h, a.n, a.in_p, a.in_sz, _methods(methods), a.out_p, a.out_sz, a.status)
+    if rc < 0:
+        raise RuntimeError("uncompress_any_batch: " + ctx.error())
+    return a.results()
+
+
 class DeviceCodec:
     """Device-resident batches on torch tensors (torch is used for device memory and streams
     only).  All tensors must live on the context's device."""
@@ -1041,6 +1094,58 @@ class DeviceCodec:
         if rc < 0:
             raise RuntimeError("arith_best_chunk_blocks: " + self.ctx.error())
         return rc
+
+    # ---- best of several methods across codecs (include/rans4x16_hip.h part 2m) ---------------------------------
+    def compress_best_any_packed(self, d_in, in_off, in_size, d_out, out_off, out_size, status, methods, max_in_size,
+                                 chosen=None, total_in_size=0, out_capacity=None):
+        """rans4x16_hip_compress_best_any_packed_dev: compress_best_packed over a list of tagged methods (CODEC_ARITH | order
+        for arith_dynamic, a plain order word for rANS 4x16); chosen gets the winner's tagged word.  d_out None (with
+        out_capacity 0 or None) is the sizing pass."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
+        assert in_off.dtype == t.int64 and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == in_off.numel() + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert chosen is None or chosen.dtype == t.int32
+        room = d_out.numel() if d_out is not None else 0
+        cap = room if out_capacity is None else int(out_capacity)
+        assert cap <= room
+        meth = _methods(methods)
+        rc = self.L.rans4x16_hip_compress_best_any_packed_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            len(methods), meth, chosen.data_ptr() if chosen is not None else None, int(max_in_size), int(total_in_size),
+            self._stream())
+        self._check(rc, "compress_best_any_packed_dev")
+
+    def best_any_chunk_blocks(self, n, methods, max_in_size, total_in_size=0):
+        """rans4x16_hip_best_any_chunk_blocks: the blocks per chunk compress_best_any_packed plans for these arguments."""
+        meth = _methods(methods)
+        rc = self.L.rans4x16_hip_best_any_chunk_blocks(self.ctx.h, int(n), len(methods), meth, int(max_in_size), int(total_in_size))
+        if rc < 0:
+            raise RuntimeError("best_any_chunk_blocks: " + self.ctx.error())
+        return rc
+
+    def uncompress_any_packed(self, d_in, in_off, in_size, method, d_out, out_off, out_size, status, max_in_size, max_out_size,
+                              nosz_size=None, out_capacity=None):
+        """rans4x16_hip_uncompress_any_packed_dev: uncompress_packed for an arena that mixes both codecs; method (int32
+        tensor: compress_best_any_packed's chosen goes straight in) says which decodes block i."""
+        t = self.torch
+        n = in_size.numel()
+        assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
+        assert in_off.dtype == t.int64 and in_off.numel() >= n and in_size.dtype == t.int32
+        assert method.dtype == t.int32 and method.numel() == n
+        assert out_off.dtype == t.int64 and out_off.numel() == n + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert nosz_size is None or (nosz_size.dtype == t.int32 and nosz_size.numel() == n)
+        room = d_out.numel() if d_out is not None else 0
+        cap = room if out_capacity is None else int(out_capacity)
+        assert cap <= room
+        rc = self.L.rans4x16_hip_uncompress_any_packed_dev(
+            self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(), method.data_ptr(),
+            d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
+            nosz_size.data_ptr() if nosz_size is not None else None, int(max_in_size), int(max_out_size), self._stream())
+        self._check(rc, "uncompress_any_packed_dev")
 
     def set_tok3_arith(self, mode):
         """rans4x16_hip_set_tok3_arith: 0, TOK3_ARITH_DECODE (1), TOK3_ARITH_ENCODE (2) or both; returns the previous mode."""

@@ -22,6 +22,7 @@
 // as a whole before anything is written; the coded body is cut off at the input's length (the early end), five closing
 // bytes at most behind it.  All stores are plain vector stores.
 #include "r4x16_host.h"
+#include "r4x16_best_any.h"
 #include "r4x16_arith_parse.h"
 #include "r4x16_arith_enc_step.h"
 
@@ -530,11 +531,7 @@ extern "C" int rans4x16_hip_arith_compress_dev(rans4x16_hip_ctx *c, int n,
 // not tried - a stripe method on a size that is no multiple of 4 (tokenise_name3.c:1270), a block above max_in_size, a
 // slot beyond the arena (a batch that holds more than it announced) - has capacity 0: the front refuses it before it
 // makes an item, so it is neither coded nor counted.
-#define AB_MAX_K 32
-struct AbMethods { int k; int m[AB_MAX_K]; };
-struct AbWs {
-    u64 *in_off, *slot_off /*[items + 1]*/; u32 *in_size, *need, *cap, *out_size; i32 *status, *order; u32 *win /*[nb]*/; u8 *slots; u64 slot_bytes;
-};
+// (AbMethods, AbWs, AbPlan: r4x16_best_any.h - the call that picks across codecs runs this unit's candidates too)
 
 static size_t ab_carve(AbWs *w, u8 *base, size_t nb, size_t k, u64 slot_bytes)
 {
@@ -595,9 +592,9 @@ __global__ __launch_bounds__(256) void k_ab_pick(const u32 *in_size, AbWs w, AbM
     if (no_room) { win = -1; st = AR_E_UNSUPPORTED; }
     else if (win < 0) st = first >= 0 ? w.status[(size_t)lb * pm.k + first] : AR_E_UNSUPPORTED;
     w.win[lb] = win >= 0 ? (u32)win : 0u;
-    status[g] = st;
-    out_size[g] = win >= 0 ? best : 0u;
-    if (chosen) chosen[g] = win >= 0 ? pm.m[win] : -1;
+    status[lb] = st;                                                                  // (the chunk's arrays: the callers pass them from `base` on)
+    out_size[lb] = win >= 0 ? best : 0u;
+    if (chosen) chosen[lb] = win >= 0 ? pm.m[win] : -1;
 }
 
 __global__ __launch_bounds__(256) void k_ab_gather(PackedOut pk, AbWs w, int k, u32 *out_size, i32 *status, int base)
@@ -613,45 +610,76 @@ __global__ __launch_bounds__(256) void k_ab_gather(PackedOut pk, AbWs w, int k, 
     group_copy<256>(pk.out + pk.off[i], w.slots + w.slot_off[(size_t)lb * k + w.win[lb]], sz, tid);
 }
 
-// What the call plans before it enqueues: the methods, the planes a stripe candidate may have, the items an inner item
-// reserves, the batch's bytes and the blocks per chunk - this call's candidate slots (the packed arena) and the inner
+// What the call plans before it enqueues (AbPlan): the methods, the planes a stripe candidate may have, the items an inner
+// item reserves, the batch's bytes and the blocks per chunk - this call's candidate slots (the packed arena) and the inner
 // call's arena for k items a block fit the room together, so that the inner call takes the chunk in one pass.
-struct AbPlan { AbMethods pm; u32 planes; size_t per; u64 total; size_t chunk; };
 static u64 ab_slot_bytes(const AbPlan &p, size_t nb, u32 max_in)
 {
     return (u64)p.pm.k * (std::min<u64>(p.total, (u64)nb * max_in) + (u64)nb * (64u + 28u * p.planes));
 }
 static u64 ab_inner_total(const AbPlan &p, size_t nb, u32 max_in) { return (u64)p.pm.k * std::min<u64>(p.total, (u64)nb * max_in); }
 
-// the methods alone: what a call refuses before it asks for the device
-static int ab_methods(rans4x16_hip_ctx *c, int k, const int *methods, AbPlan *p)
+int r4x16_ab_methods(rans4x16_hip_ctx *c, const char *who, int k, const int *methods, AbPlan *p)
 {
     p->pm = AbMethods{};
     p->pm.k = k;
     p->planes = 0;
     for (int j = 0; j < k; j++) {
         u32 N = 0;
-        if ((methods[j] & AR_X_STRIPE) && are_order_check(21u, methods[j], &N) != AR_OK) { c->err = "arith_compress_best_packed_dev: more than 255 stripes"; return -1; }
+        if ((methods[j] & AR_X_STRIPE) && are_order_check(21u, methods[j], &N) != AR_OK) { c->err = std::string(who) + ": more than 255 stripes"; return -1; }
         p->planes = std::max(p->planes, N);
         p->pm.m[j] = methods[j];
     }
     return 0;
 }
 
-// the rest, on the context's device
-static void ab_fit(rans4x16_hip_ctx *c, int n, int k, uint32_t max_in_size, uint64_t total_in_size, AbPlan *p)
+void r4x16_ab_sizes(int n, uint32_t max_in_size, uint64_t total_in_size, AbPlan *p)
 {
     p->per = p->planes ? (size_t)p->planes * ARE_CANDS : 1;
     p->total = total_in_size ? total_in_size : (u64)n * max_in_size;
     p->chunk = 0;
+}
+
+size_t r4x16_ab_carve(AbWs *w, u8 *base, const AbPlan &p, size_t nb, u32 max_in_size)
+{
+    return ab_carve(w, base, nb, (size_t)p.pm.k, ab_slot_bytes(p, nb, max_in_size));
+}
+
+size_t r4x16_ab_inner_bytes(const AbPlan &p, size_t nb, u32 max_in_size)
+{
+    AreWs iw;
+    const size_t items = nb * (size_t)p.pm.k;
+    return are_layout(nullptr, items, p.per, are_stage_bytes(items, p.per, p.planes, ab_inner_total(p, nb, max_in_size), max_in_size), &iw);
+}
+
+// the rest, on the context's device
+static void ab_fit(rans4x16_hip_ctx *c, int n, uint32_t max_in_size, uint64_t total_in_size, AbPlan *p)
+{
+    r4x16_ab_sizes(n, max_in_size, total_in_size, p);
     if (n == 0) return;
     AbWs w;
-    AreWs iw;
-    auto bytes = [&](size_t nb) {
-        return ab_carve(&w, nullptr, nb, (size_t)k, ab_slot_bytes(*p, nb, max_in_size)) +
-               are_layout(nullptr, nb * k, p->per, are_stage_bytes(nb * k, p->per, p->planes, ab_inner_total(*p, nb, max_in_size), max_in_size), &iw);
-    };
-    p->chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / (p->per * k), r4x16_room(c, A_BIT(A_PS) | A_BIT(A_AR)), bytes);
+    auto bytes = [&](size_t nb) { return r4x16_ab_carve(&w, nullptr, *p, nb, max_in_size) + r4x16_ab_inner_bytes(*p, nb, max_in_size); };
+    p->chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / (p->per * p->pm.k), r4x16_room(c, A_BIT(A_PS) | A_BIT(A_AR)), bytes);
+}
+
+int r4x16_ab_candidates(rans4x16_hip_ctx *c, const AbPlan &p, const AbWs &w, size_t arena, size_t base, int nb, const u8 *d_in,
+                        const u64 *d_in_off, const u32 *d_in_size, u32 *out_size, i32 *status, i32 *chosen, u32 max_in_size, hipStream_t s)
+{
+    const u32 items = (u32)nb * (u32)p.pm.k;
+    const dim3 per_item((items + 255) / 256);
+    hipLaunchKernelGGL(k_ab_expand, per_item, dim3(256), 0, s, d_in_off, d_in_size, w, p.pm, (int)base, items, max_in_size);
+    r4x16_launch_packed_scan(w.need, w.slot_off, 0, (int)items, s);
+    hipLaunchKernelGGL(k_ab_admit, per_item, dim3(256), 0, s, w, items);
+    {
+        // the inner call: what is left of the ceiling beside the caller's slots, and the planes the methods ask for
+        Keep<size_t> ceiling(c->max_ws, c->max_ws > arena + ((size_t)1 << 20) ? c->max_ws - arena : (size_t)1 << 20);
+        Keep<int> stripe(c->dev_stripe_enc, (int)p.planes);
+        if (rans4x16_hip_arith_compress_dev(c, (int)items, d_in, w.in_off, w.in_size, w.slots, w.slot_off, w.cap, w.out_size, w.status, 0,
+                                            w.order, max_in_size, ab_inner_total(p, (size_t)nb, max_in_size), s) != 0)
+            return -1;
+    }
+    hipLaunchKernelGGL(k_ab_pick, dim3((u32)(nb + 255) / 256), dim3(256), 0, s, d_in_size, w, p.pm, out_size, status, chosen, (int)base, nb, max_in_size);
+    return 0;
 }
 
 extern "C" int rans4x16_hip_arith_best_chunk_blocks(rans4x16_hip_ctx *c, int n, int k, const int *methods, uint32_t max_in_size,
@@ -660,9 +688,9 @@ extern "C" int rans4x16_hip_arith_best_chunk_blocks(rans4x16_hip_ctx *c, int n, 
     if (!c) return -1;
     if (n < 0 || k < 1 || k > AB_MAX_K || !methods) { c->err = "arith_best_chunk_blocks: bad arguments"; return -1; }
     AbPlan p;
-    if (ab_methods(c, k, methods, &p) != 0) return -1;
+    if (r4x16_ab_methods(c, "arith_compress_best_packed_dev", k, methods, &p) != 0) return -1;
     HIPCHK(c, hipSetDevice(c->device));
-    ab_fit(c, n, k, max_in_size, total_in_size, &p);
+    ab_fit(c, n, max_in_size, total_in_size, &p);
     return (int)p.chunk;
 }
 
@@ -679,30 +707,16 @@ extern "C" int rans4x16_hip_arith_compress_best_packed_dev(rans4x16_hip_ctx *c, 
     PackedOut pk;
     const int go = r4x16_packed_call_args(c, "arith_compress_best_packed_dev: bad arguments", k >= 1 && k <= AB_MAX_K && methods, &a, &pk, n,
                                           d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, 0, nullptr, s,
-                                          [&] { return ab_methods(c, k, methods, &p); });
+                                          [&] { return r4x16_ab_methods(c, "arith_compress_best_packed_dev", k, methods, &p); });
     if (go <= 0) return go;
-    ab_fit(c, n, k, max_in_size, total_in_size, &p);
-    const AbMethods &pm = p.pm;
-    const u32 planes = p.planes;
+    ab_fit(c, n, max_in_size, total_in_size, &p);
     AbWs w;
-    auto slot_bytes = [&](size_t nb) { return ab_slot_bytes(p, nb, max_in_size); };
-    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_PS, ab_carve(&w, nullptr, nb, (size_t)k, slot_bytes(nb)), false); };
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_PS, r4x16_ab_carve(&w, nullptr, p, nb, max_in_size), false); };
     return r4x16_chunk_walk(c, n, p.chunk, s, grab, [&](size_t base, int nb) {
-        const u32 items = (u32)nb * (u32)k;
-        const size_t arena = ab_carve(&w, c->at(A_PS), (size_t)nb, (size_t)k, slot_bytes((size_t)nb));
-        const dim3 per_item((items + 255) / 256);
-        hipLaunchKernelGGL(k_ab_expand, per_item, dim3(256), 0, s, d_in_off, d_in_size, w, pm, (int)base, items, max_in_size);
-        r4x16_launch_packed_scan(w.need, w.slot_off, 0, (int)items, s);
-        hipLaunchKernelGGL(k_ab_admit, per_item, dim3(256), 0, s, w, items);
-        {
-            // the inner call: what is left of the ceiling beside this call's slots, and the planes the methods ask for
-            Keep<size_t> ceiling(c->max_ws, c->max_ws > arena + ((size_t)1 << 20) ? c->max_ws - arena : (size_t)1 << 20);
-            Keep<int> stripe(c->dev_stripe_enc, (int)planes);
-            if (rans4x16_hip_arith_compress_dev(c, (int)items, d_in, w.in_off, w.in_size, w.slots, w.slot_off, w.cap, w.out_size, w.status, 0,
-                                                w.order, max_in_size, ab_inner_total(p, (size_t)nb, max_in_size), s) != 0)
-                return -1;
-        }
-        hipLaunchKernelGGL(k_ab_pick, dim3((u32)(nb + 255) / 256), dim3(256), 0, s, d_in_size, w, pm, d_out_size, d_status, d_chosen, (int)base, nb, max_in_size);
+        const size_t arena = r4x16_ab_carve(&w, c->at(A_PS), p, (size_t)nb, max_in_size);
+        if (r4x16_ab_candidates(c, p, w, arena, base, nb, d_in, d_in_off, d_in_size, d_out_size + base, d_status + base,
+                                d_chosen ? d_chosen + base : nullptr, max_in_size, s) != 0)
+            return -1;
         r4x16_launch_packed_scan(d_out_size, d_out_off, (int)base, nb, s);
         hipLaunchKernelGGL(k_ab_gather, dim3((u32)nb), dim3(256), 0, s, pk, w, k, d_out_size, d_status, (int)base);
         return 0;

@@ -21,6 +21,7 @@
 // Loops: every trip count is a launch argument (k <= 32, N <= 255, K <= 4, P) or a block size that was checked against
 // the host's max_in_size first.
 #include "r4x16_host.h"
+#include "r4x16_best_any.h"
 
 #define BEST_MAX_K 32
 #define BEST_IDLE (X_CAT | X_NOSZ)
@@ -253,8 +254,7 @@ static size_t best_carve(BestWs *w, u8 *base, size_t nb, const BestArgs &e)
 // Lays the methods out (items, slots, plane sets) and runs the batch in chunks.  e->k, e->by_order, e->max_planes and
 // e->m[j].method are set by the caller; `reserve` is the number of items a by_order block keeps.  `fan` bounds the bytes
 // the inner call reads per input byte (every plain method once, every stripe method once per sub-method).
-static int best_run(rans4x16_hip_ctx *c, int n, const BatchArgs &a, BestArgs *e, i32 *d_chosen, u32 reserve,
-                    uint32_t max_in_size, uint64_t total_in_size, hipStream_t s)
+static u32 best_layout(BestArgs *e, u32 reserve, uint32_t max_in_size)
 {
     e->max_in = max_in_size;
     e->pl_stride = align_up((size_t)max_in_size + 64, 256);
@@ -297,12 +297,36 @@ static int best_run(rans4x16_hip_ctx *c, int n, const BatchArgs &a, BestArgs *e,
     }
     e->P = P;
     e->blk_bytes = off;
+    return fan;
+}
+
+// what a chunk of nb blocks takes: the candidate arena and the inner call's workspace
+static size_t best_chunk_bytes(const BestArgs &e, u32 fan, size_t nb, uint32_t max_in_size, u64 total_in)
+{
+    BestWs w;
+    return best_carve(&w, nullptr, nb, e) + r4x16_enc_ws_bytes(nb * e.P, max_in_size, (u64)fan * std::min<u64>(total_in, (u64)nb * max_in_size));
+}
+
+size_t r4x16_best_chunk_bytes(int k, const int *methods, size_t nb, uint32_t max_in_size, uint64_t total_in_size)
+{
+    BestArgs e = {};
+    e.k = k; e.by_order = 0; e.max_planes = 255;
+    for (int j = 0; j < k; j++) e.m[j].method = methods[j];
+    const u32 fan = best_layout(&e, 0, max_in_size);
+    return best_chunk_bytes(e, fan, nb, max_in_size, total_in_size ? total_in_size : (u64)nb * max_in_size);
+}
+
+static int best_run(rans4x16_hip_ctx *c, int n, const BatchArgs &a, BestArgs *e, i32 *d_chosen, u32 reserve,
+                    uint32_t max_in_size, uint64_t total_in_size, hipStream_t s)
+{
+    const u32 fan = best_layout(e, reserve, max_in_size);
+    const u32 P = e->P;
 
     // blocks per chunk: candidate arena + the inner call's workspace under the ceiling, in equal chunks
     const u64 total_in = total_in_size ? total_in_size : (u64)n * max_in_size;
     auto inner_total = [&](size_t nb) { return (u64)fan * std::min<u64>(total_in, (u64)nb * max_in_size); };
     BestWs w;
-    auto bytes = [&](size_t nb) { return best_carve(&w, nullptr, nb, *e) + r4x16_enc_ws_bytes(nb * P, max_in_size, inner_total(nb)); };
+    auto bytes = [&](size_t nb) { return best_chunk_bytes(*e, fan, nb, max_in_size, total_in); };
     // (INT_MAX / P: the inner call counts its items in an int)
     const size_t chunk = r4x16_fit_chunk((size_t)n, (size_t)INT_MAX / P, r4x16_room(c, A_BIT(A_WS) | A_BIT(A_XS)), bytes);
     // (no refusal above half of the free memory here, unlike r4x16_stripe.hip on the same arena: the chunk was planned

@@ -26,9 +26,9 @@
 // first (the size field's varint is read inside the block's in_size <= max_in_size bytes; rANS 4x8's is at a fixed place
 // and read only from blocks of 9 bytes or more).
 #include "r4x16_host.h"
+#include "r4x16_best_any.h"            // peek_one, the reader of the size field, and the slots of a method list
 
 #define PK_MAX_K 32
-#define PK_NO_SIZE 0xffffffffu
 struct PkMethods { int k; int m[PK_MAX_K]; };      // k == 0: the call's order / d_order
 
 // The internal slot of every block of the call: block i of a chunk of `chunk` blocks owns slot i % chunk.  Its capacity
@@ -109,24 +109,7 @@ __global__ __launch_bounds__(256) void k_pk_gather(PackedOut pk, const u8 *slots
 }
 
 // ---- peek ----------------------------------------------------------------------------------------------------
-// First byte and stored uncompressed size of one stream (rANS_static4x16pr.c:1360-1366 for X_STRIPE, :1435-1448
-// otherwise): the varint at byte 1, absent (PK_NO_SIZE) for X_NOSZ streams that are no stripes.
-static __device__ __forceinline__ i32 peek_one(const u8 *in, u32 in_size, u32 max_in, i32 *format, u32 *raw)
-{
-    *format = -1; *raw = PK_NO_SIZE;
-    if (in_size == 0) return ST_EMPTY;                                                // :1357
-    if (in_size > max_in) return ST_UNSUPPORTED;                                      // larger than the call was sized for
-    ByteSrc src(in);
-    const u32 flags = src.at(0);
-    *format = (i32)flags;
-    if (!(flags & X_STRIPE) && (flags & X_NOSZ)) return ST_OK;
-    u32 v = 0;
-    const u32 used = var_get(src, 1u, in_size, &v);
-    if (used == 0 || (src.at(used) & 0x80)) return ST_TRUNCATED;                      // no byte left, or the last one still continues
-    *raw = v;
-    return ST_OK;
-}
-
+// (peek_one, the first byte and the stored uncompressed size of one rANS 4x16 stream: r4x16_best_any.h)
 // The same for a rANS 4x8 stream (rANS_static.c:934-943): the order byte, and the uncompressed size in bytes 5..8; a
 // stream of fewer than 9 bytes has none (:938).  Nothing else is judged here: the decoder does that.
 static __device__ __forceinline__ i32 peek_one8(const u8 *in, u32 in_size, u32 max_in, i32 *format, u32 *raw)
@@ -215,6 +198,16 @@ void r4x16_launch_packed_slots(const BatchArgs *a, const PackedSlots *p, int n, 
     PkMethods pm = {};
     hipLaunchKernelGGL(k_pk_slots, dim3((n + 255) / 256), dim3(256), 0, s, a->in_size, a->d_order, a->order, pm, n, (u32)chunk,
                        p->stride, max_in_size, p->slot_off, p->slot_cap);
+}
+
+void r4x16_launch_packed_slots_best(const u32 *d_in_size, int k, const int *methods, const PackedSlots *p, int n, size_t chunk,
+                                    u32 max_in_size, hipStream_t s)
+{
+    PkMethods pm = {};
+    pm.k = k;
+    for (int j = 0; j < k; j++) pm.m[j] = methods[j];
+    hipLaunchKernelGGL(k_pk_slots, dim3((n + 255) / 256), dim3(256), 0, s, d_in_size, (const i32 *)nullptr, 0, pm, n, (u32)chunk, p->stride,
+                       max_in_size, p->slot_off, p->slot_cap);
 }
 
 extern "C" void r4x16_launch_packed_scan(const u32 *size, u64 *off, int base, int nb, hipStream_t s)

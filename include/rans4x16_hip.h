@@ -1041,6 +1041,91 @@ int rans4x16_hip_fqz_compress_best_batch(rans4x16_hip_ctx *ctx, int n,
                                          int vers, int k, const int *strats,
                                          unsigned char *const *out, unsigned int *out_size, int *chosen, int *status);
 
+/* ---- 2m. best of several methods ACROSS codecs: rANS 4x16 against arith_dynamic ------------------------------------
+ * A CRAM 3.1 writer at its `small` and `archive` settings tries rANS 4x16 order words and arith_dynamic order words side
+ * by side for an ordinary block, keeps the smallest stream and records the codec that won.  These calls are that loop
+ * for blocks in device memory: one enqueue, one dense arena, no read-back; and the reader's one decode call for such a
+ * mixed arena.
+ *
+ * A method is an int: a codec tag in bits 24..27 OR-ed with that codec's order word in bits 0..15.  An untagged word is a
+ * rANS 4x16 method, as in every list of parts 2 and 2a.  Any other tag value makes a call return -1 (the tag space is
+ * reserved for rANS 4x8 and fqzcomp_qual, which are no candidates here), and so does a word with a bit set in 16..23 or
+ * above the tag: nothing but the tag and the order word is carried.
+ *
+ * rans4x16_hip_compress_best_any_packed_dev takes the arguments of rans4x16_hip_compress_best_packed_dev; `methods` is a
+ * HOST array of 1..32 tagged words.  The list is split into its rANS sub-list and its arith sub-list, each in list order.
+ * For each sub-list block i has the result that codec's own best-packed call gives under it
+ * (rans4x16_hip_compress_best_packed_dev, rans4x16_hip_arith_compress_best_packed_dev: the X_STRIPE skip for sizes that
+ * are no multiple of 4, the at-most-20-bytes rule, max_in_size, more than 255 planes returning -1, X_EXT refused by
+ * arith).  Of the sub-lists whose result is status 0 block i gets the smaller stream; on equal sizes the one whose
+ * winning method stands EARLIER in `methods` (the reference loop's tie rule, tokenise_name3.c:1281-1284, over the whole
+ * list).  The bytes written are exactly that codec's stream.  A list of one codec gives byte for byte what that codec's
+ * call gives.
+ *   d_chosen[i] (may be NULL)  the winning methods[j] as given, tag included; -1 if no candidate succeeded: the block then
+ *                              has size 0 and the status of the sub-list whose first method stands first in the list.
+ *                              (An arith sub-list one of whose candidates found no room is R4X16_E_UNSUPPORTED as a
+ *                              whole, as in part 2h; the rANS sub-list's result, if it has one, still stands.)
+ *   output                     one dense arena with the rules of part 2a: d_out_off has n + 1 entries written by the call,
+ *                              the sums are taken before the capacity rule, a block that ends beyond out_capacity is
+ *                              R4X16_E_CAPACITY with size 0, d_out == NULL with out_capacity 0 is a sizing pass, and
+ *                              nothing is written outside the blocks' ranges.
+ * The call only enqueues on `stream`, reads nothing back and does not synchronise.  Per chunk of blocks both codecs'
+ * candidates are encoded into internal slots by the kernels of parts 2 and 2h and reduced to a winner a codec by their own
+ * pick kernels; one pick kernel compares the two winners (size, list position, status), the scan of part 2a runs over the
+ * winners' sizes and one gather copies each winner from whichever arena holds it to its final place: a result byte is
+ * copied once, a loser never leaves its slot.  The chunks are planned so that both codecs' slots and workspaces together
+ * stay under max_workspace_mb and three quarters of the free device memory.
+ *
+ * rans4x16_hip_best_any_chunk_blocks: the blocks per chunk the call plans for these arguments.  Host arithmetic, nothing
+ * is enqueued; -1 on bad arguments.
+ *
+ * rans4x16_hip_uncompress_any_packed_dev takes the arguments of rans4x16_hip_uncompress_packed_dev and d_method, a DEVICE
+ * int32 array of which only `& R4X16_CODEC_MASK` is looked at: the encoder's d_chosen can be passed as it is.  A negative
+ * entry is a block that was never written: it takes 0 bytes and reports R4X16_E_EMPTY.  An entry with any other tag than
+ * the two above is R4X16_E_UNSUPPORTED with 0 bytes.  Every other block claims the size its stream stores (both codecs
+ * keep it in the same place), or d_nosz_size[i] for an X_NOSZ stream (R4X16_E_SIZE where d_nosz_size is NULL); a claim
+ * above max_out_size is refused (R4X16_E_UNSUPPORTED), d_out_off is the exclusive scan of the claims, a block that ends
+ * beyond out_capacity is R4X16_E_CAPACITY with size 0, and nothing is written outside the ranges.  Then the two slot
+ * decoders (rans4x16_hip_uncompress_dev_sized, rans4x16_hip_arith_uncompress_dev) run over the same entries, each seeing
+ * length 0 for the other codec's blocks and reporting into arrays of its own.  X_STRIPE blocks of either codec decode
+ * after rans4x16_hip_set_dev_stripe_planes.
+ *
+ * rans4x16_hip_compress_best_any_batch / rans4x16_hip_uncompress_any_batch: host buffers, through the staging arena of
+ * the other host-buffer calls, in chunks of blocks.  Compress: out[i] == NULL - the library allocates exactly the result
+ * (malloc; the caller frees); otherwise out_size[i] is the capacity on entry and a result that does not fit is
+ * R4X16_E_CAPACITY for that block alone.  chosen (may be NULL) as d_chosen.  Uncompress: as rans4x16_hip_uncompress_batch
+ * - out_size[i] is the capacity on entry (also what an X_NOSZ stream decodes to), method[i] as d_method; every block has a
+ * buffer of its own and fails alone: a stream that stores more than out_size[i] is R4X16_E_CAPACITY and takes nothing from
+ * its neighbours.  Both return the number of failed blocks, -1 on a call error; where the compress call returns -1 it has
+ * freed every buffer it allocated and set those out[i] back to NULL (their out_size[i] to 0): nothing is left to free.
+ *
+ * Route read-out: R4X16_ROUTE_BEST_ANY (R4X16_BEST_ANY_*); the encode routes and R4X16_ROUTE_ARITH_ENC count their own
+ * candidate streams as before. */
+#define R4X16_CODEC_RANS4X16 0
+#define R4X16_CODEC_ARITH    (1 << 24)
+#define R4X16_CODEC_MASK     0x0F000000
+int rans4x16_hip_compress_best_any_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                              const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                              unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                              uint32_t *d_out_size, int32_t *d_status,
+                                              int k, const int *methods, int32_t *d_chosen,
+                                              uint32_t max_in_size, uint64_t total_in_size, void *stream);
+int rans4x16_hip_best_any_chunk_blocks(rans4x16_hip_ctx *ctx, int n, int k, const int *methods, uint32_t max_in_size,
+                                       uint64_t total_in_size);
+int rans4x16_hip_uncompress_any_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                           const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                           const int32_t *d_method,
+                                           unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                           uint32_t *d_out_size, int32_t *d_status, const uint32_t *d_nosz_size,
+                                           uint32_t max_in_size, uint32_t max_out_size, void *stream);
+int rans4x16_hip_compress_best_any_batch(rans4x16_hip_ctx *ctx, int n,
+                                         const unsigned char *const *in, const unsigned int *in_size,
+                                         unsigned char **out, unsigned int *out_size,
+                                         int k, const int *methods, int *chosen, int *status);
+int rans4x16_hip_uncompress_any_batch(rans4x16_hip_ctx *ctx, int n,
+                                      const unsigned char *const *in, const unsigned int *in_size, const int *method,
+                                      unsigned char *const *out, unsigned int *out_size, int *status);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
@@ -1136,7 +1221,8 @@ enum {
     R4X16_ROUTE_ENCODE_BODY = 9,/* encode chain: streams per body of the pipelined loop (R4X16_ENC_BODY_*)               */
     R4X16_ROUTE_FQZ_ENC = 10, /* fqzcomp_qual encoding (part 2j): encoded streams (R4X16_FQZ_ENC_*)                    */
     R4X16_ROUTE_FQZ_PICK = 11,/* fqzcomp_qual's parameter choice on the device (part 2k): blocks (R4X16_FQZ_PICK_*)    */
-    R4X16_ROUTE_FQZ_BEST = 12 /* fqzcomp_qual's best of several strategies (part 2l): R4X16_FQZ_BEST_*                  */
+    R4X16_ROUTE_FQZ_BEST = 12,/* fqzcomp_qual's best of several strategies (part 2l): R4X16_FQZ_BEST_*                  */
+    R4X16_ROUTE_BEST_ANY = 13 /* best of several methods across codecs (part 2m): blocks and chunks (R4X16_BEST_ANY_*)  */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -1225,6 +1311,14 @@ enum {   /* R4X16_ROUTE_FQZ_BEST: rans4x16_hip_fqz_compress_best_dev / _best_pac
     R4X16_FQZ_BEST_UNDECIDED = 3,   /* blocks left R4X16_E_UNDECIDED by one of their candidates                         */
     R4X16_FQZ_BEST_REFUSED = 4,     /* candidates out of the running, of the blocks that were decided                   */
     R4X16_FQZ_BEST_KINDS = 5
+};
+enum {   /* R4X16_ROUTE_BEST_ANY: rans4x16_hip_compress_best_any_packed_dev / _best_any_batch */
+    R4X16_BEST_ANY_RANS = 0,        /* blocks a rANS 4x16 method won (before the arena's capacity rule), ties included     */
+    R4X16_BEST_ANY_ARITH = 1,       /* blocks an arith_dynamic method won, ties included                                 */
+    R4X16_BEST_ANY_TIE = 2,         /* of those: both codecs' winners had the same size, the list position decided        */
+    R4X16_BEST_ANY_FAILED = 3,      /* blocks without a winner (d_chosen -1)                                              */
+    R4X16_BEST_ANY_CHUNKS = 4,      /* chunks the calls walked                                                            */
+    R4X16_BEST_ANY_KINDS = 5
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
