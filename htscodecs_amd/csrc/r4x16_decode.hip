@@ -709,6 +709,12 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
 // the compiler kept the sixteen hdr words and did all of it in the blocks behind the body, where a lone wave pays every
 // slot (a fence does not stop a sink at the IR level).  A trip from header to back edge: 1,062 instructions for 1,096;
 // headline step 133.8 -> 129.8 ms (profiles/dec_state.md).
+// The refill of the 16-step trips runs in practically every trip (fifteen streams, about 31 bytes of words each: some
+// stream enters a new quarter) and nothing covers it, so it is kept lean: addresses made once for both parities, a
+// side of two writes and an unconditional request (`request`: the proof that it stays inside the stream), the mirror
+// written by every lane (the pad takes the copies that are not slot 0's), the tests as scalar ands of two masks, the
+// second round behind a test of its own: 34 instructions where 107 stood, headline step 129.0 -> 125.9 ms
+// (profiles/dec_refill.md, with the two further stages that were built, measured and left out).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 *ring, gcu8 *words, u32 words_len,
                                                 gu8 *out, u32 out_sz, u32 x, bool active, u32 lane)
@@ -734,11 +740,29 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
         if (loadable) v = *(gcu32x4 *)(abase + 16ull * (c < lastc ? c : lastc));
         return v;
     };
-    // parks a quarter in the slot of stream quarter `qi`; the 8-byte wrap copy follows slot 0
+    // A refill's request: 16 bytes at byte offset min(o, 16 lastc) of the stream's chunks, o a multiple of 16.  No zero
+    // fill and no test of `loadable`: every lane that asks reads inside its own stream, which is why only lanes under
+    // `active` may ask.  Proof, by avail:
+    //   avail != 0: the address is abase + 16 c with c <= lastc = (avail - 1) >> 4, the very chunk load_chunk reads for
+    //     the same index.  It starts at or below words + words_len - 1, the stream's last byte, and at or above abase,
+    //     so it holds at least one byte of the stream and otherwise bytes of the same aligned 16 (the states in front
+    //     for c = 0, the allocation's own granule behind: that the aligned 16 bytes around a stream's last byte can be
+    //     read is what load_chunk has always relied on; it is inherited here, not newly proven).
+    //   avail == 0: words_len == 0 and off0 == 0, so abase == words is the END of the stream and must not be read.
+    //     The sixteen bytes in front of `words` are the stream's four states, which k_dec_front has read from the same
+    //     buffer before it set `words` (p + 16 <= end, then words = in + p): rbase = words - 16 with lastc == 0 reads
+    //     exactly those, aligned as words is.  What arrives is never used as a word: nwords == 0 keeps such a wave out
+    //     of the 16-step trips, and the slow trip takes a word only while cursor + pre < nwords.
+    gcu8 *rbase = avail ? abase : abase - 16;
+    const u32 lasto = 16u * lastc;
+    auto request = [&](u32 o) -> u32x4 { return *(gcu32x4 *)(rbase + (o < lasto ? o : lasto)); };
+    // parks a quarter in the slot of stream quarter `qi`; the 8-byte wrap copy follows slot 0, and every lane that does
+    // not own slot 0 writes its copy into the 8 pad bytes behind the mirror instead (RING_BYTES: nobody reads them), so
+    // the copy needs no lane mask of its own
     auto park = [&](u32 qi, u32x4 v) __attribute__((always_inline)) {
         const u32 slot = (qi & 3u) * 64u + 16u * k;
         *(u32x4 *)(ring + slot) = v;
-        if (slot == 0) *(u32x2 *)(ring + RB) = v.xy;
+        *(u32x2 *)(ring + (slot == 0 ? RB : RB + 8u)) = v.xy;
     };
     if (active) {
         park(0, load_chunk(k));
@@ -777,6 +801,10 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
             "v_subb_co_u32_e32 %[g], vcc, 3, %[g], vcc\n\t"
             "v_lshl_add_u32 %[ga], %[g], 4, %[row]"
             : [g] "=&v"(g), [ga] "=v"(ga) : [root] "v"(rootx), [m22] "v"(m22), [GM] "v"(GM), [row] "v"(row) : "vcc");
+        // (D4, the dword behind the group: only its top field is used, L[12 g + 12], which is field g of the root and 1023
+        //  for g = 3.  Made from the root in the group read's shadow - a multiply-add, a rotation, a select on the compare
+        //  above - instead of read, the step was 0.46 to 0.91 ms per benchmark step SLOWER in three pairs of three:
+        //  profiles/dec_refill.md, stage 2)
         const u32x4 Dq = *(LAS const volatile u32x4 *)(unsigned long)ga;
         D0 = Dq.x; D1 = Dq.y; D2 = Dq.z; D3 = Dq.w; D4 = *(LAS const volatile u32 *)(unsigned long)(ga + 16u);
         __builtin_amdgcn_sched_barrier(0);
@@ -866,8 +894,10 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
     // ---- 16-step trips -----------------------------------------------------------------------------
     {
         u32 b0 = 0, b1 = 0, b2 = 0;                        // with acc: the four dwords of a trip
-        if (wave_any(active)) {
-            while (!wave_any(active && (t + 16u > count || cursor + 64u > nwords))) {
+        // wave_any(active && p) of the loop test and of the refill test as a scalar and of two masks: its scc is the answer
+        const unsigned long long amask = __ballot(active);
+        if (amask != 0ull) {
+            while ((__ballot(t + 16u > count || cursor + 64u > nwords) & amask) == 0ull) {
 #pragma unroll
                 for (int u = 1; u <= 16; u++) {           // step t + u - 1, then the issue half and the bookkeeping of step t + u
                     const u32 wq = finish(std::true_type{}, true);
@@ -886,20 +916,31 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
                 t += 16u;
                 // ring refill: the cursor is at most two quarters on
                 const u32 nh = (off0 + 2 * cursor) >> 6;
-                if (wave_any(active && nh != half)) {
+                if ((__ballot(nh != half) & amask) != 0ull) {
                     // (both waiting quarters are waited for HERE, where they arrived long ago: a wait inside one of the
-                    //  branches below would also wait for the request that the branch before it has just made)
+                    //  sides below would also wait for the request that the side before it has just made)
                     asm volatile("" : : "v"(penda), "v"(pendb));
 #pragma unroll
-                    for (int r = 0; r < 2; r++)
-                        if (active && nh != half) {       // idle lanes hold garbage cursors: they must not write LDS
-                            // (a request lands in the registers of the quarter just parked, as in the 8-step loop: with
-                            //  "the younger takes the older one's registers, the request the younger one's" the compiler
-                            //  had it arrive in temporaries and waited for it AT ONCE to copy it)
-                            if (half & 1u) { park(half, pendb); pendb = load_chunk(4 * (half + 6) + k); }
-                            else { park(half, penda); penda = load_chunk(4 * (half + 6) + k); }
-                            half++;
-                        }
+                    for (int r = 0; r < 2; r++) {
+                        // the second round only where a lane is still behind (two quarters in one trip: rare)
+                        if (r == 1 && (__ballot(nh != half) & amask) == 0ull) break;
+                        // One path: the slot, the mirror's address and the request's address are made once for both
+                        // parities; a side is the two writes and the request, nothing else: three instructions under a
+                        // lane mask, where a select of the parked quarter would be four and still leave the two
+                        // requests masked.  (A request has to land in the registers of the quarter just parked: with
+                        // "the younger takes the older one's registers, the request the younger one's" it arrives in
+                        // temporaries and is waited for AT ONCE to copy it.)
+                        const bool need = active && nh != half;      // idle lanes hold garbage cursors: they must not write LDS
+                        const bool odd = (half & 1u) != 0;
+                        const u32 slot = (half & 3u) * 64u + 16u * k;
+                        u32x4 *const sp = (u32x4 *)(ring + slot);
+                        u32x2 *const mp = (u32x2 *)(ring + (slot == 0 ? RB : RB + 8u));
+                        const u32 o = half * 64u + (16u * k + 384u);
+                        gcu32x4 *const rp = (gcu32x4 *)(rbase + (o < lasto ? o : lasto));      // quarter half + 6: see `request`
+                        if (need && odd) { *sp = pendb; *mp = pendb.xy; pendb = *rp; }
+                        if (need && !odd) { *sp = penda; *mp = penda.xy; penda = *rp; }
+                        half += need ? 1u : 0u;
+                    }
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                 }
@@ -962,7 +1003,7 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
         if (wave_any(active && nh != half)) {
             if (active && nh != half) {                   // idle lanes hold garbage cursors: they must not write LDS
                 park(half, pend0);
-                pend0 = load_chunk(4 * (nh + 4) + k);
+                pend0 = request(64u * nh + (16u * k + 256u));      // quarter nh + 4
                 half = nh;
             }
             // (one wave per workgroup, LDS operations execute in issue order: see chain_decode_lds)

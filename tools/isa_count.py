@@ -64,14 +64,10 @@ def shadows(b, first, second=None):
     return out
 
 
-def trip_path(src, name, header, marker, steps):
-    """Instructions that a full trip issues from the loop header `header` (a block label) to the back edge: the body and
-    the blocks behind it (the store, the flags, the loop control), which the per-label block above does not hold, without
-    what the body's label holds but the trip does not run (the refill).  The function is cut into basic blocks at labels
-    and branches; the path is the shortest one from the header back to it that issues `marker` at least `steps` times
-    (leaving the loop and coming back in is shorter, but runs no step), taken with some lane live: s_cbranch_execz falls
-    through and s_cbranch_execnz is taken, so the code under a lane mask counts.  Returns the count and the labels met."""
-    import heapq
+def cfg_of(src, name):
+    """The function cut into basic blocks at labels and branches: the instructions, label -> index of its first
+    instruction, block start -> next block's start, and the successors of a block with some lane live
+    (s_cbranch_execz falls through and s_cbranch_execnz is taken, so the code under a lane mask counts)."""
     i = src.index(name + ':')
     ins, label_at = [], {}
     for l in src[i:src.index('.Lfunc_end', i)].split('\n'):
@@ -90,6 +86,18 @@ def trip_path(src, name, header, marker, steps):
         if op == 's_branch' or op == 's_cbranch_execnz': return [label_at[arg[0]]]
         if op.startswith('s_cbranch') and op != 's_cbranch_execz': return [label_at[arg[0]], nxt[s]]
         return [nxt[s]]
+    return ins, label_at, nxt, succ
+
+
+def trip_path(src, name, header, marker, steps, starts_too=False):
+    """Instructions that a full trip issues from the loop header `header` (a block label) to the back edge: the body and
+    the blocks behind it (the store, the flags, the loop control), which the per-label block above does not hold, without
+    what the body's label holds but the trip does not run (the refill).  The function is cut into basic blocks at labels
+    and branches; the path is the shortest one from the header back to it that issues `marker` at least `steps` times
+    (leaving the loop and coming back in is shorter, but runs no step), taken with some lane live: s_cbranch_execz falls
+    through and s_cbranch_execnz is taken, so the code under a lane mask counts.  Returns the count and the labels met."""
+    import heapq
+    ins, label_at, nxt, succ = cfg_of(src, name)
     size = lambda s: (nxt[s] or len(ins)) - s
     marks = lambda s: sum(1 for x in ins[s:s + size(s)] if x.split()[0] == marker)
     h = label_at[re.match(r'\.LBB\d+_\d+', header).group(0)]
@@ -103,10 +111,44 @@ def trip_path(src, name, header, marker, steps):
             if n == h:
                 if mk >= steps:
                     at = {v: k for k, v in label_at.items()}
-                    return cost, [at[p] for p in path if p in at]
+                    return (cost, [at[p] for p in path if p in at]) + ((path,) if starts_too else ())
                 continue
             heapq.heappush(heap, (cost + size(n), n, min(mk + marks(n), steps), path + (n,)))
-    return None, []
+    return (None, []) + (((),) if starts_too else ())
+
+
+def refill_path(src, name, header, marker, steps):
+    """Instructions that a 16-step trip issues on top of trip_path when it refills the ring: from behind the refill
+    test's branch to the join behind the wave barrier.  The test is the one block of trip_path's route with a second
+    way out that leaves the route and comes back to it further on; the figure is the shortest such detour, counted up to
+    the block where it is back on the route.  Some lane is live on it (s_cbranch_execz falls through: code under a lane
+    mask counts, which is the case of lanes of both parities crossing one quarter), and a scalar branch may take either
+    way, so a second round that is skipped by a scalar test does not count while one that is only masked does."""
+    import heapq
+    ins, label_at, nxt, succ = cfg_of(src, name)
+    n, _, route = trip_path(src, name, header, marker, steps, True)
+    if n is None:
+        return None
+    size = lambda s: (nxt[s] or len(ins)) - s
+    pos = {b: i for i, b in enumerate(route)}
+    best = None
+    for i, b in enumerate(route):
+        for e in succ(b):
+            if e is None or e in pos:
+                continue
+            heap, seen = [(0, e)], set()                 # (instructions issued before the block, the block)
+            while heap:
+                cost, s = heapq.heappop(heap)
+                if s in seen: continue
+                seen.add(s)
+                if s in pos:
+                    if pos[s] > i:                       # back on the route, further on: the join
+                        best = cost if best is None else min(best, cost)
+                        break
+                    continue
+                for m in succ(s):
+                    if m is not None: heapq.heappush(heap, (cost + size(s), m))
+    return best
 
 
 GROUP_READ = ("ds_read_b128", r"ds_read_b32 .*offset:16\b")      # lookup_step_pk's group: 16 bytes + the dword after them
@@ -148,7 +190,8 @@ def to_json(out_path):
                                             "head_shadow_per_step": shadows(b, *HEAD_READ)})
                             if least:                                    # the 16-step trip: header to back edge, no refill
                                 n, labs = trip_path(src, name, lab, marker, least[0])
-                                best[1].update({"trip_path_instructions": n, "trip_path_blocks": labs})
+                                best[1].update({"trip_path_instructions": n, "trip_path_blocks": labs,
+                                                "refill_path_instructions": refill_path(src, name, lab, marker, least[0])})
                 if best:
                     res["kernels"][label] = best[1]
     with open(out_path, 'w') as f:
@@ -179,6 +222,7 @@ def main():
                     steps = c["ds_read_b128"]
                     if steps >= 16:
                         print('   trip path, header to back edge without the refill', trip_path(src, name, lab, "v_lshrrev_b64", steps))
+                        print('   refill path, behind the test to the join', refill_path(src, name, lab, "v_lshrrev_b64", steps))
 
 if __name__ == '__main__':
     main()
