@@ -19,7 +19,7 @@ from .codec import (  # noqa: F401
     arith_compress, arith_compress_batch, arith_compress_bound, arith_compress_cap,
     fqz_scan, fqz_decompress, fqz_uncompress_batch,
     fqz_pick_parameters, fqz_compress, fqz_compress_batch, fqz_compress_best_batch, fqz_compress_cap, fqz_pick_cap,
-    compress_best_any_batch, uncompress_any_batch, CODEC_RANS4X16, CODEC_ARITH, CODEC_MASK,
+    compress_best_any_batch, uncompress_any_batch, compress_best_qual_batch, uncompress_qual_batch, CODEC_RANS4X16, CODEC_ARITH, CODEC_MASK, CODEC_FQZ,
 )
 
 __all__ = [
@@ -33,5 +33,6 @@ __all__ = [
     "arith_compress", "arith_compress_batch", "arith_compress_bound", "arith_compress_cap",
     "fqz_scan", "fqz_decompress", "fqz_uncompress_batch",
     "fqz_pick_parameters", "fqz_compress", "fqz_compress_batch", "fqz_compress_best_batch", "fqz_compress_cap", "fqz_pick_cap",
-    "compress_best_any_batch", "uncompress_any_batch", "CODEC_RANS4X16", "CODEC_ARITH", "CODEC_MASK",
+    "compress_best_any_batch", "uncompress_any_batch", "compress_best_qual_batch", "uncompress_qual_batch",
+    "CODEC_RANS4X16", "CODEC_ARITH", "CODEC_MASK", "CODEC_FQZ",
 ]

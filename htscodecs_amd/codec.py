@@ -146,7 +146,7 @@ class _Ctx:
 
     def route_read(self, which, reset=True):
         """rans4x16_hip_route_read: {kind name: count} of `which` ("encode", "decode", "expand", "launch",
-        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc", "fqz_pick", "fqz_best", "best_any") since the last reset; needs option route_count = 1 while the calls run."""
+        "result", "names", "arith", "arith_enc", "fqz", "encode_body", "fqz_enc", "fqz_pick", "fqz_best", "best_any", "best_qual") since the last reset; needs option route_count = 1 while the calls run."""
         w = ROUTE_WHICH[which]
         kinds = ROUTE_KINDS[which]
         arr = (C.c_long * len(kinds))()
@@ -158,7 +158,8 @@ class _Ctx:
 
 # include/rans4x16_hip.h: rans4x16_hip_route_read's lists and their kinds, in enum order
 ROUTE_WHICH = {"encode": 0, "decode": 1, "expand": 2, "launch": 3, "result": 4, "names": 5, "arith": 6,
-               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10, "fqz_pick": 11, "fqz_best": 12, "best_any": 13}
+               "arith_enc": 7, "fqz": 8, "encode_body": 9, "fqz_enc": 10, "fqz_pick": 11, "fqz_best": 12, "best_any": 13,
+               "best_qual": 14}
 ROUTE_KINDS = {
     "encode": ("u16", "packed", "records", "packed_freq"),
     "decode": ("l1", "l2", "l3", "l4", "l5", "direct", "mid", "short_ring"),
@@ -174,12 +175,15 @@ ROUTE_KINDS = {
     "fqz_pick": ("blocks", "sel", "split", "dedup", "undecided", "host"),
     "fqz_best": ("blocks", "candidates", "counted", "undecided", "refused"),
     "best_any": ("rans", "arith", "tie", "failed", "chunks"),
+    "best_qual": ("blocks", "chunks", "rans", "arith", "fqz", "tie", "failed", "undecided"),
 }
 
 # include/rans4x16_hip.h part 2m: a method of the cross-codec calls is a codec tag OR-ed with that codec's order word
 CODEC_RANS4X16 = 0
 CODEC_ARITH = 1 << 24
 CODEC_MASK = 0x0F000000
+# part 2n: a fqzcomp_qual strategy among the methods of the quality calls
+CODEC_FQZ = 3 << 24
 
 _tls = threading.local()
 
@@ -749,6 +753,71 @@ def uncompress_any_batch(blocks, methods, caps, ctx=None):
     return a.results()
 
 
+def compress_best_qual_batch(blocks, lens, flags, methods, vers=4, caps=None, ctx=None):
+    """rans4x16_hip_compress_best_qual_batch: quality blocks (bytes) with their record lengths and flags under a list of
+    tagged methods (a plain order word for rANS 4x16, CODEC_ARITH | order, CODEC_FQZ | strat), the smallest stream kept.
+    caps None: the library allocates exactly the result; else a capacity per block.  Returns (the streams, None for a block
+    that failed; the chosen methods; the statuses; lens and flags as the call leaves them - changed only where
+    fqzcomp_qual won)."""
+    ctx = ctx or _thread_ctx()
+    L = ctx.L
+    n = len(blocks)
+    meth = _methods(methods)
+    la = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in lens]
+    fa = [np.array([int(v) & 0xffffffff for v in x], dtype=np.uint32) for x in flags]
+    dummy = np.zeros(4, dtype=np.uint8)
+    ptr = lambda x: x.ctypes.data if len(x) else dummy.ctypes.data
+    len_p = (C.c_void_p * n)(*[ptr(x) for x in la])
+    fl_p = (C.c_void_p * n)(*[ptr(x) for x in fa])
+    nrec = (C.c_uint * n)(*[len(x) for x in la])
+    chosen = (C.c_int * n)(*([-1] * n))
+    back = lambda: ([x.tolist() for x in la], [x.tolist() for x in fa])
+    if caps is None:
+        srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+        in_p = (C.c_void_p * n)(*[ptr(s) for s in srcs])
+        in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
+        out_p = (C.c_void_p * n)()
+        out_sz = (C.c_uint * n)()
+        status = (C.c_int * n)()
+        rc = L.rans4x16_hip_compress_best_qual_batch(ctx.h, n, in_p, in_sz, nrec, len_p, fl_p, int(vers), out_p, out_sz, len(methods), meth,
+                                                     chosen, status)
+        outs = []
+        for i in range(n):
+            outs.append(C.string_at(out_p[i], out_sz[i]) if status[i] == 0 and out_p[i] else None)
+            if out_p[i]:
+                _free(out_p[i])
+        if rc < 0:
+            raise RuntimeError("compress_best_qual_batch: " + ctx.error())
+        return (outs, list(chosen), list(status)) + back()
+    a = _HostArrays(blocks, caps)
+    rc = L.rans4x16_hip_compress_best_qual_batch(ctx.h, n, a.in_p, a.in_sz, nrec, len_p, fl_p, int(vers), a.out_p, a.out_sz, len(methods), meth,
+                                                 chosen, a.status)
+    if rc < 0:
+        raise RuntimeError("compress_best_qual_batch: " + ctx.error())
+    outs, status = a.results()
+    return (outs, list(chosen), status) + back()
+
+
+def uncompress_qual_batch(blocks, methods, caps, nlengths=None, ctx=None):
+    """rans4x16_hip_uncompress_qual_batch: streams of the three codecs, methods[i] saying which (only its codec tag is looked
+    at; negative: a block that was never written), into buffers of caps[i] bytes.  nlengths: how many record lengths to take
+    per block (default: none).  Returns (the blocks, None where one failed; the statuses; the lengths - min(nlengths[i],
+    nrec[i]) entries for a CODEC_FQZ block; nrec, 0 for the other codecs' blocks)."""
+    ctx = ctx or _thread_ctx()
+    a = _HostArrays(blocks, caps)
+    n = a.n
+    nl = [0] * n if nlengths is None else [int(v) for v in nlengths]
+    lens = [np.full(max(v, 1), -1, dtype=np.int32) for v in nl]
+    len_p = (C.c_void_p * n)(*[x.ctypes.data for x in lens])
+    nl_a = (C.c_int * n)(*nl)
+    nrec = (C.c_uint * n)()
+    rc = ctx.L.rans4x16_hip_uncompress_qual_batch(ctx.h, n, a.in_p, a.in_sz, _methods(methods), a.out_p, a.out_sz, a.status, len_p, nl_a, nrec)
+    if rc < 0:
+        raise RuntimeError("uncompress_qual_batch: " + ctx.error())
+    res, status = a.results()
+    return res, status, [lens[i][:min(nl[i], nrec[i])].tolist() for i in range(n)], list(nrec)
+
+
 class DeviceCodec:
     """Device-resident batches on torch tensors (torch is used for device memory and streams
     only).  All tensors must live on the context's device."""
@@ -1146,6 +1215,66 @@ class DeviceCodec:
             d_out.data_ptr() if d_out is not None else None, cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(),
             nosz_size.data_ptr() if nosz_size is not None else None, int(max_in_size), int(max_out_size), self._stream())
         self._check(rc, "uncompress_any_packed_dev")
+
+    # ---- quality blocks: best across rANS 4x16, arith_dynamic and fqzcomp_qual (include/rans4x16_hip.h part 2n) ----------
+    def compress_best_qual_packed(self, d_in, in_off, in_size, d_len, d_flags, rec_off, nrec, d_out, out_off, out_size, status,
+                                  methods, max_in_size, max_records, vers=4, chosen=None, d_len_out=None, total_in_size=0,
+                                  out_capacity=None):
+        """rans4x16_hip_compress_best_qual_packed_dev: fqz_compress_best_packed's arguments under a list of tagged methods (a
+        plain order word for rANS 4x16, CODEC_ARITH | order, CODEC_FQZ | strat); chosen gets the winner's tagged word,
+        d_len_out the lengths of the blocks fqzcomp_qual won.  A list without a CODEC_FQZ entry takes None for the four
+        record tensors.  d_out None (with out_capacity 0 or None) is the sizing pass."""
+        t = self.torch
+        assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
+        assert in_off.dtype == t.int64 and in_size.dtype == t.int32
+        assert out_off.dtype == t.int64 and out_off.numel() == in_off.numel() + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert all(x is None or x.dtype == t.int32 for x in (d_len, d_flags, nrec, chosen, d_len_out))
+        assert rec_off is None or rec_off.dtype == t.int64
+        room = d_out.numel() if d_out is not None else 0
+        cap = room if out_capacity is None else int(out_capacity)
+        assert cap <= room
+        meth = _methods(methods)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        rc = self.L.rans4x16_hip_compress_best_qual_packed_dev(
+            self.ctx.h, in_off.numel(), d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(),
+            ptr(d_len), ptr(d_flags), ptr(rec_off), ptr(nrec), int(vers), len(methods), meth,
+            ptr(d_out), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), ptr(chosen), ptr(d_len_out),
+            int(max_in_size), int(max_records), int(total_in_size), self._stream())
+        self._check(rc, "compress_best_qual_packed_dev")
+
+    def best_qual_chunk_blocks(self, n, methods, max_in_size, max_records, total_in_size=0):
+        """rans4x16_hip_best_qual_chunk_blocks: the blocks per chunk compress_best_qual_packed plans for these arguments."""
+        meth = _methods(methods)
+        rc = self.L.rans4x16_hip_best_qual_chunk_blocks(self.ctx.h, int(n), len(methods), meth, int(max_in_size), int(max_records),
+                                                        int(total_in_size))
+        if rc < 0:
+            raise RuntimeError("best_qual_chunk_blocks: " + self.ctx.error())
+        return rc
+
+    def uncompress_qual_packed(self, d_in, in_off, in_size, method, d_out, out_off, out_size, status, max_in_size, max_out_size,
+                               nosz_size=None, out_capacity=None, d_len=None, len_off=None, len_cap=None, nrec=None):
+        """rans4x16_hip_uncompress_qual_packed_dev: uncompress_any_packed for an arena that mixes the three codecs, with
+        fqz_uncompress's four optional length arguments (written for the CODEC_FQZ blocks; nrec is 0 for the others)."""
+        t = self.torch
+        n = in_size.numel()
+        assert d_in.dtype == t.uint8 and (d_out is None or d_out.dtype == t.uint8)
+        assert in_off.dtype == t.int64 and in_off.numel() >= n and in_size.dtype == t.int32
+        assert method.dtype == t.int32 and method.numel() == n
+        assert out_off.dtype == t.int64 and out_off.numel() == n + 1
+        assert out_size.dtype == t.int32 and status.dtype == t.int32
+        assert nosz_size is None or (nosz_size.dtype == t.int32 and nosz_size.numel() == n)
+        assert d_len is None or (d_len.dtype == t.int32 and len_off.dtype == t.int64 and len_cap.dtype == t.int32)
+        assert nrec is None or nrec.dtype == t.int32
+        room = d_out.numel() if d_out is not None else 0
+        cap = room if out_capacity is None else int(out_capacity)
+        assert cap <= room
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        rc = self.L.rans4x16_hip_uncompress_qual_packed_dev(
+            self.ctx.h, n, d_in.data_ptr(), in_off.data_ptr(), in_size.data_ptr(), method.data_ptr(),
+            ptr(d_out), cap, out_off.data_ptr(), out_size.data_ptr(), status.data_ptr(), ptr(nosz_size),
+            ptr(d_len), ptr(len_off), ptr(len_cap), ptr(nrec), int(max_in_size), int(max_out_size), self._stream())
+        self._check(rc, "uncompress_qual_packed_dev")
 
     def set_tok3_arith(self, mode):
         """rans4x16_hip_set_tok3_arith: 0, TOK3_ARITH_DECODE (1), TOK3_ARITH_ENCODE (2) or both; returns the previous mode."""

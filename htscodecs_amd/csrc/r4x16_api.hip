@@ -313,8 +313,9 @@ static int route_fold(rans4x16_hip_ctx *c)
     for (auto &r : c->route_pending) {
         if (hipEventSynchronize(r.ev) != hipSuccess) rc = -1;
         else if (r.which == R4X16_ROUTE_ARITH || r.which == R4X16_ROUTE_ARITH_ENC || r.which == R4X16_ROUTE_FQZ || r.which == R4X16_ROUTE_FQZ_ENC ||
-                 r.which == R4X16_ROUTE_FQZ_PICK || r.which == R4X16_ROUTE_FQZ_BEST || r.which == R4X16_ROUTE_BEST_ANY)
-            for (int k = 0; k < R4X16_FQZ_KINDS; k++) c->route[r.which][k] += (long)r.cnt[k];   // counted per kind on the device (the words not copied are 0)
+                 r.which == R4X16_ROUTE_FQZ_PICK || r.which == R4X16_ROUTE_FQZ_BEST || r.which == R4X16_ROUTE_BEST_ANY ||
+                 r.which == R4X16_ROUTE_BEST_QUAL)
+            for (int k = 0; k < ROUTE_KINDS; k++) c->route[r.which][k] += (long)r.cnt[k];   // counted per kind on the device (the words not copied are 0)
         else
             for (u32 ci = 0; ci < CLS_MAX; ci++) {
                 int freq_table = 0;
@@ -344,11 +345,13 @@ int r4x16_route_snap(rans4x16_hip_ctx *c, int which, const u32 *d_cnt, u32 words
 }
 static const int ROUTE_NKINDS[ROUTE_WHICH] = {R4X16_ENC_KINDS, R4X16_DEC_KINDS, R4X16_EXPAND_KINDS, R4X16_LAUNCH_KINDS, R4X16_RESULT_KINDS,
                                                R4X16_NAMES_KINDS, R4X16_ARITH_KINDS, R4X16_ARITH_ENC_KINDS, R4X16_FQZ_KINDS, R4X16_ENC_BODY_KINDS,
-                                               R4X16_FQZ_ENC_KINDS, R4X16_FQZ_PICK_KINDS, R4X16_FQZ_BEST_KINDS, R4X16_BEST_ANY_KINDS};
+                                               R4X16_FQZ_ENC_KINDS, R4X16_FQZ_PICK_KINDS, R4X16_FQZ_BEST_KINDS, R4X16_BEST_ANY_KINDS,
+                                               R4X16_BEST_QUAL_KINDS};
 static_assert(R4X16_DEC_KINDS <= ROUTE_KINDS && R4X16_ENC_KINDS <= ROUTE_KINDS && R4X16_NAMES_KINDS <= ROUTE_KINDS &&
               R4X16_ARITH_KINDS <= ROUTE_KINDS && R4X16_ARITH_KINDS <= CLS_MAX &&
               R4X16_ARITH_KINDS <= R4X16_ARITH_ENC_KINDS && R4X16_ARITH_ENC_KINDS <= R4X16_FQZ_KINDS && R4X16_FQZ_KINDS <= ROUTE_KINDS && R4X16_FQZ_ENC_KINDS == R4X16_FQZ_KINDS &&
-              R4X16_FQZ_PICK_KINDS == R4X16_FQZ_KINDS && R4X16_FQZ_BEST_KINDS <= R4X16_FQZ_KINDS && R4X16_BEST_ANY_KINDS <= R4X16_FQZ_KINDS, "route kinds");
+              R4X16_FQZ_PICK_KINDS == R4X16_FQZ_KINDS && R4X16_FQZ_BEST_KINDS <= R4X16_FQZ_KINDS && R4X16_BEST_ANY_KINDS <= R4X16_FQZ_KINDS &&
+              R4X16_BEST_QUAL_KINDS <= ROUTE_KINDS && ROUTE_KINDS <= CLS_MAX, "route kinds");
 extern "C" int rans4x16_hip_route_read(rans4x16_hip_ctx *c, int which, long *counts, int n, int reset)
 {
     if (!c || which < 0 || which >= ROUTE_WHICH || n < 0 || (n && !counts)) return -1;

@@ -1,7 +1,8 @@
 // r4x16_fqz_best.h - what the three fqzcomp_qual encode units share on the device side: the pick's and the encoder's
 // per-chunk work areas (r4x16_fqz_pick.hip, r4x16_fqz_enc.hip) and the stages of either that the best-of-several call
 // (r4x16_fqz_best.hip, include/rans4x16_hip.h part 2l) runs on its own: the pick's statistics once per slice, the
-// encoder's front and encode kernels over the candidates without its back end.
+// encoder's front and encode kernels over the candidates without its back end.  The best-of-several call's own chunk, in
+// two halves, is declared at the end: the call that picks across codecs (r4x16_best_qual.hip, part 2n) runs them too.
 #pragma once
 #include "r4x16_host.h"
 #include "r4x16_fqz_pick_dec.h"
@@ -97,3 +98,38 @@ __host__ __device__ static inline u32 fqe_var_len(u32 v)
 // owes once its own back end is enqueued.
 int r4x16_fqe_stages(rans4x16_hip_ctx *c, const BatchArgs &a, const FqeIn &in, u8 *at, int base, int nb, u32 max_in_size, u32 max_params_size,
                      u32 max_records, hipStream_t s, FqeWs *w, u32 **d_route);
+
+// ---- best of several strategies (r4x16_fqz_best.hip) ------------------------------------------------------------------
+// The call in two halves, for the call that picks across codecs (r4x16_best_qual.hip, part 2n) as r4x16_ab_candidates is
+// for arith: the candidates stage - statistics, store, front, encode, k_fqb_win - leaves every block's winner known by its
+// size, and the back pass assembles the winners that are wanted at their final place.
+#define FQB_MAX_K 16
+struct FqbStrats { int k; int s[FQB_MAX_K]; };
+// a chunk's hand-over between the stages, every array indexed by item but win ([nb])
+struct FqbHand {
+    u8 *par; u32 *flags;
+    u64 *par_off, *rec_off, *len_off, *in_off;
+    u32 *par_size, *nrec, *in_size, *out_cap, *out_size;
+    i32 *pick_status, *status, *win;
+    u32 *route;                             // [R4X16_FQZ_BEST_KINDS]; nullptr in the kernels' copy: option route_count is off
+};
+// candidate sets picked elsewhere (the host): what k_fqb_store would have left, entry g * k + j of every array for
+// candidate j of block g of the whole call
+struct FqbSets {
+    const u8 *par; const u64 *par_off; const u32 *par_size;        // par_size FQB_NO_PARAMS: the pick refused the candidate
+    const u32 *len, *flags; const u64 *rec_off, *len_off; const u32 *nrec;
+    u32 max_par;
+};
+// a chunk's work area between r4x16_fqb_candidates and r4x16_fqb_back: the layouts in the arena, the encoder's inputs,
+// the route counters the back pass reads out
+struct FqbWork { FqpWs pw; FqbHand h; FqeWs fw; FqeIn ein; u32 *d_best, *d_enc; };
+// the strategies alone: what a call refuses before it asks for the device (`who` names the call in err)
+int r4x16_fqb_strats(rans4x16_hip_ctx *c, const char *who, int k, const int *strats, FqbStrats *ks);
+// the bytes a chunk of nb blocks under k strategies takes at `at`, and the blocks a chunk holds at most
+size_t r4x16_fqb_chunk_bytes(rans4x16_hip_ctx *c, size_t nb, size_t k, u32 max_in, u32 max_rec, bool sets);
+size_t r4x16_fqb_chunk_limit(int k, u32 max_rec);
+int r4x16_fqb_candidates(rans4x16_hip_ctx *c, const BatchArgs &a, const u32 *d_len, const u32 *d_flags, const u64 *d_rec_off, const u32 *d_nrec,
+                         int vers, const FqbStrats &ks, const FqbSets *sets, u8 *at, int base, int nb, u32 *out_size, i32 *status, i32 *chosen,
+                         int obase, u32 max_in, u32 max_rec, hipStream_t s, FqbWork *w);
+int r4x16_fqb_back(rans4x16_hip_ctx *c, const BatchArgs &a, const PackedOut *pk, const FqbWork &w, u32 *d_len_out, const u64 *d_rec_off,
+                   const u32 *d_nrec, int base, int nb, const i32 *take, hipStream_t s);

@@ -16,6 +16,10 @@
 //   k_fqb_back    a workgroup per block: the winner alone - varint, parameter bytes, body - at its final place, the
 //                 caller's slot or the packed offset (k_pk_scan over the winners' sizes in between)
 // The host-buffer batch enters behind the first two stages with candidate sets it picked on the host (FqbSets).
+// The chunk is offered in two halves (r4x16_fqz_best.h): r4x16_fqb_candidates, everything up to and including k_fqb_win,
+// and r4x16_fqb_back.  This unit's calls run one behind the other; the call that picks across codecs
+// (r4x16_best_qual.hip, part 2n) puts its own pick, scan and gather between them and hands the back pass the blocks
+// fqzcomp won overall.
 //
 // Loops: over k <= 16 candidates, the records of a block (nrec <= max_records, tested by k_fqp_lens before a record is
 // read), tables of fixed size.  Stores: the hand-over is sized by the chunk's items, max_records + 1 and FQP_STAGE; only
@@ -25,25 +29,8 @@
 #include "r4x16_fqz_best.h"
 #include "r4x16_fqz_pick.h"
 
-#define FQB_MAX_K 16
+// (FQB_MAX_K, FqbStrats, FqbHand, FqbSets, FqbWork: r4x16_fqz_best.h - the call that picks across codecs runs these stages too)
 #define FQB_NO_PARAMS 0xffffffffu           // a parameter size no call admits: the front end reads nothing of the item
-struct FqbStrats { int k; int s[FQB_MAX_K]; };
-// a chunk's hand-over between the stages, every array indexed by item but win ([nb])
-struct FqbHand {
-    u8 *par; u32 *flags;
-    u64 *par_off, *rec_off, *len_off, *in_off;
-    u32 *par_size, *nrec, *in_size, *out_cap, *out_size;
-    i32 *pick_status, *status, *win;
-    u32 *route;                             // [R4X16_FQZ_BEST_KINDS]; nullptr in the kernels' copy: option route_count is off
-};
-// candidate sets picked elsewhere (the host): what k_fqb_store would have left, entry g * k + j of every array for
-// candidate j of block g of the whole call
-struct FqbSets {
-    const u8 *par; const u64 *par_off; const u32 *par_size;        // par_size FQB_NO_PARAMS: the pick refused the candidate
-    const u32 *len, *flags; const u64 *rec_off, *len_off; const u32 *nrec;
-    u32 max_par;
-};
-
 static size_t fqb_hand_layout(u8 *base, size_t at, size_t nb, size_t k, u32 max_rec, bool sets, FqbHand *h)
 {
     const size_t items = nb * k;
@@ -138,11 +125,12 @@ __global__ __launch_bounds__(256) void k_fqb_items(BatchArgs a, FqbSets sets, Fq
 // limits, which refuses every candidate alike - fails the block as a whole (UNSUPPORTED): the smallest of the rest would
 // not be the smallest of the list.  A candidate refused otherwise (its parameter bytes, the slice's records) is out of the
 // running; with none left the block has the status of the first.
-__global__ __launch_bounds__(256) void k_fqb_win(BatchArgs a, FqeIn ein, FqbHand h, FqeWs fw, int k, i32 *chosen, int base, int nb)
+// out_size / status / chosen: entry obase + lb is block lb's (the call's own arrays from the chunk's base, or a chunk's from 0).
+__global__ __launch_bounds__(256) void k_fqb_win(FqeIn ein, FqbHand h, FqeWs fw, int k, u32 *out_size, i32 *status, i32 *chosen, int obase, int nb)
 {
     const int lb = (int)(blockIdx.x * 256u + threadIdx.x);
     if (lb >= nb) return;
-    const int g = base + lb;
+    const int g = obase + lb;
     int win = -1;
     i32 first = 0;
     u64 best = 0;
@@ -167,8 +155,8 @@ __global__ __launch_bounds__(256) void k_fqb_win(BatchArgs a, FqeIn ein, FqbHand
     else if (win < 0) st = first;
     else if (best > 0xffffffffull) { win = -1; st = R4X16_E_CAPACITY; }          // no 32-bit size holds it, and no slot
     h.win[lb] = win;
-    a.status[g] = st;
-    a.out_size[g] = win >= 0 ? (u32)best : 0u;
+    status[g] = st;
+    out_size[g] = win >= 0 ? (u32)best : 0u;
     if (chosen) chosen[g] = win;
     if (h.route) {
         if (undecided) atomicAdd(&h.route[R4X16_FQZ_BEST_UNDECIDED], 1u);
@@ -179,14 +167,16 @@ __global__ __launch_bounds__(256) void k_fqb_win(BatchArgs a, FqeIn ein, FqbHand
     }
 }
 
-// pk.off == nullptr: the slot form.  The capacity is tested here, on the winner alone.
+// pk.off == nullptr: the slot form.  The capacity is tested here, on the winner alone.  take (may be null): [nb], 0 for a
+// block whose winner is not wanted - another codec's stream is smaller (r4x16_best_qual.hip); a.out_size[g] is the size of
+// the stream that is.
 __global__ __launch_bounds__(256) void k_fqb_back(BatchArgs a, PackedOut pk, FqeIn ein, FqbHand h, FqeWs fw, const u32 *wlen, u64 wlen_stride,
-                                                  u32 *len_out, const u64 *rec_off, const u32 *nrec, int base, int nb)
+                                                  u32 *len_out, const u64 *rec_off, const u32 *nrec, const i32 *take, int base, int nb)
 {
     const int lb = (int)blockIdx.x, g = base + lb;
     const u32 t = threadIdx.x;
     const int win = h.win[lb];
-    if (win < 0) return;
+    if (win < 0 || (take && take[lb] == 0)) return;
     if (len_out)
         for (u32 r = t; r < nrec[g]; r += 256u) len_out[rec_off[g] + r] = wlen[(u64)lb * wlen_stride + r];
     const size_t q = (size_t)win * nb + lb;
@@ -208,7 +198,7 @@ __global__ __launch_bounds__(256) void k_fqb_back(BatchArgs a, PackedOut pk, Fqe
 }
 
 // ---- the call ---------------------------------------------------------------------------------------------------------
-static int fqb_strats(rans4x16_hip_ctx *c, const char *who, int k, const int *strats, FqbStrats *ks)
+int r4x16_fqb_strats(rans4x16_hip_ctx *c, const char *who, int k, const int *strats, FqbStrats *ks)
 {
     bool ok = k >= 1 && k <= FQB_MAX_K && strats;
     for (int j = 0; ok && j < k; j++) ok = strats[j] >= 0;
@@ -221,17 +211,78 @@ static int fqb_strats(rans4x16_hip_ctx *c, const char *who, int k, const int *st
 
 // what a chunk of nb blocks takes in the adaptive coders' arena: the pick's layout, the hand-over, the encoder's layout
 // for nb * k items
-static size_t fqb_bytes(rans4x16_hip_ctx *c, size_t nb, size_t k, u32 max_in, u32 max_rec, bool sets)
+size_t r4x16_fqb_chunk_bytes(rans4x16_hip_ctx *c, size_t nb, size_t k, u32 max_in, u32 max_rec, bool sets)
 {
     FqpWs w;
     FqbHand h;
     const size_t pick = fqb_hand_layout(nullptr, sets ? 0 : r4x16_fqp_layout(nullptr, nb, max_rec, &w), nb, k, max_rec, sets, &h);
     return pick + r4x16_fqe_chunk_bytes(c, nb * k, max_in, max_rec);
 }
+size_t r4x16_fqb_chunk_limit(int k, u32 max_rec)
+{
+    return std::max<size_t>(1, std::min<size_t>(r4x16_fqp_chunk_limit(max_rec), (size_t)INT_MAX) / (size_t)k);
+}
 static size_t fqb_fit(rans4x16_hip_ctx *c, int n, int k, u32 max_in, u32 max_rec, bool sets)
 {
-    const size_t limit = std::max<size_t>(1, std::min<size_t>(r4x16_fqp_chunk_limit(max_rec), (size_t)INT_MAX) / (size_t)k);
-    return r4x16_fit_chunk((size_t)n, limit, r4x16_room(c, A_BIT(A_AR)), [&](size_t nb) { return fqb_bytes(c, nb, (size_t)k, max_in, max_rec, sets); });
+    return r4x16_fit_chunk((size_t)n, r4x16_fqb_chunk_limit(k, max_rec), r4x16_room(c, A_BIT(A_AR)),
+                           [&](size_t nb) { return r4x16_fqb_chunk_bytes(c, nb, (size_t)k, max_in, max_rec, sets); });
+}
+
+// One chunk up to and including k_fqb_win, laid out at `at`: block lb's winner - size, status, index into the strategies -
+// in out_size / status / chosen (may be null) at entry obase + lb, and *w for r4x16_fqb_back, which the caller owes: it
+// reads out the encoder's and this unit's route counters.  sets == nullptr: both stages.  Enqueues only; 0 or -1.
+int r4x16_fqb_candidates(rans4x16_hip_ctx *c, const BatchArgs &a, const u32 *d_len, const u32 *d_flags, const u64 *d_rec_off, const u32 *d_nrec,
+                         int vers, const FqbStrats &ks, const FqbSets *sets, u8 *at, int base, int nb, u32 *out_size, i32 *status, i32 *chosen,
+                         int obase, u32 max_in, u32 max_rec, hipStream_t s, FqbWork *w)
+{
+    const int k = ks.k, items = nb * k;
+    *w = FqbWork{};
+    FqpWs &pw = w->pw;
+    FqbHand &h = w->h;
+    const size_t pick = fqb_hand_layout(at, sets ? 0 : r4x16_fqp_layout(at, (size_t)nb, max_rec, &pw), (size_t)nb, (size_t)k, max_rec,
+                                        sets != nullptr, &h);
+    w->d_best = h.route;
+    if (r4x16_route_begin(c, &h.route, R4X16_FQZ_BEST_KINDS, s) != 0) return -1;
+    FqeIn &ein = w->ein;
+    u32 max_par = FQP_STAGE;
+    if (sets) {
+        hipLaunchKernelGGL(k_fqb_items, dim3((items + 255) / 256), dim3(256), 0, s, a, *sets, h, k, base, nb);
+        ein = FqeIn{sets->par, h.par_off, h.par_size, sets->len, sets->flags, h.rec_off, h.nrec, h.len_off};
+        max_par = sets->max_par;
+    } else {
+        int any_qa = 0, any_r2 = 0;
+        for (int j = 0; j < k; j++) {
+            FqdParam pm;
+            fqd_strat(ks.s[j], &pm);
+            any_qa |= pm.do_qa != 0; any_r2 |= pm.do_r2 != 0;
+        }
+        u32 *const d_pick = pw.route;
+        if (r4x16_route_begin(c, &pw.route, R4X16_FQZ_PICK_KINDS, s) != 0) return -1;
+        const FqpIn in{d_len, d_flags, d_rec_off, d_nrec, nullptr, vers, ks.s[0], c->fqz_guard_bits, nullptr, nullptr, nullptr, any_qa, any_r2};
+        if (r4x16_fqp_stats(c, a, in, pw, base, nb, max_in, max_rec, s) != 0) return -1;
+        hipLaunchKernelGGL(k_fqb_store, dim3((items + 3) / 4), dim3(256), 0, s, a, in, pw, h, ks, base, nb);
+        if (r4x16_route_end(c, R4X16_ROUTE_FQZ_PICK, d_pick, R4X16_FQZ_PICK_KINDS, s) != 0) return -1;
+        ein = FqeIn{h.par, h.par_off, h.par_size, pw.wlen, h.flags, h.rec_off, h.nrec, h.len_off};
+    }
+    BatchArgs ea = a;                                                // the encoder's arrays: the chunk's items, from 0
+    ea.in_off = h.in_off; ea.in_size = h.in_size; ea.out = nullptr; ea.out_off = nullptr; ea.out_cap = h.out_cap; ea.out_size = h.out_size;
+    ea.status = h.status;
+    if (r4x16_fqe_stages(c, ea, ein, at + pick, 0, items, max_in, max_par, max_rec, s, &w->fw, &w->d_enc) != 0) return -1;
+    hipLaunchKernelGGL(k_fqb_win, dim3((nb + 255) / 256), dim3(256), 0, s, ein, h, w->fw, k, out_size, status, chosen, obase, nb);
+    return 0;
+}
+
+// The back pass over the chunk: the winners of the blocks with take[lb] != 0 (take == nullptr: every winner) assembled
+// at a.out + a.out_off[g] or, pk given, at pk->out + pk->off[g], where a.out_size[g] is the size of the stream that goes
+// there; d_len_out (may be null) for the same blocks.
+int r4x16_fqb_back(rans4x16_hip_ctx *c, const BatchArgs &a, const PackedOut *pk, const FqbWork &w, u32 *d_len_out, const u64 *d_rec_off,
+                   const u32 *d_nrec, int base, int nb, const i32 *take, hipStream_t s)
+{
+    const PackedOut pko = pk ? *pk : PackedOut{nullptr, nullptr, 0};
+    hipLaunchKernelGGL(k_fqb_back, dim3(nb), dim3(256), 0, s, a, pko, w.ein, w.h, w.fw, (const u32 *)w.pw.wlen, w.pw.rec_stride, d_len_out,
+                       d_rec_off, d_nrec, take, base, nb);
+    if (r4x16_route_end(c, R4X16_ROUTE_FQZ_ENC, w.d_enc, R4X16_FQZ_ENC_KINDS, s) != 0) return -1;
+    return r4x16_route_end(c, R4X16_ROUTE_FQZ_BEST, w.d_best, R4X16_FQZ_BEST_KINDS, s);
 }
 
 // `a`: the call's arrays (the packed form: out, out_off, out_cap null and *pk given).  sets == nullptr: both stages.
@@ -240,51 +291,15 @@ static int fqb_run(rans4x16_hip_ctx *c, int n, const BatchArgs &a, const PackedO
                    hipStream_t s)
 {
     const int k = ks.k;
-    int any_qa = 0, any_r2 = 0;
-    for (int j = 0; j < k; j++) {
-        FqdParam pm;
-        fqd_strat(ks.s[j], &pm);
-        any_qa |= pm.do_qa != 0; any_r2 |= pm.do_r2 != 0;
-    }
-    const PackedOut pko = pk ? *pk : PackedOut{nullptr, nullptr, 0};
     const size_t chunk = fqb_fit(c, n, k, max_in, max_rec, sets != nullptr);
-    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_AR, fqb_bytes(c, nb, (size_t)k, max_in, max_rec, sets != nullptr), false); };
+    auto grab = [&](size_t nb) { return r4x16_ensure(c, A_AR, r4x16_fqb_chunk_bytes(c, nb, (size_t)k, max_in, max_rec, sets != nullptr), false); };
     return r4x16_chunk_walk(c, n, chunk, s, grab, [&](size_t base, int nb) {
-        u8 *const at = c->at(A_AR);
-        const int items = nb * k;
-        FqpWs pw = {};
-        FqbHand h;
-        const size_t pick = fqb_hand_layout(at, sets ? 0 : r4x16_fqp_layout(at, (size_t)nb, max_rec, &pw), (size_t)nb, (size_t)k, max_rec,
-                                            sets != nullptr, &h);
-        u32 *const d_best = h.route;
-        if (r4x16_route_begin(c, &h.route, R4X16_FQZ_BEST_KINDS, s) != 0) return -1;
-        FqeIn ein;
-        u32 max_par = FQP_STAGE;
-        if (sets) {
-            hipLaunchKernelGGL(k_fqb_items, dim3((items + 255) / 256), dim3(256), 0, s, a, *sets, h, k, (int)base, nb);
-            ein = FqeIn{sets->par, h.par_off, h.par_size, sets->len, sets->flags, h.rec_off, h.nrec, h.len_off};
-            max_par = sets->max_par;
-        } else {
-            u32 *const d_pick = pw.route;
-            if (r4x16_route_begin(c, &pw.route, R4X16_FQZ_PICK_KINDS, s) != 0) return -1;
-            const FqpIn in{d_len, d_flags, d_rec_off, d_nrec, nullptr, vers, ks.s[0], c->fqz_guard_bits, nullptr, nullptr, nullptr, any_qa, any_r2};
-            if (r4x16_fqp_stats(c, a, in, pw, (int)base, nb, max_in, max_rec, s) != 0) return -1;
-            hipLaunchKernelGGL(k_fqb_store, dim3((items + 3) / 4), dim3(256), 0, s, a, in, pw, h, ks, (int)base, nb);
-            if (r4x16_route_end(c, R4X16_ROUTE_FQZ_PICK, d_pick, R4X16_FQZ_PICK_KINDS, s) != 0) return -1;
-            ein = FqeIn{h.par, h.par_off, h.par_size, pw.wlen, h.flags, h.rec_off, h.nrec, h.len_off};
-        }
-        BatchArgs ea = a;                                            // the encoder's arrays: the chunk's items, from 0
-        ea.in_off = h.in_off; ea.in_size = h.in_size; ea.out = nullptr; ea.out_off = nullptr; ea.out_cap = h.out_cap; ea.out_size = h.out_size;
-        ea.status = h.status;
-        FqeWs fw;
-        u32 *d_enc;
-        if (r4x16_fqe_stages(c, ea, ein, at + pick, 0, items, max_in, max_par, max_rec, s, &fw, &d_enc) != 0) return -1;
-        hipLaunchKernelGGL(k_fqb_win, dim3((nb + 255) / 256), dim3(256), 0, s, a, ein, h, fw, k, d_chosen, (int)base, nb);
-        if (pk) r4x16_launch_packed_scan(a.out_size, pko.off, (int)base, nb, s);
-        hipLaunchKernelGGL(k_fqb_back, dim3(nb), dim3(256), 0, s, a, pko, ein, h, fw, (const u32 *)pw.wlen, pw.rec_stride, sets ? nullptr : d_len_out,
-                           d_rec_off, d_nrec, (int)base, nb);
-        if (r4x16_route_end(c, R4X16_ROUTE_FQZ_ENC, d_enc, R4X16_FQZ_ENC_KINDS, s) != 0) return -1;
-        return r4x16_route_end(c, R4X16_ROUTE_FQZ_BEST, d_best, R4X16_FQZ_BEST_KINDS, s);
+        FqbWork w;
+        if (r4x16_fqb_candidates(c, a, d_len, d_flags, d_rec_off, d_nrec, vers, ks, sets, c->at(A_AR), (int)base, nb, a.out_size, a.status, d_chosen,
+                                 (int)base, max_in, max_rec, s, &w) != 0)
+            return -1;
+        if (pk) r4x16_launch_packed_scan(a.out_size, pk->off, (int)base, nb, s);
+        return r4x16_fqb_back(c, a, pk, w, sets ? nullptr : d_len_out, d_rec_off, d_nrec, (int)base, nb, nullptr, s);
     });
 }
 
@@ -314,7 +329,7 @@ extern "C" int rans4x16_hip_fqz_compress_best_dev(rans4x16_hip_ctx *c, int n,
     FqbStrats ks;
     const int go = r4x16_dev_call_args(c, "fqz_compress_best_dev: bad arguments", fqb_records_ok(n, d_len, d_flags, d_rec_off, d_nrec, max_records), &a,
                                        n, d_in, d_in_off, d_in_size, d_out, d_out_off, d_out_cap, d_out_size, d_status, 0, nullptr,
-                                       [&] { return fqb_strats(c, "fqz_compress_best_dev", k, strats, &ks); });
+                                       [&] { return r4x16_fqb_strats(c, "fqz_compress_best_dev", k, strats, &ks); });
     if (go <= 0) return go;
     return fqb_run(c, n, a, nullptr, d_len, d_flags, d_rec_off, d_nrec, vers, ks, d_chosen, d_len_out, max_in_size, max_records, nullptr,
                    (hipStream_t)stream);
@@ -334,7 +349,7 @@ extern "C" int rans4x16_hip_fqz_compress_best_packed_dev(rans4x16_hip_ctx *c, in
     FqbStrats ks;
     const int go = r4x16_packed_call_args(c, "fqz_compress_best_packed_dev: bad arguments", fqb_records_ok(n, d_len, d_flags, d_rec_off, d_nrec, max_records),
                                           &a, &pk, n, d_in, d_in_off, d_in_size, d_out, out_capacity, d_out_off, d_out_size, d_status, 0, nullptr, s,
-                                          [&] { return fqb_strats(c, "fqz_compress_best_packed_dev", k, strats, &ks); });
+                                          [&] { return r4x16_fqb_strats(c, "fqz_compress_best_packed_dev", k, strats, &ks); });
     if (go <= 0) return go;
     return fqb_run(c, n, a, &pk, d_len, d_flags, d_rec_off, d_nrec, vers, ks, d_chosen, d_len_out, max_in_size, max_records, nullptr, s);
 }
@@ -464,7 +479,7 @@ extern "C" int rans4x16_hip_fqz_compress_best_batch(rans4x16_hip_ctx *c, int n,
         c->err = "fqz_compress_best_batch: bad arguments";
         return -1;
     }
-    if (fqb_strats(c, "fqz_compress_best_batch", k, strats, &ks) != 0) return -1;
+    if (r4x16_fqb_strats(c, "fqz_compress_best_batch", k, strats, &ks) != 0) return -1;
     if (n == 0) return 0;
     std::vector<int> todo, host;
     std::vector<u32> cap(out_size, out_size + n);

@@ -68,7 +68,7 @@ u32  r4x8_compress_bound(u32 size);
 struct TimedLaunch { hipEvent_t a, b; };
 // route read-out (option route_count): a copy of one chain launch's per-class stream counts, on its way to pinned memory
 struct RouteSnap { int which; u32 *cnt; hipEvent_t ev; };
-#define ROUTE_WHICH 14
+#define ROUTE_WHICH 15
 // R4X16_ROUTE_ENCODE_BODY rides on the encode chain's copy: the word of the per-class counts that k_enc_chain's affine
 // waves count their streams in (no launch has that many classes; r4x16_enc_chain.hip)
 #define ENC_ROUTE_AFF_WORD (CLS_MAX - 1u)

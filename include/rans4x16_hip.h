@@ -1126,6 +1126,94 @@ int rans4x16_hip_uncompress_any_batch(rans4x16_hip_ctx *ctx, int n,
                                       const unsigned char *const *in, const unsigned int *in_size, const int *method,
                                       unsigned char *const *out, unsigned int *out_size, int *status);
 
+/* ---- 2n. quality blocks: best of several methods across rANS 4x16, arith_dynamic and fqzcomp_qual -------------------
+ * For a slice's quality series a CRAM 3.1 writer at `small` / `archive` tries rANS 4x16 order words, arith_dynamic order
+ * words AND the fqzcomp_qual strategies, keeps the smallest stream and records the codec.  These calls are that loop for
+ * slices in device memory, and the reader's one decode call for the arena it leaves.  Part 2m's calls keep their contract:
+ * they still refuse the tag below.
+ *
+ * A method is a tagged int as in part 2m, with one tag more: R4X16_CODEC_FQZ | strat is a fqzcomp_qual strategy under part
+ * 2l's rule for strat (>= 0; 4 and above the all-zero row).  `methods` is a HOST array of 1..32 words, at most 16 of them
+ * with the FQZ tag.  Any other tag, a bit in 16..23 or above the tag, or a sub-list its own call refuses outright (more
+ * than 255 stripe planes) makes a call return -1 before it touches the device.
+ *
+ * rans4x16_hip_compress_best_qual_packed_dev takes the arguments of rans4x16_hip_fqz_compress_best_packed_dev with
+ * `k, methods` in place of `k, strats`, and total_in_size as in part 2m.  The list is split into its three sub-lists, each
+ * in list order; for each, block i has exactly what that codec's own best-packed call gives under it
+ * (rans4x16_hip_compress_best_packed_dev, rans4x16_hip_arith_compress_best_packed_dev,
+ * rans4x16_hip_fqz_compress_best_packed_dev: their skips, limits and statuses).  Of the sub-lists whose result is status 0
+ * the block gets the smaller stream, on equal sizes the one whose winning method stands EARLIER in `methods`; the bytes are
+ * that codec's stream, unchanged.  A list of one codec gives byte for byte what that codec's call gives; a list without an
+ * FQZ entry gives what part 2m's call gives and does not look at the record arrays (they may be NULL).
+ *   R4X16_E_UNDECIDED   the fqzcomp sub-list cannot decide the block (part 2l): the whole block is undecided - size 0,
+ *                       d_chosen -1, nothing written; the smallest of the others need not be the smallest of the list
+ *   any other failure of the fqzcomp sub-list (the records' R4X16_E_SIZE / R4X16_E_CONTEXT, R4X16_E_UNSUPPORTED,
+ *   R4X16_E_TABLE) takes only that codec out of the running, as a writer goes on when fqz_compress returns NULL.  With no
+ *   sub-list left the block has size 0, d_chosen -1 and the status of the sub-list whose first method stands first.
+ *   d_chosen[i] (may be NULL)  the winning methods[j] as given, tag included
+ *   d_len_out (may be NULL)    written only for the blocks the fqzcomp sub-list won: the lengths as its fix-ups leave them
+ *   output                     one dense arena with the rules of part 2a (sums before the capacity rule, R4X16_E_CAPACITY
+ *                              with size 0 beyond out_capacity, d_out == NULL: a sizing pass)
+ * The caller's input, lengths and flags are never written.  The call only enqueues on `stream`, reads nothing back and
+ * writes nothing outside the winners' ranges.  Per chunk the rANS and arith candidates are encoded and reduced as in part
+ * 2m; the fqzcomp candidates run part 2l's stages until the winner's size is known; one pick kernel compares up to three
+ * winners (size, list position, status); after the scan one gather copies the rANS and arith winners, and part 2l's back
+ * pass assembles, from the encoder's stage, the streams of the blocks fqzcomp won overall: a result byte moves once, a
+ * loser never leaves its slot, and a fqzcomp stream that lost is never assembled.  DESIGN.md 4.10.
+ *
+ * rans4x16_hip_best_qual_chunk_blocks: the blocks per chunk the call plans - the largest for which the rANS slots and
+ * workspace, the arith slots and inner arena and the fqzcomp pick layout, hand-over and encoder layout (model slots:
+ * rans4x16_hip_set_fqz_limits) stay under max_workspace_mb and three quarters of the free memory.  Host arithmetic; -1 on
+ * bad arguments.
+ *
+ * rans4x16_hip_uncompress_qual_packed_dev takes the arguments of rans4x16_hip_uncompress_any_packed_dev and the four
+ * length arguments of rans4x16_hip_fqz_uncompress_dev (all may be NULL).  d_method[i] & R4X16_CODEC_MASK selects the
+ * decoder; a negative entry is R4X16_E_EMPTY with 0 bytes, an unknown tag R4X16_E_UNSUPPORTED.  An FQZ block claims the
+ * varint at byte 0 (rans4x16_hip_fqz_peek_dev), the others claim as in part 2m; scan, capacity rule and confinement are
+ * part 2m's.  The three slot decoders run over the same entries, each seeing length 0 for the other codecs' blocks.
+ * d_nrec[i] and the lengths are written for FQZ blocks; d_nrec[i] is 0 for every other.
+ *
+ * rans4x16_hip_compress_best_qual_batch / rans4x16_hip_uncompress_qual_batch: host buffers, through the staging arena of
+ * the other host-buffer calls, in chunks of blocks, with the ownership rules of part 2m's batch calls (out[i] == NULL: the
+ * library allocates exactly the result; where the compress call returns -1 it has freed what it allocated).  nrec, len,
+ * flags as in rans4x16_hip_fqz_compress_best_batch (not looked at by a list without an FQZ entry: they may be NULL).  A
+ * block the device leaves R4X16_E_UNDECIDED goes into a second trip of those blocks alone, counted under
+ * R4X16_FQZ_PICK_HOST: its fqzcomp candidates are picked on the host (rans4x16_hip_fqz_pick_parameters) and coded under
+ * their parameter bytes (rans4x16_hip_fqz_compress_batch, which runs rans4x16_hip_fqz_compress_dev), its rANS and arith
+ * methods run through part 2m's batch call, and the host compares the results by the same rule.  len[i] comes back as the
+ * fix-ups leave it and flags[i][rec] &= 0xffff where fqzcomp won; otherwise both are untouched.  Uncompress: method[i] as
+ * d_method, out_size[i] the capacity on entry; lengths / nlengths / nrec as in rans4x16_hip_fqz_uncompress_batch, written
+ * for the FQZ blocks (nrec[i] = 0 for every other); the model slots are sized for the largest max_sym of the FQZ streams.
+ * Both return the number of failed blocks, -1 on a call error.
+ *
+ * Route read-out: R4X16_ROUTE_BEST_QUAL (R4X16_BEST_QUAL_*); the per-codec routes count their own candidates as before. */
+#define R4X16_CODEC_FQZ      (3 << 24)
+int rans4x16_hip_compress_best_qual_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                               const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                               const uint32_t *d_len, const uint32_t *d_flags, const uint64_t *d_rec_off, const uint32_t *d_nrec,
+                                               int vers, int k, const int *methods,
+                                               unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                               uint32_t *d_out_size, int32_t *d_status, int32_t *d_chosen, uint32_t *d_len_out,
+                                               uint32_t max_in_size, uint32_t max_records, uint64_t total_in_size, void *stream);
+int rans4x16_hip_best_qual_chunk_blocks(rans4x16_hip_ctx *ctx, int n, int k, const int *methods, uint32_t max_in_size,
+                                        uint32_t max_records, uint64_t total_in_size);
+int rans4x16_hip_uncompress_qual_packed_dev(rans4x16_hip_ctx *ctx, int n,
+                                            const unsigned char *d_in, const uint64_t *d_in_off, const uint32_t *d_in_size,
+                                            const int32_t *d_method,
+                                            unsigned char *d_out, uint64_t out_capacity, uint64_t *d_out_off,
+                                            uint32_t *d_out_size, int32_t *d_status, const uint32_t *d_nosz_size,
+                                            uint32_t *d_len, const uint64_t *d_len_off, const uint32_t *d_len_cap, uint32_t *d_nrec,
+                                            uint32_t max_in_size, uint32_t max_out_size, void *stream);
+int rans4x16_hip_compress_best_qual_batch(rans4x16_hip_ctx *ctx, int n,
+                                          const unsigned char *const *in, const unsigned int *in_size,
+                                          const unsigned int *nrec, uint32_t *const *len, uint32_t *const *flags, int vers,
+                                          unsigned char **out, unsigned int *out_size,
+                                          int k, const int *methods, int *chosen, int *status);
+int rans4x16_hip_uncompress_qual_batch(rans4x16_hip_ctx *ctx, int n,
+                                       const unsigned char *const *in, const unsigned int *in_size, const int *method,
+                                       unsigned char *const *out, unsigned int *out_size, int *status,
+                                       int *const *lengths, const int *nlengths, unsigned int *nrec);
+
 /* ---- 2b. options ---------------------------------------------------------------------------
  * Everything that can be tuned or switched is an option of the context, set by name; the value is a long.
  * The R4X16_* environment variables named below only provide the DEFAULTS: they are read once per process, when the
@@ -1222,7 +1310,8 @@ enum {
     R4X16_ROUTE_FQZ_ENC = 10, /* fqzcomp_qual encoding (part 2j): encoded streams (R4X16_FQZ_ENC_*)                    */
     R4X16_ROUTE_FQZ_PICK = 11,/* fqzcomp_qual's parameter choice on the device (part 2k): blocks (R4X16_FQZ_PICK_*)    */
     R4X16_ROUTE_FQZ_BEST = 12,/* fqzcomp_qual's best of several strategies (part 2l): R4X16_FQZ_BEST_*                  */
-    R4X16_ROUTE_BEST_ANY = 13 /* best of several methods across codecs (part 2m): blocks and chunks (R4X16_BEST_ANY_*)  */
+    R4X16_ROUTE_BEST_ANY = 13,/* best of several methods across codecs (part 2m): blocks and chunks (R4X16_BEST_ANY_*)  */
+    R4X16_ROUTE_BEST_QUAL = 14/* quality blocks, best across three codecs (part 2n): R4X16_BEST_QUAL_*                  */
 };
 enum {   /* R4X16_ROUTE_DECODE: the decoder's row kinds (r4x16_common.h levels) */
     R4X16_DEC_L1 = 0,         /* packed 10-bit rows, 13..48 symbols                                                   */
@@ -1319,6 +1408,17 @@ enum {   /* R4X16_ROUTE_BEST_ANY: rans4x16_hip_compress_best_any_packed_dev / _b
     R4X16_BEST_ANY_FAILED = 3,      /* blocks without a winner (d_chosen -1)                                              */
     R4X16_BEST_ANY_CHUNKS = 4,      /* chunks the calls walked                                                            */
     R4X16_BEST_ANY_KINDS = 5
+};
+enum {   /* R4X16_ROUTE_BEST_QUAL: rans4x16_hip_compress_best_qual_packed_dev */
+    R4X16_BEST_QUAL_BLOCKS = 0,     /* blocks the call compared                                                           */
+    R4X16_BEST_QUAL_CHUNKS = 1,     /* chunks the call walked                                                             */
+    R4X16_BEST_QUAL_RANS = 2,       /* blocks a rANS 4x16 method won (before the arena's capacity rule), ties included     */
+    R4X16_BEST_QUAL_ARITH = 3,      /* blocks an arith_dynamic method won, ties included                                 */
+    R4X16_BEST_QUAL_FQZ = 4,        /* blocks a fqzcomp_qual strategy won, ties included                                  */
+    R4X16_BEST_QUAL_TIE = 5,        /* of the three above: two codecs' winners shared the smallest size, the list decided */
+    R4X16_BEST_QUAL_FAILED = 6,     /* blocks without a winner (d_chosen -1) that were decided                            */
+    R4X16_BEST_QUAL_UNDECIDED = 7,  /* blocks left R4X16_E_UNDECIDED by the fqzcomp sub-list                              */
+    R4X16_BEST_QUAL_KINDS = 8
 };
 /* counts[k] = the count of kind k, for k < n; reset != 0 starts the counts of `which` afresh.  Waits for the work it counts (call
  * it after the calls, not while another thread uses the context).  Returns the number of kinds of `which`, -1 on error. */
