@@ -96,6 +96,29 @@ class _HostArrays:
         return [self.outs[i][:self.out_sz[i]].tobytes() if self.status[i] == 0 else None for i in range(self.n)], list(self.status)
 
 
+def _library_allocates(blocks, call, who, ctx):
+    """A host-batch compress call with out[i] == NULL: the library allocates exactly the result.  call(n, in_p, in_sz,
+    out_p, out_sz, status) makes the library's call and returns its return code; the buffers are read and freed whatever
+    that is.  Returns (the streams, None for a block that failed; the statuses)."""
+    n = len(blocks)
+    srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
+    dummy = np.zeros(4, dtype=np.uint8)
+    in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
+    in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
+    out_p = (C.c_void_p * n)()
+    out_sz = (C.c_uint * n)()
+    status = (C.c_int * n)()
+    rc = call(n, in_p, in_sz, out_p, out_sz, status)
+    outs = []
+    for i in range(n):
+        outs.append(C.string_at(out_p[i], out_sz[i]) if status[i] == 0 and out_p[i] else None)
+        if out_p[i]:
+            _free(out_p[i])
+    if rc < 0:
+        raise RuntimeError(who + ": " + ctx.error())
+    return outs, list(status)
+
+
 def _host_batch8(blocks, decode, orders=None, caps=None):
     ctx = _thread_ctx()
     L = ctx.L
@@ -717,22 +740,10 @@ def compress_best_any_batch(blocks, methods, caps=None, ctx=None):
     meth = _methods(methods)
     chosen = (C.c_int * n)()
     if caps is None:
-        srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-        dummy = np.zeros(1, dtype=np.uint8)
-        in_p = (C.c_void_p * n)(*[(s.ctypes.data if len(s) else dummy.ctypes.data) for s in srcs])
-        in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-        out_p = (C.c_void_p * n)()
-        out_sz = (C.c_uint * n)()
-        status = (C.c_int * n)()
-        rc = L.rans4x16_hip_compress_best_any_batch(ctx.h, n, in_p, in_sz, out_p, out_sz, len(methods), meth, chosen, status)
-        outs = []
-        for i in range(n):
-            outs.append(C.string_at(out_p[i], out_sz[i]) if status[i] == 0 and out_p[i] else None)
-            if out_p[i]:
-                _free(out_p[i])
-        if rc < 0:
-            raise RuntimeError("compress_best_any_batch: " + ctx.error())
-        return outs, list(chosen), list(status)
+        call = lambda n, in_p, in_sz, out_p, out_sz, status: L.rans4x16_hip_compress_best_any_batch(
+            ctx.h, n, in_p, in_sz, out_p, out_sz, len(methods), meth, chosen, status)
+        outs, status = _library_allocates(blocks, call, "compress_best_any_batch", ctx)
+        return outs, list(chosen), status
     a = _HostArrays(blocks, caps)
     rc = L.rans4x16_hip_compress_best_any_batch(ctx.h, n, a.in_p, a.in_sz, a.out_p, a.out_sz, len(methods), meth, chosen, a.status)
     if rc < 0:
@@ -773,22 +784,10 @@ def compress_best_qual_batch(blocks, lens, flags, methods, vers=4, caps=None, ct
     chosen = (C.c_int * n)(*([-1] * n))
     back = lambda: ([x.tolist() for x in la], [x.tolist() for x in fa])
     if caps is None:
-        srcs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-        in_p = (C.c_void_p * n)(*[ptr(s) for s in srcs])
-        in_sz = (C.c_uint * n)(*[len(s) for s in srcs])
-        out_p = (C.c_void_p * n)()
-        out_sz = (C.c_uint * n)()
-        status = (C.c_int * n)()
-        rc = L.rans4x16_hip_compress_best_qual_batch(ctx.h, n, in_p, in_sz, nrec, len_p, fl_p, int(vers), out_p, out_sz, len(methods), meth,
-                                                     chosen, status)
-        outs = []
-        for i in range(n):
-            outs.append(C.string_at(out_p[i], out_sz[i]) if status[i] == 0 and out_p[i] else None)
-            if out_p[i]:
-                _free(out_p[i])
-        if rc < 0:
-            raise RuntimeError("compress_best_qual_batch: " + ctx.error())
-        return (outs, list(chosen), list(status)) + back()
+        call = lambda n, in_p, in_sz, out_p, out_sz, status: L.rans4x16_hip_compress_best_qual_batch(
+            ctx.h, n, in_p, in_sz, nrec, len_p, fl_p, int(vers), out_p, out_sz, len(methods), meth, chosen, status)
+        outs, status = _library_allocates(blocks, call, "compress_best_qual_batch", ctx)
+        return (outs, list(chosen), status) + back()
     a = _HostArrays(blocks, caps)
     rc = L.rans4x16_hip_compress_best_qual_batch(ctx.h, n, a.in_p, a.in_sz, nrec, len_p, fl_p, int(vers), a.out_p, a.out_sz, len(methods), meth,
                                                  chosen, a.status)

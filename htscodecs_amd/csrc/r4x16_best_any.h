@@ -1,5 +1,5 @@
-// r4x16_best_any.h - what the best-of-k units hand to the call that picks across codecs (r4x16_best_any.hip,
-// include/rans4x16_hip.h part 2m): each codec's candidates of one chunk of blocks, encoded into that codec's own internal
+// r4x16_best_any.h - what the best-of-k units hand to the call that picks across codecs (r4x16_best_qual.hip,
+// include/rans4x16_hip.h parts 2m and 2n): each codec's candidates of one chunk of blocks, encoded into that codec's own internal
 // slots and reduced to one winner a block by that codec's own pick kernel - everything of its best-packed call but the
 // scan and the gather -, the bytes such a chunk takes, and the reader of a stream's size field that both codecs share.
 #pragma once

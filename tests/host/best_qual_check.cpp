@@ -1,8 +1,9 @@
-// best_qual_check.cpp - checks htscodecs_amd/csrc/r4x16_best_qual.h on the host, alone: what the quality calls (include/
-// rans4x16_hip.h part 2n) refuse of a method list before they ask for a device, with the reason they give, and the three
-// sub-lists they make of a list they take.  Built with -fsanitize=address,undefined and run as a program of its own
-// (tests/test_best_qual_cpu.py); prints one line per list - "<name> <reason or ok>" - and, for a list that is taken, the
-// sub-lists; then "best_qual_check: ok" and 0, or 1 where a check of its own failed.
+// best_qual_check.cpp - checks htscodecs_amd/csrc/r4x16_best_qual.h on the host, alone: what the best-of calls across codecs
+// (include/rans4x16_hip.h parts 2m and 2n) refuse of a method list before they ask for a device, with the reason they give,
+// and the three sub-lists they make of a list they take.  Built with -fsanitize=address,undefined and run as a program of
+// its own (tests/test_best_qual_cpu.py); prints one line per list under the quality calls' flavour, which admits all three
+// tags - "<name>: <reason or ok>" and, for a list that is taken, the sub-lists - and the same again as "2m <name>: ..."
+// under part 2m's, which admits no fqzcomp tag; then "best_qual_check: ok" and 0, or 1 where a check of its own failed.
 #include "r4x16_best_qual.h"
 
 #include <stdio.h>
@@ -21,12 +22,12 @@ static int g_failed = 0;
     } while (0)
 
 // k may differ from the list's length (k = 0, k = 33 over a list that is long enough); a NULL list has no entries
-static const char *run(const char *name, int k, const std::vector<int> &methods, bool null_list = false)
+static const char *run_as(const char *flavour, unsigned admit, const char *name, int k, const std::vector<int> &methods, bool null_list)
 {
     BqSplit p;
     memset(&p, 0x5a, sizeof p);
-    const char *why = bq_split(k, null_list ? nullptr : methods.data(), &p);
-    printf("%s: %s", name, why ? why : "ok");
+    const char *why = bq_split(k, null_list ? nullptr : methods.data(), &p, admit);
+    printf("%s%s: %s", flavour, name, why ? why : "ok");
     if (!why) {
         CHECK(p.pm.k == k && p.kr + p.ka + p.kf == k, "%s: %d + %d + %d of %d", name, p.kr, p.ka, p.kf, k);
         printf(" | rans");
@@ -42,6 +43,12 @@ static const char *run(const char *name, int k, const std::vector<int> &methods,
     }
     printf("\n");
     return why;
+}
+
+static void run(const char *name, int k, const std::vector<int> &methods, bool null_list = false)
+{
+    run_as("", BQ_RANS | BQ_ARITH | BQ_FQZ, name, k, methods, null_list);
+    run_as("2m ", BQ_RANS | BQ_ARITH, name, k, methods, null_list);
 }
 
 int main()

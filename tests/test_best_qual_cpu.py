@@ -46,6 +46,9 @@ REFUSED = {
     "an arith stripe method of 256 planes": "more than 255 stripes",
     "seventeen strategies": "more than 16 fqzcomp_qual strategies",
 }
+# the lists above that hold a CODEC_FQZ tag: part 2m's calls, which admit none, meet the tag before the word's own checks
+WITH_FQZ = ("triple", "reversed", "eight", "one strategy", "sixteen strategies among 32", "the tag behind fqzcomp's", "bits above the tag",
+            "a negative strategy", "a strategy with bit 16", "a strategy with bit 23", "seventeen strategies")
 
 
 def test_the_method_lists_refusals_without_a_device(tmp_path):
@@ -65,22 +68,35 @@ def test_the_method_lists_refusals_without_a_device(tmp_path):
     got = dict(l.split(": ", 1) for l in lines[:-1])
     want = dict(TAKEN)
     want.update(REFUSED)
+    # part 2m's flavour: a list without the tag gives the same line, every list with one is refused for the tag
+    assert set(WITH_FQZ) <= set(want) and all(v.endswith("| fqz") for k, v in TAKEN.items() if k not in WITH_FQZ)
+    for name, line in list(want.items()):
+        want["2m " + name] = "unknown codec tag" if name in WITH_FQZ else line
+    assert want["2m one strategy"] == want["2m seventeen strategies"] == want["2m a strategy with bit 16"] == "unknown codec tag"
+    assert want["2m no strategy"] == TAKEN["no strategy"] and want["2m k = 33"] == "bad arguments" and len(want) == 2 * (len(TAKEN) + len(REFUSED))
     assert got == want
 
 
 def test_the_unit_puts_the_refusal_in_front_of_the_device():
-    """the calls' first step after the context is the list's check, and its reason goes into the error text under the
-    call's name, as any_methods does it"""
+    """the calls of both parts hand their arguments to one routine under their flavour and touch nothing themselves; that
+    routine's first step after the context is the list's check, and its reason goes into the error text under the call's
+    name"""
     text = open(os.path.join(ROOT, "htscodecs_amd", "csrc", "r4x16_best_qual.hip")).read()
-    assert 'if (const char *why = bq_split(k, methods, p)) { c->err = std::string(who) + ": " + why; return -1; }' in text
-    for name, who in (("rans4x16_hip_compress_best_qual_packed_dev", "compress_best_qual_packed_dev"),
-                      ("rans4x16_hip_best_qual_chunk_blocks", "best_qual_chunk_blocks"),
-                      ("rans4x16_hip_compress_best_qual_batch", "compress_best_qual_batch")):
-        body = text[text.index('extern "C" int %s(' % name):]
+    assert 'if (const char *why = bq_split(k, methods, p, f.admit)) { c->err = std::string(who) + ": " + why; return -1; }' in text
+    touches = ("hipSetDevice", "r4x16_packed_call_args", "hipLaunchKernelGGL", "r4x16_ensure", "hipMemcpy")
+    for routine, who, calls in (("bq_compress_dev", "enc_dev", ("compress_best_%s_packed_dev",)), ("bq_chunk_blocks", "fit", ("best_%s_chunk_blocks",)),
+                                ("bq_compress_batch", "enc_batch", ("compress_best_%s_batch",))):
+        body = text[text.index("static int %s(" % routine):]
         body = body[:body.index("\n}\n")]
-        check = body.index('bq_methods(c, "%s", k, methods, &p)' % who)
-        for touched in ("hipSetDevice", "r4x16_packed_call_args", "hipLaunchKernelGGL", "r4x16_ensure", "hipMemcpy"):
-            assert touched not in body[:check], (name, touched)
+        check = body.index("bq_methods(c, f, f.who.%s, k, methods, &p)" % who)
+        for touched in touches:
+            assert touched not in body[:check], (routine, touched)
+        for call in calls:
+            for part, flavour in (("any", "BQ_ANY"), ("qual", "BQ_QUAL")):
+                assert '"%s"' % (call % part) in text[text.index("static const BqFlavour %s = " % flavour):].split(";")[0]
+                entry = text[text.index('extern "C" int rans4x16_hip_%s(' % (call % part)):]
+                entry = entry[entry.index("\n{\n") + 3:entry.index("\n}\n")]
+                assert entry.startswith("    return %s(c, %s, " % (routine, flavour)) and entry.count(";") == 1, (call % part, entry)
 
 
 def test_the_new_symbols_are_declared_exported_bound_and_wrapped():

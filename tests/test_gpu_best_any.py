@@ -344,6 +344,35 @@ def test_an_x_nosz_stream_of_each_codec(dc):
     _check_decoded(r, [data] * 4, [0, 0, B.UNSUPPORTED, 0], "an unknown tag")
 
 
+def test_an_fqzcomp_tagged_block_is_no_candidate_of_these_calls(dc):
+    """CODEC_FQZ is the quality calls' tag (part 2n): here the device says UNSUPPORTED at the claim, the block takes no room,
+    its neighbours decode and the fqzcomp decoder is not run; the host batch says the same, not its own CAPACITY"""
+    import torch
+    import htscodecs_amd as H
+    data = B.text("q4")[:2000]
+    quals = bytes((7 * i + i // 9) % 41 for i in range(300))
+    fqz_stream = H.fqz_compress(quals, [100] * 3, [0] * 3, 4, 0)[0]
+    # the premise of the host half: byte 1, read as a size field (the second byte of varint(300)), claims no more than 300
+    assert fqz_stream[:2] == bytes([0x80 | (300 >> 7), 300 & 0x7f]) and fqz_stream[1] == 44 <= 300
+    streams = [B._rans_stream(data, 1), fqz_stream, B._arith_stream(data, 0), b""]
+    methods = [B.rans(1), H.CODEC_FQZ | 0, B.arith(0), -1]
+    blocks, want = [data, quals, data, b""], [0, B.UNSUPPORTED, 0, B.EMPTY]
+    d_in, in_off, in_size = _inputs(dc, streams)
+    method = torch.tensor(methods, dtype=torch.int32, device=dc.dev)
+    dc.set_option("route_count", 1)
+    try:
+        dc.route_read("fqz")
+        r = _decode(dc, d_in, in_off, in_size, method, [2000, 300, 2000, 8])
+        route = dc.route_read("fqz")
+    finally:
+        dc.set_option("route_count", 0)
+    _check_decoded(r, blocks, want, "an fqzcomp tag")
+    assert r.off == [0, 2000, 2000, 4000, 4000] and r.off[2] == r.off[1]
+    assert route == dict.fromkeys(route, 0), route
+    back, st = H.uncompress_any_batch(streams, methods, [2000, 300, 2000, 8], ctx=dc.ctx)
+    assert st == want and back == [data, None, data, None]
+
+
 # ---- host buffers ---------------------------------------------------------------------------------------------------------------
 def test_the_host_batches(dc):
     import htscodecs_amd as H

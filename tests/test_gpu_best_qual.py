@@ -552,6 +552,11 @@ def test_the_host_batches(dc):
     assert st == [Q.CAPACITY if i in (0, short) else 0 for i in range(len(blocks))], st
     back, st, _, nrec = H.uncompress_qual_batch([b""] + outs[:3], [-1] + chosen[:3], [8] + [len(d) for d in datas[:3]], ctx=dc.ctx)
     assert st == [Q.EMPTY, 0, 0, 0] and back[1:] == [bytes(d) for d in datas[:3]]
+    # a list without an fqzcomp method, and no records: part 2m's batch
+    eight, pair = datas[20:28], [A.rans(1), A.arith(1), A.arith(65), A.rans(65)]
+    own = H.compress_best_any_batch(eight, pair, ctx=dc.ctx)
+    got = H.compress_best_qual_batch(eight, [[]] * 8, [[]] * 8, pair, ctx=dc.ctx)
+    assert own[2] == [0] * 8 and got[:3] == own and got[3:] == ([[]] * 8, [[]] * 8)
 
 
 def test_the_host_batch_picks_an_undecided_block_on_the_host(dc):

@@ -16,7 +16,8 @@ other; the warm-up pass of the one call is also decoded again by rans4x16_hip_un
 input.
 
 --only one_call | baseline runs that way alone, for a kernel trace in a run of its own (rocprofv3 --kernel-trace --stats):
-the new kernels' share of the call is the time of k_any_pick and k_any_gather over the time of all kernels."""
+the share of the call that picks across codecs is the time of k_bq_pick and k_bq_gather - the kernels parts 2m and 2n
+share - over the time of all kernels."""
 import argparse
 import json
 import os
