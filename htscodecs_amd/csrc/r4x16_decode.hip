@@ -691,7 +691,8 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
 // In front of the 8-step loop runs a loop of 16-step trips, all fast, while every stream of the wave has sixteen
 // steps and 64 words left: one 16-byte store per trip from four accumulators that are never rotated, no (t & 15) test,
 // no first-trip conditions (a step's bookkeeping belongs to the shadow of the NEXT step's group read, so the byte of a
-// trip's last step is booked, and the trip's store made, at the end of that same trip).  It hands the 8-step loop
+// trip's last step is booked at the end of that same trip; the trip's store is made in the next trip's eighth shadow, or
+// in the epilogue behind the loop).  It hands the 8-step loop
 // t = tb, a multiple of 16, with everything up to step tb booked and stored: that loop's first trip skips step 0's
 // bookkeeping where it used to test t > 0, and the tail after the loop knows that nothing is queued if no trip followed.
 // Ring: FOUR live quarters (h .. h + 3 while the cursor is in h: a 16-step trip moves it by up to 128 bytes - one word
@@ -715,6 +716,9 @@ __device__ __forceinline__ u32 chain_decode_lds(const u8 *img_lds, u32 nsym, u8 
 // written by every lane (the pad takes the copies that are not slot 0's), the tests as scalar ands of two masks, the
 // second round behind a test of its own: 34 instructions where 107 stood, headline step 129.0 -> 125.9 ms
 // (profiles/dec_refill.md, with the two further stages that were built, measured and left out).
+// Since then that refill runs in the immediate form only where a lane is two quarters on at a trip's end, and in the
+// epilogue; the refill of a lane one quarter on, the trip's store, its last flags and the loop test stand in the group-read
+// shadows of the next trip (the comment at the 16-step loop; profiles/dec_tail.md).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 *ring, gcu8 *words, u32 words_len,
                                                 gu8 *out, u32 out_sz, u32 x, bool active, u32 lane)
@@ -892,66 +896,183 @@ __device__ __forceinline__ u32 chain_decode_pk2(const u8 *img_lds, u32 nsym, u8 
     issue_end();
 
     // ---- 16-step trips -----------------------------------------------------------------------------
+    // What used to stand behind the body, where nothing covers it, stands in the group-read shadows of the NEXT trip's
+    // first eight steps, as asm volatile between `issue`'s reads and `issue_end` (a branch would end the body's block,
+    // and plain C++ sinks behind it):
+    //   * the refill of a lane that is ONE quarter on at the trip's end.  Its slot `half` is next read when a step's
+    //     12-byte window reaches stream quarter half + 4, at least 128 bytes ahead of the end of quarter half + 1; a step
+    //     moves the cursor by at most 8 bytes and reads 12 further, so the park, the mirror write and the request are
+    //     safe up to step 14 and stand in shadows 6 and 7 (tests/test_dec_tail_cpu.py sweeps the step).  The two parity
+    //     sides are two LDS writes and the request under an exec mask set and restored by scalar instructions; the
+    //     wait for the waiting quarters (asked for a trip or two ago) stands in front of them, the store behind them.
+    //     The compiler does not see these requests: whatever reads penda / pendb outside the body waits by hand.
+    //   * a lane TWO quarters on cannot wait: one scalar test of a mask made in the sixteenth shadow leads to the
+    //     immediate refill (`refill_now`, both rounds), which is also what the epilogue runs.  Nothing deferred is open
+    //     at a trip's end but that trip's own refill and store.
+    //   * the trip's store and the advance of `op` (shadow 8, from four copies made in shadows 1 to 4, before the next
+    //     bytes overwrite the accumulators; idle lanes masked off by scalar moves), the flags of the row in use at
+    //     the trip's last step (it counts if step t + 16 exists, and it does wherever a further trip of sixteen runs; the
+    //     epilogue tests it otherwise), and the operands of the loop test (shadows 12 to 14).
+    // The loop is entered by the exact test and left by a conservative one made from the cursor at step 12: the four steps
+    // left take at most 16 words, so `cursor12 + 80 > nwords` covers `cursor + 64 > nwords`; a wave may leave a trip
+    // early, the 8-step loop takes over.  Behind the body stand the trip count, the test for the immediate refill and
+    // the exit test (profiles/dec_tail.md).
     {
         u32 b0 = 0, b1 = 0, b2 = 0;                        // with acc: the four dwords of a trip
-        // wave_any(active && p) of the loop test and of the refill test as a scalar and of two masks: its scc is the answer
+        // wave_any(active && p) of the entry test and of the refill test as a scalar and of two masks: its scc is the answer
         const unsigned long long amask = __ballot(active);
-        if (amask != 0ull) {
-            while ((__ballot(t + 16u > count || cursor + 64u > nwords) & amask) == 0ull) {
+        // the immediate refill, up to two quarters: the epilogue's, and the trip's where a lane is two quarters on
+        auto refill_now = [&]() __attribute__((always_inline)) {
+            const u32 nh = (off0 + 2 * cursor) >> 6;
+            if ((__ballot(nh != half) & amask) != 0ull) {
+#pragma unroll
+                for (int r = 0; r < 2; r++) {
+                    // the second round only where a lane is still behind (two quarters in one trip: rare)
+                    if (r == 1 && (__ballot(nh != half) & amask) == 0ull) break;
+                    // One path: the slot, the mirror's address and the request's address are made once for both
+                    // parities; a side is the two writes and the request, nothing else: three instructions under a
+                    // lane mask, where a select of the parked quarter would be four and still leave the two
+                    // requests masked.  (A request has to land in the registers of the quarter just parked: with
+                    // "the younger takes the older one's registers, the request the younger one's" it arrives in
+                    // temporaries and is waited for AT ONCE to copy it.)
+                    const bool need = active && nh != half;      // idle lanes hold garbage cursors: they must not write LDS
+                    const bool odd = (half & 1u) != 0;
+                    const u32 slot = (half & 3u) * 64u + 16u * k;
+                    u32x4 *const sp = (u32x4 *)(ring + slot);
+                    u32x2 *const mp = (u32x2 *)(ring + (slot == 0 ? RB : RB + 8u));
+                    const u32 o = half * 64u + (16u * k + 384u);
+                    gcu32x4 *const rp = (gcu32x4 *)(rbase + (o < lasto ? o : lasto));      // quarter half + 6: see `request`
+                    if (need && odd) { *sp = pendb; *mp = pendb.xy; pendb = *rp; }
+                    if (need && !odd) { *sp = penda; *mp = penda.xy; penda = *rp; }
+                    half += need ? 1u : 0u;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        };
+        if (amask != 0ull && (__ballot(t + 16u > count || cursor + 64u > nwords) & amask) == 0ull) {
+            const u32 wlim = nwords - 80u;                // signed compare: nwords >= 64 here, below 2^31 always
+            const u32 ringa = lds_addr(ring), k16 = 16u * k, k384 = 16u * k + 384u;
+            unsigned long long smask = 0ull, leave, leave_t;      // lanes that store in shadow 8: none in the first trip
+            unsigned long long two = 0ull, need1 = 0ull, oddm = 0ull, side_o = 0ull, side_e = 0ull, sv;
+            u32 hdr16 = 0;                                // flags of the row in use at a trip's end: booked by the next trip
+            u32 s0 = 0, s1 = 0, s2 = 0, s3 = 0;           // the trip's sixteen bytes until they are stored
+            u32 dq = 0, qs = 0, par = 0, sa = 0, ma = 0, ro = 0;      // quarters on at the trip's end; the deferred refill's addresses
+            u64 opa = (u64)op - 16u;                      // shadow 8 advances it in every trip, the first one's too
+            do {
 #pragma unroll
                 for (int u = 1; u <= 16; u++) {           // step t + u - 1, then the issue half and the bookkeeping of step t + u
                     const u32 wq = finish(std::true_type{}, true);
                     issue(wq, true);
-                    // flags of the row now in use (ROW_EMPTY is tested after the loop), two steps per three-way or;
-                    // the row in use at t + 16 counts only if that step exists.  The or and the byte's shift are PINNED
-                    // here, in the group read's shadow (asm volatile: as plain C++ the compiler sinks both behind the
-                    // body); each is read a step or more later, so neither gets an asm's pad
+                    // flags of the row now in use (ROW_EMPTY is tested after the loop), two steps per three-way or.
+                    // The ors and the byte's shift are PINNED here, in the group read's shadow (asm volatile: as plain
+                    // C++ the compiler sinks them behind the body); each is read a step or more later, so none gets an
+                    // asm's pad
                     u32 &A = u <= 4 ? b0 : u <= 8 ? b1 : u <= 12 ? b2 : acc;
-                    if (u == 16) bad |= hdr_even | (t + 16u < count ? hdr : 0u);
+                    // ---- the tail of the trip before (shadows 1 .. 8) ----
+                    if (u == 1)
+                        asm volatile("v_mov_b32_e32 %[s0], %[b0]\n\t"
+                                     "v_cmp_ne_u32_e64 %[n], 0, %[dq]\n\t"
+                                     "v_or_b32_e32 %[bad], %[bad], %[h16]"
+                                     : [s0] "=&v"(s0), [n] "=&s"(need1), [bad] "+v"(bad) : [b0] "v"(b0), [dq] "v"(dq), [h16] "v"(hdr16));
+                    if (u == 2)
+                        asm volatile("v_mov_b32_e32 %[s1], %[b1]\n\t"
+                                     "v_and_b32_e32 %[qs], 3, %[half]\n\t"
+                                     "v_and_b32_e32 %[par], 1, %[half]\n\t"
+                                     "s_and_b64 %[n], %[n], %[am]"
+                                     : [s1] "=&v"(s1), [qs] "=&v"(qs), [par] "=&v"(par), [n] "+s"(need1)
+                                     : [b1] "v"(b1), [half] "v"(half), [am] "s"(amask) : "scc");
+                    if (u == 3)
+                        asm volatile("v_mov_b32_e32 %[s2], %[b2]\n\t"
+                                     "v_lshl_or_b32 %[qs], %[qs], 6, %[k16]\n\t"
+                                     "v_cmp_eq_u32_e64 %[o], 1, %[par]"
+                                     : [s2] "=&v"(s2), [qs] "+v"(qs), [o] "=&s"(oddm) : [b2] "v"(b2), [k16] "v"(k16), [par] "v"(par));
+                    if (u == 4)                           // slot 0's lane writes the mirror, every other lane the pad behind it
+                        asm volatile("v_mov_b32_e32 %[s3], %[acc]\n\t"
+                                     "v_min_u32_e32 %[ma], 8, %[qs]\n\t"
+                                     "v_add_u32_e32 %[sa], %[ring], %[qs]\n\t"
+                                     "v_add_u32_e32 %[ma], %[ring], %[ma]"
+                                     : [s3] "=&v"(s3), [ma] "=&v"(ma), [sa] "=&v"(sa) : [acc] "v"(acc), [qs] "v"(qs), [ring] "v"(ringa));
+                    if (u == 5)                           // quarter half + 6, clamped: see `request`
+                        asm volatile("v_lshl_add_u32 %[ro], %[half], 6, %[k384]\n\t"
+                                     "s_and_b64 %[so], %[n], %[o]\n\t"
+                                     "v_min_u32_e32 %[ro], %[ro], %[lasto]\n\t"
+                                     "s_andn2_b64 %[se], %[n], %[o]"
+                                     : [ro] "=&v"(ro), [so] "=&s"(side_o), [se] "=&s"(side_e)
+                                     : [half] "v"(half), [k384] "v"(k384), [lasto] "v"(lasto), [n] "s"(need1), [o] "s"(oddm) : "scc");
+                    if (u == 6) {                         // the odd side, behind the wait for both waiting quarters
+                        gcu8 *const rp = rbase + ro;
+                        const u32x2 lo = {pendb.x, pendb.y};
+                        asm volatile("s_waitcnt vmcnt(0)\n\t"
+                                     "s_and_saveexec_b64 %[sv], %[m]\n\t"
+                                     "ds_write_b128 %[sa], %[p]\n\t"
+                                     "ds_write_b64 %[ma], %[lo] offset:256\n\t"
+                                     "global_load_dwordx4 %[p], %[rp], off\n\t"
+                                     "s_mov_b64 exec, %[sv]"
+                                     : [sv] "=&s"(sv), [p] "+v"(pendb) : [m] "s"(side_o), [sa] "v"(sa), [ma] "v"(ma), [lo] "v"(lo), [rp] "v"(rp)
+                                     : "memory", "scc");
+                    }
+                    if (u == 7) {                         // the even side
+                        gcu8 *const rp = rbase + ro;
+                        const u32x2 lo = {penda.x, penda.y};
+                        asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
+                                     "ds_write_b128 %[sa], %[p]\n\t"
+                                     "ds_write_b64 %[ma], %[lo] offset:256\n\t"
+                                     "global_load_dwordx4 %[p], %[rp], off\n\t"
+                                     "s_mov_b64 exec, %[sv]"
+                                     : [sv] "=&s"(sv), [p] "+v"(penda) : [m] "s"(side_e), [sa] "v"(sa), [ma] "v"(ma), [lo] "v"(lo), [rp] "v"(rp)
+                                     : "memory", "scc");
+                    }
+                    if (u == 8) {
+                        // the sixteen bytes of the trip before, one store per lane, BEHIND that trip's refill (vmcnt
+                        // counts stores: a wait for quarters behind a store waits for the store); the lane is now in `half`
+                        const u32x4 v = {s0, s1, s2, s3};
+                        asm volatile("s_and_saveexec_b64 %[sv], %[sm]\n\t"
+                                     "global_store_dwordx4 %[op], %[v], off\n\t"
+                                     "s_mov_b64 exec, %[sv]\n\t"
+                                     "v_lshl_add_u64 %[op], %[op], 0, 16\n\t"
+                                     "s_mov_b64 %[sm], %[am]\n\t"
+                                     "v_addc_co_u32_e64 %[half], vcc, %[half], 0, %[n]"
+                                     : [sv] "=&s"(sv), [sm] "+s"(smask), [op] "+v"(opa), [half] "+v"(half)
+                                     : [v] "v"(v), [am] "s"(amask), [n] "s"(need1) : "memory", "vcc", "scc");
+                    }
+                    if (u == 16) hdr16 = hdr;
+                    else if (u == 15) asm volatile("v_or_b32_e32 %0, %0, %1" : "+v"(bad) : "v"(hdr));
                     else if (u & 1) hdr_even = hdr;
                     else asm volatile("v_or3_b32 %0, %0, %1, %2" : "+v"(bad) : "v"(hdr), "v"(hdr_even));
                     asm volatile("v_alignbit_b32 %0, %1, %0, 8" : "+v"(A) : "v"(hdr));
+                    // the loop test: lanes that have no further sixteen steps, or may not have 64 words at the trip's end
+                    if (u == 12) asm volatile("v_cmp_gt_i32_e64 %0, %1, %2" : "=s"(leave) : "v"(cursor), "v"(wlim));
+                    if (u == 13) asm volatile("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(leave_t) : "s"(t + 32u), "v"(count));
+                    if (u == 14)
+                        asm volatile("s_or_b64 %0, %0, %1\n\ts_and_b64 %0, %0, %2" : "+s"(leave) : "s"(leave_t), "s"(amask) : "scc");
+                    // quarters on at the trip's end (the cursor is whole: `issue` has counted step 16's words)
+                    if (u == 16)
+                        asm volatile("v_lshrrev_b32_e32 %[dq], 6, %[cb]\n\t"
+                                     "v_sub_u32_e32 %[dq], %[dq], %[half]\n\t"
+                                     "v_cmp_lt_u32_e64 %[two], 1, %[dq]"
+                                     : [dq] "=&v"(dq), [two] "=&s"(two) : [cb] "v"(cb), [half] "v"(half));
                     issue_end();
                 }
                 t += 16u;
-                // ring refill: the cursor is at most two quarters on
-                const u32 nh = (off0 + 2 * cursor) >> 6;
-                if ((__ballot(nh != half) & amask) != 0ull) {
-                    // (both waiting quarters are waited for HERE, where they arrived long ago: a wait inside one of the
-                    //  sides below would also wait for the request that the side before it has just made)
-                    asm volatile("" : : "v"(penda), "v"(pendb));
-#pragma unroll
-                    for (int r = 0; r < 2; r++) {
-                        // the second round only where a lane is still behind (two quarters in one trip: rare)
-                        if (r == 1 && (__ballot(nh != half) & amask) == 0ull) break;
-                        // One path: the slot, the mirror's address and the request's address are made once for both
-                        // parities; a side is the two writes and the request, nothing else: three instructions under a
-                        // lane mask, where a select of the parked quarter would be four and still leave the two
-                        // requests masked.  (A request has to land in the registers of the quarter just parked: with
-                        // "the younger takes the older one's registers, the request the younger one's" it arrives in
-                        // temporaries and is waited for AT ONCE to copy it.)
-                        const bool need = active && nh != half;      // idle lanes hold garbage cursors: they must not write LDS
-                        const bool odd = (half & 1u) != 0;
-                        const u32 slot = (half & 3u) * 64u + 16u * k;
-                        u32x4 *const sp = (u32x4 *)(ring + slot);
-                        u32x2 *const mp = (u32x2 *)(ring + (slot == 0 ? RB : RB + 8u));
-                        const u32 o = half * 64u + (16u * k + 384u);
-                        gcu32x4 *const rp = (gcu32x4 *)(rbase + (o < lasto ? o : lasto));      // quarter half + 6: see `request`
-                        if (need && odd) { *sp = pendb; *mp = pendb.xy; pendb = *rp; }
-                        if (need && !odd) { *sp = penda; *mp = penda.xy; penda = *rp; }
-                        half += need ? 1u : 0u;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
+                if ((two & amask) != 0ull) {
+                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(penda), "+v"(pendb) : : "memory");
+                    refill_now();
+                    dq = 0;                               // nothing is left for the next trip's shadows
                 }
-                // the trip's sixteen bytes, BEHIND the refill: vmcnt counts stores as well, and the refill's wait for
-                // its quarters would wait for a store issued in front of it (144.3 ms per benchmark step against 140.0)
-                if (active) {
-                    const u32x4 v = {b0, b1, b2, acc};
-                    *(GAS u32x4_unaligned *)op = v;
-                }
-                op += 16;
+            } while (leave == 0ull);
+            // what the next trip would have done in its shadows: the last trip's refill, then its store, and the flags
+            // of the row in use at its end.  The 8-step loop gets everything up to tb booked and stored, and `half`
+            // and the waiting quarters as before.
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(penda), "+v"(pendb) : : "memory");
+            refill_now();
+            op = (gu8 *)opa;
+            if (active) {
+                const u32x4 v = {b0, b1, b2, acc};
+                *(GAS u32x4_unaligned *)op = v;
             }
+            op += 16;
+            bad |= t < count ? hdr16 : 0u;
         }
         tb = t;
     }

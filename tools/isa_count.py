@@ -3,7 +3,9 @@
 usage: tools/isa_count.py <kernel-name-substring> [block-label-substring]
        tools/isa_count.py --json <out>     the hot bodies' counts (and, for the decode chain on packed rows, the number of
                                            instructions in the shadow of each step's group read and head read, and the
-                                           instructions of one 16-step trip from loop header to back edge: trip_path)"""
+                                           instructions of one 16-step trip from loop header to back edge, trip_path, and of
+                                           what it issues between its last step's fence and the next trip's first wait:
+                                           trip_tail)"""
 import re
 import sys
 from collections import Counter
@@ -151,6 +153,41 @@ def refill_path(src, name, header, marker, steps):
     return best
 
 
+def trip_tail(src, name, header, marker, steps):
+    """Instructions that a 16-step trip issues, on the route a refilling trip takes, from the fence that closes the
+    sixteenth issue_end (the body's last sched_barrier) to the wait in front of the next trip's first finish (the first
+    s_waitcnt for lgkmcnt behind the loop header): what stands behind the body and in the loop header, where no read
+    covers it.  It is trip_path, plus refill_path where the body itself holds no request (a global_load_dwordx4 in the
+    body is the deferred refill: the detour that is left is the rare immediate one and does not count), less the
+    instructions from that wait to that fence."""
+    n, _ = trip_path(src, name, header, marker, steps)
+    if n is None:
+        return None
+    i = src.index(name + ':')
+    i = src.index(re.match(r'\.LBB\d+_\d+', header).group(0) + ':', i)
+    k, first_wait, last_fence, marks, in_body_request = 0, None, None, 0, False
+    for l in src[i:src.index('.Lfunc_end', i)].split('\n')[1:]:
+        t = l.strip()
+        if re.match(r'^\.LBB\d+_\d+:', l) and marks >= steps:
+            break
+        if t.startswith('; sched_barrier'):
+            last_fence = k
+        if not t or t.startswith(('.', ';')):
+            continue
+        op = t.split()[0]
+        if op.startswith(('s_branch', 's_cbranch')) and marks >= steps:
+            break
+        if first_wait is None and op == 's_waitcnt' and 'lgkmcnt' in t:
+            first_wait = k
+        marks += op == marker
+        in_body_request |= marks > 0 and op == 'global_load_dwordx4'
+        k += 1
+    if first_wait is None or last_fence is None:
+        return None
+    detour = 0 if in_body_request else (refill_path(src, name, header, marker, steps) or 0)
+    return n + detour - (last_fence - first_wait)
+
+
 GROUP_READ = ("ds_read_b128", r"ds_read_b32 .*offset:16\b")      # lookup_step_pk's group: 16 bytes + the dword after them
 HEAD_READ = ("ds_read_b64", None)                                 # the head entry of the symbol just decoded
 
@@ -191,7 +228,8 @@ def to_json(out_path):
                             if least:                                    # the 16-step trip: header to back edge, no refill
                                 n, labs = trip_path(src, name, lab, marker, least[0])
                                 best[1].update({"trip_path_instructions": n, "trip_path_blocks": labs,
-                                                "refill_path_instructions": refill_path(src, name, lab, marker, least[0])})
+                                                "refill_path_instructions": refill_path(src, name, lab, marker, least[0]),
+                                                "trip_tail_instructions": trip_tail(src, name, lab, marker, least[0])})
                 if best:
                     res["kernels"][label] = best[1]
     with open(out_path, 'w') as f:
@@ -223,6 +261,7 @@ def main():
                     if steps >= 16:
                         print('   trip path, header to back edge without the refill', trip_path(src, name, lab, "v_lshrrev_b64", steps))
                         print('   refill path, behind the test to the join', refill_path(src, name, lab, "v_lshrrev_b64", steps))
+                        print('   trip tail, the last fence to the first wait on the refilling route', trip_tail(src, name, lab, "v_lshrrev_b64", steps))
 
 if __name__ == '__main__':
     main()
