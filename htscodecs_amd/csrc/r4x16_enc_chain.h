@@ -113,6 +113,9 @@ struct EncOutT {
     u32x4 held;          // a half read out of the ring, stored one double-trip later
     gu8 *held_dst;
     u32 above = (0xeu << k) & 0xfu;                      // the quad's lanes that write before this one (chains k + 1 .. 3)
+    u32 wm1 = 0, mlo = 0, mhi = 0;                       // trip_freq's form of `written` and its lane masks (trip_enter)
+    u32 fthr = 0, fhalf = 0, fsum = 0;                   // flush_pipelined<true>'s form of `flushed` (trip_enter)
+    gu8 *fdst = nullptr;
     static constexpr u32 HALF_SHIFT = BYTE ? 6u : 5u;    // units per 64-byte half, as a shift
     // the 16-bit renormalisation of one step (rANS_word.h:300-306): the state's low word into the ring where x is over
     // x_max; returns the state the step carries on with
@@ -203,57 +206,82 @@ struct EncOutT {
     //  - `emit ? x >> 16 : x` is ONE select with a word pick (SDWA), which takes its condition from vcc only - the C++ form
     //    has the compare as a bool beside a ballot and gets a shift and a select;
     //  - a vector instruction reads vcc two slots behind the compare that wrote it at the earliest.  Nothing of the step
-    //    itself can stand there (all of it hangs on the compare), so the PREVIOUS step's ring address and ring write do;
-    //    the first step has the starts of two of the next trip's symbols there, and the last one's write stands at the end;
+    //    itself can stand there (all of it hangs on the compare), so the PREVIOUS step's ring write and DPP move do
+    //    (ENC_TRIP_WRITE); the first step has the starts of two of the next trip's symbols there, and the last step's
+    //    write and move stand at the end;
+    //  - a lone wave issues an instruction that reads its predecessor's result 1.7 slots behind it (profiles/enc_quad.md),
+    //    so the count's instructions alternate with the division's and the ring address closes the step: every
+    //    instruction stands at least two slots behind the one it reads from;
     //  - one statement, not one per step: the compiler puts an idle slot between a statement and the next instruction
     //    or statement that reads one of its outputs, and every piece of a step reads the one before.
     // The state alternates between two registers (xa, xb), so the one a step started from is still there when the next
-    // step writes its low word out.  The quad's mask is a 64-bit shift whose low half alone is used, and a statement
-    // cannot name half an operand: it goes through a fixed register pair (ENC_TRIP_EM), declared as clobbered.
+    // step writes its low word out.
+    // The quad's count (trip_enter): a quad lies wholly in lanes 0..31 or wholly in lanes 32..63, so the compare's mask is
+    // and-ed half by half with two lane constants of which one is 0 - `mlo` / `mhi` hold, at the quad's place in its half,
+    // this lane's bit and those of the quad's lanes that write before it (chains k .. 3).  Each instruction reads one
+    // scalar register, which is what VOP2 / VOP3 allow.  One bit count with accumulate onto `wm1` - the words written by
+    // the quad so far, MINUS ONE - gives t = wm1 + (emitting lanes among this one and those before it): an emitting
+    // lane's own slot, where `written` + (those before it) stood.  The quad's lane 0 counts the whole quad, so its t is
+    // the next step's wm1: one DPP move (quad_perm 0,0,0,0) brings it to the four lanes.  No 64-bit shift, no second
+    // mask, no second count, no fixed register pair.  (tests/test_enc_quad_cpu.py: the count against emit16q's.)
     // The ring writes are not counted by the compiler's LDS waits, which is safe: LDS operations return in order and a
     // wait for "at most N outstanding" can only cover more with an operation it does not know of.
-    // Hazards inside (gfx950): vcc written by a compare is read 3 slots later at the earliest; the SDWA forms write
-    // whole dwords (no forwarding hazard); nothing else here is on the list.
-#define ENC_TRIP_EM    "v[30:31]"
-#define ENC_TRIP_EM_LO "v30"
-#define ENC_TRIP_EM_CLOBBER "v30", "v31"
+    // Hazards inside (gfx950): vcc written by a compare is read 3 slots later at the earliest; a DPP operand is read two
+    // slots behind the vector instruction that wrote it at the earliest - the move stands in the NEXT step's compare
+    // slots, eight instructions behind the count; the SDWA forms write whole dwords (no forwarding hazard); nothing
+    // else here is on the list.
+    // Every lane of the wave runs the statement (lanes without a stream code neutral symbols), so the move's source lane
+    // is always enabled.
 #define ENC_TRIP_WRITE(xp) \
-        "v_mad_i32_i24 %[q], %[pj], -2, %[r126]\n\t" \
-        "ds_write_b16 %[q], %[" xp "]\n\t"
+        "ds_write_b16 %[pj], %[" xp "]\n\t" \
+        "v_mov_b32_dpp %[wm1], %[t] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t"
 #define ENC_TRIP_STEP(gap, xi, xo, n) \
         "v_cmp_ge_u32_e32 vcc, %[" xi "], %[X" n "]\n\t" \
         gap \
-        "v_lshrrev_b64 " ENC_TRIP_EM ", %[sh], vcc\n\t" \
         "v_cndmask_b32_sdwa %[xs], %[" xi "], %[" xi "], vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t" \
-        "v_and_b32_e32 %[t], %[above], " ENC_TRIP_EM_LO "\n\t" \
+        "v_and_b32_e32 %[t], vcc_lo, %[mlo]\n\t" \
         "v_mul_hi_u32 %[q], %[xs], %[m" n "]\n\t" \
-        "v_and_b32_e32 " ENC_TRIP_EM_LO ", 15, " ENC_TRIP_EM_LO "\n\t" \
-        "v_bcnt_u32_b32 %[t], %[t], %[wr]\n\t" \
+        "v_and_or_b32 %[t], vcc_hi, %[mhi], %[t]\n\t" \
         "v_add_u32_e32 %[q], %[xs], %[q]\n\t" \
-        "v_bcnt_u32_b32 %[wr], " ENC_TRIP_EM_LO ", %[wr]\n\t" \
+        "v_bcnt_u32_b32 %[t], %[t], %[wm1]\n\t" \
         "v_lshrrev_b32_sdwa %[q], %[w" n "], %[q] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD\n\t" \
-        "v_and_b32_e32 %[t], 63, %[t]\n\t" \
+        "v_and_b32_e32 %[pj], 63, %[t]\n\t" \
         "v_mul_u32_u24_e32 %[q], %[q], %[w" n "]\n\t" \
-        "v_cndmask_b32_e32 %[pj], -1, %[t], vcc\n\t" \
-        "v_add3_u32 %[" xo "], %[xs], %[s" n "], %[q]\n\t"
+        "v_cndmask_b32_e32 %[pj], -1, %[pj], vcc\n\t" \
+        "v_add3_u32 %[" xo "], %[xs], %[s" n "], %[q]\n\t" \
+        "v_mad_i32_i24 %[pj], %[pj], -2, %[r126]\n\t"
+    // the lane constants of the statement's count, and `written` -> wm1: once, in front of the pipelined loop
+    __device__ __forceinline__ void trip_enter()
+    {
+        const u32 aos = (above | 1u << k) << (lane & 28u);
+        mlo = lane < 32u ? aos : 0u;
+        mhi = lane < 32u ? 0u : aos;
+        wm1 = written - 1u;
+        fthr = (flushed << 5) + 31u;
+        const u32 rk = (u32)(unsigned long)(LAS u8 *)ring + 16u * k;
+        fhalf = rk + ((flushed & 1u) ? 0u : 64u);
+        fsum = 2u * rk + 64u;
+        fdst = send + 16u * k - 2;
+    }
+    // wm1 -> `written`, fthr -> `flushed`: once, behind the loop; everything outside it reads those
+    __device__ __forceinline__ void trip_leave() { written = wm1 + 1u; flushed = (fthr - 31u) >> 5; }
     // na, nb: two pairs of the NEXT trip as they come out of the row; their starts (the low eleven bits) are taken in the
     // two slots behind the first compare, where the first step has no ring write to place.
     __device__ __forceinline__ void trip_freq(u32 &x, u32x4 m, u32x4 w, u32 s0, u32 s1, u32 s2, u32 s3, u32 X0, u32 X1, u32 X2, u32 X3,
                                               u32 &na, u32 &nb)
     {
         u32 xb, xs, t, q, pj;
-        const u32 sh = lane & ~3u;
         asm volatile(ENC_TRIP_STEP("v_and_b32_e32 %[na], 0x7ff, %[na]\n\t"
                                    "v_and_b32_e32 %[nb], 0x7ff, %[nb]\n\t", "xa", "xb", "0")
                      ENC_TRIP_STEP(ENC_TRIP_WRITE("xa"), "xb", "xa", "1")
                      ENC_TRIP_STEP(ENC_TRIP_WRITE("xb"), "xa", "xb", "2")
                      ENC_TRIP_STEP(ENC_TRIP_WRITE("xa"), "xb", "xa", "3")
                      ENC_TRIP_WRITE("xb")
-                     : [xa] "+v"(x), [wr] "+v"(written), [na] "+v"(na), [nb] "+v"(nb), [xb] "=&v"(xb), [xs] "=&v"(xs), [t] "=&v"(t), [q] "=&v"(q), [pj] "=&v"(pj)
-                     : [sh] "v"(sh), [above] "v"(above), [r126] "v"(ring126),
+                     : [xa] "+v"(x), [wm1] "+v"(wm1), [na] "+v"(na), [nb] "+v"(nb), [xb] "=&v"(xb), [xs] "=&v"(xs), [t] "=&v"(t), [q] "=&v"(q), [pj] "=&v"(pj)
+                     : [mlo] "v"(mlo), [mhi] "v"(mhi), [r126] "v"(ring126),
                        [m0] "v"(m.x), [w0] "v"(w.x), [s0] "v"(s0), [X0] "v"(X0), [m1] "v"(m.y), [w1] "v"(w.y), [s1] "v"(s1), [X1] "v"(X1),
                        [m2] "v"(m.z), [w2] "v"(w.z), [s2] "v"(s2), [X2] "v"(X2), [m3] "v"(m.w), [w3] "v"(w.w), [s3] "v"(s3), [X3] "v"(X3)
-                     : "vcc", "memory", ENC_TRIP_EM_CLOBBER);
+                     : "vcc", "memory");
     }
     // conditional form: copy out the half that has just been completed, if any
     __device__ __forceinline__ void flush()
@@ -268,9 +296,24 @@ struct EncOutT {
         }
     }
     // unconditional form for the main loop: store what was read out last time, read out the next
+    // WM1: between trip_enter and trip_leave, where wm1 = written - 1 is what the steps carry and `flushed` is carried as
+    // fthr = 32 flushed + 31.  written >> 5 != flushed means written >= 32 (flushed + 1), as a half is read out as soon
+    // as it is complete: wm1 >= fthr, signed (wm1 starts at -1).  The half to read next is an LDS address that changes
+    // sides when a half is due (fhalf, fsum - fhalf), and the place of the half in the stream is send - 64 (flushed + 1)
+    // + 16 k = (send + 16 k - 2) - 2 fthr: a shift and a 64-bit subtract, no multiply under a branch.
+    template <bool WM1 = false>
     __device__ __forceinline__ void flush_pipelined()
     {
         *(GAS u32x4_unaligned *)held_dst = held;
+        if (WM1) {
+            const bool due = active && (int)wm1 >= (int)fthr;
+            held = *(LAS const u32x4 *)(unsigned long)fhalf;
+            gu8 *dst = fdst - (u64)(2u * fthr);
+            held_dst = due ? dst : dump;
+            fhalf = due ? fsum - fhalf : fhalf;
+            fthr += due ? 32u : 0u;
+            return;
+        }
         const bool due = active && (written >> HALF_SHIFT) != flushed;
         held = *(const u32x4 *)(ring + ((flushed & 1u) ? 0u : 64u) + 16u * k);
         held_dst = due ? send - 64ull * (flushed + 1u) + 16u * k : dump;
@@ -565,12 +608,14 @@ __device__ __forceinline__ u32 chain_encode_o1_lds(const u8 *img_lds, u8 *ring, 
         };
         // double-trip d: trip 2d looks up the bytes of trip 2d+3 (piece d+1, low dword), trip 2d+1
         // those of trip 2d+4 (piece d+2, high dword); piece d+4 is requested into the slot of piece d
+        if (FT) o.trip_enter();
         for (u32 d = 0; wave_any(d < npair); d += 4) {
-            Q0 = load8(d + 4); o.flush_pipelined(); trip(Q1.x); trip(Q2.y);
-            Q1 = load8(d + 5); o.flush_pipelined(); trip(Q2.x); trip(Q3.y);
-            Q2 = load8(d + 6); o.flush_pipelined(); trip(Q3.x); trip(Q0.y);
-            Q3 = load8(d + 7); o.flush_pipelined(); trip(Q0.x); trip(Q1.y);
+            Q0 = load8(d + 4); o.template flush_pipelined<FT>(); trip(Q1.x); trip(Q2.y);
+            Q1 = load8(d + 5); o.template flush_pipelined<FT>(); trip(Q2.x); trip(Q3.y);
+            Q2 = load8(d + 6); o.template flush_pipelined<FT>(); trip(Q3.x); trip(Q0.y);
+            Q3 = load8(d + 7); o.template flush_pipelined<FT>(); trip(Q0.x); trip(Q1.y);
         }
+        if (FT) o.trip_leave();
         o.flush_drain();
         o.flush();                               // fewer than 32 words may stay in the ring from here on
         // (packed rows: the loop does not carry the symbol that follows its last live trip - it is read again)

@@ -208,12 +208,15 @@ def to_json(out_path):
             for pre, (label, marker, *least) in HOT.items():
                 if not name.startswith(pre):
                     continue
-                best = None
+                best, bodies = None, []
                 for lab, b in blocks_of(src, name):
                     steps = sum(1 for x in b if x.split()[0] == marker)
                     if steps < (least[0] if least else 4):
                         continue
                     per = len(b) / steps
+                    # every body of the kernel's loops (the encode chain has an affine and a look-up one: the latter reads idx_of[])
+                    bodies.append({"steps_in_block": steps, "instructions_in_block": len(b), "instructions_per_step": round(per, 2),
+                                   "ds_read_u8_in_block": sum(1 for x in b if x.split()[0] == "ds_read_u8")})
                     if best is None or per < best[0]:            # the leanest body with >= 4 steps: the full-trip one
                         c = Counter(x.split()[0] for x in b)
                         cat = lambda p: sum(v for k, v in c.items() if k.startswith(p))
@@ -232,6 +235,7 @@ def to_json(out_path):
                                                 "trip_tail_instructions": trip_tail(src, name, lab, marker, least[0])})
                 if best:
                     res["kernels"][label] = best[1]
+                    res["kernels"][label]["bodies"] = bodies
     with open(out_path, 'w') as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res, indent=1))
